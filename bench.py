@@ -30,10 +30,17 @@ engine's own RCCL calls.  `per_rank` breaks a step into force / sym_reduce /
 reduce_scatter / integrate / allgather (nb_step_times2), next to ms_per_step.
 Default --scaling strong: the metric is quoted at N=262,144 for every GPU count.
 
+A plain run sets up, warms up, times --steps steps and prints the line.  Everything
+else the benchmark measures or checks runs only with --full: the per-kernel
+event-timed leg (roofline, per_rank), the run's energy drift, the N=1,024 golden
+fixture, the `also` measurements, the CPU baseline and the rehearsal's unsharded
+comparison.  --dump-outputs DIR writes the bodies / vel / accel arrays of the
+timed handle after its last timed step as DIR/{bodies,vel,accel}.npy.
+
 The line is only printed with a value when the run's own correctness checks
 pass (a sampled row of the benchmarked launch shape against an fp64 direct sum,
-replica agreement across ranks, the N=1,024 golden fixture); otherwise the
-value is null and the exit code 1.
+replica agreement across ranks; with --full also the N=1,024 golden fixture
+and every `also` entry); otherwise the value is null and the exit code 1.
 """
 import argparse
 import json
@@ -71,10 +78,15 @@ def parse():
     ap.add_argument("--variant", type=int, default=0)
     ap.add_argument("--jsplit", type=int, default=0)
     ap.add_argument("--flags", type=int, default=0, help="nb_config.flags (NB_FLAG_LDS_ONLY = 4, NB_FLAG_NO_FUSE = 8)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the event-timed leg (roofline, per_rank), energy drift, "
+                         "the fixture check, the `also` measurements, the CPU baseline, the rehearsal's unsharded comparison")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the timed handle's bodies / vel / accel after the last timed step as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) skip the CPU baseline")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
-    ap.add_argument("--no-check", action="store_true", help="skip the N=1,024 fixture check (the sampled-row check of "
-                                                            "the benchmarked shape always runs)")
+    ap.add_argument("--no-check", action="store_true", help="(--full) skip the N=1,024 fixture check (the sampled-row check "
+                                                            "of the benchmarked shape always runs)")
     ap.add_argument("--exchange", default="native", choices=["native", "torch", "host"],
                     help="native: the engine's own in-place ncclAllGather; torch: torch.distributed all-gather through "
                          "the exchange hook; host: REHEARSAL ONLY -- gloo group + host staging so several ranks can "
@@ -84,7 +96,7 @@ def parse():
     ap.add_argument("--force-dist", action="store_true",
                     help="run the distributed exchange path even with one rank (plumbing test)")
     ap.add_argument("--no-also", action="store_true",
-                    help="skip the secondary single-GPU measurements (BASELINE configs 2 and 5, config 4's N=1,048,576 on one GPU, the "
+                    help="(--full) skip the secondary single-GPU measurements (BASELINE configs 2 and 5, config 4's N=1,048,576 on one GPU, the "
                          "reference's default N=40,002 system) that the default 1-GPU headline run appends under the `also` key")
     return ap.parse_args()
 
@@ -538,9 +550,17 @@ def main():
             return "pairshard%d+reducescatter+allgather%s" % (world, "(overlapped)" if overlap else "")
         return "ishard%d+allgather%s" % (world, "(overlapped)" if overlap else "")
 
-    def measure(flags, want_energy):
-        """One protocol, start to finish: handle, gates, warm-up, the timed steps, the per-part breakdown.  Returns (result, sim)
-        with the handle still open (the caller closes it)."""
+    def dump_outputs(sim):
+        """What a caller of the timed path receives after its last timed step: the handle's bodies, vel and accel (n rows;
+        on a shard handle vel / accel rows outside this rank's shard are zero).  Rank 0 writes them."""
+        b, v, a = sim.read()
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, arr in (("bodies", b), ("vel", v), ("accel", a)):
+            np.save(os.path.join(args.dump_outputs, name + ".npy"), np.ascontiguousarray(arr[:n]))
+
+    def measure(flags, want_energy, dump=False):
+        """One protocol, start to finish: handle, gates, warm-up, the timed steps, (--full) the per-part breakdown.  Returns
+        (result, sim) with the handle still open (the caller closes it)."""
         sim, exchange, t_bodies = open_sim(flags)
         sim._bench_keepalive = t_bodies          # torch-owned position array (exchange through torch): lives as long as the handle
         sim.init(bodies_p, vel_p)
@@ -568,13 +588,17 @@ def main():
         sim.simulate(args.steps)
         barrier()
         elapsed = time.perf_counter() - t0
-        # ... and a separate leg of the same number of steps with the kernels stamped at their own begin / end (HIP events on the
-        # engine's stream: plain launches, no graph) for roofline.avg_launch_ms and the per-part breakdown; outside the timed region
-        sim.enable_timing(True)
-        sim.simulate(args.steps)
-        barrier()
-        parts = sim.step_breakdown()
-        sim.enable_timing(False)
+        if dump and rank == 0:
+            dump_outputs(sim)
+        parts = None
+        if args.full:
+            # ... and a separate leg of the same number of steps with the kernels stamped at their own begin / end (HIP events on the
+            # engine's stream: plain launches, no graph) for roofline.avg_launch_ms and the per-part breakdown; outside the timed region
+            sim.enable_timing(True)
+            sim.simulate(args.steps)
+            barrier()
+            parts = sim.step_breakdown()
+            sim.enable_timing(False)
         if dist is not None:
             t = torch.tensor([elapsed], device=cpu_dev, dtype=torch.float64)
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -592,6 +616,7 @@ def main():
             res["replicas_ok"] = bool(t[0].item() == -t[1].item()) and bool(np.isfinite(digest))
             res["replica_check"] = {"abs_sum_of_positions_max_over_ranks": float(t[0].item()),
                                     "abs_sum_of_positions_min_over_ranks": float(-t[1].item()), "pass": res["replicas_ok"]}
+        if dist is not None and parts is not None:
             # what the collectives move, per rank and step (payload; a ring forwards each block g - 1 times):
             #   all-gather: this rank's new position rows go to every other rank;
             #   reduce-scatter (rank form): g - 1 of the g row blocks of this rank's partial-acceleration array go out, one block comes back summed
@@ -620,7 +645,7 @@ def main():
                                "sum_of_parts_over_span": total / parts["span_ms"] if parts["span_ms"] > 0 else None,
                                "sum_of_parts_over_ms_per_step": total / ms_step if ms_step > 0 else None,
                                "max_over_ranks": dict(zip(names, [float(v) for v in tmax.tolist()]))}
-        if rehearsal and rank == 0:   # the sharded state must equal an unsharded run of the same number of steps
+        if rehearsal and rank == 0 and args.full:   # the sharded state must equal an unsharded run of the same number of steps
             got = sim.read(vel=False, accel=False)[0][:n]
             with Simulation(n, precision=args.precision, device=local_rank) as ref:
                 ref.init(bodies.astype(np_dtype), vel.astype(np_dtype))
@@ -631,9 +656,9 @@ def main():
 
     pairs_step = n * (n - 1)
     roof_pairs = PEAK_FP32_TFLOPS * 1e12 / FLOPS_PER_PAIR * (0.5 if args.precision == "f64" else 1.0)
-    main_res, sim = measure(args.flags, world == 1 and dist is None)
+    main_res, sim = measure(args.flags, args.full and world == 1 and dist is None, dump=args.dump_outputs is not None)
     elapsed, parts, variant = main_res["elapsed"], main_res["parts"], main_res["variant"]
-    f_ms, i_ms, launches = parts["force_ms"], parts["integrate_ms"], parts["launches"]
+    f_ms, i_ms, launches = (parts["force_ms"], parts["integrate_ms"], parts["launches"]) if parts else (0.0, 0.0, 0)
     value = pairs_step * args.steps / elapsed
     out = {
         "metric": "pair-interactions/s", "value": value, "unit": "pair-interactions/s",
@@ -649,7 +674,8 @@ def main():
     }
     if dist is not None:
         out["exchange"] = main_res["exchange"]
-        out["per_rank"] = main_res["per_rank"]
+        if "per_rank" in main_res:
+            out["per_rank"] = main_res["per_rank"]
         out["replica_check"] = main_res["replica_check"]
     if rehearsal:
         out["REHEARSAL"] = "ranks share one GPU, exchange staged through host memory over gloo: not a result"
@@ -706,7 +732,7 @@ def main():
                                         "dE_rel": abs((ke + pe_prev - main_res["e_start"]) / main_res["e_start"])}
     sim.close()
     ok = main_res["shape_ok"] and main_res["replicas_ok"]
-    if dist is not None and "symwrank" in variant and not rehearsal:
+    if args.full and dist is not None and "symwrank" in variant and not rehearsal:
         # The same launch also measures the protocol north_star spells out -- i-sharded ordered-pair force pass + per-step
         # all-gather of the positions (NB_FLAG_NO_SYM) -- so that both are on record from ONE run: same ranks, same
         # workload, same gates; its own communicator.
@@ -724,15 +750,15 @@ def main():
                         "exchange": lit["exchange"], "per_rank": lit["per_rank"], "shape_check": lit["shape_check"],
                         "replica_check": lit["replica_check"], "pass": bool(lit["shape_ok"] and lit["replicas_ok"])}]
         ok = ok and out["also"][0]["pass"]
-    if rank == 0 and not args.no_check:
+    if args.full and rank == 0 and not args.no_check:
         out["check"] = fixture_check()
         ok = ok and out["check"]["pass"]
     default_run = (world == 1 and dist is None and not args.n and args.workload == "plummer" and args.precision == "f32"
                    and not args.variant and not args.jsplit and not args.flags)
-    if default_run and not args.no_also:
+    if args.full and default_run and not args.no_also:
         out["also"] = also_measurements(Simulation, ic, local_rank)
         ok = ok and all(e.get("pass") for e in out["also"])
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(bodies, G, args.cpu_seconds)
     if dist is not None:
         ok = all_ranks(ok)

@@ -4,9 +4,11 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 from conftest import ROOT
+from nbody3d_amd import ic
 
 pytestmark = pytest.mark.gpu
 
@@ -16,7 +18,7 @@ REQUIRED = ["metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step
 
 def test_bench_emits_one_well_formed_json_line():
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--nbodies", "16384", "--steps", "5", "--warmup", "2",
-                        "--cpu-seconds", "0.5"], capture_output=True, text=True, timeout=600)
+                        "--cpu-seconds", "0.5", "--full"], capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1
@@ -38,13 +40,43 @@ def test_bench_emits_one_well_formed_json_line():
     assert d["check"]["pass"] is True and d["check"]["max_rel_pos_err_vs_f64_oracle"] < 1e-4
 
 
+def test_plain_run_times_exactly_its_steps_and_dumps_what_the_timed_handle_holds(tmp_path):
+    """Without --full the line carries the headline fields and nothing that takes runs of its own; --dump-outputs writes the
+    timed handle's bodies / vel / accel after the last timed step; two runs with the same arguments start from the same seeded
+    system and write the same arrays."""
+    n, dumps = 16384, []
+    for k in range(2):
+        out = tmp_path / ("run%d" % k)
+        p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--nbodies", str(n), "--steps", "7", "--warmup", "2",
+                            "--dump-outputs", str(out)], capture_output=True, text=True, timeout=600)
+        assert p.returncode == 0, p.stderr[-2000:]
+        lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1
+        d = json.loads(lines[0])
+        for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps", "warmup", "shape_check"):
+            assert key in d, key
+        for key in ("roofline", "cpu_baseline", "also", "check", "energy_drift_over_run"):
+            assert key not in d, key
+        assert d["steps"] == 7 and d["shape_check"]["pass"] is True
+        assert abs(d["value"] - n * (n - 1) * 7 / (d["ms_per_step"] * 7e-3)) < 1e-6 * d["value"]
+        arrs = {name: np.load(out / (name + ".npy")) for name in ("bodies", "vel", "accel")}
+        for a in arrs.values():
+            assert a.shape == (n, 4) and a.dtype == np.float32 and np.isfinite(a).all()
+        dumps.append(arrs)
+    b0, _ = ic.plummer(n, seed=1)
+    assert np.array_equal(dumps[0]["bodies"][:, 3], b0[:, 3]) and not np.array_equal(dumps[0]["bodies"], b0)
+    assert np.abs(dumps[0]["accel"][:, :3]).max() > 0
+    for name in ("bodies", "vel", "accel"):
+        assert np.allclose(dumps[0][name], dumps[1][name], rtol=1e-5, atol=1e-6), name
+
+
 def test_force_dist_line_reports_both_protocols_and_a_breakdown_that_adds_up():
     """The N>1 code path on one rank (--force-dist: the process group, the native RCCL communicator, the in-place
     ncclReduceScatter and ncclAllGather all really run): the line names the protocol that ran, times BOTH collectives
     (nb_step_times2), its per-rank parts add up to the step, and the north_star-literal protocol (i-shard + all-gather,
     NB_FLAG_NO_SYM) is measured by the same launch under `also`."""
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--force-dist", "--nbodies", "65536", "--steps", "10", "--warmup", "3",
-                        "--no-cpu-baseline", "--no-check"], capture_output=True, text=True, timeout=600)
+                        "--no-cpu-baseline", "--no-check", "--full"], capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stderr[-2000:]
     d = json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][-1])
     assert d["value"] and d["config"]["parallelism"] == "pairshard1+reducescatter+allgather", d["config"]

@@ -126,7 +126,7 @@ def test_bench_distributed_path_with_one_rank(exchange):
     """bench.py --force-dist: process group on the nccl (= RCCL) backend, sharded handle on torch's
     stream, per-step all-gather (the engine's own ncclAllGather, or torch's through the hook)."""
     p, out = _bench("--force-dist", "--exchange", exchange, "--nbodies", "16384", "--steps", "4", "--warmup", "1",
-                    "--no-cpu-baseline")
+                    "--no-cpu-baseline", "--full")
     assert p.returncode == 0 and out, p.stderr[-2000:]
     assert out["n_gpus"] == 1 and out["value"] > 0
     assert out["exchange"]["kind"].startswith("rccl-native" if exchange == "native" else "torch"), out["exchange"]
@@ -152,7 +152,7 @@ def test_bench_two_rank_control_flow_rehearsal():
     through host memory over gloo: RCCL refuses two ranks on one device).  Marked REHEARSAL in the
     line; the sharded state must equal an unsharded run."""
     p, out = _bench("--gpus", "2", "--exchange", "host", "--nbodies", "16384", "--steps", "3", "--warmup", "2",
-                    "--no-cpu-baseline", timeout=600)
+                    "--no-cpu-baseline", "--full", timeout=600)
     assert p.returncode == 0 and out, (p.stderr + p.stdout)[-2000:]
     assert out["n_gpus"] == 2 and "REHEARSAL" in out and out["value"] > 0
     assert out["replica_check"]["pass"] and out["shape_check"]["pass"] and out["check"]["pass"]

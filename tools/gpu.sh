@@ -19,7 +19,7 @@ while [ $# -gt 0 ]; do
     tests) step pytest_gpu 1100 python -m pytest tests -m gpu -x -q --durations=15; tail -25 gpurun_out/pytest_gpu.txt ;;
     new)   step pytest_new 900 python -m pytest ${NB_NEW_TESTS:-tests/test_sym_gpu.py} -m gpu -x -q --durations=10; tail -25 gpurun_out/pytest_new.txt ;;
     smoke) step smoke 300 python __graft_entry__.py smoke; tail -2 gpurun_out/smoke.txt ;;
-    bench) step bench 600 python bench.py; tail -1 gpurun_out/bench.txt | cut -c1-3000 ;;
+    bench) step bench 600 python bench.py --full ;;
     sizes) args=(); while [ $# -gt 0 ] && [[ $1 =~ ^[0-9]+$ ]]; do args+=("$1"); shift; done
            step size_scan 900 python tools/size_scan.py "${args[@]}"; cat gpurun_out/size_scan.txt ;;
     shapes) args=(); while [ $# -gt 0 ] && [[ $1 =~ ^[0-9]+$ ]]; do args+=("$1"); shift; done
