@@ -38,11 +38,12 @@ extern "C" {
 #endif
 
 #define NB_ABI_VERSION 2u /* major: a client and a library must agree on it (nb_abi_version) */
-#define NB_ABI_MINOR 3u   /* additions within major 2; a client needs nb_abi_minor() >= the minor it was written against:
+#define NB_ABI_MINOR 4u   /* additions within major 2; a client needs nb_abi_minor() >= the minor it was written against:
                              2.1 (round 3)  nb_force_pass, nb_frame_request / nb_frame_acquire, nb_shape_info, NB_FLAG_SYM_SHARD
                              2.2 (round 4)  nb_step_times2, nb_plan_query, NB_FLAG_WHOLE_SWEEPS, nb_config.layer_budget_mib
                              2.3 (round 5)  nb_abi_minor, NB_MULTI_PEER_OVERLAP; nb_plan_info / nb_plan_query moved to nbody3d_hip_plan.h; force_variant 7 II LL 3 takes LL up to 64;
-                                            nb_plan_query's table holds four words per wave instead of the W + 1 starts */
+                                            nb_plan_query's table holds four words per wave instead of the W + 1 starts
+                             2.4 (round 6)  nb_field_eval, nb_multi_field_eval, nb_field_request, NB_FIELD_* */
 
 typedef struct nb_sim nb_sim; /* opaque */
 
@@ -373,6 +374,51 @@ int nb_frame_acquire(nb_sim *s, int wait, const float **bodies, const float **sp
  *          (-G/2 * sum_i sum_{j != i} m_i m_j / sqrt(r^2 + eps2), i in shard),
  * out[2..4] = momentum of the shard.  Accumulated in fp64 on the device. */
 int nb_diagnostics(nb_sim *s, double out[5]);
+
+/* ---- field queries (ABI 2.4; no reference analogue) ------------------------------------------
+ * Acceleration and potential of the handle's N bodies at M points, M x N ordered pairs:
+ *     a(p)   =   sum_j G m_j (x_j - p) / (|x_j - p|^2 + eps2)^(3/2)
+ *     phi(p) = - sum_j G m_j / sqrt(|x_j - p|^2 + eps2)
+ * with the handle's eps2 and the G of the last nb_set_params, on the positions AS THEY STAND BEHIND EVERY STEP ENQUEUED SO FAR
+ * (a shard handle finishes a pending gather first, as nb_diagnostics does).  Any handle kind: whole system, shard (its bodies
+ * array is replicated), fused / ping-pong, symmetric with padded rows (zero-mass rows add exactly nothing).
+ *   - Element type of points / accel / phi: the handle's precision.  With NB_FIELD_F64 on an f32 handle the pair arithmetic and
+ *     the sums run in fp64 on the stored f32 rows and the two OUTPUTS are double (points stay float): the on-device audit of the
+ *     f32 sums.  On an f64 handle NB_FIELD_F64 is accepted and changes nothing.
+ *   - Arbitrary points leave nothing out.  A point that coincides with a body gets exactly 0 acceleration from it (eps2 > 0) and
+ *     -G m / sqrt(eps2) of potential.  NB_FIELD_AT_BODIES: point k is body first_body + k and leaves ITSELF out of both sums --
+ *     inside the loop (that one pair carries a weight of zero), never by subtracting the self term afterwards, so a body of
+ *     mass 1e7 gets the small potential of its neighbours to full precision.
+ *   - At least one of accel / phi is non-NULL; an output that is not asked for is not computed.
+ *   - Errors: NB_ERR_INVALID (NULL handle or request, wrong struct_size, m == 0, both outputs NULL, points given with
+ *     NB_FIELD_AT_BODIES or missing without it, first_body + m > n, unknown flag bits), NB_ERR_STATE (nothing uploaded, no
+ *     parameters set); nb_last_error names the field.
+ *   - The simulation state, the engine's side copies of it, the captured step graphs and the step counter are untouched:
+ *     stepping after a call is bit-identical to stepping without it.
+ *   - Deterministic: the same request on the same state gives the same bits (fixed summation order, no atomics).  The order
+ *     may depend on m, so a sub-range's bits need not equal the same rows of a larger request.
+ *   - Host pointers: the call blocks until the outputs are written; no pointer is kept.  NB_FIELD_DEVICE: the three pointers are
+ *     device memory on the handle's device, the work is enqueued on the handle's stream and the call returns at once.
+ *   - Memory: engine-owned staging for a host-pointer request (O(m)) and partial sums of a bounded number of (point, j-chunk)
+ *     rows (2^20 rows of 16 or 32 bytes, or two launches' worth of workgroups where that is more); grown on demand, released by
+ *     nb_destroy; nothing proportional to m x N.  Large m goes through in batches of at most 262,144 points. */
+#define NB_FIELD_AT_BODIES 1u  /* points = current positions of bodies [first_body, first_body + m); each leaves ITSELF out of its sums */
+#define NB_FIELD_F64       2u  /* f32 handle: pair arithmetic and sums in fp64 on the stored f32 rows; outputs are double (audit mode) */
+#define NB_FIELD_DEVICE    4u  /* points / accel / phi are DEVICE pointers on the handle's device; the work is enqueued on the
+                                  handle's stream and the call returns without synchronising */
+typedef struct nb_field_request {
+    uint32_t struct_size;   /* sizeof(nb_field_request) */
+    uint32_t m;             /* number of points, >= 1 */
+    uint32_t flags;         /* NB_FIELD_* */
+    uint32_t first_body;    /* NB_FIELD_AT_BODIES only */
+    const void *points;     /* 4*m elements x, y, z, (ignored); must be NULL with NB_FIELD_AT_BODIES */
+    void *accel;            /* out, optional: 4*m elements ax, ay, az, 0 */
+    void *phi;              /* out, optional: m elements */
+} nb_field_request;
+int nb_field_eval(nb_sim *s, const nb_field_request *req);
+/* The same on a multi-shard system.  The bodies are replicated on every shard after a step, so the request is evaluated on
+ * shard 0 (its device, its stream); first_body counts the caller's UNPADDED rows. */
+int nb_multi_field_eval(nb_multi *m, const nb_field_request *req);
 
 #if defined(__GNUC__)
 #pragma GCC visibility pop

@@ -690,6 +690,19 @@ int nb_multi_diagnostics(nb_multi* m, double out[5])
     return NB_OK;
 }
 
+int nb_multi_field_eval(nb_multi* m, const nb_field_request* req)
+{
+    if (!m) return mfail(nullptr, NB_ERR_INVALID, "nb_multi_field_eval: null handle");
+    if (!req) return mfail(m, NB_ERR_INVALID, "nb_multi_field_eval: null request");
+    // the caller's rows are the first n of the padded system: its indices are shard 0's, only the bound is the multi handle's
+    if (req->struct_size == sizeof(nb_field_request) && (req->flags & NB_FIELD_AT_BODIES) && (uint64_t)req->first_body + req->m > m->n)
+        return mfail(m, NB_ERR_INVALID, "nb_multi_field_eval: first_body + m exceeds n");
+    if (int rc = nb_multi_sync(m)) return rc;      // every shard's gather has landed: shard 0 holds all rows (padding: zero mass)
+    nb_sim* s = m->shard[0];
+    const int rc = nb_field_eval(s, req);
+    return rc == NB_OK ? rc : mfail(m, rc, s->err);
+}
+
 int nb_multi_download(nb_multi* m, void* bodies, void* vel, void* accel)
 {
     if (!m) return NB_ERR_INVALID;

@@ -689,6 +689,7 @@ int nb_create(const nb_config* cfg_in, nb_sim** out)
     else { NB_HIPC(hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking)); s->own_stream = true; }
 
     const int n_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
+    s->n_cu = n_cu;
     const double clock_hz = prop.clockRate > 0 ? 1e3 * prop.clockRate : 2.4e9;     // clockRate is in kHz
     plan_handle(s, cfg, n_cu, clock_hz, (double)prop.totalGlobalMem);
     if (s->sym && (!s->sym_rank || s->sym_local) && !cfg.force_variant) {
@@ -806,6 +807,7 @@ void nb_destroy(nb_sim* s)
     if (s->sym_queue) (void)hipFree(s->sym_queue);
     if (s->sym_A) (void)hipFree(s->sym_A);
     if (s->diag) (void)hipFree(s->diag);
+    for (auto* b : {&s->fld_pts, &s->fld_acc, &s->fld_phi, &s->fld_part}) if (b->p) (void)hipFree(b->p);
     if (s->zero_row) (void)hipFree(s->zero_row);
     if (s->own_stream && s->stream) (void)hipStreamDestroy(s->stream);
     delete s;
@@ -1238,6 +1240,138 @@ int nb_diagnostics(nb_sim* s, double out[5])
     for (int q = 0; q < 5; ++q) out[q] = 0.0;
     for (uint32_t b = 0; b < s->diag_blocks; ++b)
         for (int q = 0; q < 5; ++q) out[q] += h[(size_t)b * 5 + q];
+    return NB_OK;
+}
+
+/* ---- field queries ------------------------------------------------------------------------ */
+
+namespace {
+
+// Makes an engine-owned buffer hold at least `bytes` (a grown buffer is a new allocation: whatever the stream still runs on the
+// old one is waited for first).
+int field_reserve(nb_sim* s, nb_sim::field_buf& b, size_t bytes)
+{
+    if (bytes <= b.cap) return NB_OK;
+    if (b.p) { NB_HIP(s, hipStreamSynchronize(s->stream)); (void)hipFree(b.p); b.p = nullptr; b.cap = 0; }
+    if (hipMalloc(&b.p, bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        b.p = nullptr;
+        return fail(s, NB_ERR_NOMEM, "nb_field_eval: cannot allocate " + std::to_string(bytes) + " bytes of device memory");
+    }
+    b.cap = bytes;
+    return NB_OK;
+}
+
+constexpr uint32_t kFieldPartRows = 1u << 20;    // most (point, j-chunk) rows of partial sums in flight (or two launches' worth of workgroups, if that is more)
+constexpr uint32_t kFieldWavesPerSimd = 8;       // waves per SIMD a launch is cut into, at least (when m x n gives that many): twice the four that are
+                                                 // resident.  M = N = 262,144, both outputs, against nb_force_pass: 2 -> 1.285, 4 -> 1.21, 8 -> 1.18, 16 -> 1.165
+constexpr uint32_t kFieldMinChunk = 2048;         // bodies of a j-chunk below which only the two-waves-per-SIMD floor cuts (m = 1,024 against N = 1,048,576:
+                                                 // 0.33 ms with 512 chunks of 2,048 bodies, 0.42 ms with 2,048 chunks of 512)
+constexpr uint32_t kFieldMaxChunk = 1u << 20;    // most bodies of one j-chunk (bounds the second-level sums of nb_field_pk)
+
+// Workgroups a launch should have at least, however few the points are.
+uint32_t field_blocks_wanted(const nb_sim* s)
+{
+    uint32_t per_simd = kFieldWavesPerSimd;
+#ifdef NB_TUNING    // calibration build only: the launch-shape constant from the environment (tools/field_bench.py --only-big)
+    if (const char* e = getenv("NB_FIELD_WAVES")) per_simd = (uint32_t)std::max(1, atoi(e));
+#endif
+    return per_simd * (uint32_t)s->n_cu;       // workgroups of 4 waves, one wave on each SIMD of a CU
+}
+
+// j-chunks for a batch of `pblocks` point blocks: that many workgroups -- but chunks shorter than kFieldMinChunk bodies only as far
+// as a quarter of them needs it (two waves per SIMD is the floor a launch reaches whenever m x n gives it; past that, a short
+// chunk pays more in its prologue and in nb_field_reduce than the finer cut returns) -- in whole 256-body tiles.
+void field_shape(const nb_sim* s, uint32_t pblocks, uint32_t* chunks, uint32_t* j_per_chunk)
+{
+    const uint32_t want = field_blocks_wanted(s);
+    const uint32_t c_hi = ceil_div(want, pblocks), c_lo = ceil_div(ceil_div(want, 4u), pblocks);
+    uint32_t c = std::min(c_hi, std::max(c_lo, s->n / kFieldMinChunk));
+    c = std::max(c, ceil_div(s->n, kFieldMaxChunk));
+    c = std::max(1u, std::min(c, ceil_div(s->n, (uint32_t)nb::kTile)));
+    const uint32_t per = ceil_div(ceil_div(s->n, c), (uint32_t)nb::kTile) * nb::kTile;
+    *j_per_chunk = per;
+    *chunks = ceil_div(s->n, per);
+}
+
+}  // namespace
+
+int nb_field_eval(nb_sim* s, const nb_field_request* req)
+{
+    if (!s) return fail(nullptr, NB_ERR_INVALID, "nb_field_eval: null handle");
+    if (!req) return fail(s, NB_ERR_INVALID, "nb_field_eval: null request");
+    if (req->struct_size != sizeof(nb_field_request)) return fail(s, NB_ERR_INVALID, "nb_field_eval: struct_size must be sizeof(nb_field_request)");
+    if (req->flags & ~(NB_FIELD_AT_BODIES | NB_FIELD_F64 | NB_FIELD_DEVICE)) return fail(s, NB_ERR_INVALID, "nb_field_eval: unknown bits in flags");
+    const bool at = (req->flags & NB_FIELD_AT_BODIES) != 0, dev = (req->flags & NB_FIELD_DEVICE) != 0;
+    if (at && req->points) return fail(s, NB_ERR_INVALID, "nb_field_eval: points must be NULL with NB_FIELD_AT_BODIES");
+    if (!at && !req->points) return fail(s, NB_ERR_INVALID, "nb_field_eval: points is NULL (and NB_FIELD_AT_BODIES is not set)");
+    if (req->m == 0) return fail(s, NB_ERR_INVALID, "nb_field_eval: m must be >= 1");
+    if (!req->accel && !req->phi) return fail(s, NB_ERR_INVALID, "nb_field_eval: accel and phi are both NULL");
+    if (at && (uint64_t)req->first_body + req->m > s->n) return fail(s, NB_ERR_INVALID, "nb_field_eval: first_body + m exceeds n");
+    if (!s->uploaded) return fail(s, NB_ERR_STATE, "nb_field_eval: nothing uploaded yet");
+    if (!s->params_set) return fail(s, NB_ERR_STATE, "nb_field_eval: nb_set_params has not been called (G)");
+    NB_HIP(s, hipSetDevice(s->device));
+    if (int rc = finish_gather(s)) return rc;     // other ranks' rows must have landed
+
+    const bool wide = s->f64 || (req->flags & NB_FIELD_F64);      // fp64 arithmetic and outputs
+    const size_t in_row = 4 * s->esz, out_esz = wide ? 8 : 4;
+    const uint32_t m = req->m;
+    const char* pts = at ? (const char*)s->bodies[s->cur] + in_row * req->first_body : (const char*)req->points;
+    char* acc = (char*)req->accel;
+    char* phi = (char*)req->phi;
+    if (!dev) {
+        if (!at) {
+            if (int rc = field_reserve(s, s->fld_pts, in_row * m)) return rc;
+            NB_HIP(s, hipMemcpyAsync(s->fld_pts.p, req->points, in_row * m, hipMemcpyHostToDevice, s->stream));
+            pts = (const char*)s->fld_pts.p;
+        }
+        if (req->accel) { if (int rc = field_reserve(s, s->fld_acc, 4 * out_esz * m)) return rc; acc = (char*)s->fld_acc.p; }
+        if (req->phi) { if (int rc = field_reserve(s, s->fld_phi, out_esz * m)) return rc; phi = (char*)s->fld_phi.p; }
+    }
+
+    const uint32_t rows = wide ? nb::kFieldRows64 : nb::kFieldRows;      // points per workgroup
+    const uint32_t batch_max = wide ? 65536u : 262144u;
+    const uint64_t part_rows = std::max<uint64_t>(kFieldPartRows, (uint64_t)2 * field_blocks_wanted(s) * rows);
+    const void* bodies = s->bodies[s->cur];
+    const void* zero_row = s->zero_row;
+    uint32_t n = s->n, at_flag = at ? 1u : 0u;
+    double G = s->G, eps2d = s->eps2;
+    float eps2f = (float)s->eps2;
+    for (uint32_t done = 0; done < m;) {
+        uint32_t mb = std::min(m - done, batch_max), chunks, per;
+        field_shape(s, ceil_div(mb, rows), &chunks, &per);
+        while ((uint64_t)chunks * mb > part_rows && mb > rows) {     // fewer points at once: the partial sums stay bounded
+            mb = std::max(rows, (mb / 2 + rows - 1) / rows * rows);
+            field_shape(s, ceil_div(mb, rows), &chunks, &per);
+        }
+        if (int rc = field_reserve(s, s->fld_part, (size_t)4 * out_esz * chunks * mb)) return rc;
+        const void* p = pts + in_row * done;
+        void* part = s->fld_part.p;
+        void* a = acc ? acc + 4 * out_esz * done : nullptr;
+        void* f = phi ? phi + out_esz * done : nullptr;
+        uint32_t self0 = req->first_body + done;
+        dim3 grid(ceil_div(mb, rows), chunks), block(nb::kBlock);
+        if (wide) {
+            void* args[] = {&bodies, &p, &part, &n, &mb, &per, &eps2d, &at_flag, &self0};
+            const void* fn = s->f64 ? (const void*)&nb::nb_field64<double> : (const void*)&nb::nb_field64<float>;
+            NB_HIP(s, hipLaunchKernel(fn, grid, block, args, 0, s->stream));
+            void* rargs[] = {&part, &mb, &chunks, &G, &a, &f};
+            NB_HIP(s, hipLaunchKernel((const void*)&nb::nb_field_reduce<double, double>, dim3(ceil_div(mb, nb::kBlock)), block, rargs, 0, s->stream));
+        } else {
+            void* args[] = {&bodies, &p, &part, &n, &mb, &per, &eps2f, &at_flag, &self0, &zero_row};
+            const void* fn = a && f ? (const void*)&nb::nb_field_pk<true, true>
+                             : a ? (const void*)&nb::nb_field_pk<true, false> : (const void*)&nb::nb_field_pk<false, true>;
+            NB_HIP(s, hipLaunchKernel(fn, grid, block, args, 0, s->stream));
+            void* rargs[] = {&part, &mb, &chunks, &G, &a, &f};
+            NB_HIP(s, hipLaunchKernel((const void*)&nb::nb_field_reduce<float, float>, dim3(ceil_div(mb, nb::kBlock)), block, rargs, 0, s->stream));
+        }
+        done += mb;
+    }
+    if (!dev) {
+        if (req->accel) NB_HIP(s, hipMemcpyAsync(req->accel, acc, 4 * out_esz * m, hipMemcpyDeviceToHost, s->stream));
+        if (req->phi) NB_HIP(s, hipMemcpyAsync(req->phi, phi, out_esz * m, hipMemcpyDeviceToHost, s->stream));
+        NB_HIP(s, hipStreamSynchronize(s->stream));
+    }
     return NB_OK;
 }
 

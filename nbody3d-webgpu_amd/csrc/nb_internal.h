@@ -138,6 +138,10 @@ struct nb_sim {
     nb_frame_slot frame[kFrameSlots];
     int frame_next = 0;              // slot the next request writes
     int frame_latest = -1;           // most recently requested slot
+    // nb_field_eval: engine-owned buffers, grown on demand, released by nb_destroy.  pts / acc / phi stage a host-pointer request
+    // (O(m)); part holds one (ax, ay, az, sum m/r) row per (j-chunk, point of a batch): a bounded number of rows whatever m and n are
+    int n_cu = 256;
+    struct field_buf { void* p = nullptr; size_t cap = 0; } fld_pts, fld_acc, fld_phi, fld_part;
 };
 
 namespace nbi {

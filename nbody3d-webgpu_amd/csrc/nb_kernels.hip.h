@@ -49,6 +49,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "nb_plan.h"
 
 // The device code lives in kernels/*.hip.h, in dependency order:
@@ -57,3 +59,4 @@
 #include "kernels/symmetric.hip.h"   // nb_force_sym*, nb_sym_reduce, nb_peer_*, nb_integrate_sym*
 #include "kernels/jpk.hip.h"         // nb_step_jpk, nb_pairs_pack, nb_gm_pack
 #include "kernels/integrate.hip.h"   // nb_integrate, nb_integrate_swap, nb_frame_pack, nb_diag
+#include "kernels/field.hip.h"       // nb_field_pk, nb_field64, nb_field_reduce (nb_field_eval: the field at arbitrary points)

@@ -57,6 +57,8 @@ static int (*p_step_times2)(nb_sim *, nb_step_timing *);
 static int (*p_frame_request)(nb_sim *);
 static int (*p_frame_acquire)(nb_sim *, int, const float **, const float **, uint64_t *);
 static int (*p_plan_query)(const nb_config *, int, double, nb_plan_info *, uint32_t *, uint32_t);
+static int (*p_field_eval)(nb_sim *, const nb_field_request *);
+static int (*p_multi_field_eval)(nb_multi *, const nb_field_request *);
 
 /* one JS handle = a single-device nb_sim or a single-process multi-device nb_multi */
 typedef struct { nb_sim *sim; nb_multi *multi; uint32_t n; int f64; } handle_t;
@@ -132,6 +134,7 @@ static napi_value js_load(napi_env env, napi_callback_info info)
         SYM(p_multi_set_collective, "nb_multi_set_collective"); SYM(p_multi_collective_info, "nb_multi_collective_info");
         SYM(p_step_times, "nb_step_times"); SYM(p_step_times2, "nb_step_times2"); SYM(p_frame_request, "nb_frame_request"); SYM(p_frame_acquire, "nb_frame_acquire");
         SYM(p_plan_query, "nb_plan_query");
+        SYM(p_field_eval, "nb_field_eval"); SYM(p_multi_field_eval, "nb_multi_field_eval");
 #undef SYM
         g_lib = h;
     }
@@ -560,6 +563,58 @@ static napi_value js_frame(napi_env env, napi_callback_info info)
     return v;
 }
 
+/* fieldEval(handle, points|null, firstBody, count, accelOut|null, phiOut|null): nb_field_eval / nb_multi_field_eval.
+ * points: typed array of the handle's precision with 4*m elements (x, y, z, ignored) -- or null, and then the points are
+ * the bodies [firstBody, firstBody + count) themselves (NB_FIELD_AT_BODIES).  accelOut (4*m) / phiOut (m): typed arrays of the
+ * handle's precision, written in place; no copy beyond the engine's own. */
+static napi_value js_field_eval(napi_env env, napi_callback_info info)
+{
+    size_t argc = 6; napi_value argv[6];
+    CHECK_NAPI(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    if (argc < 6) { napi_throw_type_error(env, NULL, "fieldEval(handle, points|null, firstBody, count, accelOut|null, phiOut|null)"); return NULL; }
+    handle_t *h = get_handle(env, argv[0]); if (!h) return NULL;
+    const napi_typedarray_type want = h->f64 ? napi_float64_array : napi_float32_array;
+    void *ptr[3] = {NULL, NULL, NULL}; size_t len[3] = {0, 0, 0};
+    static const int arg_of[3] = {1, 4, 5};
+    static const char *const what[3] = {"points", "accelOut", "phiOut"};
+    for (int k = 0; k < 3; ++k) {
+        napi_valuetype vt; napi_typeof(env, argv[arg_of[k]], &vt);
+        if (vt == napi_null || vt == napi_undefined) continue;
+        bool is_ta = false; napi_is_typedarray(env, argv[arg_of[k]], &is_ta);
+        napi_typedarray_type tt; napi_value ab; size_t off;
+        if (!is_ta || napi_get_typedarray_info(env, argv[arg_of[k]], &tt, &len[k], &ptr[k], &ab, &off) != napi_ok || tt != want) {
+            char buf[160]; snprintf(buf, sizeof buf, "fieldEval: %s must be a %s or null", what[k], h->f64 ? "Float64Array" : "Float32Array");
+            napi_throw_type_error(env, NULL, buf); return NULL;
+        }
+    }
+    double first = 0, count = 0;
+    napi_get_value_double(env, argv[2], &first); napi_get_value_double(env, argv[3], &count);
+    nb_field_request req;
+    memset(&req, 0, sizeof req);
+    req.struct_size = sizeof req;
+    if (ptr[0]) {
+        if (len[0] % 4 != 0 || len[0] / 4 > 0xffffffffu) { napi_throw_range_error(env, NULL, "fieldEval: points must hold 4*m elements"); return NULL; }
+        req.m = (uint32_t)(len[0] / 4);
+        req.points = ptr[0];
+    } else {
+        if (!(first >= 0 && first <= 4294967295.0 && count >= 0 && count <= 4294967295.0)) { napi_throw_range_error(env, NULL, "fieldEval: firstBody / count out of range"); return NULL; }
+        req.flags = NB_FIELD_AT_BODIES;
+        req.first_body = (uint32_t)first; req.m = (uint32_t)count;
+    }
+    if ((ptr[1] && len[1] != (size_t)4 * req.m) || (ptr[2] && len[2] != (size_t)req.m)) {
+        napi_throw_range_error(env, NULL, "fieldEval: accelOut must hold 4*m elements and phiOut m"); return NULL;
+    }
+    req.accel = ptr[1]; req.phi = ptr[2];
+    if (h->multi) {
+        int rcm = p_multi_field_eval(h->multi, &req);
+        if (rcm != NB_OK) return throw_msg(env, rcm, p_multi_last_error(h->multi), "nb_multi_field_eval");
+    } else {
+        int rc = p_field_eval(h->sim, &req);
+        if (rc != NB_OK) return throw_nb(env, rc, h->sim, "nb_field_eval");
+    }
+    return undefined(env);
+}
+
 static napi_value init_module(napi_env env, napi_value exports)
 {
     static const struct { const char *name; napi_callback fn; } fns[] = {
@@ -568,6 +623,7 @@ static napi_value init_module(napi_env env, napi_value exports)
         {"destroy", js_destroy}, {"enableTiming", js_enable_timing}, {"kernelTimes", js_kernel_times},
         {"variant", js_variant}, {"diagnostics", js_diagnostics}, {"stepTimes", js_step_times},
         {"collectiveInfo", js_collective_info}, {"requestFrame", js_request_frame}, {"frame", js_frame}, {"planQuery", js_plan_query},
+        {"fieldEval", js_field_eval},
     };
     for (size_t i = 0; i < sizeof fns / sizeof fns[0]; ++i) {
         napi_value f;

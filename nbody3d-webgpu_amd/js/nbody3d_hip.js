@@ -227,6 +227,31 @@ class Simulation {
   variant() { this._need(); return addon.variant(this._h); }
   diagnostics() { this._need(); addon.setParams(this._h, this.dt, this.G); return addon.diagnostics(this._h); }
 
+  /** Field query (nb_field_eval; no reference analogue): acceleration and potential of the system at `points` -- a typed or
+   *  plain array of 4*m elements x, y, z, (ignored) -- or, with options.bodies = [first, count] (and points null), at the
+   *  current positions of those bodies, each leaving itself out of its sums.  Returns {accel: 4*m elements ax, ay, az, 0;
+   *  phi: m elements} in the handle's precision (Float32Array, Float64Array for f64 handles); options.accel === false /
+   *  options.phi === false leave that output out (null).  The positions are those behind every step issued so far; the
+   *  simulation state is not touched. */
+  field(points, options) {
+    this._need();
+    const o = options || {}, T = this.ArrayType;
+    let pts = null, first = 0, m;
+    if (o.bodies) { first = o.bodies[0] >>> 0; m = o.bodies[1] >>> 0; }
+    if (points !== null && points !== undefined) {
+      if (points instanceof T) pts = points;
+      else if (typeof points.length === 'number') pts = T.from(points);
+      else throw new TypeError('points: expected ' + T.name);
+      if (pts.length % 4 !== 0) throw new RangeError('points must hold 4*m elements (x, y, z, ignored)');
+      if (o.bodies) throw new RangeError('field(): give either points or options.bodies, not both');
+      m = pts.length / 4;
+    } else if (!o.bodies) throw new TypeError('field(): points, or options.bodies = [first, count], required');
+    const out = { accel: o.accel === false ? null : new T(4 * m), phi: o.phi === false ? null : new T(m) };
+    addon.setParams(this._h, this.dt, this.G);
+    addon.fieldEval(this._h, pts, first, m, out.accel, out.phi);
+    return out;
+  }
+
   destroy() {
     if (this._h) { addon.destroy(this._h); this._h = null; this._frame = null; }
   }

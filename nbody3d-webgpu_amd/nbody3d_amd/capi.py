@@ -31,6 +31,7 @@ NB_RCCL_ID_BYTES = 128
 NB_RCCL_OVERLAP = 1
 NB_MULTI_PEER, NB_MULTI_RCCL, NB_MULTI_PEER_OVERLAP = 0, 1, 2
 NB_NOT_READY = 7
+NB_FIELD_AT_BODIES, NB_FIELD_F64, NB_FIELD_DEVICE = 1, 2, 4      # nb_field_request.flags (ABI 2.4)
 STATUS = {0: "NB_OK", 1: "NB_ERR_INVALID", 2: "NB_ERR_NO_DEVICE", 3: "NB_ERR_HIP",
           4: "NB_ERR_STATE", 5: "NB_ERR_NOMEM", 6: "NB_ERR_COMM", 7: "NB_NOT_READY"}
 ABI_VERSION = 2      # NB_ABI_VERSION (major)
@@ -69,6 +70,11 @@ class nb_step_timing(C.Structure):          # include/nbody3d_hip.h
                 ("span_ms", C.c_double), ("reduce_scatters", C.c_uint32), ("allgathers", C.c_uint32)]
 
 
+class nb_field_request(C.Structure):        # include/nbody3d_hip.h (ABI 2.4)
+    _fields_ = [("struct_size", C.c_uint32), ("m", C.c_uint32), ("flags", C.c_uint32), ("first_body", C.c_uint32),
+                ("points", C.c_void_p), ("accel", C.c_void_p), ("phi", C.c_void_p)]
+
+
 EXCHANGE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p)
 EXCHANGE_WAIT_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p)
 
@@ -82,7 +88,7 @@ SYMBOLS = ["nb_abi_version", "nb_device_count", "nb_create", "nb_destroy", "nb_u
            "nb_multi_diagnostics", "nb_multi_set_collective", "nb_multi_collective_info",
            "nb_rccl_unique_id", "nb_rccl_attach", "nb_rccl_detach", "nb_rccl_info",
            "nb_step_times", "nb_step_times2", "nb_integrate_pass", "nb_force_pass", "nb_frame_request", "nb_frame_acquire", "nb_shape_info", "nb_plan_query",
-           "nb_abi_minor"]
+           "nb_abi_minor", "nb_field_eval", "nb_multi_field_eval"]
 
 _lib = None
 
@@ -151,6 +157,9 @@ def load_library():
     L.nb_frame_request.argtypes = [vp]
     L.nb_frame_acquire.argtypes = [vp, C.c_int, C.POINTER(C.POINTER(C.c_float)), C.POINTER(C.POINTER(C.c_float)),
                                    C.POINTER(C.c_uint64)]
+    if L.nb_abi_minor() >= 4:       # an older library of the same major still loads; field() then raises
+        L.nb_field_eval.argtypes = [vp, C.POINTER(nb_field_request)]
+        L.nb_multi_field_eval.argtypes = [vp, C.POINTER(nb_field_request)]
     _lib = L
     return L
 
@@ -179,6 +188,42 @@ def rccl_unique_id():
 
 def _ptr(a):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
+
+
+def _field_request(n, dtype, points, bodies, accel, phi, f64):
+    """The nb_field_request of field(): (request, points array kept alive, accel array | None, phi array | None)."""
+    if load_library().nb_abi_minor() < 4:
+        raise NBodyError(1, "field(): the loaded library is ABI %d.%d; nb_field_eval needs 2.4" % (abi_version(), abi_minor()))
+    req = nb_field_request()
+    req.struct_size = C.sizeof(nb_field_request)
+    pts = None
+    # (both or neither of points / bodies: passed on as they are -- the engine's NB_ERR_INVALID names the field)
+    if bodies is not None:
+        first, count = int(bodies[0]), int(bodies[1])
+        if not (0 <= first < 2 ** 32 and 0 <= count < 2 ** 32):
+            raise ValueError("field(): bodies=(first, count) out of range")
+        req.flags |= NB_FIELD_AT_BODIES
+        req.first_body, req.m = first, count
+    if points is not None:
+        pts = np.asarray(points, dtype=dtype)
+        if pts.ndim == 1:
+            pts = pts.reshape(-1, 3 if pts.size % 4 else 4)
+        if pts.ndim != 2 or pts.shape[1] not in (3, 4):
+            raise ValueError("field(): points must have shape (m, 3) or (m, 4)")
+        if pts.shape[1] == 3:
+            pts = np.concatenate([pts, np.zeros((len(pts), 1), dtype)], axis=1)
+        pts = np.ascontiguousarray(pts)
+        if bodies is None:
+            req.m = len(pts)
+        req.points = _ptr(pts) if len(pts) else None
+    out_t = np.float64 if (f64 or dtype == np.float64) else np.float32
+    if f64:
+        req.flags |= NB_FIELD_F64
+    a = np.zeros((req.m, 4), out_t) if accel else None
+    f = np.zeros((req.m,), out_t) if phi else None
+    req.accel = _ptr(a) if a is not None and a.size else None
+    req.phi = _ptr(f) if f is not None and f.size else None
+    return req, pts, a, f
 
 
 SYMW_PLAN_WORDS = ("np", "nsb", "W", "total_hi", "total_lo", "n_hi", "H", "r_layer0", "t_layer0", "L", "zc")
@@ -503,6 +548,48 @@ class Simulation:
         self._check(self._L.nb_diagnostics(self._h, out))
         return out[0], out[1], np.array(out[2:5])
 
+    def field(self, points=None, *, bodies=None, accel=True, phi=True, f64=False):
+        """nb_field_eval: acceleration and potential of the system at ``points`` ((m, 3) or (m, 4); the fourth column is ignored)
+        or, with ``bodies=(first, count)``, at the current positions of those bodies, each leaving itself out of its sums.
+        Returns ``(accel (m, 4) | None, phi (m,) | None)`` in the handle's precision, float64 with ``f64=True`` (fp64 arithmetic on
+        the stored rows: the audit of the f32 sums).  Uses the handle's eps2 and the G of the last set_params(); the positions are
+        those behind every step issued so far; the simulation state is not touched."""
+        req, pts, a, f = _field_request(self.n, self.dtype, points, bodies, accel, phi, f64)
+        self._check(self._L.nb_field_eval(self._h, C.byref(req)))
+        return a, f
+
+    def field_device(self, points_ptr, m, accel_ptr, phi_ptr, *, bodies=None, f64=False):
+        """The device-pointer form (NB_FIELD_DEVICE): ``points_ptr`` / ``accel_ptr`` / ``phi_ptr`` are device addresses on the handle's
+        device (e.g. ``tensor.data_ptr()``; 0 or None for an output that is not wanted), element types as for field().  The work is
+        enqueued on the handle's stream and the call returns without waiting.  ``bodies=(first, count)`` selects the bodies' own
+        positions (``points_ptr`` must then be None and ``m`` is ignored)."""
+        if self._L.nb_abi_minor() < 4:
+            raise NBodyError(1, "field_device(): the loaded library is ABI %d.%d; nb_field_eval needs 2.4" % (abi_version(), abi_minor()))
+        req = nb_field_request()
+        req.struct_size = C.sizeof(nb_field_request)
+        req.flags = NB_FIELD_DEVICE | (NB_FIELD_F64 if f64 else 0)
+        if bodies is not None:
+            req.flags |= NB_FIELD_AT_BODIES
+            req.first_body, req.m = int(bodies[0]), int(bodies[1])
+        else:
+            req.m = int(m)
+        req.points = points_ptr or None
+        req.accel = accel_ptr or None
+        req.phi = phi_ptr or None
+        self._check(self._L.nb_field_eval(self._h, C.byref(req)))
+
+    def body_energies(self):
+        """Per-body energies as two float64 arrays ``(kinetic, potential)``: ``0.5 m_i |v_i|^2`` and ``m_i phi_i``, phi_i the potential
+        of all OTHER bodies at body i (one field(bodies=(0, n)) call plus read()).  A body is bound when the two add up to less
+        than 0; the potential energy of the system is HALF the sum of the second array (every pair appears in two of its
+        entries).  Time pairing: the stored velocities lag the positions by one step, so after a step the two
+        arrays belong to different times -- read right after init() they pair exactly."""
+        b, v, _ = self.read(accel=False)
+        _, p = self.field(bodies=(0, self.n), accel=False, phi=True)
+        m = b[:, 3].astype(np.float64)
+        v = v[:, :3].astype(np.float64)
+        return 0.5 * m * (v * v).sum(1), m * p.astype(np.float64)
+
     def energy_drift(self, steps, every):
         """Runs ``steps`` steps (parameters as set) and samples the total energy every ``every`` steps with the bookkeeping of
         SURVEY.md §8(c): the stored velocity lags the positions by one call (nbody3d.js:278-283), so KE(vel after call n) pairs
@@ -627,6 +714,13 @@ class MultiSimulation:
         out = (C.c_double * 5)()
         self._check(self._L.nb_multi_diagnostics(self._h, out))
         return out[0], out[1], np.array(out[2:5])
+
+    def field(self, points=None, *, bodies=None, accel=True, phi=True, f64=False):
+        """nb_multi_field_eval: Simulation.field() on the whole system (evaluated on shard 0, which holds every row);
+        ``bodies=(first, count)`` counts the caller's unpadded rows."""
+        req, pts, a, f = _field_request(self.n, self.dtype, points, bodies, accel, phi, f64)
+        self._check(self._L.nb_multi_field_eval(self._h, C.byref(req)))
+        return a, f
 
     @property
     def variant(self):
