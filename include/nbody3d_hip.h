@@ -43,7 +43,8 @@ extern "C" {
                              2.2 (round 4)  nb_step_times2, nb_plan_query, NB_FLAG_WHOLE_SWEEPS, nb_config.layer_budget_mib
                              2.3 (round 5)  nb_abi_minor, NB_MULTI_PEER_OVERLAP; nb_plan_info / nb_plan_query moved to nbody3d_hip_plan.h; force_variant 7 II LL 3 takes LL up to 64;
                                             nb_plan_query's table holds four words per wave instead of the W + 1 starts
-                             2.4 (round 6)  nb_field_eval, nb_multi_field_eval, nb_field_request, NB_FIELD_* */
+                             2.4 (round 6)  nb_field_eval, nb_multi_field_eval, nb_field_request, NB_FIELD_*; NB_FLAG_SINGLE_SWEEPS (an older
+                                            library ignores the bit: it runs every sweep on its own anyway) */
 
 typedef struct nb_sim nb_sim; /* opaque */
 
@@ -91,6 +92,10 @@ typedef enum nb_precision { NB_F32 = 0, NB_F64 = 1 } nb_precision;
 #define NB_FLAG_WHOLE_SWEEPS 256u /* tuning/A-B: the symmetric pass cuts its wave ranges at whole chunk-sweeps (64 rotation steps), as in
                                    ABI 2.0; by default systems with few sweeps per wave cut them in quarter sweeps (variant suffix
                                    "_u4"), which evens out the SIMDs' work (N = 16,384: the longest SIMD runs 4.25 sweeps instead of 5) */
+
+#define NB_FLAG_SINGLE_SWEEPS 512u /* tuning/A-B: the wave-granular symmetric pass (f32, one traveler per lane) runs every chunk-sweep on its
+                                    own, as before ABI 2.4's paired sweeps (two whole sweeps rotate together: 14 instead of 20 lane
+                                    moves per two traveler-steps).  Same plan, same layers; sums differ in the order of additions */
 
 /* nb_array: selector for nb_device_ptr */
 typedef enum nb_array { NB_BODIES = 0, NB_VEL = 1, NB_ACCEL = 2 } nb_array;

@@ -18,6 +18,9 @@ namespace nb {
 //     resident side, v_pk_mul + 3 v_pk_fma (negated) for the traveler side = 16 packed + 2 transcendental per FOUR
 //     interactions, + 10 v_mov_b32_dpp per traveler and step: 90 issue slots per 16 interactions against 128 --
 //     measured 74.7 % of the fp32 roofline for the bare loop (profiles/r03/ubench6_*.txt) against 60 %;
+//     (the wave-granular form with one traveler per lane runs whole sweeps in PAIRS, nb_force_symw_pairs below: two travelers packed,
+//     a traveler's sum ONE dword instead of two half-sums -- 7 moves per traveler-step instead of 10, the arithmetic unchanged:
+//     with 16 residents 302 issue slots per two traveler-steps against 308, 668 issue cycles per 32 interactions against 680)
 //   * coverage: the bodies form nsb SUPER-BLOCKS of S = 512*WS rows (one 512-row block per wave of a workgroup).
 //     Workgroup (g, q) keeps super-block g resident and sweeps segment q (of Q nearly equal ones) of g's chunk list: the chunks of the H =
 //     (nsb-1)/2 super-blocks that follow g on the ring (plus the antipodal one for g < nsb/2 when nsb is even) --
@@ -62,6 +65,25 @@ __device__ __forceinline__ float wave_rot1(float v)
 {
     const int iv = __builtin_bit_cast(int, v);      // old = src: every lane is written, no init move
     return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(iv, iv, 0x13C /* wave_ror:1 */, 0xF, 0xF, false));
+}
+
+// r of the lane before + s of this lane, in one v_add_f32_dpp: how a paired sweep's traveler sums move on (nb_force_symw_pairs)
+// (by hand: hipcc keeps wave_rot1(r) + s as a move and a packed add, and copies the halves together for it.  The compiler does not see
+// the DPP read of r here, so r must not be written by a vector instruction just in front: in the paired loop only this instruction
+// writes it, a whole trip earlier)
+__device__ __forceinline__ void wave_rot1_add(float& r, float s)
+{
+    asm("v_add_f32_dpp %0, %0, %1 wave_ror:1 row_mask:0xf bank_mask:0xf" : "+v"(r) : "v"(s));
+}
+
+// The packed operations of a paired sweep's form Y (nb_force_symw_pairs; cross == 0: form X, plain): the traveler operand with its halves swapped.
+__device__ __forceinline__ nb_f2 symw_swap(nb_f2 v) { return __builtin_shufflevector(v, v, 1, 0); }
+__device__ __forceinline__ nb_f2 symw_sub(int cross, nb_f2 t, nb_f2 res) { return (cross ? symw_swap(t) : t) - res; }
+__device__ __forceinline__ nb_f2 symw_mul(int cross, nb_f2 t, nb_f2 r) { return (cross ? symw_swap(t) : t) * r; }
+// acc - s * d per half (x_i - x_t = -(x_t - x_i), exactly); cross: half 0 of the sums belongs to the traveler the product's half 1 met
+__device__ __forceinline__ nb_f2 symw_fnma(int cross, nb_f2 s, nb_f2 d, nb_f2 acc)
+{
+    return cross ? __builtin_elementwise_fma(-symw_swap(s), symw_swap(d), acc) : __builtin_elementwise_fma(-s, d, acc);
 }
 
 // NG packed groups = 2*NG residents per lane (NG = 4: 128 VGPRs, 4 waves per SIMD; NG = 8: the rotation is amortised over
@@ -250,12 +272,12 @@ __device__ __forceinline__ SymWK symw_plan_words(uint32_t S, uint32_t cps, uint3
     return SymWK{(nsb + (zc ? 1u : 0u)) * S, nsb, W, total_hi, total_lo, n_hi, zc, ups, r_layer0, t_layer0};
 }
 
-template <int NG, int J>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NG >= 4 ? 2 : 4, NG > 4 ? 2 : (NG < 4 ? 8 : 4))))
-void nb_force_symw(const uint32_t* __restrict__ gtab, const float4* __restrict__ bodies, SymRow* __restrict__ partial, SymRow* __restrict__ spill,
-                   SYMW_PLAN_PARAMS, const float eps2_arg /* read by hand, with the table record: symw_record_and_tail */,
-                   uint32_t* __restrict__ queue, const uint32_t npieces, const uint32_t pieces_off)
+// (the body of the two kernels below: nb_force_symw<NG, J> runs every sweep on its own, nb_force_symw_pairs<NG> runs whole sweeps two at a time)
+template <int NG, int J, bool PAIR>
+__device__ __forceinline__ void symw_sweeps(const uint32_t* __restrict__ gtab, const float4* __restrict__ bodies, SymRow* __restrict__ partial, SymRow* __restrict__ spill,
+                                            SYMW_PLAN_PARAMS, uint32_t* __restrict__ queue, const uint32_t npieces, const uint32_t pieces_off)
 {
+    static_assert(!PAIR || J == 1, "paired sweeps: one traveler per lane and sweep");
     constexpr uint32_t S = 128u * NG;          // rows per super-block = one wave's residents
     constexpr int GW = NG < 4 ? NG : 4;        // packed groups evaluated stage-major together
     constexpr uint32_t CH = 64u * J;           // travelers per chunk
@@ -327,16 +349,35 @@ void nb_force_symw(const uint32_t* __restrict__ gtab, const float4* __restrict__
             while (u < ug_end) {
                 // the wave's steps [s0, s1) of sweep k
                 const uint32_t q0 = u & (ups - 1u);
+                // PAIRED SWEEPS.  Two consecutive WHOLE sweeps k, k + 1 that both keep traveler sums run together (greedy from wherever the
+                // wave stands: a function of the plan alone, so the sums are the same from run to run and whichever wave draws a piece).
+                // The lane holds traveler t0 of sweep k and t1 of sweep k + 1 PACKED -- {t0.x, t1.x} ... {t0.m, t1.m} -- and their sums as
+                // six dwords: a traveler's sum is ONE dword where the single form drags two half-sums (one per resident
+                // of a packed group) round the wave: 8 + 6 = 14 lane moves per step for two travelers instead of 2 x 10.  Per packed
+                // group of residents {a, b} two "crossed" forms, 16 packed + 2 v_rsq_f32 each as in the single form:
+                //   X: lanes (t0, a), (t1, b) -- every operand straight;
+                //   Y: lanes (t1, a), (t0, b) -- the TRAVELER operands read with swapped halves (op_sel: positions in the three subtractions,
+                //      the mass in si), the resident-side FMAs straight, the traveler-side FMAs with both product operands swapped.
+                // The residents are never swapped (a swapped loop-invariant operand is hoisted into a second copy: 64 registers).  Every
+                // per-pair product is the single form's, only the order of the additions differs.
+                // The traveler sums: one chain of 64 x 2 NG terms per traveler would take a large term early (a heavy resident) and then lose
+                // the low bits of every small one after it -- twice the single form's loss, whose other half-sum stays small (measured on
+                // the reference's galaxies, two 1e7 masses among 40,000 of order 1: 1.2e-5 of a row's acceleration against 7e-6).  So a
+                // step's 2 NG terms are summed from zero (sx, sy, sz) and join the running sum ONCE per step, in the instruction that moves
+                // the sum on: v_add_f32_dpp, r[lane] = r[lane - 1] + s[lane].  The sums therefore trail their travelers by one lane -- after
+                // the 64 steps lane l holds the sums of the traveler whose home is lane l + 1 -- and no running sum takes more than 64 terms.
+                bool pair = false;
+                if constexpr (PAIR) pair = q0 == 0u && ug_end - u >= 2u * ups && k + 1u < both_end;
                 uint32_t nun = ups - q0;
                 if (nun > ug_end - u) nun = ug_end - u;
                 const uint32_t s0 = q0 * ustep, s1 = s0 + nun * ustep;
-                u += nun;
+                u += pair ? 2u * ups : nun;
                 if (since >= kFlushSteps) {
                     flush_resident_sums<NG>(red[wi], lane, flushed, ax, ay, az);
                     flushed = true;
                     since = 0;
                 }
-                since += s1 - s0;
+                since += pair ? 128u : s1 - s0;
                 const bool sym = k < both_end, zsweep = k >= ring && sym;
                 const uint32_t d = k / CPS;                              // ring distance - 1 (ring sweeps)
                 uint32_t tb = g + 1 + d;
@@ -347,6 +388,79 @@ void nb_force_symw(const uint32_t* __restrict__ gtab, const float4* __restrict__
                 // (Tried in round 5 and dropped: requesting the travelers of sweep k + 1 before the rotation steps of sweep k -- the wait
                 // moved behind the loop, in front of the stores.  0.3-1 % SLOWER from N = 10,000 to 65,536 at one and two waves per SIMD,
                 // profiles/r05/ab_traveler_prefetch_head_vs_tree.txt: this round trip is not what the short lists wait for.)
+                if constexpr (PAIR) {
+                    if (pair) {
+                        // the second sweep of the pair (it may lie at the next ring distance, or be the first over Z's chunks)
+                        const bool zsweep1 = k >= ring;
+                        const uint32_t d1 = k / CPS;
+                        uint32_t tb1 = g + 1 + d1;
+                        if (tb1 >= pl.nsb) tb1 -= pl.nsb;
+                        const uint32_t tstart1 = zsweep1 ? pl.nsb * S + (k - ring) * CH : tb1 * S + (k % CPS) * CH;
+                        const uint32_t zrow1 = g * pl.zc + (k - ring);
+                        ++k;
+                        const float4 t0 = ld4(bodies + tstart + lane), t1 = ld4(bodies + tstart1 + lane);
+                        nb_f2 tx = nb_f2{t0.x, t1.x}, ty = nb_f2{t0.y, t1.y}, tz = nb_f2{t0.z, t1.z}, tm = nb_f2{t0.w, t1.w};
+                        float bx0 = 0, bx1 = 0, by0 = 0, by1 = 0, bz0 = 0, bz1 = 0;
+                        if (first_part) NB_STAMP(2);
+                        for (uint32_t st = 0; st < 64u; ++st) {
+                            nb_f2 sx = nb_f2{0, 0}, sy = nb_f2{0, 0}, sz = nb_f2{0, 0};   // what this step adds to the two travelers' sums
+#pragma unroll
+                            for (int c0g = 0; c0g < NG; c0g += GW) {         // stage-major over four groups, form X then form Y
+#pragma unroll
+                                for (int f = 0; f < 2; ++f) {
+                                    nb_f2 dx[GW], dy[GW], dz[GW], d2[GW], r[GW], si[GW], sj[GW];
+#pragma unroll
+                                    for (int c = 0; c < GW; ++c) dx[c] = symw_sub(f, tx, xi[c0g + c]);                       // :233
+#pragma unroll
+                                    for (int c = 0; c < GW; ++c) dy[c] = symw_sub(f, ty, yi[c0g + c]);
+#pragma unroll
+                                    for (int c = 0; c < GW; ++c) dz[c] = symw_sub(f, tz, zi[c0g + c]);
+#pragma unroll
+                                    for (int c = 0; c < GW; ++c) d2[c] = __builtin_elementwise_fma(dx[c], dx[c], e2);         // :234
+#pragma unroll
+                                    for (int c = 0; c < GW; ++c) d2[c] = __builtin_elementwise_fma(dy[c], dy[c], d2[c]);
+#pragma unroll
+                                    for (int c = 0; c < GW; ++c) d2[c] = __builtin_elementwise_fma(dz[c], dz[c], d2[c]);
+#pragma unroll
+                                    for (int c = 0; c < GW; ++c) r[c] = d2[c] * d2[c];                                       // :235
+#pragma unroll
+                                    for (int c = 0; c < GW; ++c) r[c] = r[c] * d2[c];
+#pragma unroll
+                                    for (int c = 0; c < GW; ++c) r[c] = nb_f2{nb_rsq(r[c].x), nb_rsq(r[c].y)};
+#pragma unroll
+                                    for (int c = 0; c < GW; ++c) si[c] = symw_mul(f, tm, r[c]);    // (G m_t) inv: resident side, :236
+#pragma unroll
+                                    for (int c = 0; c < GW; ++c) sj[c] = mi[c0g + c] * r[c];       // (G m_i) inv: traveler side
+#pragma unroll
+                                    for (int c = 0; c < GW; ++c) ax[c0g + c] = __builtin_elementwise_fma(si[c], dx[c], ax[c0g + c]);
+#pragma unroll
+                                    for (int c = 0; c < GW; ++c) ay[c0g + c] = __builtin_elementwise_fma(si[c], dy[c], ay[c0g + c]);
+#pragma unroll
+                                    for (int c = 0; c < GW; ++c) az[c0g + c] = __builtin_elementwise_fma(si[c], dz[c], az[c0g + c]);
+#pragma unroll
+                                    for (int c = 0; c < GW; ++c) sx = symw_fnma(f, sj[c], dx[c], sx);
+#pragma unroll
+                                    for (int c = 0; c < GW; ++c) sy = symw_fnma(f, sj[c], dy[c], sy);
+#pragma unroll
+                                    for (int c = 0; c < GW; ++c) sz = symw_fnma(f, sj[c], dz[c], sz);
+                                }
+                            }
+                            tx = nb_f2{wave_rot1(tx.x), wave_rot1(tx.y)}; ty = nb_f2{wave_rot1(ty.x), wave_rot1(ty.y)};
+                            tz = nb_f2{wave_rot1(tz.x), wave_rot1(tz.y)}; tm = nb_f2{wave_rot1(tm.x), wave_rot1(tm.y)};
+                            wave_rot1_add(bx0, sx.x); wave_rot1_add(bx1, sx.y); wave_rot1_add(by0, sy.x); wave_rot1_add(by1, sy.y);
+                            wave_rot1_add(bz0, sz.x); wave_rot1_add(bz1, sz.y);
+                            __builtin_amdgcn_sched_barrier(0);               // the loop counter's three 32-bit instructions stay together behind the 64-bit ones
+                        }
+                        if (first_part) { NB_STAMP_LIGHT(3); first_part = false; }
+                        // after 64 steps the travelers are back in their home lanes, their sums one lane behind: each to its own sweep's rows
+                        const uint32_t home = ((uint32_t)lane + 1u) & 63u;
+                        SymRow* out0 = (zsweep ? spill + (size_t)zrow * CH : partial + (size_t)(pl.t_layer0 + d) * pl.np + tstart) + home;
+                        SymRow* out1 = (zsweep1 ? spill + (size_t)zrow1 * CH : partial + (size_t)(pl.t_layer0 + d1) * pl.np + tstart1) + home;
+                        *out0 = SymRow{bx0, by0, bz0};
+                        *out1 = SymRow{bx1, by1, bz1};
+                        continue;
+                    }
+                }
                 float tx[J], ty[J], tz[J], tm[J];
                 nb_f2 bx[J], by[J], bz[J];
                 const uint32_t src = ((uint32_t)lane - s0) & 63u;        // the traveler this lane holds after s0 rotation steps
@@ -521,6 +635,25 @@ void nb_force_symw(const uint32_t* __restrict__ gtab, const float4* __restrict__
         }
     }
     NB_STAMP(4);
+}
+
+#define SYMW_KERNEL_PARAMS const uint32_t* __restrict__ gtab, const float4* __restrict__ bodies, SymRow* __restrict__ partial, SymRow* __restrict__ spill, \
+                           SYMW_PLAN_PARAMS, const float eps2_arg /* read by hand, with the table record: symw_record_and_tail */,                       \
+                           uint32_t* __restrict__ queue, const uint32_t npieces, const uint32_t pieces_off
+#define SYMW_KERNEL_ARGS gtab, bodies, partial, spill, W_, ups_, nsb_, zc_, r_layer0_, t_layer0_, queue, npieces, pieces_off
+template <int NG, int J>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NG >= 4 ? 2 : 4, NG > 4 ? 2 : (NG < 4 ? 8 : 4))))
+void nb_force_symw(SYMW_KERNEL_PARAMS)
+{
+    symw_sweeps<NG, J, false>(SYMW_KERNEL_ARGS);
+}
+// The same plan, the same table, the same layers; whole sweeps that keep traveler sums run two at a time (see `PAIR` above).  A kernel of its
+// own and not a third loop form inside nb_force_symw: NB_FLAG_SINGLE_SWEEPS launches the one above on the same plan (the A/B arm).
+template <int NG>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, NG > 4 ? 2 : 4)))
+void nb_force_symw_pairs(SYMW_KERNEL_PARAMS)
+{
+    symw_sweeps<NG, 1, true>(SYMW_KERNEL_ARGS);
 }
 
 // The fp64 form (BASELINE config 5): non-packed, IPL residents per lane, one traveler per lane.  Per unordered pair: 3 adds,

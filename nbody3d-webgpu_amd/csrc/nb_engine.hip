@@ -133,7 +133,8 @@ const void* rank_kernel_of(bool f64, int ipl)
 }
 
 // The kernel a shape launches (nullptr: no such instantiation).
-const void* kernel_of(bool f64, const Shape& sh)
+// single_sweeps (NB_FLAG_SINGLE_SWEEPS): the wave-granular symmetric pass with one traveler per lane runs every sweep on its own.
+const void* kernel_of(bool f64, const Shape& sh, bool single_sweeps = false)
 {
     switch (sh.kind) {
         case kScalar: return f64 ? scalar_kernel<double>(sh.ipl, sh.ls) : scalar_kernel<float>(sh.ipl, sh.ls);
@@ -149,8 +150,10 @@ const void* kernel_of(bool f64, const Shape& sh)
             if (f64) return sh.ipl == 8 && sh.x == 3 ? (const void*)&nb::nb_force_symw64<8> : nullptr;      // 8 residents, 1 traveler per lane
             if (sh.x == 4) return sh.ipl == 8 ? (const void*)&nb::nb_force_sym<4, 4, 2> : nullptr;
             if (sh.ipl == 4) return sh.x == 3 ? (const void*)&nb::nb_force_symw<2, 1> : nullptr;      // (an arm: whole sweeps round finer with 4 residents)
-            if (sh.ipl == 8) return sh.x == 1 ? (const void*)&nb::nb_force_symw<4, 2> : sh.x == 3 ? (const void*)&nb::nb_force_symw<4, 1> : nullptr;
-            if (sh.ipl == 16) return sh.x == 1 ? (const void*)&nb::nb_force_symw<8, 2> : sh.x == 3 ? (const void*)&nb::nb_force_symw<8, 1> : nullptr;
+            if (sh.ipl == 8 && sh.x == 3) return single_sweeps ? (const void*)&nb::nb_force_symw<4, 1> : (const void*)&nb::nb_force_symw_pairs<4>;
+            if (sh.ipl == 16 && sh.x == 3) return single_sweeps ? (const void*)&nb::nb_force_symw<8, 1> : (const void*)&nb::nb_force_symw_pairs<8>;
+            if (sh.ipl == 8) return sh.x == 1 ? (const void*)&nb::nb_force_symw<4, 2> : nullptr;
+            if (sh.ipl == 16) return sh.x == 1 ? (const void*)&nb::nb_force_symw<8, 2> : nullptr;
             return nullptr;
         case kJpk:
             if (f64 || sh.ipl != 1 || sh.ls != 1) return nullptr;
@@ -287,7 +290,7 @@ void launch_force(nb_sim* s, int part = 0, hipEvent_t t0 = nullptr, hipEvent_t t
         } else {
             float e2 = (float)s->eps2;
             void* args[] = {&tab, &b, &p, &sp, &pl.W, &pl.ups, &pl.nsb, &pl.zc, &pl.r_layer0, &pl.t_layer0, &e2, &queue, &npieces, &pieces_off};
-            launch_kernel(kernel_of(false, sh), dim3(ceil_div(pl.W, 4u)), dim3(256), args, s->stream, t0, t1);
+            launch_kernel(kernel_of(false, sh, s->single_sweeps), dim3(ceil_div(pl.W, 4u)), dim3(256), args, s->stream, t0, t1);
         }
         return;
     }
@@ -711,6 +714,7 @@ int nb_create(const nb_config* cfg_in, nb_sim** out)
         }
     }
     if (!kernel_of(s->f64, shape_of(s))) return bail(NB_ERR_INVALID, "nb_create: no kernel for shape " + s->variant);
+    s->single_sweeps = (cfg.flags & NB_FLAG_SINGLE_SWEEPS) != 0;
 
     const size_t row = 4 * s->esz;
     if (cfg.ext_bodies) { s->bodies[0] = cfg.ext_bodies; s->own_bodies = false; }

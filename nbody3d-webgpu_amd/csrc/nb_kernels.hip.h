@@ -10,7 +10,8 @@
 //   one kernel    nb_step_fused  (reads bodies_in, writes bodies_out: ping-pong buffers)
 //
 //   K1 forms:   nb_force_symw<NG,J>      f32, SYMMETRIC pass (default from N ~ 13,000): every unordered pair once, both
-//               nb_force_symw64<8>       accelerations; residents in registers, travelers rotate through the wave by DPP
+//               nb_force_symw_pairs<NG>  accelerations; residents in registers, travelers rotate through the wave by DPP
+//               nb_force_symw64<8>       (_pairs: one traveler per lane and sweep, whole sweeps two at a time -- the default f32 kernel)
 //               nb_force_sym<WS,NG,J>    (f64 form; workgroup form with LDS-combined traveler sums: A/B arm)
 //               nb_force_pk_sgpr<NG,WS>  f32, packed math, ordered pairs, j broadcast from SGPRs (shards without the native exchange)
 //               nb_force_pk<NG,LS,TL>    f32, packed math, j-tile staged in LDS

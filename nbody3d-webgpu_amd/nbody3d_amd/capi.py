@@ -27,6 +27,7 @@ NB_FLAG_JPK_FENCED = 32
 NB_FLAG_NO_SYM = 64
 NB_FLAG_SYM_SHARD = 128
 NB_FLAG_WHOLE_SWEEPS = 256
+NB_FLAG_SINGLE_SWEEPS = 512
 NB_RCCL_ID_BYTES = 128
 NB_RCCL_OVERLAP = 1
 NB_MULTI_PEER, NB_MULTI_RCCL, NB_MULTI_PEER_OVERLAP = 0, 1, 2
