@@ -44,7 +44,10 @@ extern "C" {
                              2.3 (round 5)  nb_abi_minor, NB_MULTI_PEER_OVERLAP; nb_plan_info / nb_plan_query moved to nbody3d_hip_plan.h; force_variant 7 II LL 3 takes LL up to 64;
                                             nb_plan_query's table holds four words per wave instead of the W + 1 starts
                              2.4 (round 6)  nb_field_eval, nb_multi_field_eval, nb_field_request, NB_FIELD_*; NB_FLAG_SINGLE_SWEEPS (an older
-                                            library ignores the bit: it runs every sweep on its own anyway) */
+                                            library ignores the bit: it runs every sweep on its own anyway)
+                             2.4 (round 7)  additions WITHIN 2.4, the minor stays 4: nb_config.integrator (in the place of reserved[0]; an older
+                                            library ignores it), NB_INT_*, nb_download_jerk, nb_upload_derivs, NB_JERK.  A client detects them by
+                                            the presence of the symbol nb_download_jerk (dlsym), not by the minor */
 
 typedef struct nb_sim nb_sim; /* opaque */
 
@@ -98,7 +101,10 @@ typedef enum nb_precision { NB_F32 = 0, NB_F64 = 1 } nb_precision;
                                     moves per two traveler-steps).  Same plan, same layers; sums differ in the order of additions */
 
 /* nb_array: selector for nb_device_ptr */
-typedef enum nb_array { NB_BODIES = 0, NB_VEL = 1, NB_ACCEL = 2 } nb_array;
+typedef enum nb_array { NB_BODIES = 0, NB_VEL = 1, NB_ACCEL = 2, NB_JERK = 3 /* Hermite handles only */ } nb_array;
+
+/* nb_config.integrator (no reference analogue: the reference has the one lagged leapfrog, nbody3d.js:274-290) */
+typedef enum nb_integrator { NB_INT_LEAPFROG = 0, NB_INT_HERMITE4 = 1 } nb_integrator;
 
 /*
  * Engine configuration.  Replaces: buffer creation (nbody3d.js:179-204), the
@@ -155,7 +161,10 @@ typedef struct nb_config {
                                device's memory, at most 96 GiB (N up to ~4 M on an MI355X).  nb_create also checks
                                the memory that is FREE: a whole-system handle whose layers would not fit it falls back
                                the same way (a rank-form shard fails instead: its peers expect the reduce-scatter) */
-    uint32_t reserved[4];
+    uint32_t integrator;    /* nb_integrator; 0 -> NB_INT_LEAPFROG, the reference's scheme.  NB_INT_HERMITE4: see "Hermite handles"
+                               below (no reference analogue).  Takes the place of reserved[0]: sizeof(nb_config) is unchanged, and a
+                               struct_size that ends in front of this field reads it as 0 */
+    uint32_t reserved[3];
 } nb_config;
 
 /* Library / ABI version; callable with no device. */
@@ -356,6 +365,48 @@ int nb_shape_info(nb_sim *s, uint32_t *jsplit, uint32_t *j_per_split, uint32_t *
 /* Planner introspection (the launch plan nb_create WOULD build for a configuration, with the symmetric pass's kernel-internal
  * plan words and tables: for reports, sizing runs and the host-side planner tests) lives in nbody3d_hip_plan.h -- nothing a host
  * that replaces nbody3d.js:179-204,470-490 needs. */
+
+/* ---- Hermite handles (nb_config.integrator = NB_INT_HERMITE4; no reference analogue) --------------------
+ * The 4th-order Hermite predictor-corrector of Makino & Aarseth (1992) with one shared step dt, on the force and its time
+ * derivative, the jerk:
+ *     a_i = sum_j G m_j dr / rho^3          j_i = sum_j G m_j [ dv / rho^3 - 3 (dr.dv) dr / rho^5 ]
+ *     dr = x_j - x_i,  dv = v_j - v_i,  rho^2 = |dr|^2 + eps2
+ *   - State: bodies = (x, y, z, m) and vel = v, BOTH AT THE SAME INSTANT t (no lag: nb_diagnostics and nb_field_eval describe one
+ *     instant).  accel = a(t) and jerk = j(t) are DERIVED quantities.
+ *   - The derived arrays go stale with: nb_upload (its accel argument is ignored on a Hermite handle), nb_device_ptr(NB_BODIES) or
+ *     nb_device_ptr(NB_VEL) (the caller may write through them), a change of G since they were evaluated.  They are refreshed by
+ *     the next nb_step, nb_download with accel != NULL, nb_download_jerk, nb_device_ptr(NB_ACCEL / NB_JERK): each first evaluates
+ *     them on the state as it stands with one force+jerk pass on the handle's stream (needs nb_set_params: G).
+ *   - One step, h = dt:
+ *         xp = x + h v + h^2/2 a + h^3/6 j          vp = v + h a + h^2/2 j
+ *         (a1, j1) = FJ(xp, vp)                     -- the only O(N^2) pass of the step
+ *         v1 = v + h/2 (a + a1) + h^2/12 (j - j1)
+ *         x1 = x + h/2 (v + v1) + h^2/12 (a - a1)
+ *         state <- (x1, v1, a1, j1)
+ *     The mass lane and vel.w are carried unchanged; accel.w = jerk.w = 0.  Note that the (a, j) a step leaves behind were
+ *     evaluated at the PREDICTED state: a restore that recomputes them from (x, v) continues within the scheme's accuracy but not
+ *     bit-identically -- nb_upload_derivs is the bit-exact checkpoint path.
+ *   - dt <= 0 is a no-op, as for leapfrog; dt may change between steps; G may change (the derivatives are then re-evaluated).
+ *   - Deterministic: fixed summation order, no atomics; the same state and dt give the same bits; nb_step(k) is bit-identical to
+ *     k x nb_step(1) (plain launches; Hermite steps are not graph-captured).
+ *   - Restrictions, each NB_ERR_INVALID from nb_create before any device call, the message naming the field: an unknown integrator
+ *     value; integrator = 1 with shard_count != 0, with ext_bodies, with force_variant != 0 or with jsplit != 0.  nb_multi_create
+ *     and nb_plan_query with integrator != 0: NB_ERR_INVALID.  nb_set_exchange, nb_set_exchange_overlapped, nb_rccl_attach and
+ *     nb_integrate_pass on a Hermite handle: NB_ERR_STATE.  The tuning flags are ignored; ext_stream works.
+ *   - nb_diagnostics, nb_field_eval, nb_frame_request / nb_frame_acquire work unchanged (they read bodies and vel only).
+ *     nb_force_pass runs the force+jerk pass (kernel + reduce) into scratch: state and derivatives untouched.  nb_enable_timing /
+ *     nb_step_times2: force_ms = the force+jerk kernel and its reduce, integrate_ms = predictor + corrector.  nb_variant_name starts
+ *     with "hermite4_"; nb_shape_info reports the j-chunks of the force+jerk pass and the bodies per chunk.
+ *   - Leapfrog handles: nb_download_jerk, nb_upload_derivs and nb_device_ptr(NB_JERK) return NB_ERR_STATE. */
+
+/* download_jerk (no reference analogue): fills 4*n elements (jx, jy, jz, 0), element type of the handle's precision; blocks. */
+int nb_download_jerk(nb_sim *s, void *jerk);
+
+/* upload_derivs (no reference analogue): the checkpoint restore of a Hermite handle.  Both pointers are required, 4*n elements
+ * each; valid after nb_upload.  Marks the handle's derivatives as current (for the G in force, or the G of the next nb_set_params
+ * when none was made yet), so the next step continues bit-identically from a (bodies, vel, accel, jerk) read with nb_download +
+ * nb_download_jerk. */
+int nb_upload_derivs(nb_sim *s, const void *accel, const void *jerk);
 
 /* ---- viewer frame feed ------------------------------------------------
  * The reference's render pass reads bodyBuffer and velBuffer in place every frame

@@ -200,6 +200,7 @@ int nb_rccl_attach(nb_sim* s, const void* id_in, int nranks, int rank, uint32_t 
     if (!id_in || nranks < 1 || rank < 0 || rank >= nranks) return fail(s, NB_ERR_INVALID, "nb_rccl_attach: bad argument");
     if (s->rccl) return fail(s, NB_ERR_STATE, "nb_rccl_attach: a communicator is already attached");
     if (s->xfn) return fail(s, NB_ERR_STATE, "nb_rccl_attach: an exchange hook is set (clear it with nb_set_exchange(s, NULL, NULL))");
+    if (s->hermite) return fail(s, NB_ERR_STATE, "nb_rccl_attach: a Hermite handle is a whole system on one device: nothing to exchange");
     if (s->fused) return fail(s, NB_ERR_STATE, "nb_rccl_attach: a fused whole-system handle has nothing to exchange (create the shard handle with shard_count set)");
     // equal row blocks, as ncclAllGather wants them
     if ((uint64_t)s->sc * (uint32_t)nranks != s->n || s->sb != (uint32_t)rank * s->sc)
@@ -331,12 +332,13 @@ int nb_multi_create(const nb_config* cfg_in, uint32_t n_shards, const int32_t* d
 {
     if (out) *out = nullptr;
     if (!cfg_in || !out || n_shards == 0) return mfail(nullptr, NB_ERR_INVALID, "nb_multi_create: bad argument");
-    if (cfg_in->struct_size < offsetof(nb_config, reserved))
+    if (cfg_in->struct_size < offsetof(nb_config, integrator))
         return mfail(nullptr, NB_ERR_INVALID, "nb_multi_create: struct_size too small");
     nb_config cfg;
     memset(&cfg, 0, sizeof cfg);
     memcpy(&cfg, cfg_in, cfg_in->struct_size < sizeof cfg ? cfg_in->struct_size : sizeof cfg);
     if (cfg.n == 0) return mfail(nullptr, NB_ERR_INVALID, "nb_multi_create: n must be >= 1");
+    if (cfg.integrator != NB_INT_LEAPFROG) return mfail(nullptr, NB_ERR_INVALID, "nb_multi_create: integrator must be NB_INT_LEAPFROG (a Hermite handle is a whole system on one device)");
     if (cfg.n > (1u << 30) - 1024u * n_shards) return mfail(nullptr, NB_ERR_INVALID, "nb_multi_create: n too large (the padded system must stay <= 2^30 rows)");
     if (cfg.shard_count || cfg.ext_bodies || cfg.ext_stream)
         return mfail(nullptr, NB_ERR_INVALID, "nb_multi_create: shard/ext_* fields are managed by the multi handle");

@@ -524,6 +524,91 @@ void free_frames(nb_sim* s)
     s->frame_next = 0; s->frame_latest = -1;
 }
 
+// ---- NB_INT_HERMITE4 ---------------------------------------------------------------------------
+constexpr uint32_t kFjWavesPerSimd = 8;        // workgroups a force+jerk launch is cut into, per SIMD, when N x N gives that many
+constexpr uint32_t kFjMinChunk = 2048;         // fewest bodies of a j-chunk once there is more than one (two flushes of the first-level sums)
+constexpr uint32_t kFjMaxChunk = 1u << 20;     // most bodies of one j-chunk (bounds the second-level sums of nb_fj_pk)
+
+// The j-chunks of a handle's force+jerk pass: enough workgroups for kFjWavesPerSimd per SIMD, in chunks of whole 256-row tiles and
+// at least kFjMinChunk bodies; the partial sums (2 x chunks x n rows) stay below ~ 2 x (workgroups wanted x rows per workgroup + n) rows.
+void fj_shape(uint32_t n, bool f64, int n_cu, uint32_t* chunks, uint32_t* per)
+{
+    const uint32_t rows = f64 ? nb::kFjRows64 : nb::kFjRows;
+    const uint32_t want = kFjWavesPerSimd * (uint32_t)n_cu;
+    uint32_t c = std::min(ceil_div(want, ceil_div(n, rows)), n / kFjMinChunk);
+    c = std::max(std::max(c, 1u), ceil_div(n, kFjMaxChunk));
+    *per = ceil_div(ceil_div(n, c), (uint32_t)nb::kTile) * nb::kTile;
+    *chunks = ceil_div(n, *per);
+}
+
+// One force+jerk pass on the state (pos, vel): the O(N^2) kernel into fj_part, then the fp64 reduce into (acc_out, jerk_out).
+// Errors are picked up by the caller's hipGetLastError.
+void launch_fj(nb_sim* s, const void* pos, const void* vel, void* acc_out, void* jerk_out)
+{
+    uint32_t n = s->n, chunks = s->fj_chunks, per = s->fj_per;
+    void* pa = s->fj_part;
+    void* pj = (char*)s->fj_part + (size_t)4 * (s->f64 ? 8 : 4) * chunks * n;
+    double G = s->G;
+    void* rargs[] = {&pa, &pj, &n, &chunks, &G, &acc_out, &jerk_out};
+    if (s->f64) {
+        double e2 = s->eps2;
+        void* args[] = {&pos, &vel, &pa, &pj, &n, &per, &e2};
+        (void)hipLaunchKernel((const void*)&nb::nb_fj64<double>, dim3(ceil_div(n, nb::kFjRows64), chunks), dim3(nb::kBlock), args, 0, s->stream);
+        (void)hipLaunchKernel((const void*)&nb::nb_fj_reduce<double, double>, dim3(ceil_div(n, nb::kBlock)), dim3(nb::kBlock), rargs, 0, s->stream);
+    } else {
+        float e2 = (float)s->eps2;
+        const void* zr = s->zero_row;
+        void* args[] = {&pos, &vel, &pa, &pj, &n, &per, &e2, &zr};
+        (void)hipLaunchKernel((const void*)&nb::nb_fj_pk<nb::kFjNG>, dim3(ceil_div(n, nb::kFjRows), chunks), dim3(nb::kBlock), args, 0, s->stream);
+        (void)hipLaunchKernel((const void*)&nb::nb_fj_reduce<float, float>, dim3(ceil_div(n, nb::kBlock)), dim3(nb::kBlock), rargs, 0, s->stream);
+    }
+}
+
+// Makes acc / jerk the derivatives of (bodies, vel) for the G in force (a no-op while they are current).
+int ensure_derivs(nb_sim* s, const char* who)
+{
+    if (!s->params_set) return fail(s, NB_ERR_STATE, std::string(who) + ": nb_set_params has not been called (G)");
+    if (s->derivs_ok && s->derivs_any_G) { s->derivs_any_G = false; s->derivs_G = s->G; }
+    if (s->derivs_ok && s->derivs_G == s->G) return NB_OK;
+    launch_fj(s, s->bodies[0], s->vel, s->acc, s->jerk);
+    NB_HIP(s, hipGetLastError());
+    s->derivs_ok = true; s->derivs_any_G = false; s->derivs_G = s->G;
+    return NB_OK;
+}
+
+template <typename T>
+void launch_hermite_oc(nb_sim* s, bool correct)
+{
+    using V4 = typename nb::vec4<T>::type;
+    V4 *x = (V4*)s->bodies[0], *v = (V4*)s->vel, *a = (V4*)s->acc, *j = (V4*)s->jerk, *hx = (V4*)s->hx, *hv = (V4*)s->hv;
+    uint32_t n = s->n;
+    double h = s->dt;
+    void* args[] = {&x, &v, &a, &j, &hx, &hv, &n, &h};      // predict: (x, v, a, j) -> (xp, vp); correct: (x, v, a, j) <- with (a1, j1)
+    const void* fn = correct ? (const void*)&nb::nb_hermite_correct<T> : (const void*)&nb::nb_hermite_predict<T>;
+    (void)hipLaunchKernel(fn, dim3(ceil_div(n, nb::kBlock)), dim3(nb::kBlock), args, 0, s->stream);
+}
+
+// nb_step of a Hermite handle: plain launches, nsteps x (predict, force+jerk at the predicted state, correct).
+// Timed steps record e[6] predict e[0] force+jerk, reduce e[1] correct e[2] (collect_times).
+int hermite_step(nb_sim* s, uint32_t nsteps)
+{
+    if (int rc = ensure_derivs(s, "nb_step")) return rc;
+    for (uint32_t k = 0; k < nsteps; ++k) {
+        nb_events ev;
+        const bool rec = s->timing && get_events(s, &ev) == 0;
+        if (rec) NB_HIP(s, hipEventRecord(ev.e[6], s->stream));
+        if (s->f64) launch_hermite_oc<double>(s, false); else launch_hermite_oc<float>(s, false);
+        if (rec) NB_HIP(s, hipEventRecord(ev.e[0], s->stream));
+        launch_fj(s, s->hx, s->hv, s->hx, s->hv);         // (a1, j1) over the predicted state: the reduce runs after every read of it
+        if (rec) NB_HIP(s, hipEventRecord(ev.e[1], s->stream));
+        if (s->f64) launch_hermite_oc<double>(s, true); else launch_hermite_oc<float>(s, true);
+        if (rec) { NB_HIP(s, hipEventRecord(ev.e[2], s->stream)); s->pending.push_back(ev); }
+        NB_HIP(s, hipGetLastError());
+        ++s->steps_done;
+    }
+    return NB_OK;
+}
+
 }  // namespace
 
 namespace nbi {
@@ -628,7 +713,7 @@ int nb_device_count(void)
 static int read_config(const nb_config* cfg_in, const char* who, nb_config* cfg, uint32_t* sb_out, uint32_t* sc_out, double* eps2_out)
 {
     const std::string w(who);
-    if (cfg_in->struct_size < offsetof(nb_config, reserved))
+    if (cfg_in->struct_size < offsetof(nb_config, integrator))
         return fail(nullptr, NB_ERR_INVALID, w + ": struct_size too small (set it to sizeof(nb_config))");
     memset(cfg, 0, sizeof *cfg);
     memcpy(cfg, cfg_in, cfg_in->struct_size < sizeof *cfg ? cfg_in->struct_size : sizeof *cfg);
@@ -643,6 +728,14 @@ static int read_config(const nb_config* cfg_in, const char* who, nb_config* cfg,
     uint32_t sb = cfg->shard_begin, sc = cfg->shard_count;
     if (sc == 0) { sb = 0; sc = cfg->n; }
     if ((uint64_t)sb + sc > cfg->n) return fail(nullptr, NB_ERR_INVALID, w + ": shard exceeds n");
+    if (cfg->integrator > NB_INT_HERMITE4) return fail(nullptr, NB_ERR_INVALID, w + ": unknown integrator");
+    if (cfg->integrator == NB_INT_HERMITE4) {
+        // a Hermite handle is a whole system on one device with the one force+jerk kernel of its precision
+        if (cfg->shard_count != 0) return fail(nullptr, NB_ERR_INVALID, w + ": integrator = NB_INT_HERMITE4 needs shard_count == 0 (whole system)");
+        if (cfg->ext_bodies) return fail(nullptr, NB_ERR_INVALID, w + ": integrator = NB_INT_HERMITE4 does not take ext_bodies");
+        if (cfg->force_variant != 0) return fail(nullptr, NB_ERR_INVALID, w + ": integrator = NB_INT_HERMITE4 does not take a force_variant");
+        if (cfg->jsplit != 0) return fail(nullptr, NB_ERR_INVALID, w + ": integrator = NB_INT_HERMITE4 does not take a jsplit");
+    }
     *sb_out = sb; *sc_out = sc; *eps2_out = eps2;
     return NB_OK;
 }
@@ -694,6 +787,25 @@ int nb_create(const nb_config* cfg_in, nb_sim** out)
     const int n_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
     s->n_cu = n_cu;
     const double clock_hz = prop.clockRate > 0 ? 1e3 * prop.clockRate : 2.4e9;     // clockRate is in kHz
+    if (cfg.integrator == NB_INT_HERMITE4) {
+        // plain unpadded arrays, no planner: (x, v) at one instant, the derived (a, j), the predicted state and the bounded partials
+        s->hermite = true;
+        fj_shape(s->n, s->f64, n_cu, &s->fj_chunks, &s->fj_per);
+        s->jsplit = s->fj_chunks; s->j_per_split = s->fj_per;      // what nb_shape_info reports
+        s->variant = std::string("hermite4_") + (s->f64 ? "f64" : "f32pk") + "_c" + std::to_string(s->fj_chunks) + "_j" + std::to_string(s->fj_per);
+        const size_t hrow = 4 * s->esz;
+        NB_HIPC(hipMalloc(&s->bodies[0], hrow * s->n));
+        s->own_bodies = true;
+        for (void** p : {&s->vel, &s->acc, &s->jerk, &s->hx, &s->hv}) NB_HIPC(hipMalloc(p, hrow * s->n));
+        NB_HIPC(hipMalloc(&s->fj_part, (size_t)2 * hrow * s->fj_chunks * s->n));
+        NB_HIPC(hipMalloc(&s->zero_row, 64));
+        NB_HIPC(hipMemsetAsync(s->zero_row, 0, 64, s->stream));
+        s->diag_chunk = nb::kTile * std::min(16u, std::max(1u, s->n / 16384u));
+        s->diag_blocks = ceil_div(s->sc, nb::kDiagRows) * ceil_div(s->n, s->diag_chunk);
+        NB_HIPC(hipMalloc((void**)&s->diag, sizeof(double) * 5 * s->diag_blocks));
+        *out = s;
+        return NB_OK;
+    }
     plan_handle(s, cfg, n_cu, clock_hz, (double)prop.totalGlobalMem);
     if (s->sym && (!s->sym_rank || s->sym_local) && !cfg.force_variant) {
         // The planner budgets the symmetric pass's layers against the device's TOTAL memory; what is FREE right now may be less
@@ -810,6 +922,7 @@ void nb_destroy(nb_sim* s)
     if (s->sym_spill) (void)hipFree(s->sym_spill);
     if (s->sym_queue) (void)hipFree(s->sym_queue);
     if (s->sym_A) (void)hipFree(s->sym_A);
+    for (void* p : {s->jerk, s->hx, s->hv, s->fj_part}) if (p) (void)hipFree(p);
     if (s->diag) (void)hipFree(s->diag);
     for (auto* b : {&s->fld_pts, &s->fld_acc, &s->fld_phi, &s->fld_part}) if (b->p) (void)hipFree(b->p);
     if (s->zero_row) (void)hipFree(s->zero_row);
@@ -831,6 +944,11 @@ int nb_upload(nb_sim* s, const void* bodies, const void* vel, const void* accel)
     NB_HIP(s, hipStreamSynchronize(s->stream));
     NB_HIP(s, hipMemcpy(s->bodies[s->cur], bodies, row * s->n, hipMemcpyHostToDevice));
     NB_HIP(s, hipMemcpy(s->vel, (const char*)vel + row * s->sb, row * s->sc, hipMemcpyHostToDevice));
+    if (s->hermite) {          // accel is a derived array here: ignored, re-evaluated with the jerk when next needed
+        s->uploaded = true;
+        s->derivs_ok = false;
+        return NB_OK;
+    }
     if (accel) NB_HIP(s, hipMemcpy(s->acc, (const char*)accel + row * s->sb, row * s->sc, hipMemcpyHostToDevice));
     else {
         // WebGPU zero-init, nbody3d.js:195-199.  On the ENGINE stream: a hipMemset on the null stream is
@@ -860,6 +978,7 @@ int nb_step(nb_sim* s, uint32_t nsteps)
     if (!s->params_set) return fail(s, NB_ERR_STATE, "nb_step: nb_set_params has not been called");
     if (!(s->dt > 0.0)) return NB_OK;   // `if (dt > 0)` gate, nbody3d.js:474
     NB_HIP(s, hipSetDevice(s->device));
+    if (s->hermite) return hermite_step(s, nsteps);
     const bool exchange = s->xfn || s->rccl;
     ensure_pairs(s);      // the j-packed step's position copy, if something outside the step rewrote the positions or G
     if (gm_active(s) && !s->gm_ok) { if (int rc = finish_gather(s)) return rc; }
@@ -971,6 +1090,7 @@ int nb_download(nb_sim* s, void* bodies, void* vel, void* accel)
     if (!s->uploaded) return fail(s, NB_ERR_STATE, "nb_download: nothing uploaded yet");
     NB_HIP(s, hipSetDevice(s->device));
     if (int rc = finish_gather(s)) return rc;
+    if (s->hermite && accel) { if (int rc = ensure_derivs(s, "nb_download")) return rc; }
     NB_HIP(s, hipStreamSynchronize(s->stream));
     const size_t row = 4 * s->esz;
     if (bodies) NB_HIP(s, hipMemcpy(bodies, s->bodies[s->cur], row * s->n, hipMemcpyDeviceToHost));
@@ -982,18 +1102,55 @@ int nb_download(nb_sim* s, void* bodies, void* vel, void* accel)
 int nb_device_ptr(nb_sim* s, int which, void** out)
 {
     if (!s || !out) return NB_ERR_INVALID;
+    if (which == NB_JERK && !s->hermite) return fail(s, NB_ERR_STATE, "nb_device_ptr: NB_JERK needs a Hermite handle (nb_config.integrator)");
+    if (s->hermite && (which == NB_ACCEL || which == NB_JERK)) {
+        if (!s->uploaded) return fail(s, NB_ERR_STATE, "nb_device_ptr: nothing uploaded yet");
+        NB_HIP(s, hipSetDevice(s->device));
+        if (int rc = ensure_derivs(s, "nb_device_ptr")) return rc;
+    }
     switch (which) {
-        case NB_BODIES: *out = s->bodies[s->cur]; s->pairs_ok = false; s->gm_ok = false; break;   // the caller may write through it
-        case NB_VEL: *out = s->vel; break;
+        case NB_BODIES: *out = s->bodies[s->cur]; s->pairs_ok = false; s->gm_ok = false; s->derivs_ok = false; break;   // the caller may write through it
+        case NB_VEL: *out = s->vel; s->derivs_ok = false; break;
         case NB_ACCEL: *out = s->acc; break;
+        case NB_JERK: *out = s->jerk; break;
         default: return fail(s, NB_ERR_INVALID, "nb_device_ptr: unknown array");
     }
+    return NB_OK;
+}
+
+int nb_download_jerk(nb_sim* s, void* jerk)
+{
+    if (!s) return fail(nullptr, NB_ERR_INVALID, "nb_download_jerk: null handle");
+    if (!jerk) return fail(s, NB_ERR_INVALID, "nb_download_jerk: jerk is NULL");
+    if (!s->hermite) return fail(s, NB_ERR_STATE, "nb_download_jerk: needs a Hermite handle (nb_config.integrator = NB_INT_HERMITE4)");
+    if (!s->uploaded) return fail(s, NB_ERR_STATE, "nb_download_jerk: nothing uploaded yet");
+    NB_HIP(s, hipSetDevice(s->device));
+    if (int rc = ensure_derivs(s, "nb_download_jerk")) return rc;
+    NB_HIP(s, hipStreamSynchronize(s->stream));
+    NB_HIP(s, hipMemcpy(jerk, s->jerk, 4 * s->esz * s->n, hipMemcpyDeviceToHost));
+    return NB_OK;
+}
+
+int nb_upload_derivs(nb_sim* s, const void* accel, const void* jerk)
+{
+    if (!s) return fail(nullptr, NB_ERR_INVALID, "nb_upload_derivs: null handle");
+    if (!accel || !jerk) return fail(s, NB_ERR_INVALID, "nb_upload_derivs: accel and jerk are required");
+    if (!s->hermite) return fail(s, NB_ERR_STATE, "nb_upload_derivs: needs a Hermite handle (nb_config.integrator = NB_INT_HERMITE4)");
+    if (!s->uploaded) return fail(s, NB_ERR_STATE, "nb_upload_derivs: nb_upload has not been called");
+    NB_HIP(s, hipSetDevice(s->device));
+    NB_HIP(s, hipStreamSynchronize(s->stream));
+    NB_HIP(s, hipMemcpy(s->acc, accel, 4 * s->esz * s->n, hipMemcpyHostToDevice));
+    NB_HIP(s, hipMemcpy(s->jerk, jerk, 4 * s->esz * s->n, hipMemcpyHostToDevice));
+    s->derivs_ok = true;
+    s->derivs_any_G = !s->params_set;
+    s->derivs_G = s->G;
     return NB_OK;
 }
 
 int nb_set_exchange(nb_sim* s, nb_exchange_fn fn, void* user)
 {
     if (!s) return NB_ERR_INVALID;
+    if (s->hermite) return fail(s, NB_ERR_STATE, "nb_set_exchange: a Hermite handle is a whole system on one device: nothing to exchange");
     if (fn && s->fused) return fail(s, NB_ERR_STATE, "nb_set_exchange: a fused whole-system handle has nothing to exchange");
     if (fn && s->rccl) return fail(s, NB_ERR_STATE, "nb_set_exchange: a native RCCL communicator is attached (nb_rccl_detach first)");
     if (int rc = finish_gather(s)) return rc;
@@ -1005,6 +1162,7 @@ int nb_set_exchange_overlapped(nb_sim* s, nb_exchange_fn begin, nb_exchange_wait
 {
     if (!s) return NB_ERR_INVALID;
     if (!begin || !wait) return fail(s, NB_ERR_INVALID, "nb_set_exchange_overlapped: both hooks are required");
+    if (s->hermite) return fail(s, NB_ERR_STATE, "nb_set_exchange_overlapped: a Hermite handle is a whole system on one device: nothing to exchange");
     if (s->fused) return fail(s, NB_ERR_STATE, "nb_set_exchange_overlapped: a fused whole-system handle has nothing to exchange");
     if (s->rccl) return fail(s, NB_ERR_STATE, "nb_set_exchange_overlapped: a native RCCL communicator is attached");
     if (int rc = finish_gather(s)) return rc;
@@ -1029,6 +1187,16 @@ static int collect_times(nb_sim* s, nb_step_timing* t)
     uint32_t nx = 0, nrs = 0;
     for (auto& ev : s->pending) {
         float a = 0, b = 0, c = 0, d = 0, r1 = 0, r2 = 0, sp = 0;
+        if (s->hermite) {
+            // e6 predict e0 force+jerk kernel, reduce e1 correct e2
+            float pr = 0, co = 0;
+            NB_HIP(s, hipEventElapsedTime(&pr, ev.e[6], ev.e[0]));
+            NB_HIP(s, hipEventElapsedTime(&a, ev.e[0], ev.e[1]));
+            NB_HIP(s, hipEventElapsedTime(&co, ev.e[1], ev.e[2]));
+            NB_HIP(s, hipEventElapsedTime(&sp, ev.e[6], ev.e[2]));
+            f += a; g += pr + co; span += sp;
+            continue;
+        }
         if (ev.rs) {
             // rank form: e0 force e7 nb_sym_reduce e1 reduce-scatter e6 integrate e2 [all-gather e5]; with the force pass split at the
             // gather: e0 own-row sweeps e7 [wait for the other ranks' rows] e3 the rest e4 nb_sym_reduce e1 ...
@@ -1094,6 +1262,7 @@ int nb_integrate_pass(nb_sim* s, uint32_t reps, double* avg_ms)
 {
     if (!s || !avg_ms) return NB_ERR_INVALID;
     if (!s->uploaded) return fail(s, NB_ERR_STATE, "nb_integrate_pass: nothing uploaded yet");
+    if (s->hermite) return fail(s, NB_ERR_STATE, "nb_integrate_pass: a Hermite handle has no integrate kernel to run on its own (predictor and corrector belong to a step)");
     if (s->fused) return fail(s, NB_ERR_STATE, "nb_integrate_pass: a fused handle has no integrate kernel (create it with NB_FLAG_NO_FUSE)");
     if (reps == 0) return fail(s, NB_ERR_INVALID, "nb_integrate_pass: reps must be >= 1");
     NB_HIP(s, hipSetDevice(s->device));
@@ -1132,7 +1301,9 @@ int nb_force_pass(nb_sim* s, uint32_t reps, double* avg_ms)
     NB_HIP(s, hipSetDevice(s->device));
     if (int rc = finish_gather(s)) return rc;
     if (int rc = ensure_gm(s)) return rc;
+    if (s->hermite && !s->params_set) return fail(s, NB_ERR_STATE, "nb_force_pass: nb_set_params has not been called (G)");
     auto once = [&]() -> int {
+        if (s->hermite) { launch_fj(s, s->bodies[0], s->vel, s->hx, s->hv); return NB_OK; }      // into the step's scratch: state and derivatives untouched
         if (s->sym_rank) return s->f64 ? nbi::sym_rank_phase_a_t<double>(s, nullptr, false) : nbi::sym_rank_phase_a_t<float>(s, nullptr, false);
         if (s->f64) launch_force<double>(s); else launch_force<float>(s);
         return NB_OK;
@@ -1173,6 +1344,7 @@ int nb_plan_query(const nb_config* cfg_in, int n_cu, double clock_hz, nb_plan_in
     uint32_t sb, sc;
     double eps2;
     if (const int rc = read_config(cfg_in, "nb_plan_query", &cfg, &sb, &sc, &eps2)) return rc;
+    if (cfg.integrator != NB_INT_LEAPFROG) return fail(nullptr, NB_ERR_INVALID, "nb_plan_query: integrator must be NB_INT_LEAPFROG (a Hermite handle has no launch plan: nb_shape_info reports its j-chunks)");
     int count = 0;
     double device_mem = 0.0;                      // 0: the planner's default (an MI355X's 288 GB)
     if (hipGetDeviceCount(&count) != hipSuccess) { (void)hipGetLastError(); count = 0; }

@@ -143,6 +143,17 @@ struct nb_sim {
     // (O(m)); part holds one (ax, ay, az, sum m/r) row per (j-chunk, point of a batch): a bounded number of rows whatever m and n are
     int n_cu = 256;
     struct field_buf { void* p = nullptr; size_t cap = 0; } fld_pts, fld_acc, fld_phi, fld_part;
+    // NB_INT_HERMITE4: bodies[0] / vel are the state at ONE instant, acc / jerk the derivatives derived from it.  None of the
+    // leapfrog launch fields above is used: plain unpadded arrays, no planner, no graphs.
+    bool hermite = false;
+    void* jerk = nullptr;
+    void* hx = nullptr;            // the predicted positions (xp, with the mass lane), then a1: what nb_fj_reduce leaves for the corrector
+    void* hv = nullptr;            // the predicted velocities (vp), then j1
+    void* fj_part = nullptr;       // 2 x fj_chunks x n rows of partial sums: accelerations, then jerks
+    uint32_t fj_chunks = 1, fj_per = 0;   // the force+jerk pass's j-chunks (grid.y) and bodies per chunk (whole 256-row tiles)
+    bool derivs_ok = false;        // acc / jerk belong to (bodies, vel) and derivs_G
+    bool derivs_any_G = false;     // nb_upload_derivs before the first nb_set_params: the derivatives belong to whatever G comes
+    double derivs_G = 0.0;
 };
 
 namespace nbi {

@@ -59,6 +59,8 @@ static int (*p_frame_acquire)(nb_sim *, int, const float **, const float **, uin
 static int (*p_plan_query)(const nb_config *, int, double, nb_plan_info *, uint32_t *, uint32_t);
 static int (*p_field_eval)(nb_sim *, const nb_field_request *);
 static int (*p_multi_field_eval)(nb_multi *, const nb_field_request *);
+static int (*p_download_jerk)(nb_sim *, void *);                        /* the Hermite additions within ABI 2.4: optional symbols */
+static int (*p_upload_derivs)(nb_sim *, const void *, const void *);
 
 /* one JS handle = a single-device nb_sim or a single-process multi-device nb_multi */
 typedef struct { nb_sim *sim; nb_multi *multi; uint32_t n; int f64; } handle_t;
@@ -136,6 +138,9 @@ static napi_value js_load(napi_env env, napi_callback_info info)
         SYM(p_plan_query, "nb_plan_query");
         SYM(p_field_eval, "nb_field_eval"); SYM(p_multi_field_eval, "nb_multi_field_eval");
 #undef SYM
+        /* present from the library that has NB_INT_HERMITE4; an older 2.4 library still loads */
+        *(void **)(&p_download_jerk) = dlsym(h, "nb_download_jerk");
+        *(void **)(&p_upload_derivs) = dlsym(h, "nb_upload_derivs");
         g_lib = h;
     }
     if (p_abi_version() != NB_ABI_VERSION) { napi_throw_error(env, "NB_ABI", "ABI version mismatch"); return NULL; }
@@ -199,6 +204,7 @@ static void read_config(napi_env env, napi_value opts, nb_config *cfg)
     if (get_u32_prop(env, opts, "tile", &u)) cfg->tile = u;
     if (get_u32_prop(env, opts, "flags", &u)) cfg->flags = u;
     if (get_u32_prop(env, opts, "layerBudgetMiB", &u)) cfg->layer_budget_mib = u;
+    if (get_u32_prop(env, opts, "integrator", &u)) cfg->integrator = u;     /* nb_integrator: 0 leapfrog, 1 Hermite 4th order */
 }
 
 /* planQuery(options) -> {variant, kind, ipl, ls, x, jsplit, jPerSplit, sym, symRows, symLayers, symUnitsPerSweep, symSpillRows, layerBytes}: nb_plan_query -- the launch
@@ -237,6 +243,9 @@ static napi_value js_create(napi_env env, napi_callback_info info)
     CHECK_NAPI(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
     if (argc < 1) { napi_throw_type_error(env, NULL, "create(options) requires an object"); return NULL; }
     nb_config cfg; read_config(env, argv[0], &cfg);
+    if (cfg.integrator != NB_INT_LEAPFROG && !p_download_jerk) {
+        napi_throw_error(env, "NB_1", "create: the loaded library has no Hermite integrator (nb_download_jerk is missing)"); return NULL;
+    }
     uint32_t shards = 0, collective = 0;
     get_u32_prop(env, argv[0], "shards", &shards);
     get_u32_prop(env, argv[0], "collective", &collective);   /* 0 peer copies, 1 RCCL (nb_multi_collective) */
@@ -615,6 +624,37 @@ static napi_value js_field_eval(napi_env env, napi_callback_info info)
     return undefined(env);
 }
 
+/* downloadJerk(handle, jerkOut): nb_download_jerk -- 4*n elements (jx, jy, jz, 0) of a Hermite handle, written in place. */
+static napi_value js_download_jerk(napi_env env, napi_callback_info info)
+{
+    size_t argc = 2; napi_value argv[2];
+    CHECK_NAPI(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    if (argc < 2) { napi_throw_type_error(env, NULL, "downloadJerk(handle, jerkOut)"); return NULL; }
+    handle_t *h = get_handle(env, argv[0]); if (!h) return NULL;
+    if (h->multi || !p_download_jerk) return throw_msg(env, NB_ERR_STATE, "needs a single-device Hermite handle and a library with nb_download_jerk", "nb_download_jerk");
+    void *j;
+    if (!get_array(env, argv[1], h, 0, &j, "jerkOut must be a typed array of 4*n elements")) return NULL;
+    int rc = p_download_jerk(h->sim, j);
+    if (rc != NB_OK) return throw_nb(env, rc, h->sim, "nb_download_jerk");
+    return undefined(env);
+}
+
+/* uploadDerivs(handle, accel, jerk): nb_upload_derivs -- the checkpoint restore of a Hermite handle, after upload(). */
+static napi_value js_upload_derivs(napi_env env, napi_callback_info info)
+{
+    size_t argc = 3; napi_value argv[3];
+    CHECK_NAPI(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    if (argc < 3) { napi_throw_type_error(env, NULL, "uploadDerivs(handle, accel, jerk)"); return NULL; }
+    handle_t *h = get_handle(env, argv[0]); if (!h) return NULL;
+    if (h->multi || !p_upload_derivs) return throw_msg(env, NB_ERR_STATE, "needs a single-device Hermite handle and a library with nb_upload_derivs", "nb_upload_derivs");
+    void *a, *j;
+    if (!get_array(env, argv[1], h, 0, &a, "accel must be a typed array of 4*n elements")) return NULL;
+    if (!get_array(env, argv[2], h, 0, &j, "jerk must be a typed array of 4*n elements")) return NULL;
+    int rc = p_upload_derivs(h->sim, a, j);
+    if (rc != NB_OK) return throw_nb(env, rc, h->sim, "nb_upload_derivs");
+    return undefined(env);
+}
+
 static napi_value init_module(napi_env env, napi_value exports)
 {
     static const struct { const char *name; napi_callback fn; } fns[] = {
@@ -623,7 +663,7 @@ static napi_value init_module(napi_env env, napi_value exports)
         {"destroy", js_destroy}, {"enableTiming", js_enable_timing}, {"kernelTimes", js_kernel_times},
         {"variant", js_variant}, {"diagnostics", js_diagnostics}, {"stepTimes", js_step_times},
         {"collectiveInfo", js_collective_info}, {"requestFrame", js_request_frame}, {"frame", js_frame}, {"planQuery", js_plan_query},
-        {"fieldEval", js_field_eval},
+        {"fieldEval", js_field_eval}, {"downloadJerk", js_download_jerk}, {"uploadDerivs", js_upload_derivs},
     };
     for (size_t i = 0; i < sizeof fns / sizeof fns[0]; ++i) {
         napi_value f;

@@ -16,6 +16,7 @@
  *   restore(state)         util.js:230-244     importSimulation's buffer writes
  *   G / dt / pause()       nbody3d.js:6-7, util.js:36-64 (dt and G are mutable
  *                          between frames; pause saves dt and sets it to 0)
+ *   readJerk()             (no reference analogue) the jerk of a {integrator: 'hermite4'} simulation
  *   requestFrame()/frame() nbody3d.js:408-415,482-487 what the render pass reads each frame
  *                          (bodies + speed), delivered asynchronously to a host-side viewer
  *
@@ -32,6 +33,7 @@ const TILE_SIZE = 256;      // nbody3d.js:4
 const DEFAULT_G = 0.0001;   // nbody3d.js:6
 const DEFAULT_DT = 1e-4;    // nbody3d.js:7
 const EPS2 = 1e-4;          // nbody3d.js:234
+const INTEGRATORS = { leapfrog: 0, hermite4: 1 };   // nb_integrator
 
 let addon = null;
 let abi = 0;
@@ -68,7 +70,10 @@ function asParticles(particles) {
 }
 
 class Simulation {
-  /** options: {G, dt, f64, eps2, device, shards, collective, shardBegin, shardCount, variant, jsplit, flags, layerBudgetMiB}
+  /** options: {G, dt, f64, eps2, device, shards, collective, shardBegin, shardCount, variant, jsplit, flags, layerBudgetMiB, integrator}
+   *  integrator: 'leapfrog' (default: the reference's lagged scheme, nbody3d.js:274-290) or 'hermite4' (no reference analogue:
+   *  4th-order Hermite predictor-corrector; bodies and vel belong to ONE instant, accel and the jerk are derived from them;
+   *  whole system on one device).  Anything else throws RangeError here, before the engine is touched.
    *  layerBudgetMiB: nb_config.layer_budget_mib (device memory the symmetric pass may take for its partial sums; 0 = default).
    *  shards > 1: single-process multi-device (i-shards round-robin over the visible GPUs; all-gather
    *  of positions after every step through collective: 'peer' -- event-ordered device-to-device
@@ -80,6 +85,10 @@ class Simulation {
     this.G = o.G !== undefined ? o.G : DEFAULT_G;
     this.dt = o.dt !== undefined ? o.dt : DEFAULT_DT;
     this.f64 = !!o.f64;
+    this.integrator = o.integrator !== undefined ? o.integrator : 'leapfrog';
+    if (!Object.prototype.hasOwnProperty.call(INTEGRATORS, this.integrator)) {
+      throw new RangeError("integrator: expected 'leapfrog' or 'hermite4', got " + String(o.integrator));
+    }
     this._oldDt = null;     // util.js:35
     this._h = null;
     this.nBodies = 0;       // nbody3d.js:14
@@ -112,6 +121,7 @@ class Simulation {
         device: o.device !== undefined ? o.device : -1, shardBegin: o.shardBegin || 0, shardCount: o.shardCount || 0,
         variant: o.variant || 0, jsplit: o.jsplit || 0, tile: o.tile || 0, shards: o.shards || 0,
         flags: o.flags || 0, layerBudgetMiB: o.layerBudgetMiB || 0, collective: o.collective === 'rccl' ? 1 : 0,
+        integrator: INTEGRATORS[this.integrator],
       });
       this._frame = null;
     }
@@ -156,6 +166,7 @@ class Simulation {
   /** util.js:163-178: fresh copies {bodies, vel, accel}. */
   read() {
     this._need();
+    if (this.integrator !== 'leapfrog') addon.setParams(this._h, this.dt, this.G);   // accel is derived on demand: needs G
     const T = this.ArrayType, len = 4 * this.nBodies;
     const out = { bodies: new T(len), vel: new T(len), accel: new T(len) };
     addon.download(this._h, out.bodies, out.vel, out.accel);
@@ -169,11 +180,23 @@ class Simulation {
     return b;
   }
 
-  /** util.js:230-244: write the three arrays into the EXISTING buffers (N must match). */
+  /** The jerk (jx, jy, jz, 0 per body) of a 'hermite4' simulation at the state as it stands (nb_download_jerk; no reference
+   *  analogue).  {...read(), jerk: readJerk()} is the whole checkpoint restore() continues bit-identically from. */
+  readJerk() {
+    this._need();
+    addon.setParams(this._h, this.dt, this.G);
+    const j = new this.ArrayType(4 * this.nBodies);
+    addon.downloadJerk(this._h, j);
+    return j;
+  }
+
+  /** util.js:230-244: write the three arrays into the EXISTING buffers (N must match).  A 'hermite4' simulation ignores accel on its
+   *  own (a derived array); with BOTH state.accel and state.jerk it takes them as its derivatives (nb_upload_derivs). */
   restore(state) {
     this._need();
     addon.upload(this._h, this._coerce(state.bodies, 'bodies'), this._coerce(state.vel, 'vel'),
       state.accel ? this._coerce(state.accel, 'accel') : null);
+    if (state.accel && state.jerk) addon.uploadDerivs(this._h, this._coerce(state.accel, 'accel'), this._coerce(state.jerk, 'jerk'));
     return this;
   }
 

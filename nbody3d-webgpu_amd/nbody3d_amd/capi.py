@@ -33,6 +33,8 @@ NB_RCCL_OVERLAP = 1
 NB_MULTI_PEER, NB_MULTI_RCCL, NB_MULTI_PEER_OVERLAP = 0, 1, 2
 NB_NOT_READY = 7
 NB_FIELD_AT_BODIES, NB_FIELD_F64, NB_FIELD_DEVICE = 1, 2, 4      # nb_field_request.flags (ABI 2.4)
+NB_INT_LEAPFROG, NB_INT_HERMITE4 = 0, 1                          # nb_config.integrator (added within ABI 2.4)
+INTEGRATORS = {"leapfrog": NB_INT_LEAPFROG, "hermite4": NB_INT_HERMITE4}
 STATUS = {0: "NB_OK", 1: "NB_ERR_INVALID", 2: "NB_ERR_NO_DEVICE", 3: "NB_ERR_HIP",
           4: "NB_ERR_STATE", 5: "NB_ERR_NOMEM", 6: "NB_ERR_COMM", 7: "NB_NOT_READY"}
 ABI_VERSION = 2      # NB_ABI_VERSION (major)
@@ -51,7 +53,7 @@ class nb_config(C.Structure):
         ("eps2", C.c_double), ("device", C.c_int32), ("shard_begin", C.c_uint32), ("shard_count", C.c_uint32),
         ("ext_stream", C.c_void_p), ("ext_bodies", C.c_void_p),
         ("force_variant", C.c_uint32), ("jsplit", C.c_uint32), ("flags", C.c_uint32), ("layer_budget_mib", C.c_uint32),
-        ("reserved", C.c_uint32 * 4),
+        ("integrator", C.c_uint32), ("reserved", C.c_uint32 * 3),
     ]
 
 
@@ -89,7 +91,7 @@ SYMBOLS = ["nb_abi_version", "nb_device_count", "nb_create", "nb_destroy", "nb_u
            "nb_multi_diagnostics", "nb_multi_set_collective", "nb_multi_collective_info",
            "nb_rccl_unique_id", "nb_rccl_attach", "nb_rccl_detach", "nb_rccl_info",
            "nb_step_times", "nb_step_times2", "nb_integrate_pass", "nb_force_pass", "nb_frame_request", "nb_frame_acquire", "nb_shape_info", "nb_plan_query",
-           "nb_abi_minor", "nb_field_eval", "nb_multi_field_eval"]
+           "nb_abi_minor", "nb_field_eval", "nb_multi_field_eval", "nb_download_jerk", "nb_upload_derivs"]
 
 _lib = None
 
@@ -161,6 +163,9 @@ def load_library():
     if L.nb_abi_minor() >= 4:       # an older library of the same major still loads; field() then raises
         L.nb_field_eval.argtypes = [vp, C.POINTER(nb_field_request)]
         L.nb_multi_field_eval.argtypes = [vp, C.POINTER(nb_field_request)]
+    if hasattr(L, "nb_download_jerk"):      # the Hermite additions within 2.4: detected by the symbol, not by the minor
+        L.nb_download_jerk.argtypes = [vp, vp]
+        L.nb_upload_derivs.argtypes = [vp, vp, vp]
     _lib = L
     return L
 
@@ -317,10 +322,15 @@ class Simulation:
     uniforms, compute pipeline) bundle, nbody3d.js:13,179-204,296-311."""
 
     def __init__(self, n, precision="f32", eps2=None, device=-1, shard=None, stream=None, ext_bodies=None,
-                 force_variant=0, jsplit=0, tile=0, flags=0, layer_budget_mib=0):
+                 force_variant=0, jsplit=0, tile=0, flags=0, layer_budget_mib=0, integrator="leapfrog"):
         L = load_library()
         self._L = L
         self.n = int(n)
+        if integrator not in INTEGRATORS:
+            raise ValueError("integrator must be one of %s, got %r" % (sorted(INTEGRATORS), integrator))
+        if integrator != "leapfrog" and not hasattr(L, "nb_download_jerk"):
+            raise NBodyError(1, "integrator=%r: the loaded library has no Hermite integrator (nb_download_jerk is missing)" % (integrator,))
+        self.integrator = integrator
         self.dtype = np.float64 if precision in ("f64", NB_F64, np.float64) else np.float32
         cfg = nb_config()
         cfg.struct_size = C.sizeof(nb_config)
@@ -341,6 +351,7 @@ class Simulation:
         cfg.jsplit = jsplit
         cfg.flags |= int(flags)
         cfg.layer_budget_mib = int(layer_budget_mib)
+        cfg.integrator = INTEGRATORS[integrator]
         h = C.c_void_p()
         rc = L.nb_create(C.byref(cfg), C.byref(h))
         if rc != 0:
@@ -414,10 +425,29 @@ class Simulation:
         self._check(self._L.nb_download(self._h, _ptr(out[0]), _ptr(out[1]), _ptr(out[2])))
         return tuple(out)
 
+    # -- Hermite handles (integrator="hermite4") -----------------------------
+    def read_jerk(self):
+        """nb_download_jerk: the jerk (jx, jy, jz, 0) of the state as it stands, shape (N,4).  With read() this is the whole
+        checkpoint of a Hermite handle: (bodies, vel) at one instant and the derivatives the next step starts from."""
+        if not hasattr(self._L, "nb_download_jerk"):
+            raise NBodyError(1, "read_jerk(): the loaded library has no nb_download_jerk")
+        out = np.zeros((self.n, 4), self.dtype)
+        self._check(self._L.nb_download_jerk(self._h, _ptr(out)))
+        return out
+
+    def upload_derivs(self, accel, jerk):
+        """nb_upload_derivs: after init() / restore(), hands a checkpoint's (accel, jerk) back, so that the next step continues
+        bit-identically (a step leaves derivatives evaluated at the PREDICTED state: recomputing them from (x, v) is close, not equal)."""
+        if not hasattr(self._L, "nb_upload_derivs"):
+            raise NBodyError(1, "upload_derivs(): the loaded library has no nb_upload_derivs")
+        a, j = self._arr(accel, "accel"), self._arr(jerk, "jerk")
+        self._check(self._L.nb_upload_derivs(self._h, _ptr(a), _ptr(j)))
+        return self
+
     # -- multi-GPU / measurement / diagnostics ------------------------------
     def device_ptr(self, which):
         p = C.c_void_p()
-        self._check(self._L.nb_device_ptr(self._h, {"bodies": 0, "vel": 1, "accel": 2}[which], C.byref(p)))
+        self._check(self._L.nb_device_ptr(self._h, {"bodies": 0, "vel": 1, "accel": 2, "jerk": 3}[which], C.byref(p)))
         return p.value
 
     def set_exchange(self, fn):
