@@ -47,7 +47,9 @@ extern "C" {
                                             library ignores the bit: it runs every sweep on its own anyway)
                              2.4 (round 7)  additions WITHIN 2.4, the minor stays 4: nb_config.integrator (in the place of reserved[0]; an older
                                             library ignores it), NB_INT_*, nb_download_jerk, nb_upload_derivs, NB_JERK.  A client detects them by
-                                            the presence of the symbol nb_download_jerk (dlsym), not by the minor */
+                                            the presence of the symbol nb_download_jerk (dlsym), not by the minor
+                             2.4 (round 8)  likewise within 2.4: nb_set_block_steps, nb_block_stats, nb_download_levels, nb_upload_levels,
+                                            NB_BLOCK_*.  Detected by the presence of the symbol nb_set_block_steps */
 
 typedef struct nb_sim nb_sim; /* opaque */
 
@@ -407,6 +409,72 @@ int nb_download_jerk(nb_sim *s, void *jerk);
  * when none was made yet), so the next step continues bit-identically from a (bodies, vel, accel, jerk) read with nb_download +
  * nb_download_jerk. */
 int nb_upload_derivs(nb_sim *s, const void *accel, const void *jerk);
+
+/* ---- block individual time steps on a Hermite handle (no reference analogue) ----------------------------
+ * With one shared step a single tight pair puts the whole system on the pair's step.  nb_set_block_steps gives every body a step
+ * of its own, dt / 2^l_i with a LEVEL l_i in [min_level, max_level] (Makino & Aarseth 1992; NBODY4/6, phi-GPU): at every block
+ * time only the bodies due there get a new force+jerk, against the predicted positions of all the others.
+ *   - nb_step(s, k) still advances the system by exactly k x dt (dt of nb_set_params): k OUTER steps, after each of which all bodies
+ *     are at the same instant.  nb_download, nb_download_jerk, nb_diagnostics, nb_field_eval, nb_frame_request / nb_frame_acquire,
+ *     nb_device_ptr and nb_upload_derivs keep their meaning; dt <= 0 is a no-op.  nb_step(k) equals k x nb_step(1) bit for bit, two
+ *     handles give the same bits, and (bodies, vel, accel, jerk, levels) uploaded into a fresh handle (nb_upload, nb_upload_derivs,
+ *     nb_set_block_steps, nb_upload_levels) continues bit-identically.
+ *   - The scheme.  L = max_level, tick = dt / 2^L, body i steps by s_i = 2^(L - l_i) ticks.  level_for(tau) is the smallest l in
+ *     [min_level, L] with dt / 2^l <= tau; if there is none it is L and the decision counts as `clamped`.
+ *     Start (levels not current): (a, j) are made current, then l_i = level_for((eta / 2) |a_i| / |j_i|); |j_i| = 0 gives min_level.
+ *     An outer step sets t_i = 0 for all bodies and repeats until t_next == 2^L:
+ *       1. t_next = min_i (t_i + s_i), the active set A = { i : t_i + s_i == t_next };
+ *       2. EVERY body is predicted from its own (x, v, a, j) at t_i over (t_next - t_i) ticks (the predictor polynomial of a
+ *          shared step, fp64, rounded once) -- always from the stored state, never from an earlier prediction;
+ *       3. (a1, j1) of i in A against all n predicted rows (the self term is exactly 0);
+ *       4. i in A is corrected over h = s_i ticks with the corrector of a shared step: (x, v, a, j)_i <- (x1, v1, a1, j1);
+ *       5. a2 = (-6 (a0 - a1) - h (4 j0 + 2 j1)) / h^2, a3 = (12 (a0 - a1) + 6 h (j0 + j1)) / h^3, a2e = a2 + h a3,
+ *          tau = sqrt(eta (|a1| |a2e| + |j1|^2) / (|j1| |a3| + |a2e|^2)), inf when the denominator is 0; a1 and j1 as stored
+ *          (rounded to the handle's precision); all of this in fp64;
+ *       6. unless NB_BLOCK_FROZEN: want = level_for(tau); want >= l_i is taken (refining by any depth); want < l_i coarsens by ONE
+ *          level, and only if t_next is a multiple of 2 s_i; otherwise l_i stays;
+ *       7. t_i = t_next.
+ *   - The levels go stale with everything that stales the derivatives (nb_upload, nb_device_ptr(NB_BODIES / NB_VEL)), with a change of
+ *     dt or G and with nb_set_block_steps; stale levels are re-initialised by the start rule at the next nb_step or
+ *     nb_download_levels.  With NB_BLOCK_FROZEN stale levels put every body at min_level.
+ *   - HOST SYNCHRONISATION (this first version's design).  nb_step on a block handle synchronises with the device ONCE PER BLOCK STEP:
+ *     the host reads a small header (active count, next block time) from pinned memory and sizes the next launches by it; the
+ *     clamp count and the finest level stay on the device until nb_block_stats asks.  Such a step cannot be captured into a
+ *     caller's graph; ext_stream keeps working otherwise.
+ *   - nb_force_pass still runs the full N x N pass into scratch.  nb_enable_timing / nb_step_times2 report one OUTER step per launch:
+ *     force_ms is its whole span, integrate_ms = 0 (as on a fused handle).  nb_variant_name is unchanged.
+ *   - binary32 handles store the state, a and j in binary32: below steps of about dt / 2^10 (Plummer units) a3 is rounding noise and
+ *     the criterion degrades towards smaller steps -- safe, but slower.  Deep hierarchies belong on NB_F64 handles.
+ *   - Leapfrog handles: all four calls return NB_ERR_STATE.  A NULL handle, a wrong struct_size, max_level > 30, min_level >
+ *     max_level, eta <= 0 or NaN, unknown flag bits, an uploaded level outside [min_level, max_level]: NB_ERR_INVALID, with a message
+ *     that names the function and the field. */
+#define NB_BLOCK_FROZEN 1u  /* levels stay as initialised / uploaded: no step-size decisions */
+typedef struct nb_block_steps {
+    uint32_t struct_size;   /* sizeof(nb_block_steps) */
+    uint32_t max_level;     /* finest step = dt / 2^max_level; 0 -> 20; at most 30 */
+    uint32_t min_level;     /* coarsest step = dt / 2^min_level; <= max_level */
+    uint32_t flags;         /* NB_BLOCK_* */
+    double   eta;           /* accuracy parameter; 0 -> 0.02; must be > 0 */
+} nb_block_steps;
+/* set_block_steps: switches a Hermite handle to block steps (or re-configures them); NULL: back to one shared step.  The state and
+ * the derivatives stay; the levels go stale. */
+int nb_set_block_steps(nb_sim *s, const nb_block_steps *cfg /* NULL: back to one shared step */);
+
+/* (a struct TAG without a typedef: the function below carries the same name, and in C a typedef name and a function share one name
+ * space, a tag does not.  Write `struct nb_block_stats` in C and in C++.) */
+struct nb_block_stats {
+    uint32_t struct_size, enabled;
+    uint64_t outer_steps, block_steps, body_steps;  /* body_steps = sum of active bodies over the block steps */
+    uint64_t clamped;                               /* decisions that wanted a step finer than dt / 2^max_level */
+    uint32_t finest_level, reserved;                /* deepest level any body held since the last reset */
+};
+/* block_stats: the counters since the last reset (set out->struct_size); blocks.  reset != 0 zeroes them after the read.  A Hermite
+ * handle without block steps reports enabled = 0 and zeros. */
+int nb_block_stats(nb_sim *s, struct nb_block_stats *out, int reset);
+/* download_levels / upload_levels: n bytes, one level per body.  Both need block steps switched on and an uploaded state
+ * (NB_ERR_STATE otherwise).  upload_levels is the last call of a checkpoint restore. */
+int nb_download_levels(nb_sim *s, uint8_t *levels /* n */);       /* blocks; initialises the levels first if they are not current */
+int nb_upload_levels(nb_sim *s, const uint8_t *levels /* n */);   /* after nb_upload (+ nb_upload_derivs): marks the levels current */
 
 /* ---- viewer frame feed ------------------------------------------------
  * The reference's render pass reads bodyBuffer and velBuffer in place every frame

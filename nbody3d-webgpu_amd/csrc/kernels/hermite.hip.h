@@ -35,19 +35,23 @@ constexpr uint32_t kFjFlush = 4;                    // tiles between two flushes
 //   Registers: 12 packed i-values, 2 x 6 packed sums per group, ~20 live per chain.  Four chains (two tile rows x two groups,
 // issued stage-major so that no dependent instruction follows its producer) need ~160 VGPRs: the kernel runs two waves per SIMD
 // (256 VGPRs each), where the second wave covers the first one's LDS waits and barriers.  profiles/r07/hermite.md.
-template <int NG>
-__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(NB_FJ_WAVES, NB_FJ_WAVES)))
-void nb_fj_pk(const float4* __restrict__ pos, const float4* __restrict__ vel, float4* __restrict__ pa, float4* __restrict__ pj,
-              uint32_t n, uint32_t j_per_chunk, float eps2, const float4* __restrict__ zero_row)
+//   The body is shared with nb_blk_fj_pk (kernels/block.hip.h): with GATHER the ni i-rows are act[0 .. ni) and the partial rows are
+// compact (row k of chunk c belongs to act[k]); without it ni == n and row k is body k.  Everything between the prologue's loads
+// and the epilogue's stores is the same code.
+template <int NG, bool GATHER>
+__device__ __forceinline__ void fj_pk_body(const float4* __restrict__ pos, const float4* __restrict__ vel,
+                                           const uint32_t* __restrict__ act, uint32_t ni, float4* __restrict__ pa,
+                                           float4* __restrict__ pj, uint32_t n, uint32_t j_per_chunk, float eps2,
+                                           const float4* __restrict__ zero_row)
 {
-    static_assert(kBlock * 2 * NG == kFjRows, "the engine sizes the grid by kFjRows");
     constexpr int TILE = kTile;
     constexpr int U = 8;                  // tile rows per unrolled chunk
-    constexpr int JB = 2;                 // j-bodies per stage: JB * NG = 4 independent chains
+    constexpr int JB = 4 / NG;            // j-bodies per stage: JB * NG = 4 independent chains
+    constexpr uint32_t ROWS = kBlock * 2 * NG;
     constexpr int NC = JB * NG;
     __shared__ float4 tile[2][2][TILE];   // [buffer][0 = positions, 1 = velocities][row]
     const int tid = threadIdx.x;
-    const uint32_t i0 = blockIdx.x * kFjRows;
+    const uint32_t i0 = blockIdx.x * ROWS;
     const uint32_t j0 = blockIdx.y * j_per_chunk;
     const uint32_t j1 = j0 + j_per_chunk < n ? j0 + j_per_chunk : n;
 
@@ -55,7 +59,8 @@ void nb_fj_pk(const float4* __restrict__ pos, const float4* __restrict__ vel, fl
 #pragma unroll
     for (int g = 0; g < NG; ++g) {
         const uint32_t il0 = i0 + (2 * g) * kBlock + tid, il1 = il0 + kBlock;
-        const uint32_t c0 = il0 < n ? il0 : n - 1, c1 = il1 < n ? il1 : n - 1;      // clamped, branch-free (never stored)
+        uint32_t c0 = il0 < ni ? il0 : ni - 1, c1 = il1 < ni ? il1 : ni - 1;        // clamped, branch-free (never stored)
+        if constexpr (GATHER) { c0 = act[c0]; c1 = act[c1]; }
         const float4 b0 = ld4(pos + c0), b1 = ld4(pos + c1), v0 = ld4(vel + c0), v1 = ld4(vel + c1);
         xi[g] = nb_f2{b0.x, b1.x}; yi[g] = nb_f2{b0.y, b1.y}; zi[g] = nb_f2{b0.z, b1.z};
         ui[g] = nb_f2{v0.x, v1.x}; vi[g] = nb_f2{v0.y, v1.y}; wi[g] = nb_f2{v0.z, v1.z};
@@ -192,22 +197,33 @@ void nb_fj_pk(const float4* __restrict__ pos, const float4* __restrict__ vel, fl
     }
     flush();
 
-    float4* oa = pa + (size_t)blockIdx.y * n;
-    float4* oj = pj + (size_t)blockIdx.y * n;
+    float4* oa = pa + (size_t)blockIdx.y * ni;
+    float4* oj = pj + (size_t)blockIdx.y * ni;
 #pragma unroll
     for (int g = 0; g < NG; ++g) {
         const uint32_t il0 = i0 + (2 * g) * kBlock + tid, il1 = il0 + kBlock;
-        if (il0 < n) { oa[il0] = float4{AX[g].x, AY[g].x, AZ[g].x, 0.0f}; oj[il0] = float4{JX[g].x, JY[g].x, JZ[g].x, 0.0f}; }
-        if (il1 < n) { oa[il1] = float4{AX[g].y, AY[g].y, AZ[g].y, 0.0f}; oj[il1] = float4{JX[g].y, JY[g].y, JZ[g].y, 0.0f}; }
+        if (il0 < ni) { oa[il0] = float4{AX[g].x, AY[g].x, AZ[g].x, 0.0f}; oj[il0] = float4{JX[g].x, JY[g].x, JZ[g].x, 0.0f}; }
+        if (il1 < ni) { oa[il1] = float4{AX[g].y, AY[g].y, AZ[g].y, 0.0f}; oj[il1] = float4{JX[g].y, JY[g].y, JZ[g].y, 0.0f}; }
     }
+}
+
+template <int NG>
+__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(NB_FJ_WAVES, NB_FJ_WAVES)))
+void nb_fj_pk(const float4* __restrict__ pos, const float4* __restrict__ vel, float4* __restrict__ pa, float4* __restrict__ pj,
+              uint32_t n, uint32_t j_per_chunk, float eps2, const float4* __restrict__ zero_row)
+{
+    static_assert(kBlock * 2 * NG == kFjRows, "the engine sizes the grid by kFjRows");
+    fj_pk_body<NG, false>(pos, vel, nullptr, n, pa, pj, n, j_per_chunk, eps2, zero_row);
 }
 
 // fp64 handles (T = double).  One body per lane, the two j-tiles staged through registers; v_rsq_f64 seed + one correction as in
 // nb_field64 (y0 (1 + e/2), e = 1 - rho^2 y0^2: relative error ~ 3 e^2 / 8 < 1e-16); every difference, product and sum is fp64.
-template <typename T>
-__global__ __launch_bounds__(kBlock) void nb_fj64(const typename vec4<T>::type* __restrict__ pos,
-                                                 const typename vec4<T>::type* __restrict__ vel, double4* __restrict__ pa,
-                                                 double4* __restrict__ pj, uint32_t n, uint32_t j_per_chunk, double eps2)
+// fj64_body<T, GATHER>: shared with nb_blk_fj64, as fj_pk_body above.
+template <typename T, bool GATHER>
+__device__ __forceinline__ void fj64_body(const typename vec4<T>::type* __restrict__ pos,
+                                          const typename vec4<T>::type* __restrict__ vel, const uint32_t* __restrict__ act,
+                                          uint32_t ni, double4* __restrict__ pa, double4* __restrict__ pj, uint32_t n,
+                                          uint32_t j_per_chunk, double eps2)
 {
     __shared__ double4 tp[kTile];
     __shared__ double4 tv[kTile];
@@ -215,7 +231,8 @@ __global__ __launch_bounds__(kBlock) void nb_fj64(const typename vec4<T>::type* 
     const uint32_t il = blockIdx.x * kFjRows64 + tid;
     const uint32_t j0 = blockIdx.y * j_per_chunk;
     const uint32_t j1 = j0 + j_per_chunk < n ? j0 + j_per_chunk : n;
-    const uint32_t ic = il < n ? il : n - 1;
+    uint32_t ic = il < ni ? il : ni - 1;
+    if constexpr (GATHER) ic = act[ic];
     const auto bi = ld4(pos + ic);
     const auto wi = ld4(vel + ic);
     const double xi = (double)bi.x, yi = (double)bi.y, zi = (double)bi.z;
@@ -254,10 +271,18 @@ __global__ __launch_bounds__(kBlock) void nb_fj64(const typename vec4<T>::type* 
             ax = nb_fma(s3, dx, ax); ay = nb_fma(s3, dy, ay); az = nb_fma(s3, dz, az);
         }
     }
-    if (il < n) {
-        pa[(size_t)blockIdx.y * n + il] = double4{ax, ay, az, 0.0};
-        pj[(size_t)blockIdx.y * n + il] = double4{jx, jy, jz, 0.0};
+    if (il < ni) {
+        pa[(size_t)blockIdx.y * ni + il] = double4{ax, ay, az, 0.0};
+        pj[(size_t)blockIdx.y * ni + il] = double4{jx, jy, jz, 0.0};
     }
+}
+
+template <typename T>
+__global__ __launch_bounds__(kBlock) void nb_fj64(const typename vec4<T>::type* __restrict__ pos,
+                                                 const typename vec4<T>::type* __restrict__ vel, double4* __restrict__ pa,
+                                                 double4* __restrict__ pj, uint32_t n, uint32_t j_per_chunk, double eps2)
+{
+    fj64_body<T, false>(pos, vel, nullptr, n, pa, pj, n, j_per_chunk, eps2);
 }
 
 // Adds a body's chunk rows in ascending chunk order in fp64, multiplies by G once and writes the two derivative rows

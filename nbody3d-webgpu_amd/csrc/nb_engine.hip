@@ -500,13 +500,13 @@ int get_events(nb_sim* s, nb_events* out)
     if (s->pool_next == s->pool.size()) {
         if (s->pool.size() >= 4096) return 1;   // stop recording, keep running
         nb_events t;
-        t.two = t.xchg = t.rs = false;
+        t.two = t.xchg = t.rs = t.blk = false;
         for (auto& e : t.e)
             if (hipEventCreate(&e) != hipSuccess) return 1;
         s->pool.push_back(t);
     }
     *out = s->pool[s->pool_next++];
-    out->two = out->xchg = out->rs = false;
+    out->two = out->xchg = out->rs = out->blk = false;
     return 0;
 }
 
@@ -604,6 +604,107 @@ int hermite_step(nb_sim* s, uint32_t nsteps)
         if (s->f64) launch_hermite_oc<double>(s, true); else launch_hermite_oc<float>(s, true);
         if (rec) { NB_HIP(s, hipEventRecord(ev.e[2], s->stream)); s->pending.push_back(ev); }
         NB_HIP(s, hipGetLastError());
+        ++s->steps_done;
+    }
+    return NB_OK;
+}
+
+// ---- block individual time steps (nb_set_block_steps; kernels/block.hip.h) ----------------------
+// Makes the levels current: the start rule on current derivatives (or every body at min_level on a frozen handle; uploaded levels
+// are kept), and the clock of the outer step at 0.
+int ensure_levels(nb_sim* s, const char* who)
+{
+    if (int rc = ensure_derivs(s, who)) return rc;      // also: a changed G re-evaluates them
+    if (s->levels == 2) return NB_OK;
+    void *a = s->acc, *j = s->jerk;
+    uint32_t n = s->n, lmin = s->blk_lmin, L = s->blk_L;
+    int mode = s->levels == 1 ? 2 : s->blk_frozen ? 1 : 0;
+    double eta = s->blk_eta, dt = s->dt;
+    void* args[] = {&a, &j, &s->blk_lev, &s->blk_due, &s->blk_hdr, &n, &mode, &eta, &dt, &lmin, &L};
+    const void* fn = s->f64 ? (const void*)&nb::nb_blk_start<double> : (const void*)&nb::nb_blk_start<float>;
+    (void)hipLaunchKernel(fn, dim3(ceil_div(n, nb::kBlock)), dim3(nb::kBlock), args, 0, s->stream);
+    NB_HIP(s, hipGetLastError());
+    s->levels = 2;
+    return NB_OK;
+}
+
+// The force+jerk launch of one block step: `na` gathered i-rows against all n predicted rows.  Rows per workgroup and j-chunks are
+// chosen so that a small active set still fills the machine (chunks down to one 256-row tile), bounded by the partial rows the
+// handle owns (fj_chunks x n each for accelerations and jerks).  A function of (n, na) alone: the summation order is fixed.
+void launch_blk_fj(nb_sim* s, uint32_t na, uint32_t* chunks_out, void** pa_out, void** pj_out)
+{
+    const uint32_t n = s->n, want = kFjWavesPerSimd * (uint32_t)s->n_cu, tiles = ceil_div(n, (uint32_t)nb::kTile);
+    uint32_t rows = s->f64 ? nb::kFjRows64 : nb::kFjRows;
+    if (!s->f64 && (na <= rows / 2 || (uint64_t)ceil_div(na, rows) * tiles < want)) rows /= 2;      // NG = 1
+    const uint32_t iblocks = ceil_div(na, rows);
+    const uint32_t cap = (uint32_t)std::min<uint64_t>((uint64_t)s->fj_chunks * n / na, tiles);
+    uint32_t c = std::min(ceil_div(want, iblocks), cap);
+    c = std::max(std::max(c, 1u), ceil_div(n, kFjMaxChunk));
+    uint32_t per = ceil_div(ceil_div(n, c), (uint32_t)nb::kTile) * nb::kTile;
+    uint32_t chunks = ceil_div(n, per);
+    void* pa = s->fj_part;
+    void* pj = (char*)s->fj_part + (size_t)4 * s->esz * chunks * na;
+    const void *pos = s->hx, *vel = s->hv;
+    uint32_t nn = n;
+    if (s->f64) {
+        double e2 = s->eps2;
+        void* args[] = {&pos, &vel, &s->blk_act, &na, &pa, &pj, &nn, &per, &e2};
+        (void)hipLaunchKernel((const void*)&nb::nb_blk_fj64<double>, dim3(iblocks, chunks), dim3(nb::kBlock), args, 0, s->stream);
+    } else {
+        float e2 = (float)s->eps2;
+        const void* zr = s->zero_row;
+        void* args[] = {&pos, &vel, &s->blk_act, &na, &pa, &pj, &nn, &per, &e2, &zr};
+        const void* fn = rows == nb::kFjRows ? (const void*)&nb::nb_blk_fj_pk<2> : (const void*)&nb::nb_blk_fj_pk<1>;
+        (void)hipLaunchKernel(fn, dim3(iblocks, chunks), dim3(nb::kBlock), args, 0, s->stream);
+    }
+    *chunks_out = chunks; *pa_out = pa; *pj_out = pj;
+}
+
+// nb_step of a block-step handle: nsteps outer steps of dt.  Per block step: schedule and predict-all (launched right behind the
+// previous corrector), ONE host wait for the header (the active count sizes the next launch), force+jerk of the active bodies,
+// reduce + correct + new levels.
+int block_step(nb_sim* s, uint32_t nsteps)
+{
+    if (int rc = ensure_levels(s, "nb_step")) return rc;
+    const uint32_t L = s->blk_L, end = 1u << L;
+    uint32_t n = s->n, lmin = s->blk_lmin, Lk = L;
+    int frozen = s->blk_frozen ? 1 : 0;
+    double eta = s->blk_eta, dt = s->dt, G = s->G, tick = std::ldexp(s->dt, -(int)L);
+    void *x = s->bodies[0], *v = s->vel, *a = s->acc, *j = s->jerk, *hx = s->hx, *hv = s->hv;
+    auto schedule_and_predict = [&]() {
+        void* sargs[] = {&s->blk_due, &s->blk_lev, &n, &s->blk_act, &s->blk_hdr, &s->blk_hdr_pub};
+        (void)hipLaunchKernel((const void*)&nb::nb_blk_sched<nb::kBlkSched>, dim3(1), dim3(nb::kBlkSched), sargs, 0, s->stream);
+        void* pargs[] = {&x, &v, &a, &j, &s->blk_due, &s->blk_lev, &hx, &hv, &n, &s->blk_hdr, &Lk, &tick};
+        const void* pf = s->f64 ? (const void*)&nb::nb_blk_predict<double> : (const void*)&nb::nb_blk_predict<float>;
+        (void)hipLaunchKernel(pf, dim3(ceil_div(n, nb::kBlock)), dim3(nb::kBlock), pargs, 0, s->stream);
+    };
+    bool ahead = false;      // the first schedule + predict of this outer step went out behind the previous one's last corrector
+    for (uint32_t k = 0; k < nsteps; ++k) {
+        nb_events ev;
+        const bool rec = s->timing && get_events(s, &ev) == 0;
+        if (rec) NB_HIP(s, hipEventRecord(ev.e[0], s->stream));
+        if (!ahead) schedule_and_predict();
+        ahead = false;
+        for (;;) {
+            NB_HIP(s, hipStreamSynchronize(s->stream));
+            uint32_t na = s->blk_hdr_host[nb::kBlkCount], t_next = s->blk_hdr_host[nb::kBlkNext];
+            if (na == 0 || na > n || t_next == 0 || t_next > end)
+                return fail(s, NB_ERR_HIP, "nb_step: block schedule out of range (active " + std::to_string(na) + ", tick " + std::to_string(t_next) + ")");
+            uint32_t chunks = 1;
+            void *pa = nullptr, *pj = nullptr;
+            launch_blk_fj(s, na, &chunks, &pa, &pj);
+            void* cargs[] = {&pa, &pj, &s->blk_act, &na, &chunks, &G, &x, &v, &a, &j, &s->blk_due, &s->blk_lev, &s->blk_hdr, &t_next, &Lk, &lmin, &frozen, &eta, &dt};
+            const void* cf = s->f64 ? (const void*)&nb::nb_blk_correct<double, double> : (const void*)&nb::nb_blk_correct<float, float>;
+            (void)hipLaunchKernel(cf, dim3(ceil_div(na, nb::kBlock)), dim3(nb::kBlock), cargs, 0, s->stream);
+            ++s->blk_steps; s->blk_body_steps += na;
+            if (t_next == end) break;
+            schedule_and_predict();
+            NB_HIP(s, hipGetLastError());
+        }
+        if (rec) { NB_HIP(s, hipEventRecord(ev.e[1], s->stream)); ev.blk = true; s->pending.push_back(ev); }
+        if (k + 1 < nsteps && !s->timing) { schedule_and_predict(); ahead = true; }      // (timed steps launch it inside their own span)
+        NB_HIP(s, hipGetLastError());
+        ++s->blk_outer;
         ++s->steps_done;
     }
     return NB_OK;
@@ -922,7 +1023,8 @@ void nb_destroy(nb_sim* s)
     if (s->sym_spill) (void)hipFree(s->sym_spill);
     if (s->sym_queue) (void)hipFree(s->sym_queue);
     if (s->sym_A) (void)hipFree(s->sym_A);
-    for (void* p : {s->jerk, s->hx, s->hv, s->fj_part}) if (p) (void)hipFree(p);
+    for (void* p : {s->jerk, s->hx, s->hv, s->fj_part, (void*)s->blk_lev, (void*)s->blk_due, (void*)s->blk_act, (void*)s->blk_hdr}) if (p) (void)hipFree(p);
+    if (s->blk_hdr_host) (void)hipHostFree(s->blk_hdr_host);
     if (s->diag) (void)hipFree(s->diag);
     for (auto* b : {&s->fld_pts, &s->fld_acc, &s->fld_phi, &s->fld_part}) if (b->p) (void)hipFree(b->p);
     if (s->zero_row) (void)hipFree(s->zero_row);
@@ -947,6 +1049,7 @@ int nb_upload(nb_sim* s, const void* bodies, const void* vel, const void* accel)
     if (s->hermite) {          // accel is a derived array here: ignored, re-evaluated with the jerk when next needed
         s->uploaded = true;
         s->derivs_ok = false;
+        s->levels = 0;
         return NB_OK;
     }
     if (accel) NB_HIP(s, hipMemcpy(s->acc, (const char*)accel + row * s->sb, row * s->sc, hipMemcpyHostToDevice));
@@ -967,6 +1070,7 @@ int nb_set_params(nb_sim* s, double dt, double G)
 {
     if (!s) return NB_ERR_INVALID;
     if (!(dt == dt) || !(G == G)) return fail(s, NB_ERR_INVALID, "nb_set_params: NaN");
+    if (s->params_set && (dt != s->dt || G != s->G)) s->levels = 0;      // block steps: the levels belong to (dt, G)
     s->dt = dt; s->G = G; s->params_set = true;
     return NB_OK;
 }
@@ -978,7 +1082,7 @@ int nb_step(nb_sim* s, uint32_t nsteps)
     if (!s->params_set) return fail(s, NB_ERR_STATE, "nb_step: nb_set_params has not been called");
     if (!(s->dt > 0.0)) return NB_OK;   // `if (dt > 0)` gate, nbody3d.js:474
     NB_HIP(s, hipSetDevice(s->device));
-    if (s->hermite) return hermite_step(s, nsteps);
+    if (s->hermite) return s->blk ? block_step(s, nsteps) : hermite_step(s, nsteps);
     const bool exchange = s->xfn || s->rccl;
     ensure_pairs(s);      // the j-packed step's position copy, if something outside the step rewrote the positions or G
     if (gm_active(s) && !s->gm_ok) { if (int rc = finish_gather(s)) return rc; }
@@ -1109,8 +1213,8 @@ int nb_device_ptr(nb_sim* s, int which, void** out)
         if (int rc = ensure_derivs(s, "nb_device_ptr")) return rc;
     }
     switch (which) {
-        case NB_BODIES: *out = s->bodies[s->cur]; s->pairs_ok = false; s->gm_ok = false; s->derivs_ok = false; break;   // the caller may write through it
-        case NB_VEL: *out = s->vel; s->derivs_ok = false; break;
+        case NB_BODIES: *out = s->bodies[s->cur]; s->pairs_ok = false; s->gm_ok = false; s->derivs_ok = false; s->levels = 0; break;   // the caller may write through it
+        case NB_VEL: *out = s->vel; s->derivs_ok = false; s->levels = 0; break;
         case NB_ACCEL: *out = s->acc; break;
         case NB_JERK: *out = s->jerk; break;
         default: return fail(s, NB_ERR_INVALID, "nb_device_ptr: unknown array");
@@ -1144,6 +1248,89 @@ int nb_upload_derivs(nb_sim* s, const void* accel, const void* jerk)
     s->derivs_ok = true;
     s->derivs_any_G = !s->params_set;
     s->derivs_G = s->G;
+    return NB_OK;
+}
+
+int nb_set_block_steps(nb_sim* s, const nb_block_steps* cfg)
+{
+    if (!s) return fail(nullptr, NB_ERR_INVALID, "nb_set_block_steps: null handle");
+    if (!s->hermite) return fail(s, NB_ERR_STATE, "nb_set_block_steps: needs a Hermite handle (nb_config.integrator = NB_INT_HERMITE4)");
+    if (!cfg) { s->blk = false; s->levels = 0; return NB_OK; }
+    if (cfg->struct_size != sizeof(nb_block_steps)) return fail(s, NB_ERR_INVALID, "nb_set_block_steps: struct_size must be sizeof(nb_block_steps)");
+    const uint32_t L = cfg->max_level ? cfg->max_level : 20u;
+    if (cfg->max_level > 30) return fail(s, NB_ERR_INVALID, "nb_set_block_steps: max_level is at most 30");
+    if (cfg->min_level > L) return fail(s, NB_ERR_INVALID, "nb_set_block_steps: min_level must not exceed max_level");
+    if (cfg->flags & ~NB_BLOCK_FROZEN) return fail(s, NB_ERR_INVALID, "nb_set_block_steps: unknown flags");
+    if (!(cfg->eta >= 0.0)) return fail(s, NB_ERR_INVALID, "nb_set_block_steps: eta must be > 0 (0: the default 0.02)");
+    NB_HIP(s, hipSetDevice(s->device));
+    // allocated when first switched on (each on its own: a failed call may be repeated)
+    if (!s->blk_lev) NB_HIP(s, hipMalloc((void**)&s->blk_lev, s->n));
+    if (!s->blk_due) NB_HIP(s, hipMalloc((void**)&s->blk_due, sizeof(uint32_t) * s->n));
+    if (!s->blk_act) NB_HIP(s, hipMalloc((void**)&s->blk_act, sizeof(uint32_t) * s->n));
+    if (!s->blk_hdr) {
+        NB_HIP(s, hipMalloc((void**)&s->blk_hdr, sizeof(uint32_t) * nb::kBlkWords));
+        NB_HIP(s, hipMemsetAsync(s->blk_hdr, 0, sizeof(uint32_t) * nb::kBlkWords, s->stream));
+    }
+    if (!s->blk_hdr_host) NB_HIP(s, hipHostMalloc((void**)&s->blk_hdr_host, sizeof(uint32_t) * nb::kBlkWords, hipHostMallocDefault));
+    if (!s->blk_hdr_pub) NB_HIP(s, hipHostGetDevicePointer((void**)&s->blk_hdr_pub, s->blk_hdr_host, 0));
+    s->blk = true;
+    s->blk_L = L; s->blk_lmin = cfg->min_level; s->blk_frozen = (cfg->flags & NB_BLOCK_FROZEN) != 0;
+    s->blk_eta = cfg->eta > 0.0 ? cfg->eta : 0.02;
+    s->levels = 0;
+    return NB_OK;
+}
+
+int nb_block_stats(nb_sim* s, struct nb_block_stats* out, int reset)
+{
+    if (!s) return fail(nullptr, NB_ERR_INVALID, "nb_block_stats: null handle");
+    if (!s->hermite) return fail(s, NB_ERR_STATE, "nb_block_stats: needs a Hermite handle (nb_config.integrator = NB_INT_HERMITE4)");
+    if (!out || out->struct_size != sizeof(struct nb_block_stats)) return fail(s, NB_ERR_INVALID, "nb_block_stats: set out->struct_size to sizeof(nb_block_stats)");
+    std::memset(out, 0, sizeof(*out));
+    out->struct_size = sizeof(*out);
+    out->enabled = s->blk ? 1u : 0u;
+    if (!s->blk_hdr) return NB_OK;
+    NB_HIP(s, hipSetDevice(s->device));
+    uint32_t words[nb::kBlkWords];
+    NB_HIP(s, hipStreamSynchronize(s->stream));
+    NB_HIP(s, hipMemcpy(words, s->blk_hdr, sizeof words, hipMemcpyDeviceToHost));
+    out->outer_steps = s->blk_outer; out->block_steps = s->blk_steps; out->body_steps = s->blk_body_steps;
+    out->clamped = words[nb::kBlkClamped];
+    out->finest_level = words[nb::kBlkFinest];
+    if (reset) {
+        s->blk_outer = s->blk_steps = s->blk_body_steps = 0;
+        NB_HIP(s, hipMemsetAsync(s->blk_hdr, 0, sizeof(uint32_t) * nb::kBlkWords, s->stream));
+    }
+    return NB_OK;
+}
+
+int nb_download_levels(nb_sim* s, uint8_t* levels)
+{
+    if (!s) return fail(nullptr, NB_ERR_INVALID, "nb_download_levels: null handle");
+    if (!s->hermite) return fail(s, NB_ERR_STATE, "nb_download_levels: needs a Hermite handle (nb_config.integrator = NB_INT_HERMITE4)");
+    if (!levels) return fail(s, NB_ERR_INVALID, "nb_download_levels: levels is NULL");
+    if (!s->blk) return fail(s, NB_ERR_STATE, "nb_download_levels: block steps are not switched on (nb_set_block_steps)");
+    if (!s->uploaded) return fail(s, NB_ERR_STATE, "nb_download_levels: nothing uploaded yet");
+    NB_HIP(s, hipSetDevice(s->device));
+    if (int rc = ensure_levels(s, "nb_download_levels")) return rc;
+    NB_HIP(s, hipStreamSynchronize(s->stream));
+    NB_HIP(s, hipMemcpy(levels, s->blk_lev, s->n, hipMemcpyDeviceToHost));
+    return NB_OK;
+}
+
+int nb_upload_levels(nb_sim* s, const uint8_t* levels)
+{
+    if (!s) return fail(nullptr, NB_ERR_INVALID, "nb_upload_levels: null handle");
+    if (!s->hermite) return fail(s, NB_ERR_STATE, "nb_upload_levels: needs a Hermite handle (nb_config.integrator = NB_INT_HERMITE4)");
+    if (!levels) return fail(s, NB_ERR_INVALID, "nb_upload_levels: levels is NULL");
+    if (!s->blk) return fail(s, NB_ERR_STATE, "nb_upload_levels: block steps are not switched on (nb_set_block_steps)");
+    if (!s->uploaded) return fail(s, NB_ERR_STATE, "nb_upload_levels: nb_upload has not been called");
+    for (uint32_t i = 0; i < s->n; ++i)
+        if (levels[i] < s->blk_lmin || levels[i] > s->blk_L)
+            return fail(s, NB_ERR_INVALID, "nb_upload_levels: levels[" + std::to_string(i) + "] = " + std::to_string(levels[i]) + " is outside [min_level, max_level]");
+    NB_HIP(s, hipSetDevice(s->device));
+    NB_HIP(s, hipStreamSynchronize(s->stream));
+    NB_HIP(s, hipMemcpy(s->blk_lev, levels, s->n, hipMemcpyHostToDevice));
+    s->levels = 1;      // the start kernel keeps these levels and starts the clock (due_i = s_i)
     return NB_OK;
 }
 
@@ -1187,6 +1374,11 @@ static int collect_times(nb_sim* s, nb_step_timing* t)
     uint32_t nx = 0, nrs = 0;
     for (auto& ev : s->pending) {
         float a = 0, b = 0, c = 0, d = 0, r1 = 0, r2 = 0, sp = 0;
+        if (ev.blk) {       // one outer step of a block-step handle: its whole span is force time (as a fused step's)
+            NB_HIP(s, hipEventElapsedTime(&a, ev.e[0], ev.e[1]));
+            f += a; span += a;
+            continue;
+        }
         if (s->hermite) {
             // e6 predict e0 force+jerk kernel, reduce e1 correct e2
             float pr = 0, co = 0;

@@ -19,7 +19,7 @@
 // Rank form of the symmetric pass (plain records on the engine stream): e[0] force pass e[7] nb_sym_reduce e[1]
 // ncclReduceScatter e[6] integrate e[2] ncclAllGather e[5]; with the overlapped gather the force pass is two launches,
 // e[0]..e[7] (own-row sweeps, issued before the wait) and e[3]..e[4] (the rest), and `rs` says the e[7]/e[1]/e[6] chain is valid.
-struct nb_events { hipEvent_t e[8]; bool two, xchg, rs; };
+struct nb_events { hipEvent_t e[8]; bool two, xchg, rs, blk; };   // blk: one outer step of a block-step handle, e[0]..e[1]
 
 struct nb_rccl;   // nb_comm.hip
 
@@ -154,6 +154,19 @@ struct nb_sim {
     bool derivs_ok = false;        // acc / jerk belong to (bodies, vel) and derivs_G
     bool derivs_any_G = false;     // nb_upload_derivs before the first nb_set_params: the derivatives belong to whatever G comes
     double derivs_G = 0.0;
+    // nb_set_block_steps: block individual time steps (kernels/block.hip.h).  Allocated when first switched on.
+    bool blk = false, blk_frozen = false;
+    uint32_t blk_L = 20, blk_lmin = 0;
+    double blk_eta = 0.02;
+    uint8_t* blk_lev = nullptr;      // device: level per body
+    uint32_t* blk_due = nullptr;     // device: tick of the body's next corrector
+    uint32_t* blk_act = nullptr;     // device: the active list of the block step in flight
+    uint32_t* blk_hdr = nullptr;     // device: nb::kBlkWords header words
+    uint32_t* blk_hdr_host = nullptr;   // pinned host copy (count, next block time) the step loop reads after its wait
+    uint32_t* blk_hdr_pub = nullptr;    // the device's address of blk_hdr_host: nb_blk_sched stores into it
+    int levels = 0;                  // 0: stale; 1: blk_lev came from nb_upload_levels, the outer step's clock (blk_due) is not started yet;
+                                     // 2: blk_lev / blk_due belong to the state, dt, G and the configuration
+    uint64_t blk_outer = 0, blk_steps = 0, blk_body_steps = 0;
 };
 
 namespace nbi {

@@ -61,6 +61,10 @@ static int (*p_field_eval)(nb_sim *, const nb_field_request *);
 static int (*p_multi_field_eval)(nb_multi *, const nb_field_request *);
 static int (*p_download_jerk)(nb_sim *, void *);                        /* the Hermite additions within ABI 2.4: optional symbols */
 static int (*p_upload_derivs)(nb_sim *, const void *, const void *);
+static int (*p_set_block_steps)(nb_sim *, const nb_block_steps *);      /* block time steps, also within ABI 2.4: optional symbols */
+static int (*p_block_stats)(nb_sim *, struct nb_block_stats *, int);
+static int (*p_download_levels)(nb_sim *, uint8_t *);
+static int (*p_upload_levels)(nb_sim *, const uint8_t *);
 
 /* one JS handle = a single-device nb_sim or a single-process multi-device nb_multi */
 typedef struct { nb_sim *sim; nb_multi *multi; uint32_t n; int f64; } handle_t;
@@ -141,6 +145,10 @@ static napi_value js_load(napi_env env, napi_callback_info info)
         /* present from the library that has NB_INT_HERMITE4; an older 2.4 library still loads */
         *(void **)(&p_download_jerk) = dlsym(h, "nb_download_jerk");
         *(void **)(&p_upload_derivs) = dlsym(h, "nb_upload_derivs");
+        *(void **)(&p_set_block_steps) = dlsym(h, "nb_set_block_steps");
+        *(void **)(&p_block_stats) = dlsym(h, "nb_block_stats");
+        *(void **)(&p_download_levels) = dlsym(h, "nb_download_levels");
+        *(void **)(&p_upload_levels) = dlsym(h, "nb_upload_levels");
         g_lib = h;
     }
     if (p_abi_version() != NB_ABI_VERSION) { napi_throw_error(env, "NB_ABI", "ABI version mismatch"); return NULL; }
@@ -655,6 +663,106 @@ static napi_value js_upload_derivs(napi_env env, napi_callback_info info)
     return undefined(env);
 }
 
+/* the single-device handle of a block-step call, or NULL with an exception pending */
+static handle_t *block_handle(napi_env env, napi_value v, const void *sym, const char *where)
+{
+    handle_t *h = get_handle(env, v); if (!h) return NULL;
+    if (h->multi || !sym) { throw_msg(env, NB_ERR_STATE, "needs a single-device Hermite handle and a library with nb_set_block_steps", where); return NULL; }
+    return h;
+}
+
+/* setBlockSteps(handle, null) | setBlockSteps(handle, eta, maxLevel, minLevel, frozen): nb_set_block_steps (eta 0 / maxLevel 0: the defaults) */
+static napi_value js_set_block_steps(napi_env env, napi_callback_info info)
+{
+    size_t argc = 5; napi_value argv[5];
+    CHECK_NAPI(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    if (argc < 2) { napi_throw_type_error(env, NULL, "setBlockSteps(handle, null | eta, maxLevel, minLevel, frozen)"); return NULL; }
+    handle_t *h = block_handle(env, argv[0], *(void **)&p_set_block_steps, "nb_set_block_steps"); if (!h) return NULL;
+    napi_valuetype t; napi_typeof(env, argv[1], &t);
+    int rc;
+    if (t == napi_null || t == napi_undefined) rc = p_set_block_steps(h->sim, NULL);
+    else {
+        if (argc < 5) { napi_throw_type_error(env, NULL, "setBlockSteps(handle, eta, maxLevel, minLevel, frozen)"); return NULL; }
+        nb_block_steps cfg;
+        memset(&cfg, 0, sizeof cfg);
+        cfg.struct_size = sizeof cfg;
+        uint32_t u = 0; bool frozen = false;
+        CHECK_NAPI(env, napi_get_value_double(env, argv[1], &cfg.eta));
+        CHECK_NAPI(env, napi_get_value_uint32(env, argv[2], &u)); cfg.max_level = u;
+        CHECK_NAPI(env, napi_get_value_uint32(env, argv[3], &u)); cfg.min_level = u;
+        CHECK_NAPI(env, napi_get_value_bool(env, argv[4], &frozen));
+        cfg.flags = frozen ? NB_BLOCK_FROZEN : 0u;
+        rc = p_set_block_steps(h->sim, &cfg);
+    }
+    if (rc != NB_OK) return throw_nb(env, rc, h->sim, "nb_set_block_steps");
+    return undefined(env);
+}
+
+/* blockStats(handle, reset) -> {enabled, outerSteps, blockSteps, bodySteps, clamped, finestLevel} (counts as doubles) */
+static napi_value js_block_stats(napi_env env, napi_callback_info info)
+{
+    size_t argc = 2; napi_value argv[2];
+    CHECK_NAPI(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    if (argc < 1) { napi_throw_type_error(env, NULL, "blockStats(handle, reset)"); return NULL; }
+    handle_t *h = block_handle(env, argv[0], *(void **)&p_block_stats, "nb_block_stats"); if (!h) return NULL;
+    bool reset = false;
+    if (argc > 1) napi_get_value_bool(env, argv[1], &reset);
+    struct nb_block_stats st;
+    memset(&st, 0, sizeof st);
+    st.struct_size = sizeof st;
+    int rc = p_block_stats(h->sim, &st, reset ? 1 : 0);
+    if (rc != NB_OK) return throw_nb(env, rc, h->sim, "nb_block_stats");
+    napi_value o, v;
+    CHECK_NAPI(env, napi_create_object(env, &o));
+    napi_get_boolean(env, st.enabled != 0, &v); napi_set_named_property(env, o, "enabled", v);
+    napi_create_double(env, (double)st.outer_steps, &v); napi_set_named_property(env, o, "outerSteps", v);
+    napi_create_double(env, (double)st.block_steps, &v); napi_set_named_property(env, o, "blockSteps", v);
+    napi_create_double(env, (double)st.body_steps, &v); napi_set_named_property(env, o, "bodySteps", v);
+    napi_create_double(env, (double)st.clamped, &v); napi_set_named_property(env, o, "clamped", v);
+    napi_create_uint32(env, st.finest_level, &v); napi_set_named_property(env, o, "finestLevel", v);
+    return o;
+}
+
+/* a Uint8Array of n elements */
+static int get_levels(napi_env env, napi_value v, const handle_t *h, uint8_t **out)
+{
+    bool is_ta = false; napi_is_typedarray(env, v, &is_ta);
+    napi_typedarray_type tt = napi_int8_array; size_t len = 0; void *data = NULL; napi_value ab; size_t off;
+    if (!is_ta || napi_get_typedarray_info(env, v, &tt, &len, &data, &ab, &off) != napi_ok || tt != napi_uint8_array) {
+        napi_throw_type_error(env, NULL, "levels must be a Uint8Array of n elements"); return 0;
+    }
+    if (len != (size_t)h->n) { napi_throw_range_error(env, NULL, "levels must be a Uint8Array of n elements"); return 0; }
+    *out = (uint8_t *)data; return 1;
+}
+
+/* downloadLevels(handle, levelsOut): nb_download_levels -- n levels, written in place */
+static napi_value js_download_levels(napi_env env, napi_callback_info info)
+{
+    size_t argc = 2; napi_value argv[2];
+    CHECK_NAPI(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    if (argc < 2) { napi_throw_type_error(env, NULL, "downloadLevels(handle, levelsOut)"); return NULL; }
+    handle_t *h = block_handle(env, argv[0], *(void **)&p_download_levels, "nb_download_levels"); if (!h) return NULL;
+    uint8_t *lv;
+    if (!get_levels(env, argv[1], h, &lv)) return NULL;
+    int rc = p_download_levels(h->sim, lv);
+    if (rc != NB_OK) return throw_nb(env, rc, h->sim, "nb_download_levels");
+    return undefined(env);
+}
+
+/* uploadLevels(handle, levels): nb_upload_levels -- the last call of a block-step checkpoint restore */
+static napi_value js_upload_levels(napi_env env, napi_callback_info info)
+{
+    size_t argc = 2; napi_value argv[2];
+    CHECK_NAPI(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    if (argc < 2) { napi_throw_type_error(env, NULL, "uploadLevels(handle, levels)"); return NULL; }
+    handle_t *h = block_handle(env, argv[0], *(void **)&p_upload_levels, "nb_upload_levels"); if (!h) return NULL;
+    uint8_t *lv;
+    if (!get_levels(env, argv[1], h, &lv)) return NULL;
+    int rc = p_upload_levels(h->sim, lv);
+    if (rc != NB_OK) return throw_nb(env, rc, h->sim, "nb_upload_levels");
+    return undefined(env);
+}
+
 static napi_value init_module(napi_env env, napi_value exports)
 {
     static const struct { const char *name; napi_callback fn; } fns[] = {
@@ -664,6 +772,8 @@ static napi_value init_module(napi_env env, napi_value exports)
         {"variant", js_variant}, {"diagnostics", js_diagnostics}, {"stepTimes", js_step_times},
         {"collectiveInfo", js_collective_info}, {"requestFrame", js_request_frame}, {"frame", js_frame}, {"planQuery", js_plan_query},
         {"fieldEval", js_field_eval}, {"downloadJerk", js_download_jerk}, {"uploadDerivs", js_upload_derivs},
+        {"setBlockSteps", js_set_block_steps}, {"blockStats", js_block_stats}, {"downloadLevels", js_download_levels},
+        {"uploadLevels", js_upload_levels},
     };
     for (size_t i = 0; i < sizeof fns / sizeof fns[0]; ++i) {
         napi_value f;

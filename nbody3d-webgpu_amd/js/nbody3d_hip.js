@@ -17,6 +17,8 @@
  *   G / dt / pause()       nbody3d.js:6-7, util.js:36-64 (dt and G are mutable
  *                          between frames; pause saves dt and sets it to 0)
  *   readJerk()             (no reference analogue) the jerk of a {integrator: 'hermite4'} simulation
+ *   setBlockSteps() / blockStats() / readLevels() / uploadLevels()
+ *                          (no reference analogue) block individual time steps of a 'hermite4' simulation
  *   requestFrame()/frame() nbody3d.js:408-415,482-487 what the render pass reads each frame
  *                          (bodies + speed), delivered asynchronously to a host-side viewer
  *
@@ -188,6 +190,38 @@ class Simulation {
     const j = new this.ArrayType(4 * this.nBodies);
     addon.downloadJerk(this._h, j);
     return j;
+  }
+
+  /** Block individual time steps of a 'hermite4' simulation (nb_set_block_steps; no reference analogue): every body steps by
+   *  dt / 2^level, minLevel <= level <= maxLevel, chosen from its own derivatives with the accuracy parameter eta; step() and
+   *  simulate() still advance by whole dt.  {eta, maxLevel, minLevel, frozen}: missing eta / maxLevel take the library's defaults
+   *  (0.02, 20); frozen keeps the levels as initialised or uploaded.  setBlockSteps(null) switches back to one shared step. */
+  setBlockSteps(options) {
+    this._need();
+    if (options === null || options === undefined) { addon.setBlockSteps(this._h, null); return this; }
+    addon.setBlockSteps(this._h, options.eta || 0, (options.maxLevel || 0) >>> 0, (options.minLevel || 0) >>> 0, !!options.frozen);
+    return this;
+  }
+
+  /** {enabled, outerSteps, blockSteps, bodySteps, clamped, finestLevel} since the last reset (nb_block_stats). */
+  blockStats(reset) { this._need(); return addon.blockStats(this._h, !!reset); }
+
+  /** The level of every body (Uint8Array of N; nb_download_levels), initialised first if not current. */
+  readLevels() {
+    this._need();
+    addon.setParams(this._h, this.dt, this.G);
+    const l = new Uint8Array(this.nBodies);
+    addon.downloadLevels(this._h, l);
+    return l;
+  }
+
+  /** The last call of a block-step checkpoint restore: restore({bodies, vel, accel, jerk}), setBlockSteps(...), uploadLevels(levels). */
+  uploadLevels(levels) {
+    this._need();
+    const l = levels instanceof Uint8Array ? levels : Uint8Array.from(levels);
+    if (l.length !== this.nBodies) throw new RangeError('levels: expected ' + this.nBodies + ' elements, got ' + l.length);
+    addon.uploadLevels(this._h, l);
+    return this;
   }
 
   /** util.js:230-244: write the three arrays into the EXISTING buffers (N must match).  A 'hermite4' simulation ignores accel on its

@@ -78,6 +78,19 @@ class nb_field_request(C.Structure):        # include/nbody3d_hip.h (ABI 2.4)
                 ("points", C.c_void_p), ("accel", C.c_void_p), ("phi", C.c_void_p)]
 
 
+NB_BLOCK_FROZEN = 1
+
+
+class nb_block_steps(C.Structure):          # include/nbody3d_hip.h (block individual time steps of a Hermite handle)
+    _fields_ = [("struct_size", C.c_uint32), ("max_level", C.c_uint32), ("min_level", C.c_uint32), ("flags", C.c_uint32),
+                ("eta", C.c_double)]
+
+
+class nb_block_stats(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("enabled", C.c_uint32), ("outer_steps", C.c_uint64), ("block_steps", C.c_uint64),
+                ("body_steps", C.c_uint64), ("clamped", C.c_uint64), ("finest_level", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 EXCHANGE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p)
 EXCHANGE_WAIT_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p)
 
@@ -91,7 +104,8 @@ SYMBOLS = ["nb_abi_version", "nb_device_count", "nb_create", "nb_destroy", "nb_u
            "nb_multi_diagnostics", "nb_multi_set_collective", "nb_multi_collective_info",
            "nb_rccl_unique_id", "nb_rccl_attach", "nb_rccl_detach", "nb_rccl_info",
            "nb_step_times", "nb_step_times2", "nb_integrate_pass", "nb_force_pass", "nb_frame_request", "nb_frame_acquire", "nb_shape_info", "nb_plan_query",
-           "nb_abi_minor", "nb_field_eval", "nb_multi_field_eval", "nb_download_jerk", "nb_upload_derivs"]
+           "nb_abi_minor", "nb_field_eval", "nb_multi_field_eval", "nb_download_jerk", "nb_upload_derivs",
+           "nb_set_block_steps", "nb_block_stats", "nb_download_levels", "nb_upload_levels"]
 
 _lib = None
 
@@ -166,6 +180,11 @@ def load_library():
     if hasattr(L, "nb_download_jerk"):      # the Hermite additions within 2.4: detected by the symbol, not by the minor
         L.nb_download_jerk.argtypes = [vp, vp]
         L.nb_upload_derivs.argtypes = [vp, vp, vp]
+    if hasattr(L, "nb_set_block_steps"):    # block time steps, also within 2.4 and detected by the symbol
+        L.nb_set_block_steps.argtypes = [vp, C.POINTER(nb_block_steps)]
+        L.nb_block_stats.argtypes = [vp, C.POINTER(nb_block_stats), C.c_int]
+        L.nb_download_levels.argtypes = [vp, vp]
+        L.nb_upload_levels.argtypes = [vp, vp]
     _lib = L
     return L
 
@@ -442,6 +461,57 @@ class Simulation:
             raise NBodyError(1, "upload_derivs(): the loaded library has no nb_upload_derivs")
         a, j = self._arr(accel, "accel"), self._arr(jerk, "jerk")
         self._check(self._L.nb_upload_derivs(self._h, _ptr(a), _ptr(j)))
+        return self
+
+    # -- block individual time steps of a Hermite handle -----------------------
+    def _need_block(self, what):
+        if not hasattr(self._L, "nb_set_block_steps"):
+            raise NBodyError(1, "%s: the loaded library has no nb_set_block_steps" % what)
+
+    def set_block_steps(self, *args, **kw):
+        """set_block_steps(eta=None, max_level=None, min_level=0, frozen=False): nb_set_block_steps -- every body steps by
+        dt / 2^level, level in [min_level, max_level], chosen from its own (a, j, a2, a3) with the accuracy parameter eta (None:
+        the library's defaults, eta 0.02 and max_level 20); frozen=True keeps the levels as initialised or uploaded.  step() /
+        simulate() still advance by whole dt.  set_block_steps(None) switches back to one shared step."""
+        self._need_block("set_block_steps()")
+        if args == (None,) and not kw:
+            self._check(self._L.nb_set_block_steps(self._h, None))
+            return self
+
+        def bind(eta=None, max_level=None, min_level=0, frozen=False):
+            return eta, max_level, min_level, frozen
+        eta, max_level, min_level, frozen = bind(*args, **kw)
+        cfg = nb_block_steps()
+        cfg.struct_size = C.sizeof(nb_block_steps)
+        cfg.max_level = 0 if max_level is None else int(max_level)
+        cfg.min_level = int(min_level)
+        cfg.flags = NB_BLOCK_FROZEN if frozen else 0
+        cfg.eta = 0.0 if eta is None else float(eta)
+        self._check(self._L.nb_set_block_steps(self._h, C.byref(cfg)))
+        return self
+
+    def block_stats(self, reset=False):
+        """nb_block_stats: {enabled, outer_steps, block_steps, body_steps, clamped, finest_level} since the last reset."""
+        self._need_block("block_stats()")
+        st = nb_block_stats()
+        st.struct_size = C.sizeof(nb_block_stats)
+        self._check(self._L.nb_block_stats(self._h, C.byref(st), 1 if reset else 0))
+        return {k: int(getattr(st, k)) for k in ("enabled", "outer_steps", "block_steps", "body_steps", "clamped", "finest_level")}
+
+    def read_levels(self):
+        """nb_download_levels: the level of every body (uint8, shape (N,)); initialises them first if they are not current."""
+        self._need_block("read_levels()")
+        out = np.zeros(self.n, np.uint8)
+        self._check(self._L.nb_download_levels(self._h, _ptr(out)))
+        return out
+
+    def upload_levels(self, levels):
+        """nb_upload_levels: the last call of a checkpoint restore (init, upload_derivs, set_block_steps, upload_levels)."""
+        self._need_block("upload_levels()")
+        lv = np.ascontiguousarray(levels, np.uint8)
+        if lv.shape != (self.n,):
+            raise ValueError("levels must have shape (%d,)" % self.n)
+        self._check(self._L.nb_upload_levels(self._h, _ptr(lv)))
         return self
 
     # -- multi-GPU / measurement / diagnostics ------------------------------

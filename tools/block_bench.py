@@ -1,0 +1,181 @@
+#!/usr/bin/env python3
+"""Measures block individual time steps (Simulation.set_block_steps) on one GPU and prints ONE JSON line.
+
+  (a) full     one outer step with every body pinned at level 0 (ONE block step with |A| = N: nb_blk_sched, the host's wait,
+               nb_blk_predict, nb_blk_fj_pk / nb_blk_fj64 over the full gathered set, nb_blk_correct) against nb_force_pass of a plain
+               Hermite handle (nb_fj_pk / nb_fj64 + nb_fj_reduce) and against its whole shared step, in turns, --rounds times; N = --full-n,
+               f32 and f64.  The kernels alone: run this part under `rocprofv3 --kernel-trace --stats -- python tools/block_bench.py --only a`.
+  (b) end2end  ic.plummer at each N of --sizes with 1 % of the bodies re-placed as tight pairs (the two bodies at +-0.02 about the pair's
+               centre, on the circular orbit of their masses): wall time of one time unit with block steps (eta 0.02, outer step
+               --outer-dt), |dE/E0| from nb_diagnostics, body_steps, block_steps and the level histogram; then shared-step Hermite at
+               dt = 2^-k, k rising from --shared-from until its |dE/E0| is no worse (at most --shared-to: past that the run is recorded as
+               not reached), with each run's wall time.  --pair-half / --eps2 make the pairs hard (e.g. 0.001 and 1e-8: a period of ~0.1
+               time units at N = 16,384 instead of ~4.5), the case the step hierarchy is for
+  (c) small    microseconds per block step with |A| = 64 at N = --full-n: frozen levels, 64 bodies at level 6 and the rest at level 0
+               (64 block steps per outer step, 63 of them with |A| = 64) minus the same outer step with every body at level 0, over 63
+
+Needs a GPU (no fallback)."""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.normpath(os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
+sys.path.insert(0, os.path.join(ROOT, "nbody3d-webgpu_amd"))
+from nbody3d_amd import Simulation, capi, ic  # noqa: E402
+
+
+def hermite(n, prec, eps2=None):
+    return Simulation(n, precision=prec, integrator="hermite4", eps2=eps2)
+
+
+def with_tight_pairs(n, seed=1, frac=0.01, half=0.02):
+    """ic.plummer with frac * n bodies (consecutive pairs from body 0) re-placed: +-half along x about the pair's centre, velocities
+    +-w along y about the pair's mean velocity, w m_other / (m0 + m1) each with w = sqrt((m0 + m1) / (2 half)) (G = 1)."""
+    b, v = ic.plummer(n, seed=seed)
+    b, v = b.astype(np.float64), v.astype(np.float64)
+    for p in range(int(frac * n) // 2):
+        i, k = 2 * p, 2 * p + 1
+        m0, m1 = b[i, 3], b[k, 3]
+        c = (m0 * b[i, :3] + m1 * b[k, :3]) / (m0 + m1)
+        u = (m0 * v[i, :3] + m1 * v[k, :3]) / (m0 + m1)
+        w = np.sqrt((m0 + m1) / (2 * half))
+        b[i, :3], b[k, :3] = c + (half, 0, 0), c - (half, 0, 0)
+        v[i, :3], v[k, :3] = u + (0, w * m1 / (m0 + m1), 0), u - (0, w * m0 / (m0 + m1), 0)
+    return b.astype(np.float32), v.astype(np.float32)
+
+
+def wall(sim, steps):
+    sim.sync()
+    t = time.perf_counter()
+    sim.simulate(steps)
+    sim.sync()
+    return time.perf_counter() - t
+
+
+def energy(sim):
+    ke, pe, _ = sim.diagnostics()
+    return ke + pe
+
+
+def part_a(args, out):
+    n = args.full_n
+    b, v = ic.plummer(n, seed=1)
+    for prec in ("f32", "f64"):
+        with hermite(n, prec) as blk, hermite(n, prec) as plain:
+            for s in (blk, plain):
+                s.init(b, v)
+                s.set_params(1e-3, 1.0)
+            blk.set_block_steps(max_level=0, frozen=True)
+            est = plain.force_pass(2)
+            reps = max(4, int(np.ceil(args.min_seconds * 1e3 / est)))
+            got = {"force_pass_ms": [], "shared_step_ms": [], "block_step_ms": []}
+            for _ in range(args.rounds):
+                plain.force_pass(reps)
+                got["force_pass_ms"].append(plain.force_pass(reps))
+                wall(plain, reps)
+                got["shared_step_ms"].append(1e3 * wall(plain, reps) / reps)
+                wall(blk, reps)
+                got["block_step_ms"].append(1e3 * wall(blk, reps) / reps)
+            r = {k: {"median": float(np.median(x)), "best": min(x), "all": x} for k, x in got.items()}
+            r["variant"] = plain.variant
+            r["block_over_force_pass"] = r["block_step_ms"]["median"] / r["force_pass_ms"]["median"]
+            r["block_over_shared_step"] = r["block_step_ms"]["median"] / r["shared_step_ms"]["median"]
+            out["full"]["%s_%d" % (prec, n)] = r
+
+
+def part_b(args, out):
+    for n in args.sizes:
+        b, v = with_tight_pairs(n, half=args.pair_half)
+        outer = int(round(1.0 / args.outer_dt))
+        r = {"n": n, "pairs": int(0.01 * n) // 2, "precision": args.precision, "outer_dt": args.outer_dt, "eta": 0.02,
+             "pair_half": args.pair_half, "eps2": args.eps2}
+        with hermite(n, args.precision, args.eps2) as sim:
+            sim.init(b, v)
+            sim.set_params(args.outer_dt, 1.0)
+            sim.set_block_steps(eta=0.02, max_level=args.max_level)
+            e0 = energy(sim)
+            lev0 = sim.read_levels()
+            sim.block_stats(reset=True)
+            t = wall(sim, outer)
+            r["block"] = {"wall_s": t, "dE": abs((energy(sim) - e0) / e0), "stats": sim.block_stats(),
+                          "levels_start": np.bincount(lev0).tolist(), "levels_end": np.bincount(sim.read_levels()).tolist()}
+        r["block"]["full_force_equivalents"] = r["block"]["stats"]["body_steps"] / n
+        r["shared"] = []
+        for k in range(args.shared_from, args.shared_to + 1):
+            with hermite(n, args.precision, args.eps2) as sim:
+                sim.init(b, v)
+                sim.set_params(2.0 ** -k, 1.0)
+                e0 = energy(sim)
+                t = wall(sim, 2 ** k)
+                row = {"level": k, "wall_s": t, "dE": abs((energy(sim) - e0) / e0)}
+            r["shared"].append(row)
+            if row["dE"] <= r["block"]["dE"]:
+                r["shared_match"] = row
+                r["speedup"] = row["wall_s"] / r["block"]["wall_s"]
+                break
+        else:
+            r["shared_match"] = None      # not reached by 2^-shared_to: the speedup over the LAST run is a lower bound
+            r["speedup_at_least"] = r["shared"][-1]["wall_s"] / r["block"]["wall_s"]
+        out["end2end"].append(r)
+
+
+def part_c(args, out):
+    n, L, k = args.full_n, 6, 64
+    b, v = ic.plummer(n, seed=1)
+    lev = np.zeros(n, np.uint8)
+    lev[np.random.default_rng(5).choice(n, k, replace=False)] = L
+    for prec in ("f32", "f64"):
+        t = {}
+        with hermite(n, prec) as sim:
+            sim.init(b, v)
+            sim.set_params(1e-3, 1.0)
+            for name, levels in (("all_level0", np.zeros(n, np.uint8)), ("64_at_level6", lev)):
+                sim.set_block_steps(max_level=L, frozen=True)
+                sim.upload_levels(levels)
+                wall(sim, 4)
+                sim.block_stats(reset=True)
+                runs = []
+                for _ in range(args.rounds):
+                    sim.upload_levels(levels)      # the same state of the levels' clock before every timed run
+                    runs.append(wall(sim, args.small_outer) / args.small_outer)
+                st = sim.block_stats(reset=True)
+                t[name] = {"outer_step_us": 1e6 * float(np.median(runs)), "block_steps_per_outer": st["block_steps"] / st["outer_steps"],
+                           "body_steps_per_outer": st["body_steps"] / st["outer_steps"]}
+        t["us_per_small_block_step"] = (t["64_at_level6"]["outer_step_us"] - t["all_level0"]["outer_step_us"]) / (2 ** L - 1)
+        out["small"]["%s_%d" % (prec, n)] = t
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--only", choices=["a", "b", "c"], nargs="*", default=["a", "b", "c"])
+    ap.add_argument("--full-n", type=int, default=65536)
+    ap.add_argument("--sizes", type=int, nargs="*", default=[16384, 65536])
+    ap.add_argument("--precision", default="f32", choices=["f32", "f64"])
+    ap.add_argument("--pair-half", type=float, default=0.02, help="(b): half the separation of a pair (the issue's workload: 0.02)")
+    ap.add_argument("--eps2", type=float, default=None, help="(b): softening (default: the engine's 1e-4)")
+    ap.add_argument("--outer-dt", type=float, default=2.0 ** -4)
+    ap.add_argument("--max-level", type=int, default=16)
+    ap.add_argument("--shared-from", type=int, default=6)
+    ap.add_argument("--shared-to", type=int, default=12)
+    ap.add_argument("--small-outer", type=int, default=20)
+    ap.add_argument("--min-seconds", type=float, default=0.3)
+    ap.add_argument("--rounds", type=int, default=3)
+    args = ap.parse_args()
+    if capi.device_count() < 1:
+        sys.exit("block_bench: no GPU")
+    out = {"tool": "block_bench", "full": {}, "end2end": [], "small": {}}
+    if "a" in args.only:
+        part_a(args, out)
+    if "b" in args.only:
+        part_b(args, out)
+    if "c" in args.only:
+        part_c(args, out)
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()
