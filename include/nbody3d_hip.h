@@ -49,7 +49,9 @@ extern "C" {
                                             library ignores it), NB_INT_*, nb_download_jerk, nb_upload_derivs, NB_JERK.  A client detects them by
                                             the presence of the symbol nb_download_jerk (dlsym), not by the minor
                              2.4 (round 8)  likewise within 2.4: nb_set_block_steps, nb_block_stats, nb_download_levels, nb_upload_levels,
-                                            NB_BLOCK_*.  Detected by the presence of the symbol nb_set_block_steps */
+                                            NB_BLOCK_*.  Detected by the presence of the symbol nb_set_block_steps
+                             2.4 (round 9)  likewise within 2.4: nb_neighbors, nb_multi_neighbors, nb_neighbors_shape, nb_neighbor_request, NB_NBR_*.
+                                            Detected by the presence of the symbol nb_neighbors */
 
 typedef struct nb_sim nb_sim; /* opaque */
 
@@ -543,6 +545,63 @@ int nb_field_eval(nb_sim *s, const nb_field_request *req);
 /* The same on a multi-shard system.  The bodies are replicated on every shard after a step, so the request is evaluated on
  * shard 0 (its device, its stream); first_body counts the caller's UNPADDED rows. */
 int nb_multi_field_eval(nb_multi *m, const nb_field_request *req);
+
+/* ---- neighbour queries (added within ABI 2.4; no reference analogue) ---------------------------
+ * For each of M points: the NEAREST of the handle's N bodies, its squared distance, and the NUMBER of bodies inside a radius --
+ * M x N ordered pairs, what the collisional codes return from their O(N^2) pass: the start of close-pair detection, of a
+ * neighbour scheme, of a local-density estimate.
+ *   - Distance: the plain squared distance, NO softening, in the handle's precision:
+ *         dx = x_j - p_x, dy, dz likewise;   d2 = fma(dz, dz, fma(dy, dy, dx * dx))
+ *     binary32 on f32 handles, fp64 throughout on f64 handles.  There is no fp64 audit mode on f32 handles (the positions are
+ *     binary32 either way); 2u is not a flag here.
+ *   - State read: the positions AS THEY STAND BEHIND EVERY STEP ENQUEUED SO FAR, the state nb_field_eval reads (a shard handle
+ *     finishes a pending gather first).  Any handle kind: whole system, shard, fused / ping-pong, symmetric, Hermite, block-step.
+ *     nb_set_params is not required: G does not enter.
+ *   - All n rows of the handle are bodies whatever their mass (tracers count).
+ *   - Nearest: index = the j with the smallest d2; among equal d2 the SMALLEST j.  dist2 = that d2.  NB_NBR_AT_BODIES: point k is
+ *     body first_body + k and leaves ITSELF out, by index, not by distance: another body at exactly the same position is a
+ *     neighbour at d2 = 0.  When there is no candidate (n = 1 with NB_NBR_AT_BODIES): index 0xffffffff, dist2 +inf.
+ *   - Count: h = radii[k], or radius when radii is NULL; h2 = h * h in the handle's precision; count = the number of rows, the
+ *     own row of an NB_NBR_AT_BODIES point excluded, with d2 < h2, strictly.  The radius enters the count only: the nearest body
+ *     is reported however far it is, and without count both radii and radius are ignored (radius must still be >= 0).
+ *   - At least one of index / dist2 / count is non-NULL; an output that is not asked for is not written.
+ *   - Deterministic, and more than nb_field_eval promises: min and integer sums are exact, so the three outputs of a point depend on
+ *     that point and on the bodies ONLY -- not on m, not on the batches a large request is cut into, not on how the engine cuts
+ *     j into chunks.  A sub-range request returns the same bits as the same rows of a larger request.
+ *   - Points and bodies must be finite; the result for a non-finite one is unspecified (the call does not fault).
+ *   - Errors: NB_ERR_INVALID (NULL handle or request -- checked before any device call --, wrong struct_size, m == 0, unknown flag
+ *     bits, all three outputs NULL, points given with NB_NBR_AT_BODIES or missing without it, first_body + m > n, count with
+ *     neither radii nor radius > 0, radius negative or NaN), NB_ERR_STATE (nothing uploaded); nb_last_error names the function
+ *     and the field.
+ *   - The simulation state, the engine's side copies of it, the captured step graphs and the step counter are untouched:
+ *     stepping after a call is bit-identical to stepping without it.
+ *   - Host pointers: the call blocks until the outputs are written; no pointer is kept.  NB_NBR_DEVICE: the five pointers are
+ *     device memory on the handle's device, the work is enqueued on the handle's stream and the call returns at once.
+ *   - Memory: engine-owned staging for a host-pointer request (O(m)) and one 16-byte row per (point of a batch, j-chunk), bounded as
+ *     nb_field_eval's partial sums are (the two calls share that buffer); grown on demand, released by nb_destroy.  Large m goes
+ *     through in batches of at most 262,144 points (65,536 on f64 handles). */
+#define NB_NBR_AT_BODIES 1u  /* point k is body first_body + k and leaves ITSELF out (by index, not by distance) */
+#define NB_NBR_DEVICE    4u  /* points / radii / index / dist2 / count are DEVICE pointers on the handle's device; enqueued on the
+                                handle's stream, returns at once */
+typedef struct nb_neighbor_request {
+    uint32_t struct_size;   /* sizeof(nb_neighbor_request) */
+    uint32_t m;             /* number of points, >= 1 */
+    uint32_t flags;         /* NB_NBR_* (2u is not a flag here: NB_ERR_INVALID) */
+    uint32_t first_body;    /* NB_NBR_AT_BODIES only */
+    const void *points;     /* 4*m elements x, y, z, (ignored); NULL with NB_NBR_AT_BODIES */
+    const void *radii;      /* optional: m elements, one search radius per point (handle's precision) */
+    double radius;          /* used when radii == NULL; 0 = no radius given */
+    uint32_t *index;        /* out, optional: m elements, nearest body; 0xffffffff when there is none */
+    void *dist2;            /* out, optional: m elements (handle's precision), its squared distance; +inf when there is none */
+    uint32_t *count;        /* out, optional: m elements, bodies with d2 < h*h; needs radii or radius > 0 */
+} nb_neighbor_request;
+int nb_neighbors(nb_sim *s, const nb_neighbor_request *req);
+/* The same on a multi-shard system: evaluated on shard 0, which holds every row, against the caller's UNPADDED n rows only -- the
+ * zero-mass padding rows at the origin are never returned and never counted; first_body counts the caller's rows. */
+int nb_multi_neighbors(nb_multi *m, const nb_neighbor_request *req);
+/* The launch shape of an m-point request (no device call): the points of its first batch, the j-chunks each of them is run
+ * against, and the bodies of one chunk (whole 256-row tiles).  For tests and tools; the results do not depend on it. */
+int nb_neighbors_shape(nb_sim *s, uint32_t m, uint32_t *batch, uint32_t *chunks, uint32_t *j_per_chunk);
 
 #if defined(__GNUC__)
 #pragma GCC visibility pop

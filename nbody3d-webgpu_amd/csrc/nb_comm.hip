@@ -705,6 +705,17 @@ int nb_multi_field_eval(nb_multi* m, const nb_field_request* req)
     return rc == NB_OK ? rc : mfail(m, rc, s->err);
 }
 
+int nb_multi_neighbors(nb_multi* m, const nb_neighbor_request* req)
+{
+    if (!m) return mfail(nullptr, NB_ERR_INVALID, "nb_multi_neighbors: null handle");
+    if (!req) return mfail(m, NB_ERR_INVALID, "nb_multi_neighbors: null request");
+    if (int rc = nb_multi_sync(m)) return rc;      // every shard's gather has landed: shard 0 holds all rows
+    // the caller's rows are the first n of the padded system: the padding rows (zero mass, at the origin) are no bodies here
+    nb_sim* s = m->shard[0];
+    const int rc = nbi::neighbors(s, req, m->n, "nb_multi_neighbors");
+    return rc == NB_OK ? rc : mfail(m, rc, s->err);
+}
+
 int nb_multi_download(nb_multi* m, void* bodies, void* vel, void* accel)
 {
     if (!m) return NB_ERR_INVALID;

@@ -1026,7 +1026,8 @@ void nb_destroy(nb_sim* s)
     for (void* p : {s->jerk, s->hx, s->hv, s->fj_part, (void*)s->blk_lev, (void*)s->blk_due, (void*)s->blk_act, (void*)s->blk_hdr}) if (p) (void)hipFree(p);
     if (s->blk_hdr_host) (void)hipHostFree(s->blk_hdr_host);
     if (s->diag) (void)hipFree(s->diag);
-    for (auto* b : {&s->fld_pts, &s->fld_acc, &s->fld_phi, &s->fld_part}) if (b->p) (void)hipFree(b->p);
+    for (auto* b : {&s->fld_pts, &s->fld_acc, &s->fld_phi, &s->fld_part, &s->nbr_rad, &s->nbr_idx, &s->nbr_d2, &s->nbr_cnt, &s->nbr_inf})
+        if (b->p) (void)hipFree(b->p);
     if (s->zero_row) (void)hipFree(s->zero_row);
     if (s->own_stream && s->stream) (void)hipStreamDestroy(s->stream);
     delete s;
@@ -1617,14 +1618,14 @@ namespace {
 
 // Makes an engine-owned buffer hold at least `bytes` (a grown buffer is a new allocation: whatever the stream still runs on the
 // old one is waited for first).
-int field_reserve(nb_sim* s, nb_sim::field_buf& b, size_t bytes)
+int field_reserve(nb_sim* s, nb_sim::field_buf& b, size_t bytes, const char* who = "nb_field_eval")
 {
     if (bytes <= b.cap) return NB_OK;
     if (b.p) { NB_HIP(s, hipStreamSynchronize(s->stream)); (void)hipFree(b.p); b.p = nullptr; b.cap = 0; }
     if (hipMalloc(&b.p, bytes) != hipSuccess) {
         (void)hipGetLastError();
         b.p = nullptr;
-        return fail(s, NB_ERR_NOMEM, "nb_field_eval: cannot allocate " + std::to_string(bytes) + " bytes of device memory");
+        return fail(s, NB_ERR_NOMEM, std::string(who) + ": cannot allocate " + std::to_string(bytes) + " bytes of device memory");
     }
     b.cap = bytes;
     return NB_OK;
@@ -1740,6 +1741,129 @@ int nb_field_eval(nb_sim* s, const nb_field_request* req)
         if (req->phi) NB_HIP(s, hipMemcpyAsync(req->phi, phi, out_esz * m, hipMemcpyDeviceToHost, s->stream));
         NB_HIP(s, hipStreamSynchronize(s->stream));
     }
+    return NB_OK;
+}
+
+/* ---- neighbour queries -------------------------------------------------------------------- */
+
+namespace {
+
+// The first batch of an m-point request against `rows` bodies: its points, j-chunks and bodies per chunk -- nb_field_eval's rule
+// (field_shape on the handle's n: the answer does not depend on the cut, and rows <= n only ever leaves chunks at the end empty).
+void nbr_shape(const nb_sim* s, uint32_t m, uint32_t rows, uint32_t* batch, uint32_t* chunks, uint32_t* per)
+{
+    const uint32_t prow = s->f64 ? nb::kNbrRows64 : nb::kNbrRows;
+    const uint64_t part_rows = std::max<uint64_t>(kFieldPartRows, (uint64_t)2 * field_blocks_wanted(s) * prow);
+    uint32_t mb = std::min(m, s->f64 ? 65536u : 262144u);
+    field_shape(s, ceil_div(mb, prow), chunks, per);
+    while ((uint64_t)*chunks * mb > part_rows && mb > prow) {       // fewer points at once: the partial rows stay bounded
+        mb = std::max(prow, (mb / 2 + prow - 1) / prow * prow);
+        field_shape(s, ceil_div(mb, prow), chunks, per);
+    }
+    *chunks = std::max(1u, std::min(*chunks, ceil_div(rows, *per)));      // chunks that start past the last row hold nothing
+    *batch = mb;
+}
+
+}  // namespace
+
+extern "C++" int nbi::neighbors(nb_sim* s, const nb_neighbor_request* req, uint32_t rows, const char* who)
+{
+    const std::string w = std::string(who) + ": ";
+    if (!s) return fail(nullptr, NB_ERR_INVALID, w + "null handle");
+    if (!req) return fail(s, NB_ERR_INVALID, w + "null request");
+    if (req->struct_size != sizeof(nb_neighbor_request)) return fail(s, NB_ERR_INVALID, w + "struct_size must be sizeof(nb_neighbor_request)");
+    if (req->flags & ~(NB_NBR_AT_BODIES | NB_NBR_DEVICE)) return fail(s, NB_ERR_INVALID, w + "unknown bits in flags");
+    const bool at = (req->flags & NB_NBR_AT_BODIES) != 0, dev = (req->flags & NB_NBR_DEVICE) != 0;
+    if (at && req->points) return fail(s, NB_ERR_INVALID, w + "points must be NULL with NB_NBR_AT_BODIES");
+    if (!at && !req->points) return fail(s, NB_ERR_INVALID, w + "points is NULL (and NB_NBR_AT_BODIES is not set)");
+    if (req->m == 0) return fail(s, NB_ERR_INVALID, w + "m must be >= 1");
+    if (!req->index && !req->dist2 && !req->count) return fail(s, NB_ERR_INVALID, w + "index, dist2 and count are all NULL");
+    if (!(req->radius >= 0.0)) return fail(s, NB_ERR_INVALID, w + "radius must be >= 0 (0: none given)");
+    if (req->count && !req->radii && !(req->radius > 0.0)) return fail(s, NB_ERR_INVALID, w + "count needs radii or radius > 0");
+    if (at && (uint64_t)req->first_body + req->m > rows) return fail(s, NB_ERR_INVALID, w + "first_body + m exceeds n");
+    if (!s->uploaded) return fail(s, NB_ERR_STATE, w + "nothing uploaded yet");
+    NB_HIP(s, hipSetDevice(s->device));
+    if (int rc = finish_gather(s)) return rc;     // other ranks' rows must have landed
+
+    const size_t esz = s->esz, in_row = 4 * esz;
+    const uint32_t m = req->m;
+    const char* pts = at ? (const char*)s->bodies[s->cur] + in_row * req->first_body : (const char*)req->points;
+    const char* rad = req->count ? (const char*)req->radii : nullptr;      // the radius only enters the count
+    char* idx = (char*)req->index;
+    char* d2 = (char*)req->dist2;
+    char* cnt = (char*)req->count;
+    if (!dev) {
+        if (!at) {
+            if (int rc = field_reserve(s, s->fld_pts, in_row * m, who)) return rc;
+            NB_HIP(s, hipMemcpyAsync(s->fld_pts.p, req->points, in_row * m, hipMemcpyHostToDevice, s->stream));
+            pts = (const char*)s->fld_pts.p;
+        }
+        if (rad) {
+            if (int rc = field_reserve(s, s->nbr_rad, esz * m, who)) return rc;
+            NB_HIP(s, hipMemcpyAsync(s->nbr_rad.p, req->radii, esz * m, hipMemcpyHostToDevice, s->stream));
+            rad = (const char*)s->nbr_rad.p;
+        }
+        if (idx) { if (int rc = field_reserve(s, s->nbr_idx, 4 * (size_t)m, who)) return rc; idx = (char*)s->nbr_idx.p; }
+        if (d2) { if (int rc = field_reserve(s, s->nbr_d2, esz * m, who)) return rc; d2 = (char*)s->nbr_d2.p; }
+        if (cnt) { if (int rc = field_reserve(s, s->nbr_cnt, 4 * (size_t)m, who)) return rc; cnt = (char*)s->nbr_cnt.p; }
+    }
+    if (!s->f64 && !s->nbr_inf.p) {
+        static const float inf_row[4] = {HUGE_VALF, HUGE_VALF, HUGE_VALF, 0.0f};
+        if (int rc = field_reserve(s, s->nbr_inf, 64, who)) return rc;
+        NB_HIP(s, hipMemcpyAsync(s->nbr_inf.p, inf_row, sizeof inf_row, hipMemcpyHostToDevice, s->stream));
+    }
+
+    const uint32_t prow = s->f64 ? nb::kNbrRows64 : nb::kNbrRows;      // points per workgroup
+    const void* bodies = s->bodies[s->cur];
+    const void* inf_row = s->nbr_inf.p;
+    uint32_t n = rows, at_flag = at ? 1u : 0u;
+    double rd = req->radius;
+    float rf = (float)req->radius;
+    for (uint32_t done = 0; done < m;) {
+        uint32_t mb, chunks, per;
+        nbr_shape(s, m - done, rows, &mb, &chunks, &per);
+        if (int rc = field_reserve(s, s->fld_part, (size_t)16 * chunks * mb, who)) return rc;
+        const void* p = pts + in_row * done;
+        const void* r = rad ? rad + esz * done : nullptr;
+        void* part = s->fld_part.p;
+        void* oi = idx ? idx + (size_t)4 * done : nullptr;
+        void* od = d2 ? d2 + esz * done : nullptr;
+        void* oc = cnt ? cnt + (size_t)4 * done : nullptr;
+        uint32_t self0 = req->first_body + done;
+        dim3 grid(ceil_div(mb, prow), chunks), block(nb::kBlock);
+        void* rargs[] = {&part, &mb, &chunks, &oi, &od, &oc};
+        if (s->f64) {
+            void* args[] = {&bodies, &p, &r, &part, &n, &mb, &per, &rd, &at_flag, &self0};
+            NB_HIP(s, hipLaunchKernel((const void*)&nb::nb_nbr64<double>, grid, block, args, 0, s->stream));
+            NB_HIP(s, hipLaunchKernel((const void*)&nb::nb_nbr_reduce<double>, dim3(ceil_div(mb, nb::kBlock)), block, rargs, 0, s->stream));
+        } else {
+            void* args[] = {&bodies, &p, &r, &part, &n, &mb, &per, &rf, &at_flag, &self0, &inf_row};
+            const void* fn = oc ? (const void*)&nb::nb_nbr_pk<true> : (const void*)&nb::nb_nbr_pk<false>;
+            NB_HIP(s, hipLaunchKernel(fn, grid, block, args, 0, s->stream));
+            NB_HIP(s, hipLaunchKernel((const void*)&nb::nb_nbr_reduce<float>, dim3(ceil_div(mb, nb::kBlock)), block, rargs, 0, s->stream));
+        }
+        done += mb;
+    }
+    if (!dev) {
+        if (req->index) NB_HIP(s, hipMemcpyAsync(req->index, idx, 4 * (size_t)m, hipMemcpyDeviceToHost, s->stream));
+        if (req->dist2) NB_HIP(s, hipMemcpyAsync(req->dist2, d2, esz * m, hipMemcpyDeviceToHost, s->stream));
+        if (req->count) NB_HIP(s, hipMemcpyAsync(req->count, cnt, 4 * (size_t)m, hipMemcpyDeviceToHost, s->stream));
+        NB_HIP(s, hipStreamSynchronize(s->stream));
+    }
+    return NB_OK;
+}
+
+int nb_neighbors(nb_sim* s, const nb_neighbor_request* req) { return nbi::neighbors(s, req, s ? s->n : 0u, "nb_neighbors"); }
+
+int nb_neighbors_shape(nb_sim* s, uint32_t m, uint32_t* batch, uint32_t* chunks, uint32_t* j_per_chunk)
+{
+    if (!s) return fail(nullptr, NB_ERR_INVALID, "nb_neighbors_shape: null handle");
+    if (m == 0) return fail(s, NB_ERR_INVALID, "nb_neighbors_shape: m must be >= 1");
+    uint32_t b, c, per;
+    nbr_shape(s, m, s->n, &b, &c, &per);
+    if (batch) *batch = b;
+    if (chunks) *chunks = c;
+    if (j_per_chunk) *j_per_chunk = per;
     return NB_OK;
 }
 

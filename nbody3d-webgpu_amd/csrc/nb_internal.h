@@ -143,6 +143,10 @@ struct nb_sim {
     // (O(m)); part holds one (ax, ay, az, sum m/r) row per (j-chunk, point of a batch): a bounded number of rows whatever m and n are
     int n_cu = 256;
     struct field_buf { void* p = nullptr; size_t cap = 0; } fld_pts, fld_acc, fld_phi, fld_part;
+    // nb_neighbors: shares fld_pts (points) and fld_part (16-byte rows (d2, index, count) per (j-chunk, point of a batch)) with nb_field_eval
+    // -- the two never overlap on the stream --; rad / idx / d2 / cnt stage a host-pointer request (O(m)); inf is one row at +inf, the
+    // LDS-DMA source of nb_nbr_pk for j past the range
+    field_buf nbr_rad, nbr_idx, nbr_d2, nbr_cnt, nbr_inf;
     // NB_INT_HERMITE4: bodies[0] / vel are the state at ONE instant, acc / jerk the derivatives derived from it.  None of the
     // leapfrog launch fields above is used: plain unpadded arrays, no planner, no graphs.
     bool hermite = false;
@@ -173,6 +177,9 @@ namespace nbi {
 
 int fail(nb_sim* s, int code, const std::string& msg);
 void set_create_error(const std::string& msg);
+// nb_neighbors on the first `rows` rows of the handle (nb_multi_neighbors: the caller's unpadded rows of shard 0); `who` names the
+// public function in the messages
+int neighbors(nb_sim* s, const nb_neighbor_request* req, uint32_t rows, const char* who);
 const std::string& create_error();
 
 // nb_comm.hip: called by nb_step after the integrate kernel when a communicator is attached.

@@ -65,6 +65,8 @@ static int (*p_set_block_steps)(nb_sim *, const nb_block_steps *);      /* block
 static int (*p_block_stats)(nb_sim *, struct nb_block_stats *, int);
 static int (*p_download_levels)(nb_sim *, uint8_t *);
 static int (*p_upload_levels)(nb_sim *, const uint8_t *);
+static int (*p_neighbors)(nb_sim *, const nb_neighbor_request *);       /* neighbour queries, also within ABI 2.4: optional symbols */
+static int (*p_multi_neighbors)(nb_multi *, const nb_neighbor_request *);
 
 /* one JS handle = a single-device nb_sim or a single-process multi-device nb_multi */
 typedef struct { nb_sim *sim; nb_multi *multi; uint32_t n; int f64; } handle_t;
@@ -149,6 +151,8 @@ static napi_value js_load(napi_env env, napi_callback_info info)
         *(void **)(&p_block_stats) = dlsym(h, "nb_block_stats");
         *(void **)(&p_download_levels) = dlsym(h, "nb_download_levels");
         *(void **)(&p_upload_levels) = dlsym(h, "nb_upload_levels");
+        *(void **)(&p_neighbors) = dlsym(h, "nb_neighbors");
+        *(void **)(&p_multi_neighbors) = dlsym(h, "nb_multi_neighbors");
         g_lib = h;
     }
     if (p_abi_version() != NB_ABI_VERSION) { napi_throw_error(env, "NB_ABI", "ABI version mismatch"); return NULL; }
@@ -632,6 +636,61 @@ static napi_value js_field_eval(napi_env env, napi_callback_info info)
     return undefined(env);
 }
 
+/* neighbors(handle, points|null, firstBody, count, radii|null, radius, indexOut|null, dist2Out|null, countOut|null): nb_neighbors /
+ * nb_multi_neighbors.  points (4*m) / radii (m) / dist2Out (m): typed arrays of the handle's precision; indexOut / countOut:
+ * Uint32Array of m elements, written in place.  points null: the points are the bodies [firstBody, firstBody + count)
+ * themselves (NB_NBR_AT_BODIES). */
+static napi_value js_neighbors(napi_env env, napi_callback_info info)
+{
+    size_t argc = 9; napi_value argv[9];
+    CHECK_NAPI(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    if (argc < 9) { napi_throw_type_error(env, NULL, "neighbors(handle, points|null, firstBody, count, radii|null, radius, indexOut|null, dist2Out|null, countOut|null)"); return NULL; }
+    handle_t *h = get_handle(env, argv[0]); if (!h) return NULL;
+    if (!p_neighbors || !p_multi_neighbors) return throw_msg(env, NB_ERR_STATE, "the loaded library has no nb_neighbors", "nb_neighbors");
+    const napi_typedarray_type real = h->f64 ? napi_float64_array : napi_float32_array;
+    void *ptr[5] = {NULL, NULL, NULL, NULL, NULL}; size_t len[5] = {0, 0, 0, 0, 0};
+    static const int arg_of[5] = {1, 4, 6, 7, 8};
+    static const int is_u32[5] = {0, 0, 1, 0, 1};
+    static const char *const what[5] = {"points", "radii", "indexOut", "dist2Out", "countOut"};
+    for (int k = 0; k < 5; ++k) {
+        napi_valuetype vt; napi_typeof(env, argv[arg_of[k]], &vt);
+        if (vt == napi_null || vt == napi_undefined) continue;
+        bool is_ta = false; napi_is_typedarray(env, argv[arg_of[k]], &is_ta);
+        napi_typedarray_type tt; napi_value ab; size_t off;
+        const napi_typedarray_type want = is_u32[k] ? napi_uint32_array : real;
+        if (!is_ta || napi_get_typedarray_info(env, argv[arg_of[k]], &tt, &len[k], &ptr[k], &ab, &off) != napi_ok || tt != want) {
+            char buf[160]; snprintf(buf, sizeof buf, "neighbors: %s must be a %s or null", what[k], is_u32[k] ? "Uint32Array" : h->f64 ? "Float64Array" : "Float32Array");
+            napi_throw_type_error(env, NULL, buf); return NULL;
+        }
+    }
+    double first = 0, count = 0, radius = 0;
+    napi_get_value_double(env, argv[2], &first); napi_get_value_double(env, argv[3], &count); napi_get_value_double(env, argv[5], &radius);
+    nb_neighbor_request req;
+    memset(&req, 0, sizeof req);
+    req.struct_size = sizeof req;
+    if (ptr[0]) {
+        if (len[0] % 4 != 0 || len[0] / 4 > 0xffffffffu) { napi_throw_range_error(env, NULL, "neighbors: points must hold 4*m elements"); return NULL; }
+        req.m = (uint32_t)(len[0] / 4);
+        req.points = ptr[0];
+    } else {
+        if (!(first >= 0 && first <= 4294967295.0 && count >= 0 && count <= 4294967295.0)) { napi_throw_range_error(env, NULL, "neighbors: firstBody / count out of range"); return NULL; }
+        req.flags = NB_NBR_AT_BODIES;
+        req.first_body = (uint32_t)first; req.m = (uint32_t)count;
+    }
+    for (int k = 1; k < 5; ++k)
+        if (ptr[k] && len[k] != (size_t)req.m) { napi_throw_range_error(env, NULL, "neighbors: radii, indexOut, dist2Out and countOut must hold m elements"); return NULL; }
+    req.radii = ptr[1]; req.radius = radius;
+    req.index = (uint32_t *)ptr[2]; req.dist2 = ptr[3]; req.count = (uint32_t *)ptr[4];
+    if (h->multi) {
+        int rcm = p_multi_neighbors(h->multi, &req);
+        if (rcm != NB_OK) return throw_msg(env, rcm, p_multi_last_error(h->multi), "nb_multi_neighbors");
+    } else {
+        int rc = p_neighbors(h->sim, &req);
+        if (rc != NB_OK) return throw_nb(env, rc, h->sim, "nb_neighbors");
+    }
+    return undefined(env);
+}
+
 /* downloadJerk(handle, jerkOut): nb_download_jerk -- 4*n elements (jx, jy, jz, 0) of a Hermite handle, written in place. */
 static napi_value js_download_jerk(napi_env env, napi_callback_info info)
 {
@@ -773,7 +832,7 @@ static napi_value init_module(napi_env env, napi_value exports)
         {"collectiveInfo", js_collective_info}, {"requestFrame", js_request_frame}, {"frame", js_frame}, {"planQuery", js_plan_query},
         {"fieldEval", js_field_eval}, {"downloadJerk", js_download_jerk}, {"uploadDerivs", js_upload_derivs},
         {"setBlockSteps", js_set_block_steps}, {"blockStats", js_block_stats}, {"downloadLevels", js_download_levels},
-        {"uploadLevels", js_upload_levels},
+        {"uploadLevels", js_upload_levels}, {"neighbors", js_neighbors},
     };
     for (size_t i = 0; i < sizeof fns / sizeof fns[0]; ++i) {
         napi_value f;

@@ -309,9 +309,59 @@ class Simulation {
     return out;
   }
 
+  /** Neighbour query (nb_neighbors; no reference analogue): for each of `points` -- a typed or plain array of 4*m elements x, y, z,
+   *  (ignored) -- or, with options.bodies = [first, count] (and points null), for each of those bodies, itself left out by index,
+   *  the nearest body, its squared distance (plain, unsoftened) and, with options.radius (one for all) or options.radii (one per
+   *  point), the number of bodies strictly closer than that.  Returns {index: Uint32Array, dist2: Float32Array | Float64Array,
+   *  count?: Uint32Array}; index is 0xffffffff and dist2 Infinity where there is no candidate; of equal distances the smallest
+   *  index wins.  The positions are those behind every step issued so far; the simulation state is not touched. */
+  neighbors(points, options) {
+    this._need();
+    const o = options || {}, T = this.ArrayType;
+    let pts = null, first = 0, m;
+    if (o.bodies) { first = o.bodies[0] >>> 0; m = o.bodies[1] >>> 0; }
+    if (points !== null && points !== undefined) {
+      if (points instanceof T) pts = points;
+      else if (typeof points.length === 'number') pts = T.from(points);
+      else throw new TypeError('points: expected ' + T.name);
+      if (pts.length % 4 !== 0) throw new RangeError('points must hold 4*m elements (x, y, z, ignored)');
+      if (o.bodies) throw new RangeError('neighbors(): give either points or options.bodies, not both');
+      m = pts.length / 4;
+    } else if (!o.bodies) throw new TypeError('neighbors(): points, or options.bodies = [first, count], required');
+    let radii = null;
+    if (o.radii !== null && o.radii !== undefined) {
+      radii = o.radii instanceof T ? o.radii : T.from(o.radii);
+      if (radii.length !== m) throw new RangeError('options.radii must hold one radius per point');
+    }
+    const radius = o.radius === undefined || o.radius === null ? 0 : +o.radius;
+    const out = { index: new Uint32Array(m), dist2: new T(m) };
+    if (radii || (o.radius !== undefined && o.radius !== null)) out.count = new Uint32Array(m);
+    addon.neighbors(this._h, pts, first, m, radii, radius, out.index, out.dist2, out.count || null);
+    return out;
+  }
+
+  /** The close pairs of the system: the MUTUAL nearest neighbours (i < j, each the other's nearest body) closer than `radius`, as
+   *  {pairs: Uint32Array of 2*k elements i0, j0, i1, j1, ... sorted by i, dist2: k elements} -- one neighbors() call over all
+   *  bodies and host code on its result. */
+  closePairs(radius) {
+    this._need();
+    return mutualPairs(this.neighbors(null, { bodies: [0, this.nBodies] }), radius);
+  }
+
   destroy() {
     if (this._h) { addon.destroy(this._h); this._h = null; this._frame = null; }
   }
+}
+
+/* The mutual nearest-neighbour pairs closer than `radius` of a neighbors() result over all bodies (closePairs: pure host code). */
+function mutualPairs(nn, radius) {
+  const n = nn.index.length, T = nn.dist2.constructor, h = new T([radius]), h2 = new T([h[0] * h[0]])[0];
+  const ij = [], d2 = [];
+  for (let i = 0; i < n; i++) {
+    const j = nn.index[i];
+    if (j < n && i < j && nn.index[j] === i && nn.dist2[i] < h2) { ij.push(i, j); d2.push(nn.dist2[i]); }
+  }
+  return { pairs: Uint32Array.from(ij), dist2: T.from(d2) };
 }
 
 /* Module-level instance: the reference keeps its state in module globals
@@ -329,6 +379,6 @@ function read() { return need().read(); }
 
 module.exports = {
   Simulation: Simulation, init: init, step: step, simulate: simulate, read: read,
-  load: load, deviceCount: deviceCount, planQuery: planQuery, TILE_SIZE: TILE_SIZE, EPS2: EPS2, DEFAULT_G: DEFAULT_G, DEFAULT_DT: DEFAULT_DT,
+  load: load, deviceCount: deviceCount, planQuery: planQuery, mutualPairs: mutualPairs, TILE_SIZE: TILE_SIZE, EPS2: EPS2, DEFAULT_G: DEFAULT_G, DEFAULT_DT: DEFAULT_DT,
   get current() { return current; }, get abiVersion() { return abi; },
 };

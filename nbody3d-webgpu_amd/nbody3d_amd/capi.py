@@ -33,6 +33,8 @@ NB_RCCL_OVERLAP = 1
 NB_MULTI_PEER, NB_MULTI_RCCL, NB_MULTI_PEER_OVERLAP = 0, 1, 2
 NB_NOT_READY = 7
 NB_FIELD_AT_BODIES, NB_FIELD_F64, NB_FIELD_DEVICE = 1, 2, 4      # nb_field_request.flags (ABI 2.4)
+NB_NBR_AT_BODIES, NB_NBR_DEVICE = 1, 4                           # nb_neighbor_request.flags (added within ABI 2.4)
+NB_NBR_NONE = 0xffffffff                                         # the index of "no neighbour"
 NB_INT_LEAPFROG, NB_INT_HERMITE4 = 0, 1                          # nb_config.integrator (added within ABI 2.4)
 INTEGRATORS = {"leapfrog": NB_INT_LEAPFROG, "hermite4": NB_INT_HERMITE4}
 STATUS = {0: "NB_OK", 1: "NB_ERR_INVALID", 2: "NB_ERR_NO_DEVICE", 3: "NB_ERR_HIP",
@@ -78,6 +80,12 @@ class nb_field_request(C.Structure):        # include/nbody3d_hip.h (ABI 2.4)
                 ("points", C.c_void_p), ("accel", C.c_void_p), ("phi", C.c_void_p)]
 
 
+class nb_neighbor_request(C.Structure):     # include/nbody3d_hip.h (neighbour queries, added within ABI 2.4)
+    _fields_ = [("struct_size", C.c_uint32), ("m", C.c_uint32), ("flags", C.c_uint32), ("first_body", C.c_uint32),
+                ("points", C.c_void_p), ("radii", C.c_void_p), ("radius", C.c_double),
+                ("index", C.c_void_p), ("dist2", C.c_void_p), ("count", C.c_void_p)]
+
+
 NB_BLOCK_FROZEN = 1
 
 
@@ -105,7 +113,8 @@ SYMBOLS = ["nb_abi_version", "nb_device_count", "nb_create", "nb_destroy", "nb_u
            "nb_rccl_unique_id", "nb_rccl_attach", "nb_rccl_detach", "nb_rccl_info",
            "nb_step_times", "nb_step_times2", "nb_integrate_pass", "nb_force_pass", "nb_frame_request", "nb_frame_acquire", "nb_shape_info", "nb_plan_query",
            "nb_abi_minor", "nb_field_eval", "nb_multi_field_eval", "nb_download_jerk", "nb_upload_derivs",
-           "nb_set_block_steps", "nb_block_stats", "nb_download_levels", "nb_upload_levels"]
+           "nb_set_block_steps", "nb_block_stats", "nb_download_levels", "nb_upload_levels",
+           "nb_neighbors", "nb_multi_neighbors", "nb_neighbors_shape"]
 
 _lib = None
 
@@ -185,6 +194,10 @@ def load_library():
         L.nb_block_stats.argtypes = [vp, C.POINTER(nb_block_stats), C.c_int]
         L.nb_download_levels.argtypes = [vp, vp]
         L.nb_upload_levels.argtypes = [vp, vp]
+    if hasattr(L, "nb_neighbors"):          # neighbour queries, also within 2.4 and detected by the symbol
+        L.nb_neighbors.argtypes = [vp, C.POINTER(nb_neighbor_request)]
+        L.nb_multi_neighbors.argtypes = [vp, C.POINTER(nb_neighbor_request)]
+        L.nb_neighbors_shape.argtypes = [vp, C.c_uint32] + [C.POINTER(C.c_uint32)] * 3
     _lib = L
     return L
 
@@ -249,6 +262,67 @@ def _field_request(n, dtype, points, bodies, accel, phi, f64):
     req.accel = _ptr(a) if a is not None and a.size else None
     req.phi = _ptr(f) if f is not None and f.size else None
     return req, pts, a, f
+
+
+def _need_neighbors(what):
+    if not hasattr(load_library(), "nb_neighbors"):
+        raise NBodyError(1, "%s: the loaded library has no nb_neighbors" % what)
+
+
+def _neighbor_request(dtype, points, bodies, radius, radii):
+    """The nb_neighbor_request of neighbors(): (request, arrays kept alive, index, dist2, count | None)."""
+    _need_neighbors("neighbors()")
+    req = nb_neighbor_request()
+    req.struct_size = C.sizeof(nb_neighbor_request)
+    pts = rad = None
+    # (both or neither of points / bodies: passed on as they are -- the engine's NB_ERR_INVALID names the field)
+    if bodies is not None:
+        first, count = int(bodies[0]), int(bodies[1])
+        if not (0 <= first < 2 ** 32 and 0 <= count < 2 ** 32):
+            raise ValueError("neighbors(): bodies=(first, count) out of range")
+        req.flags |= NB_NBR_AT_BODIES
+        req.first_body, req.m = first, count
+    if points is not None:
+        pts = np.asarray(points, dtype=dtype)
+        if pts.ndim == 1:
+            pts = pts.reshape(-1, 3 if pts.size % 4 else 4)
+        if pts.ndim != 2 or pts.shape[1] not in (3, 4):
+            raise ValueError("neighbors(): points must have shape (m, 3) or (m, 4)")
+        if pts.shape[1] == 3:
+            pts = np.concatenate([pts, np.zeros((len(pts), 1), dtype)], axis=1)
+        pts = np.ascontiguousarray(pts)
+        if bodies is None:
+            req.m = len(pts)
+        req.points = _ptr(pts) if len(pts) else None
+    if radii is not None:
+        rad = np.ascontiguousarray(radii, dtype=dtype).reshape(-1)
+        if len(rad) != req.m:
+            raise ValueError("neighbors(): radii must hold one radius per point")
+        req.radii = _ptr(rad) if len(rad) else None
+    if radius is not None:
+        req.radius = float(radius)
+    index = np.zeros((req.m,), np.uint32)
+    dist2 = np.zeros((req.m,), dtype)
+    count = np.zeros((req.m,), np.uint32) if (radius is not None or radii is not None) else None
+    req.index = _ptr(index) if req.m else None
+    req.dist2 = _ptr(dist2) if req.m else None
+    req.count = _ptr(count) if count is not None and req.m else None
+    return req, (pts, rad), index, dist2, count
+
+
+def mutual_pairs(index, dist2, radius):
+    """The mutual nearest-neighbour pairs of an all-bodies neighbour result closer than ``radius``: ``(pairs (k, 2) uint32 sorted by
+    i, d2 (k,))`` with i < j, index[i] == j, index[j] == i and dist2[i] < radius * radius in the precision of dist2."""
+    index = np.asarray(index, np.uint32)
+    dist2 = np.asarray(dist2)
+    n = len(index)
+    i = np.arange(n, dtype=np.int64)
+    j = index.astype(np.int64)
+    ok = j < n                                         # NB_NBR_NONE: no neighbour
+    jj = np.where(ok, j, 0)
+    h = dist2.dtype.type(radius)
+    ok &= (i < j) & (index[jj].astype(np.int64) == i) & (dist2 < h * h)
+    return np.stack([i[ok], j[ok]], axis=1).astype(np.uint32).reshape(-1, 2), dist2[ok].copy()
 
 
 SYMW_PLAN_WORDS = ("np", "nsb", "W", "total_hi", "total_lo", "n_hi", "H", "r_layer0", "t_layer0", "L", "zc")
@@ -679,6 +753,51 @@ class Simulation:
         req.phi = phi_ptr or None
         self._check(self._L.nb_field_eval(self._h, C.byref(req)))
 
+    def neighbors(self, points=None, *, bodies=None, radius=None, radii=None):
+        """nb_neighbors: for each of ``points`` ((m, 3) or (m, 4); the fourth column is ignored) -- or, with ``bodies=(first, count)``,
+        for each of those bodies, itself left out by index -- the nearest body, its squared distance (plain, unsoftened, the handle's
+        precision) and, with ``radius`` (one for all) or ``radii`` (one per point), the number of bodies strictly closer than that.
+        Returns ``(index (m,) uint32, dist2 (m,), count (m,) uint32 | None)``; index is NB_NBR_NONE and dist2 +inf where there is no
+        candidate.  Equal distances: the smallest index.  The positions are those behind every step issued so far; the simulation
+        state is not touched; the answer for a point does not depend on the other points of the request."""
+        req, keep, index, dist2, count = _neighbor_request(self.dtype, points, bodies, radius, radii)
+        self._check(self._L.nb_neighbors(self._h, C.byref(req)))
+        return index, dist2, count
+
+    def neighbors_device(self, points_ptr, m, index_ptr, dist2_ptr, count_ptr=None, *, bodies=None, radius=None, radii_ptr=None):
+        """The device-pointer form (NB_NBR_DEVICE): device addresses on the handle's device (e.g. ``tensor.data_ptr()``; 0 or None for
+        what is not wanted), element types as for neighbors().  The work is enqueued on the handle's stream and the call returns
+        without waiting.  ``bodies=(first, count)`` selects the bodies themselves (``points_ptr`` must then be None, ``m`` is ignored)."""
+        _need_neighbors("neighbors_device()")
+        req = nb_neighbor_request()
+        req.struct_size = C.sizeof(nb_neighbor_request)
+        req.flags = NB_NBR_DEVICE
+        if bodies is not None:
+            req.flags |= NB_NBR_AT_BODIES
+            req.first_body, req.m = int(bodies[0]), int(bodies[1])
+        else:
+            req.m = int(m)
+        req.points = points_ptr or None
+        req.radii = radii_ptr or None
+        req.radius = 0.0 if radius is None else float(radius)
+        req.index = index_ptr or None
+        req.dist2 = dist2_ptr or None
+        req.count = count_ptr or None
+        self._check(self._L.nb_neighbors(self._h, C.byref(req)))
+
+    def neighbors_shape(self, m):
+        """{batch, chunks, j_per_chunk}: the launch shape nb_neighbors gives an m-point request (the answers do not depend on it)."""
+        _need_neighbors("neighbors_shape()")
+        v = [C.c_uint32() for _ in range(3)]
+        self._check(self._L.nb_neighbors_shape(self._h, int(m), *[C.byref(x) for x in v]))
+        return dict(zip(("batch", "chunks", "j_per_chunk"), (x.value for x in v)))
+
+    def close_pairs(self, radius):
+        """The close pairs of the system: the MUTUAL nearest neighbours (i < j, each the other's nearest body) closer than ``radius``,
+        as ``(pairs (k, 2) uint32 sorted by i, d2 (k,))`` -- one neighbors(bodies=(0, n)) call and host code on its result."""
+        index, dist2, _ = self.neighbors(bodies=(0, self.n))
+        return mutual_pairs(index, dist2, radius)
+
     def body_energies(self):
         """Per-body energies as two float64 arrays ``(kinetic, potential)``: ``0.5 m_i |v_i|^2`` and ``m_i phi_i``, phi_i the potential
         of all OTHER bodies at body i (one field(bodies=(0, n)) call plus read()).  A body is bound when the two add up to less
@@ -822,6 +941,13 @@ class MultiSimulation:
         req, pts, a, f = _field_request(self.n, self.dtype, points, bodies, accel, phi, f64)
         self._check(self._L.nb_multi_field_eval(self._h, C.byref(req)))
         return a, f
+
+    def neighbors(self, points=None, *, bodies=None, radius=None, radii=None):
+        """nb_multi_neighbors: Simulation.neighbors() on the whole system (evaluated on shard 0 against the caller's unpadded rows);
+        ``bodies=(first, count)`` counts the caller's unpadded rows."""
+        req, keep, index, dist2, count = _neighbor_request(self.dtype, points, bodies, radius, radii)
+        self._check(self._L.nb_multi_neighbors(self._h, C.byref(req)))
+        return index, dist2, count
 
     @property
     def variant(self):
