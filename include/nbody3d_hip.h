@@ -51,7 +51,9 @@ extern "C" {
                              2.4 (round 8)  likewise within 2.4: nb_set_block_steps, nb_block_stats, nb_download_levels, nb_upload_levels,
                                             NB_BLOCK_*.  Detected by the presence of the symbol nb_set_block_steps
                              2.4 (round 9)  likewise within 2.4: nb_neighbors, nb_multi_neighbors, nb_neighbors_shape, nb_neighbor_request, NB_NBR_*.
-                                            Detected by the presence of the symbol nb_neighbors */
+                                            Detected by the presence of the symbol nb_neighbors
+                             2.4 (round 10) likewise within 2.4: NB_FLAG_NO_EQM (an older library ignores the bit: it has the general kernels only),
+                                            nb_eqm_info.  Detected by the presence of the symbol nb_eqm_info */
 
 typedef struct nb_sim nb_sim; /* opaque */
 
@@ -103,6 +105,11 @@ typedef enum nb_precision { NB_F32 = 0, NB_F64 = 1 } nb_precision;
 #define NB_FLAG_SINGLE_SWEEPS 512u /* tuning/A-B: the wave-granular symmetric pass (f32, one traveler per lane) runs every chunk-sweep on its
                                     own, as before ABI 2.4's paired sweeps (two whole sweeps rotate together: 14 instead of 20 lane
                                     moves per two traveler-steps).  Same plan, same layers; sums differ in the order of additions */
+
+#define NB_FLAG_NO_EQM 1024u /* tuning/A-B: never run the equal-mass kernels of the symmetric pass.  A whole-system f32 handle of the
+                                wave-granular form whose plan has no padding rows runs them while every bodies.w holds the same bits and
+                                every vel.w and accel.w is zero (nb_upload decides; after nb_device_ptr the next step looks again): one
+                                G*m product per pair instead of two, no mass lane rotated.  Bit-identical results (nb_eqm_info) */
 
 /* nb_array: selector for nb_device_ptr */
 typedef enum nb_array { NB_BODIES = 0, NB_VEL = 1, NB_ACCEL = 2, NB_JERK = 3 /* Hermite handles only */ } nb_array;
@@ -365,6 +372,10 @@ const char *nb_variant_name(nb_sim *s);
  * begin-then-wait on this handle.  Any out pointer may be NULL. */
 int nb_shape_info(nb_sim *s, uint32_t *jsplit, uint32_t *j_per_split, uint32_t *own_split0,
                   uint32_t *own_splits);
+
+/* Whether the next force pass of the handle runs the equal-mass kernels (NB_FLAG_NO_EQM): *eqm = 1 or 0.  Decides it first if a
+ * pointer was handed out since it was last known (one small launch and a wait on the handle's stream).  0 before nb_upload. */
+int nb_eqm_info(nb_sim *s, int *eqm);
 
 /* Planner introspection (the launch plan nb_create WOULD build for a configuration, with the symmetric pass's kernel-internal
  * plan words and tables: for reports, sizing runs and the host-side planner tests) lives in nbody3d_hip_plan.h -- nothing a host

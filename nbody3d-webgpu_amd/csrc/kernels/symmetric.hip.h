@@ -265,6 +265,16 @@ __device__ __forceinline__ void symw_record_and_tail(const uint32_t* rec_at, nb_
     }
 }
 
+// The equal-mass kernels (EQM below) also want the one G*m of the system: the mass lane of row 0 of the j-stream, a third scalar load in the
+// same request (no kernel argument of its own: kTailOffset and SYMW_KERNEL_PARAMS stay as they are).
+template <int = 0>       // (a template as symw_record_and_tail: the host pass never sees the SGPR constraints)
+__device__ __forceinline__ void symw_record_tail_and_gm(const uint32_t* rec_at, const float4* jrows, nb_u4& rec, uint32_t& tail, uint32_t& gm)
+{
+    constexpr int kTailOffset = 4 * 8 + 6 * 4;       // as symw_record_and_tail
+    asm volatile("s_load_dwordx4 %0, %3, 0x0\n\ts_load_dword %1, %4, %6\n\ts_load_dword %2, %5, 0xc\n\ts_waitcnt lgkmcnt(0)"
+                 : "=&s"(rec), "=&s"(tail), "=&s"(gm) : "s"(rec_at), "s"(__builtin_amdgcn_kernarg_segment_ptr()), "s"(jrows), "n"(kTailOffset) : "memory");
+}
+
 __device__ __forceinline__ SymWK symw_plan_words(uint32_t S, uint32_t cps, uint32_t W, uint32_t ups, uint32_t nsb, uint32_t zc, uint32_t r_layer0, uint32_t t_layer0)
 {
     const uint32_t H = (nsb - 1u) >> 1, n_hi = (nsb & 1u) ? 0u : nsb >> 1;
@@ -272,8 +282,13 @@ __device__ __forceinline__ SymWK symw_plan_words(uint32_t S, uint32_t cps, uint3
     return SymWK{(nsb + (zc ? 1u : 0u)) * S, nsb, W, total_hi, total_lo, n_hi, zc, ups, r_layer0, t_layer0};
 }
 
-// (the body of the two kernels below: nb_force_symw<NG, J> runs every sweep on its own, nb_force_symw_pairs<NG> runs whole sweeps two at a time)
-template <int NG, int J, bool PAIR>
+// (the body of the kernels below: nb_force_symw<NG, J> runs every sweep on its own, nb_force_symw_pairs<NG> runs whole sweeps two at a time)
+// EQM: the EQUAL-MASS form (nb_force_symw_eqm, nb_force_symw_pairs_eqm; the engine launches it only on a system whose mass lanes are all the
+// same bits, without padding rows: nb_engine.hip, ensure_eqm).  (G m_t) inv and (G m_i) inv are then the SAME product, gm * inv with the one
+// scalar gm = row 0's mass lane of the j-stream: one packed multiply per group and form instead of two, no resident masses mi[], no traveler
+// mass tm and none of the lane moves that carry it -- 15 packed instructions per group and form for 16, 6 + 6 lane moves per paired step for
+// 8 + 6 (9 for 10 and 3 for 4 in the single forms).  Every product and every addition is the general form's: the same bits.
+template <int NG, int J, bool PAIR, bool EQM = false>
 __device__ __forceinline__ void symw_sweeps(const uint32_t* __restrict__ gtab, const float4* __restrict__ bodies, SymRow* __restrict__ partial, SymRow* __restrict__ spill,
                                             SYMW_PLAN_PARAMS, uint32_t* __restrict__ queue, const uint32_t npieces, const uint32_t pieces_off)
 {
@@ -301,10 +316,13 @@ __device__ __forceinline__ void symw_sweeps(const uint32_t* __restrict__ gtab, c
     const uint32_t ups = pl.ups, ush = (uint32_t)__builtin_ctz(ups), ustep = 64u >> ush,      // (ups is a power of two)
                    tab1 = 2u * (pl.np / S);
     nb_u4 rec;                                 // {first unit, end, resident layer, spill row}: one scalar load
-    uint32_t tail[1];
-    symw_record_and_tail(gtab + tab1 + 4u * (active ? w : 0u), rec, tail);
+    uint32_t tail[1], gm_bits = 0;
+    if constexpr (EQM) symw_record_tail_and_gm(gtab + tab1 + 4u * (active ? w : 0u), bodies, rec, tail[0], gm_bits);
+    else symw_record_and_tail(gtab + tab1 + 4u * (active ? w : 0u), rec, tail);
     const float eps2 = __builtin_bit_cast(float, tail[0]);
     const nb_f2 e2 = nb_f2{eps2, eps2};
+    const float gm1 = __builtin_bit_cast(float, gm_bits);
+    const nb_f2 gm = nb_f2{gm1, gm1};          // (EQM) G*m of every body
     const uint32_t first_lo = pl.n_hi * pl.total_hi, first_z = first_lo + (pl.nsb - pl.n_hi) * pl.total_lo;
     const uint32_t slot = rec.w;               // the wave's spill row (it has at most one: the sweep its range starts inside)
     NB_STAMP_LIGHT(1);
@@ -333,7 +351,8 @@ __device__ __forceinline__ void symw_sweeps(const uint32_t* __restrict__ gtab, c
 #pragma unroll
                 for (int c = 0; c < NG; ++c) {
                     const float4 b0 = ld4(rb + (2 * c) * 64), b1 = ld4(rb + (2 * c + 1) * 64);
-                    xi[c] = nb_f2{b0.x, b1.x}; yi[c] = nb_f2{b0.y, b1.y}; zi[c] = nb_f2{b0.z, b1.z}; mi[c] = nb_f2{b0.w, b1.w};
+                    xi[c] = nb_f2{b0.x, b1.x}; yi[c] = nb_f2{b0.y, b1.y}; zi[c] = nb_f2{b0.z, b1.z};
+                    if constexpr (!EQM) mi[c] = nb_f2{b0.w, b1.w};
                     ax[c] = nb_f2{0, 0}; ay[c] = nb_f2{0, 0}; az[c] = nb_f2{0, 0};
                 }
             }
@@ -428,9 +447,9 @@ __device__ __forceinline__ void symw_sweeps(const uint32_t* __restrict__ gtab, c
 #pragma unroll
                                     for (int c = 0; c < GW; ++c) r[c] = nb_f2{nb_rsq(r[c].x), nb_rsq(r[c].y)};
 #pragma unroll
-                                    for (int c = 0; c < GW; ++c) si[c] = symw_mul(f, tm, r[c]);    // (G m_t) inv: resident side, :236
+                                    for (int c = 0; c < GW; ++c) si[c] = EQM ? gm * r[c] : symw_mul(f, tm, r[c]);    // (G m_t) inv: resident side, :236
 #pragma unroll
-                                    for (int c = 0; c < GW; ++c) sj[c] = mi[c0g + c] * r[c];       // (G m_i) inv: traveler side
+                                    for (int c = 0; c < GW; ++c) sj[c] = EQM ? si[c] : mi[c0g + c] * r[c];           // (G m_i) inv: traveler side
 #pragma unroll
                                     for (int c = 0; c < GW; ++c) ax[c0g + c] = __builtin_elementwise_fma(si[c], dx[c], ax[c0g + c]);
 #pragma unroll
@@ -446,7 +465,8 @@ __device__ __forceinline__ void symw_sweeps(const uint32_t* __restrict__ gtab, c
                                 }
                             }
                             tx = nb_f2{wave_rot1(tx.x), wave_rot1(tx.y)}; ty = nb_f2{wave_rot1(ty.x), wave_rot1(ty.y)};
-                            tz = nb_f2{wave_rot1(tz.x), wave_rot1(tz.y)}; tm = nb_f2{wave_rot1(tm.x), wave_rot1(tm.y)};
+                            tz = nb_f2{wave_rot1(tz.x), wave_rot1(tz.y)};
+                            if constexpr (!EQM) tm = nb_f2{wave_rot1(tm.x), wave_rot1(tm.y)};
                             wave_rot1_add(bx0, sx.x); wave_rot1_add(bx1, sx.y); wave_rot1_add(by0, sy.x); wave_rot1_add(by1, sy.y);
                             wave_rot1_add(bz0, sz.x); wave_rot1_add(bz1, sz.y);
                             __builtin_amdgcn_sched_barrier(0);               // the loop counter's three 32-bit instructions stay together behind the 64-bit ones
@@ -509,10 +529,10 @@ __device__ __forceinline__ void symw_sweeps(const uint32_t* __restrict__ gtab, c
 #pragma unroll
                                 for (int c = 0; c < GW; ++c) r[c] = nb_f2{nb_rsq(r[c].x), nb_rsq(r[c].y)};
 #pragma unroll
-                                for (int c = 0; c < GW; ++c) si[c] = pm * r[c];                // (G m_t) inv: resident side, :236
+                                for (int c = 0; c < GW; ++c) si[c] = EQM ? gm * r[c] : pm * r[c];                    // (G m_t) inv: resident side, :236
                                 if constexpr (BOTH) {
 #pragma unroll
-                                    for (int c = 0; c < GW; ++c) sj[c] = mi[c0g + c] * r[c];   // (G m_i) inv: traveler side
+                                    for (int c = 0; c < GW; ++c) sj[c] = EQM ? si[c] : mi[c0g + c] * r[c];           // (G m_i) inv: traveler side
                                 }
 #pragma unroll
                                 for (int c = 0; c < GW; ++c) ax[c0g + c] = __builtin_elementwise_fma(si[c], dx[c], ax[c0g + c]);
@@ -532,7 +552,8 @@ __device__ __forceinline__ void symw_sweeps(const uint32_t* __restrict__ gtab, c
                         }
 #pragma unroll
                         for (int uu = 0; uu < J; ++uu) {                     // the travelers and their sums move on by one lane
-                            tx[uu] = wave_rot1(tx[uu]); ty[uu] = wave_rot1(ty[uu]); tz[uu] = wave_rot1(tz[uu]); tm[uu] = wave_rot1(tm[uu]);
+                            tx[uu] = wave_rot1(tx[uu]); ty[uu] = wave_rot1(ty[uu]); tz[uu] = wave_rot1(tz[uu]);
+                            if constexpr (!EQM) tm[uu] = wave_rot1(tm[uu]);
                             if constexpr (BOTH) {
                                 bx[uu] = nb_f2{wave_rot1(bx[uu].x), wave_rot1(bx[uu].y)};
                                 by[uu] = nb_f2{wave_rot1(by[uu].x), wave_rot1(by[uu].y)};
@@ -654,6 +675,32 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, NG > 4 ?
 void nb_force_symw_pairs(SYMW_KERNEL_PARAMS)
 {
     symw_sweeps<NG, 1, true>(SYMW_KERNEL_ARGS);
+}
+
+// The equal-mass forms of the two kernels above (`EQM`): kernels of their own, so that the general ones keep their names and their code.
+template <int NG, int J>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NG >= 4 ? 2 : 4, NG > 4 ? 2 : (NG < 4 ? 8 : 4))))
+void nb_force_symw_eqm(SYMW_KERNEL_PARAMS)
+{
+    symw_sweeps<NG, J, false, true>(SYMW_KERNEL_ARGS);
+}
+template <int NG>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, NG > 4 ? 2 : 4)))
+void nb_force_symw_pairs_eqm(SYMW_KERNEL_PARAMS)
+{
+    symw_sweeps<NG, 1, true, true>(SYMW_KERNEL_ARGS);
+}
+
+// Decides whether a system is one the equal-mass kernels may run on: every mass lane the same bits as row 0's, every vel.w and acc.w zero
+// (leapfrog() then leaves the mass lanes alone).  `flag` is zeroed in front of the launch; any row that breaks the rule sets it.
+template <int>          // (a template so that both translation units may include it, as nb_gm_pack)
+__global__ __launch_bounds__(kBlock) void nb_eqm_check(const float4* __restrict__ bodies, const float4* __restrict__ vel, const float4* __restrict__ acc,
+                                                      const uint32_t n, uint32_t* __restrict__ flag)
+{
+    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t m0 = __builtin_bit_cast(uint32_t, bodies[0].w), m = __builtin_bit_cast(uint32_t, bodies[i].w);
+    if (m != m0 || !(vel[i].w == 0.f) || !(acc[i].w == 0.f)) *flag = 1u;
 }
 
 // The fp64 form (BASELINE config 5): non-packed, IPL residents per lane, one traveler per lane.  Per unordered pair: 3 adds,

@@ -134,8 +134,15 @@ const void* rank_kernel_of(bool f64, int ipl)
 
 // The kernel a shape launches (nullptr: no such instantiation).
 // single_sweeps (NB_FLAG_SINGLE_SWEEPS): the wave-granular symmetric pass with one traveler per lane runs every sweep on its own.
-const void* kernel_of(bool f64, const Shape& sh, bool single_sweeps = false)
+// eqm: the equal-mass form of that pass (eqm_active below; only the shapes eqm_shape names have one).
+bool eqm_shape(bool f64, const Shape& sh) { return !f64 && sh.kind == kSym && sh.ls == 1 && sh.x == 3 && (sh.ipl == 8 || sh.ipl == 16); }
+const void* kernel_of(bool f64, const Shape& sh, bool single_sweeps = false, bool eqm = false)
 {
+    if (eqm) {
+        if (!eqm_shape(f64, sh)) return nullptr;
+        if (sh.ipl == 8) return single_sweeps ? (const void*)&nb::nb_force_symw_eqm<4, 1> : (const void*)&nb::nb_force_symw_pairs_eqm<4>;
+        return single_sweeps ? (const void*)&nb::nb_force_symw_eqm<8, 1> : (const void*)&nb::nb_force_symw_pairs_eqm<8>;
+    }
     switch (sh.kind) {
         case kScalar: return f64 ? scalar_kernel<double>(sh.ipl, sh.ls) : scalar_kernel<float>(sh.ipl, sh.ls);
         case kPkLds: return f64 || (sh.ipl & 1) ? nullptr : pk_force_kernel(sh.ipl / 2, sh.ls, sh.x);
@@ -234,6 +241,26 @@ int ensure_gm(nb_sim* s)
     return NB_OK;
 }
 
+// The equal-mass kernels run while the handle's state is known to be an equal-mass system (nb_sim::eqm) and nothing rewrites its rows
+// between steps (an exchange hook or a communicator may); a dt that is not finite would turn the zero w lanes into NaN (0 * inf).
+bool eqm_active(const nb_sim* s) { return s->eqm_capable && s->eqm == nb_sim::kEqmYes && !s->xfn && !s->rccl && std::isfinite((float)s->dt); }
+
+// Makes nb_sim::eqm known: one small launch and one host wait, once per invalidation (an upload decides on the host instead).
+int ensure_eqm(nb_sim* s)
+{
+    if (!s->eqm_capable || s->eqm != nb_sim::kEqmUnknown) return NB_OK;
+    const float4 *b = (const float4*)s->bodies[s->cur], *v = (const float4*)s->vel, *a = (const float4*)s->acc;
+    uint32_t n = s->n, found = 1;
+    uint32_t* flag = s->eqm_flag;
+    void* args[] = {&b, &v, &a, &n, &flag};
+    NB_HIP(s, hipMemsetAsync(flag, 0, sizeof(uint32_t), s->stream));
+    NB_HIP(s, hipLaunchKernel((const void*)&nb::nb_eqm_check<0>, dim3(ceil_div(n, nb::kBlock)), dim3(nb::kBlock), args, 0, s->stream));
+    NB_HIP(s, hipMemcpyAsync(&found, flag, sizeof found, hipMemcpyDeviceToHost, s->stream));
+    NB_HIP(s, hipStreamSynchronize(s->stream));
+    s->eqm = found ? nb_sim::kEqmNo : nb_sim::kEqmYes;
+    return NB_OK;
+}
+
 // part: 0 = all splits, 1 = only the splits inside this shard's own rows,
 //       2 = all the others
 // t0/t1 (optional): events stamped at the kernel's begin / end (hipExtLaunchKernel)
@@ -282,7 +309,9 @@ void launch_force(nb_sim* s, int part = 0, hipEvent_t t0 = nullptr, hipEvent_t t
         // (the order of kernels/symmetric.hip.h SYMW_PLAN_PARAMS: the table pointer and the plan words inside the preloaded 14 dwords)
         uint32_t* queue = s->sym_queue;
         uint32_t npieces = s->sym_pieces, pieces_off = 2u * (pl.np / ipb_of(sh)) + 4u * pl.W;      // the queued sweeps behind the wave records (lay_out_symw)
-        if (npieces) (void)hipMemsetAsync(queue, 0, sizeof(uint32_t), s->stream);                  // the queue's draw counter
+        // the queue's draw counter.  A reset that fails would leave the last launch's count (>= npieces): every wave would skip the queue
+        // and K2 would add the piece layers' stale sums -- so the error is kept for the caller (nb_step, ensure_graph, nb_force_pass)
+        if (npieces) { const hipError_t e = hipMemsetAsync(queue, 0, sizeof(uint32_t), s->stream); if (e != hipSuccess) s->force_err = e; }
         if (s->f64) {
             double G = s->G, e2 = s->eps2;
             void* args[] = {&tab, &b, &p, &sp, &pl.W, &pl.ups, &pl.nsb, &pl.zc, &pl.r_layer0, &pl.t_layer0, &G, &e2, &queue, &npieces, &pieces_off};
@@ -290,7 +319,7 @@ void launch_force(nb_sim* s, int part = 0, hipEvent_t t0 = nullptr, hipEvent_t t
         } else {
             float e2 = (float)s->eps2;
             void* args[] = {&tab, &b, &p, &sp, &pl.W, &pl.ups, &pl.nsb, &pl.zc, &pl.r_layer0, &pl.t_layer0, &e2, &queue, &npieces, &pieces_off};
-            launch_kernel(kernel_of(false, sh, s->single_sweeps), dim3(ceil_div(pl.W, 4u)), dim3(256), args, s->stream, t0, t1);
+            launch_kernel(kernel_of(false, sh, s->single_sweeps, eqm_active(s)), dim3(ceil_div(pl.W, 4u)), dim3(256), args, s->stream, t0, t1);
         }
         return;
     }
@@ -463,7 +492,7 @@ int role_parity(const nb_sim* s) { return s->cur | (s->acc_parity << 1); }
 bool ensure_graph(nb_sim* s, int which)
 {
     auto& slot = s->graphs[which];
-    if (slot.exec && slot.dt == s->dt && slot.G == s->G && slot.parity == role_parity(s)) return true;
+    if (slot.exec && slot.dt == s->dt && slot.G == s->G && slot.parity == role_parity(s) && slot.eqm == eqm_active(s)) return true;
     if (slot.exec) { (void)hipGraphExecDestroy(slot.exec); slot.exec = nullptr; }
     if (slot.graph) { (void)hipGraphDestroy(slot.graph); slot.graph = nullptr; }
     void *acc0 = s->acc, *par0 = s->partial;
@@ -475,10 +504,10 @@ bool ensure_graph(nb_sim* s, int which)
     hipGraph_t g = nullptr;
     const bool ok = hipStreamEndCapture(s->stream, &g) == hipSuccess && g;
     s->acc = acc0; s->partial = par0; s->cur = cur0; s->acc_parity = par_bit0;   // an even number of role flips: explicit for clarity
-    if (!ok) { (void)hipGetLastError(); s->graphs_ok = false; return false; }
+    if (!ok || s->force_err != hipSuccess) { if (g) (void)hipGraphDestroy(g); (void)hipGetLastError(); s->force_err = hipSuccess; s->graphs_ok = false; return false; }
     hipGraphExec_t ge = nullptr;
     if (hipGraphInstantiate(&ge, g, nullptr, nullptr, 0) != hipSuccess) { (void)hipGraphDestroy(g); (void)hipGetLastError(); s->graphs_ok = false; return false; }
-    slot.graph = g; slot.exec = ge; slot.dt = s->dt; slot.G = s->G; slot.parity = role_parity(s);
+    slot.graph = g; slot.exec = ge; slot.dt = s->dt; slot.G = s->G; slot.parity = role_parity(s); slot.eqm = eqm_active(s);
     return true;
 }
 
@@ -928,6 +957,10 @@ int nb_create(const nb_config* cfg_in, nb_sim** out)
     }
     if (!kernel_of(s->f64, shape_of(s))) return bail(NB_ERR_INVALID, "nb_create: no kernel for shape " + s->variant);
     s->single_sweeps = (cfg.flags & NB_FLAG_SINGLE_SWEEPS) != 0;
+    // the equal-mass kernels: a whole system in the wave-granular f32 form whose plan has no padding rows (zero-mass rows, and the padded
+    // lanes of a short block Z, are not of the system's one mass)
+    s->eqm_capable = !(cfg.flags & NB_FLAG_NO_EQM) && s->symw && !s->sym_rank && cfg.shard_count == 0 && !cfg.ext_bodies && s->sym_np == s->n
+                     && eqm_shape(s->f64, shape_of(s));
 
     const size_t row = 4 * s->esz;
     if (cfg.ext_bodies) { s->bodies[0] = cfg.ext_bodies; s->own_bodies = false; }
@@ -961,6 +994,7 @@ int nb_create(const nb_config* cfg_in, nb_sim** out)
             NB_HIPC(hipMalloc((void**)&s->sym_queue, 64));
             NB_HIPC(hipMemset(s->sym_queue, 0, 64));
         }
+        if (s->eqm_capable) NB_HIPC(hipMalloc((void**)&s->eqm_flag, 64));
         if (s->symw) {
             NB_HIPC(hipMalloc((void**)&s->sym_tab, sizeof(uint32_t) * s->sym_tab_host.size()));
             NB_HIPC(hipMemcpy(s->sym_tab, s->sym_tab_host.data(), sizeof(uint32_t) * s->sym_tab_host.size(), hipMemcpyHostToDevice));
@@ -1022,6 +1056,7 @@ void nb_destroy(nb_sim* s)
     if (s->sym_tab) (void)hipFree(s->sym_tab);
     if (s->sym_spill) (void)hipFree(s->sym_spill);
     if (s->sym_queue) (void)hipFree(s->sym_queue);
+    if (s->eqm_flag) (void)hipFree(s->eqm_flag);
     if (s->sym_A) (void)hipFree(s->sym_A);
     for (void* p : {s->jerk, s->hx, s->hv, s->fj_part, (void*)s->blk_lev, (void*)s->blk_due, (void*)s->blk_act, (void*)s->blk_hdr}) if (p) (void)hipFree(p);
     if (s->blk_hdr_host) (void)hipHostFree(s->blk_hdr_host);
@@ -1064,6 +1099,19 @@ int nb_upload(nb_sim* s, const void* bodies, const void* vel, const void* accel)
     s->uploaded = true;
     s->pairs_ok = false;
     s->gm_ok = false;
+    if (s->eqm_capable) {
+        // the host arrays are at hand: every mass lane the bits of row 0's, every vel.w and acc.w zero (what nb_eqm_check asks on the device)
+        const float *hb = (const float*)bodies, *hv = (const float*)vel, *ha = (const float*)accel;
+        uint32_t m0;
+        memcpy(&m0, hb + 3, sizeof m0);
+        bool same = true;
+        for (uint32_t i = 0; i < s->n && same; ++i) {
+            uint32_t m;
+            memcpy(&m, hb + 4 * (size_t)i + 3, sizeof m);
+            same = m == m0 && hv[4 * (size_t)i + 3] == 0.f && (!ha || ha[4 * (size_t)i + 3] == 0.f);
+        }
+        s->eqm = same ? nb_sim::kEqmYes : nb_sim::kEqmNo;
+    }
     return NB_OK;
 }
 
@@ -1088,6 +1136,7 @@ int nb_step(nb_sim* s, uint32_t nsteps)
     ensure_pairs(s);      // the j-packed step's position copy, if something outside the step rewrote the positions or G
     if (gm_active(s) && !s->gm_ok) { if (int rc = finish_gather(s)) return rc; }
     if (int rc = ensure_gm(s)) return rc;   // the packed K1 forms' (x, y, z, G*m) j-stream, likewise
+    if (int rc = ensure_eqm(s)) return rc;  // whether the equal-mass kernels may run, if a pointer was handed out since it was last known
     // Multi-step calls on the engine's own stream replay a captured graph of
     // kGraphChunk steps (no exchange, no per-kernel timing requested).
     if (s->own_stream && s->graphs_ok && !exchange && !s->timing && !s->sym_rank && nsteps >= kGraphChunk) {
@@ -1155,6 +1204,7 @@ int nb_step(nb_sim* s, uint32_t nsteps)
             else launch_integrate<float>(s, e ? e[6] : nullptr, e ? e[2] : nullptr);
         }
         NB_HIP(s, hipGetLastError());
+        if (s->force_err != hipSuccess) { const hipError_t queue_reset = s->force_err; s->force_err = hipSuccess; NB_HIP(s, queue_reset); }
         ++s->steps_done;
         if (exchange) s->gm_ok = false;
         if (s->rccl) {
@@ -1214,9 +1264,9 @@ int nb_device_ptr(nb_sim* s, int which, void** out)
         if (int rc = ensure_derivs(s, "nb_device_ptr")) return rc;
     }
     switch (which) {
-        case NB_BODIES: *out = s->bodies[s->cur]; s->pairs_ok = false; s->gm_ok = false; s->derivs_ok = false; s->levels = 0; break;   // the caller may write through it
-        case NB_VEL: *out = s->vel; s->derivs_ok = false; s->levels = 0; break;
-        case NB_ACCEL: *out = s->acc; break;
+        case NB_BODIES: *out = s->bodies[s->cur]; s->pairs_ok = false; s->gm_ok = false; s->derivs_ok = false; s->levels = 0; s->eqm = nb_sim::kEqmUnknown; break;   // the caller may write through it
+        case NB_VEL: *out = s->vel; s->derivs_ok = false; s->levels = 0; s->eqm = nb_sim::kEqmUnknown; break;      // (the w lanes: see ensure_eqm)
+        case NB_ACCEL: *out = s->acc; s->eqm = nb_sim::kEqmUnknown; break;
         case NB_JERK: *out = s->jerk; break;
         default: return fail(s, NB_ERR_INVALID, "nb_device_ptr: unknown array");
     }
@@ -1494,6 +1544,7 @@ int nb_force_pass(nb_sim* s, uint32_t reps, double* avg_ms)
     NB_HIP(s, hipSetDevice(s->device));
     if (int rc = finish_gather(s)) return rc;
     if (int rc = ensure_gm(s)) return rc;
+    if (int rc = ensure_eqm(s)) return rc;
     if (s->hermite && !s->params_set) return fail(s, NB_ERR_STATE, "nb_force_pass: nb_set_params has not been called (G)");
     auto once = [&]() -> int {
         if (s->hermite) { launch_fj(s, s->bodies[0], s->vel, s->hx, s->hv); return NB_OK; }      // into the step's scratch: state and derivatives untouched
@@ -1513,6 +1564,7 @@ int nb_force_pass(nb_sim* s, uint32_t reps, double* avg_ms)
     NB_HIP(s, hipEventElapsedTime(&ms, e0, e1));
     (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
     NB_HIP(s, hipGetLastError());
+    if (s->force_err != hipSuccess) { const hipError_t queue_reset = s->force_err; s->force_err = hipSuccess; NB_HIP(s, queue_reset); }
     *avg_ms = ms / reps;
     return NB_OK;
 }
@@ -1526,6 +1578,17 @@ int nb_shape_info(nb_sim* s, uint32_t* jsplit, uint32_t* j_per_split, uint32_t* 
     if (j_per_split) *j_per_split = s->j_per_split;
     if (own_split0) *own_split0 = s->own_split0;
     if (own_splits) *own_splits = s->own_splits;
+    return NB_OK;
+}
+
+int nb_eqm_info(nb_sim* s, int* eqm)
+{
+    if (!s || !eqm) return NB_ERR_INVALID;
+    *eqm = 0;
+    if (!s->eqm_capable || !s->uploaded) return NB_OK;
+    NB_HIP(s, hipSetDevice(s->device));
+    if (int rc = ensure_eqm(s)) return rc;
+    *eqm = eqm_active(s) ? 1 : 0;
     return NB_OK;
 }
 

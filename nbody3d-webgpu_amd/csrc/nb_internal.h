@@ -99,9 +99,16 @@ struct nb_sim {
     std::vector<uint32_t> sym_tab_host;
     void* sym_spill = nullptr;     // ups > 1: one spill row set per wave (traveler sums of the sweep a wave's range starts inside)
     uint32_t sym_spill_rows = 0;
-    uint32_t sym_pieces = 0;       // sweeps in the shared queue of nb_force_symw (nb_plan.cpp::lay_out_symw)
+    uint32_t sym_pieces = 0;       // pieces (several sweeps, one resident layer each) in the shared queue of nb_force_symw (nb_plan.cpp::lay_out_symw)
     bool single_sweeps = false;    // NB_FLAG_SINGLE_SWEEPS: nb_force_symw<NG, 1> instead of nb_force_symw_pairs<NG>
     uint32_t* sym_queue = nullptr; // device: the queue's draw counter, zeroed in front of every force launch
+    // The equal-mass kernels (nb_force_symw_eqm / nb_force_symw_pairs_eqm): a whole-system f32 handle of the wave-granular form whose plan has
+    // no padding rows may run them while every bodies.w is the same bits and every vel.w / acc.w is zero (nb_engine.hip, ensure_eqm).
+    bool eqm_capable = false;      // the handle's form and plan allow it (and NB_FLAG_NO_EQM is not set)
+    enum { kEqmUnknown = 0, kEqmYes = 1, kEqmNo = 2 };
+    int eqm = kEqmUnknown;         // nb_upload decides on the host; a pointer handed out makes it unknown, nb_eqm_check re-decides before the next step
+    uint32_t* eqm_flag = nullptr;  // device: what nb_eqm_check writes
+    hipError_t force_err = hipSuccess;   // launch_force: the reset of the queue's draw counter failed (picked up by whoever launched it)
     // rank form (NB_FLAG_SYM_SHARD: a shard handle whose cross-rank reduction the engine's native exchange provides): the
     // handle's own rows are the resident super-blocks [sym_g0, sym_g1); sym_A[np] = this rank's sums for EVERY row, reduce-
     // scattered across the ranks before the integrate kernel reads the rank's own rows of it
@@ -127,6 +134,7 @@ struct nb_sim {
         hipGraphExec_t exec = nullptr;
         double dt = 0.0, G = 0.0;
         int parity = 0;
+        bool eqm = false;            // captured with the equal-mass force kernel
     } graphs[2];                     // [0]: kGraphChunk steps, [1]: kGraphBig steps (a replay costs the host
                                      // ~10-16 us: amortised over 128 steps it stops showing at N ~ 1,024)
     bool graphs_ok = true;           // cleared if capture ever fails: fall back to plain launches

@@ -282,6 +282,8 @@ class Simulation {
   collectiveInfo() { this._need(); return addon.collectiveInfo(this._h); }
   kernelTimes() { this._need(); return addon.kernelTimes(this._h); }
   variant() { this._need(); return addon.variant(this._h); }
+  /** Whether the next force pass runs the equal-mass kernels (nb_eqm_info; flags: 1024 = NB_FLAG_NO_EQM keeps the general ones). */
+  eqm() { this._need(); return addon.eqm(this._h); }
   diagnostics() { this._need(); addon.setParams(this._h, this.dt, this.G); return addon.diagnostics(this._h); }
 
   /** Field query (nb_field_eval; no reference analogue): acceleration and potential of the system at `points` -- a typed or

@@ -28,6 +28,7 @@ NB_FLAG_NO_SYM = 64
 NB_FLAG_SYM_SHARD = 128
 NB_FLAG_WHOLE_SWEEPS = 256
 NB_FLAG_SINGLE_SWEEPS = 512
+NB_FLAG_NO_EQM = 1024
 NB_RCCL_ID_BYTES = 128
 NB_RCCL_OVERLAP = 1
 NB_MULTI_PEER, NB_MULTI_RCCL, NB_MULTI_PEER_OVERLAP = 0, 1, 2
@@ -114,7 +115,7 @@ SYMBOLS = ["nb_abi_version", "nb_device_count", "nb_create", "nb_destroy", "nb_u
            "nb_step_times", "nb_step_times2", "nb_integrate_pass", "nb_force_pass", "nb_frame_request", "nb_frame_acquire", "nb_shape_info", "nb_plan_query",
            "nb_abi_minor", "nb_field_eval", "nb_multi_field_eval", "nb_download_jerk", "nb_upload_derivs",
            "nb_set_block_steps", "nb_block_stats", "nb_download_levels", "nb_upload_levels",
-           "nb_neighbors", "nb_multi_neighbors", "nb_neighbors_shape"]
+           "nb_neighbors", "nb_multi_neighbors", "nb_neighbors_shape", "nb_eqm_info"]
 
 _lib = None
 
@@ -198,6 +199,8 @@ def load_library():
         L.nb_neighbors.argtypes = [vp, C.POINTER(nb_neighbor_request)]
         L.nb_multi_neighbors.argtypes = [vp, C.POINTER(nb_neighbor_request)]
         L.nb_neighbors_shape.argtypes = [vp, C.c_uint32] + [C.POINTER(C.c_uint32)] * 3
+    if hasattr(L, "nb_eqm_info"):           # the equal-mass kernels' report, also within 2.4 and detected by the symbol
+        L.nb_eqm_info.argtypes = [vp, C.POINTER(C.c_int)]
     _lib = L
     return L
 
@@ -716,6 +719,16 @@ class Simulation:
         v = [C.c_uint32() for _ in range(4)]
         self._check(self._L.nb_shape_info(self._h, *[C.byref(x) for x in v]))
         return dict(zip(("jsplit", "j_per_split", "own_split0", "own_splits"), (x.value for x in v)))
+
+    @property
+    def eqm(self):
+        """Whether the next force pass runs the equal-mass kernels (NB_FLAG_NO_EQM; nb_eqm_info).  A property of its own and not a key
+        of shape_info(): that dict is compared whole with the planner's answer, and this is a fact of the uploaded state, not of the plan."""
+        if not hasattr(self._L, "nb_eqm_info"):
+            return False
+        v = C.c_int()
+        self._check(self._L.nb_eqm_info(self._h, C.byref(v)))
+        return bool(v.value)
 
     def diagnostics(self):
         """(kinetic, potential share, momentum[3]) of this handle's shard, fp64 on device."""

@@ -2,6 +2,7 @@
 """Which share of a plan's chunk-sweeps does nb_force_symw_pairs run two at a time?  (CPU only: the planner's answer, walked as the
 kernel walks it -- kernels/symmetric.hip.h, `pair`.)  A paired sweep issues 151 instead of 154 vector instructions per rotation step
 with 16 residents per lane (8 residents: 79 instead of 82), an own-chunk sweep 116 (60): the predicted ratio of SQ_INSTS_VALU.
+The equal-mass kernels issue 142 (74), 145 (77) and 115 (59): the second ratio, against the paired kernel.
     python tools/paired_share.py [N ...] [--variant V]"""
 import os
 import sys
@@ -52,5 +53,7 @@ for n in sizes:
     both, lone = 18 * ng + 10, 14 * ng + 4
     before = (paired + single) * both + own * lone
     after = paired * (both - 3) + single * both + own * lone
-    print("N=%8d %-40s sweeps %9.0f: paired %.4f  single with sums %.4f  own chunks %.4f | predicted VALU instructions x %.5f" % (
-        n, q["variant"], tot, paired / tot, single / tot, own / tot, after / before))
+    # the equal-mass kernels (nb_force_symw_pairs_eqm): one mass product and one lane move less per traveler-step, against `after`
+    eqm = paired * (both - 3 - ng - 1) + single * (both - ng - 1) + own * (lone - 1)
+    print("N=%8d %-40s sweeps %9.0f: paired %.4f  single with sums %.4f  own chunks %.4f | predicted VALU instructions x %.5f | equal masses x %.5f" % (
+        n, q["variant"], tot, paired / tot, single / tot, own / tot, after / before, eqm / after))
