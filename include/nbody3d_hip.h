@@ -53,7 +53,9 @@ extern "C" {
                              2.4 (round 9)  likewise within 2.4: nb_neighbors, nb_multi_neighbors, nb_neighbors_shape, nb_neighbor_request, NB_NBR_*.
                                             Detected by the presence of the symbol nb_neighbors
                              2.4 (round 10) likewise within 2.4: NB_FLAG_NO_EQM (an older library ignores the bit: it has the general kernels only),
-                                            nb_eqm_info.  Detected by the presence of the symbol nb_eqm_info */
+                                            nb_eqm_info.  Detected by the presence of the symbol nb_eqm_info
+                             2.4 (round 11) likewise within 2.4: NB_FLAG_NO_EQM_POW2 (an older library ignores the bit: its equal-mass kernels keep
+                                            their mass product anyway), nb_eqm_form.  Detected by the presence of the symbol nb_eqm_form */
 
 typedef struct nb_sim nb_sim; /* opaque */
 
@@ -110,6 +112,12 @@ typedef enum nb_precision { NB_F32 = 0, NB_F64 = 1 } nb_precision;
                                 wave-granular form whose plan has no padding rows runs them while every bodies.w holds the same bits and
                                 every vel.w and accel.w is zero (nb_upload decides; after nb_device_ptr the next step looks again): one
                                 G*m product per pair instead of two, no mass lane rotated.  Bit-identical results (nb_eqm_info) */
+
+#define NB_FLAG_NO_EQM_POW2 2048u /* tuning/A-B: the equal-mass kernels keep their G*m product per pair (form 1) even where the system's
+                                     one G*m is a power of two.  By default such a system -- N-body units with N = 2^k bodies: m = 2^-k --
+                                     runs the equal-mass kernels with UNIT mass product (form 2): the sums are kept unscaled and G*m
+                                     multiplies each row once, where it is stored; a product by a power of two commutes with every
+                                     rounding, so the results are bit-identical (nb_eqm_form) */
 
 /* nb_array: selector for nb_device_ptr */
 typedef enum nb_array { NB_BODIES = 0, NB_VEL = 1, NB_ACCEL = 2, NB_JERK = 3 /* Hermite handles only */ } nb_array;
@@ -376,6 +384,12 @@ int nb_shape_info(nb_sim *s, uint32_t *jsplit, uint32_t *j_per_split, uint32_t *
 /* Whether the next force pass of the handle runs the equal-mass kernels (NB_FLAG_NO_EQM): *eqm = 1 or 0.  Decides it first if a
  * pointer was handed out since it was last known (one small launch and a wait on the handle's stream).  0 before nb_upload. */
 int nb_eqm_info(nb_sim *s, int *eqm);
+
+/* Which form of the force kernels the next force pass of the handle runs: *form = 0 the general kernels, 1 the equal-mass kernels, 2 the
+ * equal-mass kernels with unit mass product.  Form 2 runs where nb_eqm_info answers 1 and the scalar the kernels stream as G*m -- row 0's
+ * mass when G = 1, else (float)G * mass -- is a positive normal power of two with an exponent in [-32, 32] (NB_FLAG_NO_EQM_POW2 keeps
+ * form 1); it follows the G of the last nb_set_params.  Decides the equal-mass state first, as nb_eqm_info does.  0 before nb_upload. */
+int nb_eqm_form(nb_sim *s, int *form);
 
 /* Planner introspection (the launch plan nb_create WOULD build for a configuration, with the symmetric pass's kernel-internal
  * plan words and tables: for reports, sizing runs and the host-side planner tests) lives in nbody3d_hip_plan.h -- nothing a host

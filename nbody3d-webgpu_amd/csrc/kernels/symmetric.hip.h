@@ -288,11 +288,20 @@ __device__ __forceinline__ SymWK symw_plan_words(uint32_t S, uint32_t cps, uint3
 // scalar gm = row 0's mass lane of the j-stream: one packed multiply per group and form instead of two, no resident masses mi[], no traveler
 // mass tm and none of the lane moves that carry it -- 15 packed instructions per group and form for 16, 6 + 6 lane moves per paired step for
 // 8 + 6 (9 for 10 and 3 for 4 in the single forms).  Every product and every addition is the general form's: the same bits.
-template <int NG, int J, bool PAIR, bool EQM = false>
+// UNIT (with EQM): the equal-mass form with UNIT mass product (nb_force_symw_unit, nb_force_symw_pairs_unit; the engine launches it only when
+// gm is a power of two inside a window of exponents: nb_engine.hip, eqm_form).  Every term of every sum carries the factor gm, and a product
+// by a power of two commutes with every rounding while nothing leaves the normal range (the products by the engine's window; the scaled
+// SUMS by the system: a sum component that is subnormal when scaled rounds in the EQM form and not here, so the identity is not unconditional): fl(gm r) = gm r, fma(gm r, d, gm a) = gm fma(r, d, a),
+// and so on through every later addition (v_add_f32_dpp, the second level, the meeting).  So si = sj = inv, the sums stay UNSCALED in the
+// registers, in the second level and in `red`, and gm multiplies each value once, as the last operation on it, where it is stored to global
+// memory (never in front of an addition: -ffp-contract=on would fuse the two and move a rounding): 14 packed instructions per group and
+// form for 15, the same bits as the EQM form and so as the general one.
+template <int NG, int J, bool PAIR, bool EQM = false, bool UNIT = false>
 __device__ __forceinline__ void symw_sweeps(const uint32_t* __restrict__ gtab, const float4* __restrict__ bodies, SymRow* __restrict__ partial, SymRow* __restrict__ spill,
                                             SYMW_PLAN_PARAMS, uint32_t* __restrict__ queue, const uint32_t npieces, const uint32_t pieces_off)
 {
     static_assert(!PAIR || J == 1, "paired sweeps: one traveler per lane and sweep");
+    static_assert(!UNIT || EQM, "the unit mass product is a form of the equal-mass kernels");
     constexpr uint32_t S = 128u * NG;          // rows per super-block = one wave's residents
     constexpr int GW = NG < 4 ? NG : 4;        // packed groups evaluated stage-major together
     constexpr uint32_t CH = 64u * J;           // travelers per chunk
@@ -323,6 +332,11 @@ __device__ __forceinline__ void symw_sweeps(const uint32_t* __restrict__ gtab, c
     const nb_f2 e2 = nb_f2{eps2, eps2};
     const float gm1 = __builtin_bit_cast(float, gm_bits);
     const nb_f2 gm = nb_f2{gm1, gm1};          // (EQM) G*m of every body
+    // a row of sums as it leaves for global memory (UNIT: the one place gm enters)
+    auto row_of = [&](float x, float y, float z) -> SymRow {
+        if constexpr (UNIT) return SymRow{gm1 * x, gm1 * y, gm1 * z};
+        else return SymRow{x, y, z};
+    };
     const uint32_t first_lo = pl.n_hi * pl.total_hi, first_z = first_lo + (pl.nsb - pl.n_hi) * pl.total_lo;
     const uint32_t slot = rec.w;               // the wave's spill row (it has at most one: the sweep its range starts inside)
     NB_STAMP_LIGHT(1);
@@ -361,8 +375,8 @@ __device__ __forceinline__ void symw_sweeps(const uint32_t* __restrict__ gtab, c
             // binary32 register -- the stagnation that puts the reference's own ascending-j loop at 1e-5 .. 5e-4 there
             // (tests/golden/large_n_row_spread.json; this pass sat at 2e-5).  Every kFlushSteps rotation steps the register sums
             // move on to a second level kept in the wave's own part of `red` (LDS: 48 reads, adds and writes per 4,096 steps), so
-            // no accumulator takes more than 4,096 * J terms in sequence.  A range that never gets that far (every N below ~400,000
-            // on 256 CUs) never touches LDS here and adds exactly what it added before.
+            // no accumulator takes more than 4,096 * J terms in sequence.  A range that never gets that far (every N below ~90,000
+            // on 256 CUs; at N = 262,144 more than half of the ranges do) never touches LDS here and adds exactly what it added before.
             uint32_t since = 0;
             bool flushed = false;
             while (u < ug_end) {
@@ -447,7 +461,7 @@ __device__ __forceinline__ void symw_sweeps(const uint32_t* __restrict__ gtab, c
 #pragma unroll
                                     for (int c = 0; c < GW; ++c) r[c] = nb_f2{nb_rsq(r[c].x), nb_rsq(r[c].y)};
 #pragma unroll
-                                    for (int c = 0; c < GW; ++c) si[c] = EQM ? gm * r[c] : symw_mul(f, tm, r[c]);    // (G m_t) inv: resident side, :236
+                                    for (int c = 0; c < GW; ++c) si[c] = UNIT ? r[c] : EQM ? gm * r[c] : symw_mul(f, tm, r[c]);    // (G m_t) inv: resident side, :236
 #pragma unroll
                                     for (int c = 0; c < GW; ++c) sj[c] = EQM ? si[c] : mi[c0g + c] * r[c];           // (G m_i) inv: traveler side
 #pragma unroll
@@ -476,8 +490,8 @@ __device__ __forceinline__ void symw_sweeps(const uint32_t* __restrict__ gtab, c
                         const uint32_t home = ((uint32_t)lane + 1u) & 63u;
                         SymRow* out0 = (zsweep ? spill + (size_t)zrow * CH : partial + (size_t)(pl.t_layer0 + d) * pl.np + tstart) + home;
                         SymRow* out1 = (zsweep1 ? spill + (size_t)zrow1 * CH : partial + (size_t)(pl.t_layer0 + d1) * pl.np + tstart1) + home;
-                        *out0 = SymRow{bx0, by0, bz0};
-                        *out1 = SymRow{bx1, by1, bz1};
+                        *out0 = row_of(bx0, by0, bz0);
+                        *out1 = row_of(bx1, by1, bz1);
                         continue;
                     }
                 }
@@ -529,7 +543,7 @@ __device__ __forceinline__ void symw_sweeps(const uint32_t* __restrict__ gtab, c
 #pragma unroll
                                 for (int c = 0; c < GW; ++c) r[c] = nb_f2{nb_rsq(r[c].x), nb_rsq(r[c].y)};
 #pragma unroll
-                                for (int c = 0; c < GW; ++c) si[c] = EQM ? gm * r[c] : pm * r[c];                    // (G m_t) inv: resident side, :236
+                                for (int c = 0; c < GW; ++c) si[c] = UNIT ? r[c] : EQM ? gm * r[c] : pm * r[c];             // (G m_t) inv: resident side, :236
                                 if constexpr (BOTH) {
 #pragma unroll
                                     for (int c = 0; c < GW; ++c) sj[c] = EQM ? si[c] : mi[c0g + c] * r[c];           // (G m_i) inv: traveler side
@@ -571,7 +585,7 @@ __device__ __forceinline__ void symw_sweeps(const uint32_t* __restrict__ gtab, c
                     SymRow* out = (s0 != 0 ? spill + (size_t)slot * CH : zsweep ? spill + (size_t)zrow * CH : partial + (size_t)(pl.t_layer0 + d) * pl.np + tstart)
                                   + (((uint32_t)lane - s1) & 63u);
 #pragma unroll
-                    for (int uu = 0; uu < J; ++uu) out[uu * 64] = SymRow{bx[uu].x + bx[uu].y, by[uu].x + by[uu].y, bz[uu].x + bz[uu].y};
+                    for (int uu = 0; uu < J; ++uu) out[uu * 64] = row_of(bx[uu].x + bx[uu].y, by[uu].x + by[uu].y, bz[uu].x + bz[uu].y);
                 }
             }
             if (u >= uend && piece_layer != ~0u) {
@@ -582,8 +596,8 @@ __device__ __forceinline__ void symw_sweeps(const uint32_t* __restrict__ gtab, c
                         ax[c].x += red[wi][6 * c + 0][lane]; ay[c].x += red[wi][6 * c + 1][lane]; az[c].x += red[wi][6 * c + 2][lane];
                         ax[c].y += red[wi][6 * c + 3][lane]; ay[c].y += red[wi][6 * c + 4][lane]; az[c].y += red[wi][6 * c + 5][lane];
                     }
-                    out[(2 * c) * 64] = SymRow{ax[c].x, ay[c].x, az[c].x};
-                    out[(2 * c + 1) * 64] = SymRow{ax[c].y, ay[c].y, az[c].y};
+                    out[(2 * c) * 64] = row_of(ax[c].x, ay[c].x, az[c].x);
+                    out[(2 * c + 1) * 64] = row_of(ax[c].y, ay[c].y, az[c].y);
                 }
                 return g;
             }
@@ -610,8 +624,8 @@ __device__ __forceinline__ void symw_sweeps(const uint32_t* __restrict__ gtab, c
                     ax[c].x += red[wi][6 * c + 0][lane]; ay[c].x += red[wi][6 * c + 1][lane]; az[c].x += red[wi][6 * c + 2][lane];
                     ax[c].y += red[wi][6 * c + 3][lane]; ay[c].y += red[wi][6 * c + 4][lane]; az[c].y += red[wi][6 * c + 5][lane];
                 }
-                out[(2 * c) * 64] = SymRow{ax[c].x, ay[c].x, az[c].x};
-                out[(2 * c + 1) * 64] = SymRow{ax[c].y, ay[c].y, az[c].y};
+                out[(2 * c) * 64] = row_of(ax[c].x, ay[c].x, az[c].x);
+                out[(2 * c + 1) * 64] = row_of(ax[c].y, ay[c].y, az[c].y);
             }
         }
         return gfin;
@@ -638,7 +652,7 @@ __device__ __forceinline__ void symw_sweeps(const uint32_t* __restrict__ gtab, c
 #pragma unroll
             for (int j = 0; j < 4; ++j)
                 if (fin[j] == gfin) { sx += red[j][3 * r + 0][lane]; sy += red[j][3 * r + 1][lane]; sz += red[j][3 * r + 2][lane]; }
-            out[r * 64] = SymRow{sx, sy, sz};
+            out[r * 64] = row_of(sx, sy, sz);
         }
     }
     // The queue (two waves per SIMD, whole sweeps; nb_plan.cpp::lay_out_symw): the last sweeps of every older wave's range are nobody's
@@ -689,6 +703,21 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, NG > 4 ?
 void nb_force_symw_pairs_eqm(SYMW_KERNEL_PARAMS)
 {
     symw_sweeps<NG, 1, true, true>(SYMW_KERNEL_ARGS);
+}
+
+// The equal-mass forms with unit mass product (`UNIT`; the engine's form 2): kernels of their own again -- the two above keep their names and
+// their code, and NB_FLAG_NO_EQM_POW2 launches them on the same system (the A/B arm).
+template <int NG, int J>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NG >= 4 ? 2 : 4, NG > 4 ? 2 : (NG < 4 ? 8 : 4))))
+void nb_force_symw_unit(SYMW_KERNEL_PARAMS)
+{
+    symw_sweeps<NG, J, false, true, true>(SYMW_KERNEL_ARGS);
+}
+template <int NG>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, NG > 4 ? 2 : 4)))
+void nb_force_symw_pairs_unit(SYMW_KERNEL_PARAMS)
+{
+    symw_sweeps<NG, 1, true, true, true>(SYMW_KERNEL_ARGS);
 }
 
 // Decides whether a system is one the equal-mass kernels may run on: every mass lane the same bits as row 0's, every vel.w and acc.w zero

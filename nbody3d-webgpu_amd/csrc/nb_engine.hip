@@ -134,11 +134,17 @@ const void* rank_kernel_of(bool f64, int ipl)
 
 // The kernel a shape launches (nullptr: no such instantiation).
 // single_sweeps (NB_FLAG_SINGLE_SWEEPS): the wave-granular symmetric pass with one traveler per lane runs every sweep on its own.
-// eqm: the equal-mass form of that pass (eqm_active below; only the shapes eqm_shape names have one).
+// form: 0 the general kernels, 1 the equal-mass form of that pass, 2 the equal-mass form with unit mass product (eqm_form below; only the
+// shapes eqm_shape names have the two).
 bool eqm_shape(bool f64, const Shape& sh) { return !f64 && sh.kind == kSym && sh.ls == 1 && sh.x == 3 && (sh.ipl == 8 || sh.ipl == 16); }
-const void* kernel_of(bool f64, const Shape& sh, bool single_sweeps = false, bool eqm = false)
+const void* kernel_of(bool f64, const Shape& sh, bool single_sweeps = false, int form = 0)
 {
-    if (eqm) {
+    if (form == 2) {
+        if (!eqm_shape(f64, sh)) return nullptr;
+        if (sh.ipl == 8) return single_sweeps ? (const void*)&nb::nb_force_symw_unit<4, 1> : (const void*)&nb::nb_force_symw_pairs_unit<4>;
+        return single_sweeps ? (const void*)&nb::nb_force_symw_unit<8, 1> : (const void*)&nb::nb_force_symw_pairs_unit<8>;
+    }
+    if (form == 1) {
         if (!eqm_shape(f64, sh)) return nullptr;
         if (sh.ipl == 8) return single_sweeps ? (const void*)&nb::nb_force_symw_eqm<4, 1> : (const void*)&nb::nb_force_symw_pairs_eqm<4>;
         return single_sweeps ? (const void*)&nb::nb_force_symw_eqm<8, 1> : (const void*)&nb::nb_force_symw_pairs_eqm<8>;
@@ -245,19 +251,43 @@ int ensure_gm(nb_sim* s)
 // between steps (an exchange hook or a communicator may); a dt that is not finite would turn the zero w lanes into NaN (0 * inf).
 bool eqm_active(const nb_sim* s) { return s->eqm_capable && s->eqm == nb_sim::kEqmYes && !s->xfn && !s->rccl && std::isfinite((float)s->dt); }
 
+// The force kernels' form: 0 general, 1 equal masses, 2 equal masses with unit mass product (kernels/symmetric.hip.h, `UNIT`).  Form 2 asks of
+// the scalar the kernel streams -- the w lane of row 0 of the j-stream: m0 when G = 1, else (float)G * m0 as nb_gm_pack forms it -- that it be
+// a power of two (zero mantissa, positive, normal) with an exponent in [-32, 32]: gm * inv >= 2^-96 stays normal in the form-1 kernels the
+// bytes are held to (inv = rsq(d2^3) >= 2^-64), and the unscaled sums are at most 2^32 times the scaled ones.  The window bounds the
+// products only: a SUM that is subnormal when scaled (an acceleration component below about 2^-126, met on its way or at the end) is
+// rounded or flushed in form 1 and not in form 2, and there the two forms may differ in that component's last bits -- the identity
+// holds while the scaled sums themselves stay normal, which no system of physical interest leaves.  Derived from the current G:
+// nb_set_params switches the form without a new check.
+int eqm_form(const nb_sim* s)
+{
+    if (!eqm_active(s)) return 0;
+    if (s->no_eqm_pow2) return 1;
+    float m0;
+    memcpy(&m0, &s->eqm_m0, sizeof m0);
+    const float gm = (float)s->G != 1.0f ? (float)s->G * m0 : m0;      // (gm_active, nb_gm_pack)
+    uint32_t bits;
+    memcpy(&bits, &gm, sizeof bits);
+    const int e = (int)(bits >> 23) - 127;        // (sign set: e >= 129)
+    return (bits & 0x007fffffu) == 0u && e >= -32 && e <= 32 ? 2 : 1;
+}
+
 // Makes nb_sim::eqm known: one small launch and one host wait, once per invalidation (an upload decides on the host instead).
 int ensure_eqm(nb_sim* s)
 {
     if (!s->eqm_capable || s->eqm != nb_sim::kEqmUnknown) return NB_OK;
     const float4 *b = (const float4*)s->bodies[s->cur], *v = (const float4*)s->vel, *a = (const float4*)s->acc;
-    uint32_t n = s->n, found = 1;
+    uint32_t n = s->n, found = 1, m0 = 0;
     uint32_t* flag = s->eqm_flag;
     void* args[] = {&b, &v, &a, &n, &flag};
     NB_HIP(s, hipMemsetAsync(flag, 0, sizeof(uint32_t), s->stream));
     NB_HIP(s, hipLaunchKernel((const void*)&nb::nb_eqm_check<0>, dim3(ceil_div(n, nb::kBlock)), dim3(nb::kBlock), args, 0, s->stream));
     NB_HIP(s, hipMemcpyAsync(&found, flag, sizeof found, hipMemcpyDeviceToHost, s->stream));
+    // row 0's mass lane, in the same wait: with the current G it decides the form (eqm_form); used only if the system is an equal-mass one
+    NB_HIP(s, hipMemcpyAsync(&m0, (const char*)s->bodies[s->cur] + 12, sizeof m0, hipMemcpyDeviceToHost, s->stream));
     NB_HIP(s, hipStreamSynchronize(s->stream));
     s->eqm = found ? nb_sim::kEqmNo : nb_sim::kEqmYes;
+    if (!found) s->eqm_m0 = m0;
     return NB_OK;
 }
 
@@ -319,7 +349,7 @@ void launch_force(nb_sim* s, int part = 0, hipEvent_t t0 = nullptr, hipEvent_t t
         } else {
             float e2 = (float)s->eps2;
             void* args[] = {&tab, &b, &p, &sp, &pl.W, &pl.ups, &pl.nsb, &pl.zc, &pl.r_layer0, &pl.t_layer0, &e2, &queue, &npieces, &pieces_off};
-            launch_kernel(kernel_of(false, sh, s->single_sweeps, eqm_active(s)), dim3(ceil_div(pl.W, 4u)), dim3(256), args, s->stream, t0, t1);
+            launch_kernel(kernel_of(false, sh, s->single_sweeps, eqm_form(s)), dim3(ceil_div(pl.W, 4u)), dim3(256), args, s->stream, t0, t1);
         }
         return;
     }
@@ -492,7 +522,7 @@ int role_parity(const nb_sim* s) { return s->cur | (s->acc_parity << 1); }
 bool ensure_graph(nb_sim* s, int which)
 {
     auto& slot = s->graphs[which];
-    if (slot.exec && slot.dt == s->dt && slot.G == s->G && slot.parity == role_parity(s) && slot.eqm == eqm_active(s)) return true;
+    if (slot.exec && slot.dt == s->dt && slot.G == s->G && slot.parity == role_parity(s) && slot.form == eqm_form(s)) return true;
     if (slot.exec) { (void)hipGraphExecDestroy(slot.exec); slot.exec = nullptr; }
     if (slot.graph) { (void)hipGraphDestroy(slot.graph); slot.graph = nullptr; }
     void *acc0 = s->acc, *par0 = s->partial;
@@ -507,7 +537,7 @@ bool ensure_graph(nb_sim* s, int which)
     if (!ok || s->force_err != hipSuccess) { if (g) (void)hipGraphDestroy(g); (void)hipGetLastError(); s->force_err = hipSuccess; s->graphs_ok = false; return false; }
     hipGraphExec_t ge = nullptr;
     if (hipGraphInstantiate(&ge, g, nullptr, nullptr, 0) != hipSuccess) { (void)hipGraphDestroy(g); (void)hipGetLastError(); s->graphs_ok = false; return false; }
-    slot.graph = g; slot.exec = ge; slot.dt = s->dt; slot.G = s->G; slot.parity = role_parity(s); slot.eqm = eqm_active(s);
+    slot.graph = g; slot.exec = ge; slot.dt = s->dt; slot.G = s->G; slot.parity = role_parity(s); slot.form = eqm_form(s);
     return true;
 }
 
@@ -961,6 +991,7 @@ int nb_create(const nb_config* cfg_in, nb_sim** out)
     // lanes of a short block Z, are not of the system's one mass)
     s->eqm_capable = !(cfg.flags & NB_FLAG_NO_EQM) && s->symw && !s->sym_rank && cfg.shard_count == 0 && !cfg.ext_bodies && s->sym_np == s->n
                      && eqm_shape(s->f64, shape_of(s));
+    s->no_eqm_pow2 = (cfg.flags & NB_FLAG_NO_EQM_POW2) != 0;
 
     const size_t row = 4 * s->esz;
     if (cfg.ext_bodies) { s->bodies[0] = cfg.ext_bodies; s->own_bodies = false; }
@@ -1111,6 +1142,7 @@ int nb_upload(nb_sim* s, const void* bodies, const void* vel, const void* accel)
             same = m == m0 && hv[4 * (size_t)i + 3] == 0.f && (!ha || ha[4 * (size_t)i + 3] == 0.f);
         }
         s->eqm = same ? nb_sim::kEqmYes : nb_sim::kEqmNo;
+        s->eqm_m0 = m0;
     }
     return NB_OK;
 }
@@ -1589,6 +1621,17 @@ int nb_eqm_info(nb_sim* s, int* eqm)
     NB_HIP(s, hipSetDevice(s->device));
     if (int rc = ensure_eqm(s)) return rc;
     *eqm = eqm_active(s) ? 1 : 0;
+    return NB_OK;
+}
+
+int nb_eqm_form(nb_sim* s, int* form)
+{
+    if (!s || !form) return NB_ERR_INVALID;
+    *form = 0;
+    if (!s->eqm_capable || !s->uploaded) return NB_OK;
+    NB_HIP(s, hipSetDevice(s->device));
+    if (int rc = ensure_eqm(s)) return rc;
+    *form = eqm_form(s);
     return NB_OK;
 }
 

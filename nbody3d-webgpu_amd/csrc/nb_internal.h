@@ -108,6 +108,8 @@ struct nb_sim {
     enum { kEqmUnknown = 0, kEqmYes = 1, kEqmNo = 2 };
     int eqm = kEqmUnknown;         // nb_upload decides on the host; a pointer handed out makes it unknown, nb_eqm_check re-decides before the next step
     uint32_t* eqm_flag = nullptr;  // device: what nb_eqm_check writes
+    uint32_t eqm_m0 = 0;           // the bits of row 0's mass lane, kept when eqm becomes kEqmYes: with the current G they decide the form (eqm_form)
+    bool no_eqm_pow2 = false;      // NB_FLAG_NO_EQM_POW2: the equal-mass kernels keep their mass product (form 1) whatever G*m is
     hipError_t force_err = hipSuccess;   // launch_force: the reset of the queue's draw counter failed (picked up by whoever launched it)
     // rank form (NB_FLAG_SYM_SHARD: a shard handle whose cross-rank reduction the engine's native exchange provides): the
     // handle's own rows are the resident super-blocks [sym_g0, sym_g1); sym_A[np] = this rank's sums for EVERY row, reduce-
@@ -134,7 +136,7 @@ struct nb_sim {
         hipGraphExec_t exec = nullptr;
         double dt = 0.0, G = 0.0;
         int parity = 0;
-        bool eqm = false;            // captured with the equal-mass force kernel
+        int form = 0;                // the force kernel's form it was captured with (eqm_form)
     } graphs[2];                     // [0]: kGraphChunk steps, [1]: kGraphBig steps (a replay costs the host
                                      // ~10-16 us: amortised over 128 steps it stops showing at N ~ 1,024)
     bool graphs_ok = true;           // cleared if capture ever fails: fall back to plain launches

@@ -68,6 +68,7 @@ static int (*p_upload_levels)(nb_sim *, const uint8_t *);
 static int (*p_neighbors)(nb_sim *, const nb_neighbor_request *);       /* neighbour queries, also within ABI 2.4: optional symbols */
 static int (*p_multi_neighbors)(nb_multi *, const nb_neighbor_request *);
 static int (*p_eqm_info)(nb_sim *, int *);                              /* the equal-mass kernels' report, also within ABI 2.4: optional symbol */
+static int (*p_eqm_form)(nb_sim *, int *);                              /* which equal-mass form, likewise */
 
 /* one JS handle = a single-device nb_sim or a single-process multi-device nb_multi */
 typedef struct { nb_sim *sim; nb_multi *multi; uint32_t n; int f64; } handle_t;
@@ -155,6 +156,7 @@ static napi_value js_load(napi_env env, napi_callback_info info)
         *(void **)(&p_neighbors) = dlsym(h, "nb_neighbors");
         *(void **)(&p_multi_neighbors) = dlsym(h, "nb_multi_neighbors");
         *(void **)(&p_eqm_info) = dlsym(h, "nb_eqm_info");
+        *(void **)(&p_eqm_form) = dlsym(h, "nb_eqm_form");
         g_lib = h;
     }
     if (p_abi_version() != NB_ABI_VERSION) { napi_throw_error(env, "NB_ABI", "ABI version mismatch"); return NULL; }
@@ -483,6 +485,23 @@ static napi_value js_eqm(napi_env env, napi_callback_info info)
     }
     napi_value v;
     CHECK_NAPI(env, napi_get_boolean(env, eqm != 0, &v));
+    return v;
+}
+
+/* eqmForm(handle) -> 0 / 1 / 2: the general kernels, the equal-mass kernels, the equal-mass kernels with unit mass product (nb_eqm_form;
+ * an older library: nb_eqm_info's 0 / 1) */
+static napi_value js_eqm_form(napi_env env, napi_callback_info info)
+{
+    size_t argc = 1; napi_value argv[1];
+    CHECK_NAPI(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    handle_t *h = argc ? get_handle(env, argv[0]) : NULL; if (!h) return NULL;
+    int form = 0;
+    if (h->sim && (p_eqm_form || p_eqm_info)) {
+        int rc = p_eqm_form ? p_eqm_form(h->sim, &form) : p_eqm_info(h->sim, &form);
+        if (rc != NB_OK) return throw_nb(env, rc, h->sim, p_eqm_form ? "nb_eqm_form" : "nb_eqm_info");
+    }
+    napi_value v;
+    CHECK_NAPI(env, napi_create_int32(env, form, &v));
     return v;
 }
 
@@ -846,7 +865,7 @@ static napi_value init_module(napi_env env, napi_value exports)
         {"load", js_load}, {"deviceCount", js_device_count}, {"create", js_create}, {"upload", js_upload},
         {"setParams", js_set_params}, {"step", js_step}, {"download", js_download}, {"sync", js_sync},
         {"destroy", js_destroy}, {"enableTiming", js_enable_timing}, {"kernelTimes", js_kernel_times},
-        {"variant", js_variant}, {"eqm", js_eqm}, {"diagnostics", js_diagnostics}, {"stepTimes", js_step_times},
+        {"variant", js_variant}, {"eqm", js_eqm}, {"eqmForm", js_eqm_form}, {"diagnostics", js_diagnostics}, {"stepTimes", js_step_times},
         {"collectiveInfo", js_collective_info}, {"requestFrame", js_request_frame}, {"frame", js_frame}, {"planQuery", js_plan_query},
         {"fieldEval", js_field_eval}, {"downloadJerk", js_download_jerk}, {"uploadDerivs", js_upload_derivs},
         {"setBlockSteps", js_set_block_steps}, {"blockStats", js_block_stats}, {"downloadLevels", js_download_levels},

@@ -284,6 +284,9 @@ class Simulation {
   variant() { this._need(); return addon.variant(this._h); }
   /** Whether the next force pass runs the equal-mass kernels (nb_eqm_info; flags: 1024 = NB_FLAG_NO_EQM keeps the general ones). */
   eqm() { this._need(); return addon.eqm(this._h); }
+  /** The form of the force kernels the next force pass runs (nb_eqm_form): 0 general, 1 equal masses, 2 equal masses with unit mass product
+   *  (G*m a power of two; flags: 2048 = NB_FLAG_NO_EQM_POW2 keeps form 1). */
+  eqmForm() { this._need(); return addon.eqmForm(this._h); }
   diagnostics() { this._need(); addon.setParams(this._h, this.dt, this.G); return addon.diagnostics(this._h); }
 
   /** Field query (nb_field_eval; no reference analogue): acceleration and potential of the system at `points` -- a typed or

@@ -29,6 +29,7 @@ NB_FLAG_SYM_SHARD = 128
 NB_FLAG_WHOLE_SWEEPS = 256
 NB_FLAG_SINGLE_SWEEPS = 512
 NB_FLAG_NO_EQM = 1024
+NB_FLAG_NO_EQM_POW2 = 2048
 NB_RCCL_ID_BYTES = 128
 NB_RCCL_OVERLAP = 1
 NB_MULTI_PEER, NB_MULTI_RCCL, NB_MULTI_PEER_OVERLAP = 0, 1, 2
@@ -115,7 +116,7 @@ SYMBOLS = ["nb_abi_version", "nb_device_count", "nb_create", "nb_destroy", "nb_u
            "nb_step_times", "nb_step_times2", "nb_integrate_pass", "nb_force_pass", "nb_frame_request", "nb_frame_acquire", "nb_shape_info", "nb_plan_query",
            "nb_abi_minor", "nb_field_eval", "nb_multi_field_eval", "nb_download_jerk", "nb_upload_derivs",
            "nb_set_block_steps", "nb_block_stats", "nb_download_levels", "nb_upload_levels",
-           "nb_neighbors", "nb_multi_neighbors", "nb_neighbors_shape", "nb_eqm_info"]
+           "nb_neighbors", "nb_multi_neighbors", "nb_neighbors_shape", "nb_eqm_info", "nb_eqm_form"]
 
 _lib = None
 
@@ -201,6 +202,8 @@ def load_library():
         L.nb_neighbors_shape.argtypes = [vp, C.c_uint32] + [C.POINTER(C.c_uint32)] * 3
     if hasattr(L, "nb_eqm_info"):           # the equal-mass kernels' report, also within 2.4 and detected by the symbol
         L.nb_eqm_info.argtypes = [vp, C.POINTER(C.c_int)]
+    if hasattr(L, "nb_eqm_form"):           # which of the equal-mass forms, likewise
+        L.nb_eqm_form.argtypes = [vp, C.POINTER(C.c_int)]
     _lib = L
     return L
 
@@ -729,6 +732,16 @@ class Simulation:
         v = C.c_int()
         self._check(self._L.nb_eqm_info(self._h, C.byref(v)))
         return bool(v.value)
+
+    @property
+    def eqm_form(self):
+        """The form of the force kernels the next force pass runs (nb_eqm_form): 0 the general kernels, 1 the equal-mass kernels, 2 the
+        equal-mass kernels with unit mass product (G*m a power of two; NB_FLAG_NO_EQM_POW2 keeps form 1).  An older library: eqm as 0 / 1."""
+        if not hasattr(self._L, "nb_eqm_form"):
+            return int(self.eqm)
+        v = C.c_int()
+        self._check(self._L.nb_eqm_form(self._h, C.byref(v)))
+        return int(v.value)
 
     def diagnostics(self):
         """(kinetic, potential share, momentum[3]) of this handle's shard, fp64 on device."""

@@ -3,6 +3,8 @@
 kernel walks it -- kernels/symmetric.hip.h, `pair`.)  A paired sweep issues 151 instead of 154 vector instructions per rotation step
 with 16 residents per lane (8 residents: 79 instead of 82), an own-chunk sweep 116 (60): the predicted ratio of SQ_INSTS_VALU.
 The equal-mass kernels issue 142 (74), 145 (77) and 115 (59): the second ratio, against the paired kernel.
+The equal-mass kernels with unit mass product (form 2: G*m a power of two) issue 134 (70), 137 (73) and 107 (55): the third ratio, against
+the equal-mass kernels (form 1) -- what SQ_INSTS_VALU of the force kernel should show between the two forms.
     python tools/paired_share.py [N ...] [--variant V]"""
 import os
 import sys
@@ -55,5 +57,8 @@ for n in sizes:
     after = paired * (both - 3) + single * both + own * lone
     # the equal-mass kernels (nb_force_symw_pairs_eqm): one mass product and one lane move less per traveler-step, against `after`
     eqm = paired * (both - 3 - ng - 1) + single * (both - ng - 1) + own * (lone - 1)
-    print("N=%8d %-40s sweeps %9.0f: paired %.4f  single with sums %.4f  own chunks %.4f | predicted VALU instructions x %.5f | equal masses x %.5f" % (
-        n, q["variant"], tot, paired / tot, single / tot, own / tot, after / before, eqm / after))
+    # ... with unit mass product (nb_force_symw_pairs_unit): no mass product at all, one packed instruction less per group and form, against `eqm`
+    unit = paired * (both - 3 - 2 * ng - 1) + single * (both - 2 * ng - 1) + own * (lone - ng - 1)
+    print("N=%8d %-40s sweeps %9.0f: paired %.4f  single with sums %.4f  own chunks %.4f | predicted VALU instructions x %.5f | equal masses x %.5f"
+          " | unit mass product (form 2 / form 1) x %.5f" % (
+              n, q["variant"], tot, paired / tot, single / tot, own / tot, after / before, eqm / after, unit / eqm))
