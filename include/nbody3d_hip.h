@@ -55,7 +55,9 @@ extern "C" {
                              2.4 (round 10) likewise within 2.4: NB_FLAG_NO_EQM (an older library ignores the bit: it has the general kernels only),
                                             nb_eqm_info.  Detected by the presence of the symbol nb_eqm_info
                              2.4 (round 11) likewise within 2.4: NB_FLAG_NO_EQM_POW2 (an older library ignores the bit: its equal-mass kernels keep
-                                            their mass product anyway), nb_eqm_form.  Detected by the presence of the symbol nb_eqm_form */
+                                            their mass product anyway), nb_eqm_form.  Detected by the presence of the symbol nb_eqm_form
+                             2.4 (round 12) likewise within 2.4: nb_neighbor_lists, nb_multi_neighbor_lists, nb_neighbor_lists_shape,
+                                            nb_neighbor_list_request.  Detected by the presence of the symbol nb_neighbor_lists */
 
 typedef struct nb_sim nb_sim; /* opaque */
 
@@ -627,6 +629,58 @@ int nb_multi_neighbors(nb_multi *m, const nb_neighbor_request *req);
 /* The launch shape of an m-point request (no device call): the points of its first batch, the j-chunks each of them is run
  * against, and the bodies of one chunk (whole 256-row tiles).  For tests and tools; the results do not depend on it. */
 int nb_neighbors_shape(nb_sim *s, uint32_t m, uint32_t *batch, uint32_t *chunks, uint32_t *j_per_chunk);
+
+/* ---- neighbour lists (added within ABI 2.4; no reference analogue) ----------------------------
+ * For each of M points: WHICH of the handle's N bodies lie inside its radius -- the members nb_neighbors only counts --, as one
+ * row of `cap` indices per point: the neighbour lists of an Ahmad-Cohen split, the k nearest bodies of a local-density estimate
+ * (take a radius that holds them and select on the host), friends-of-friends links, all close pairs.
+ *   - Membership: body j belongs to the row of point k iff d2(k, j) < h2, strictly, with d2 and h2 computed exactly as
+ *     nb_neighbors computes them for its count: the same expression, the handle's precision, no softening, every row of the
+ *     handle a body whatever its mass.  An NB_NBR_AT_BODIES point leaves ITSELF out by index; another body at the same position
+ *     is a member at d2 = 0.  count[k] therefore equals the count of nb_neighbors bit for bit.
+ *   - Order and overflow: row k = list[k * cap .. k * cap + cap) holds the members in ASCENDING j.  With more than cap members it
+ *     holds the cap SMALLEST indices, and count[k] > cap says so (count is the true number, never clipped).  The entries
+ *     [min(count, cap), cap) of a row hold 0xffffffff: all m * cap elements are defined, in host and in device mode.
+ *   - index / dist2: the nearest body and its squared distance, as nb_neighbors returns them (the radius does not enter).
+ *   - Deterministic, as nb_neighbors: no atomics; a point's row, count, index and dist2 depend on that point and on the bodies
+ *     ONLY -- not on m, not on the batches, not on cap beyond the truncation (the first c entries of a row are the same for every
+ *     cap >= c), not on how the engine cuts j into chunks.  A sub-range request returns the bits of the same rows of a larger one.
+ *   - State read: that of nb_neighbors -- the positions behind every step enqueued so far, a shard handle finishes a pending
+ *     gather first; any handle kind, f32 and f64.  The simulation state, the engine's side copies, the captured step graphs and
+ *     the step counter are untouched: stepping after a call is bit-identical to stepping without it.
+ *   - Radii and points must be finite; the result for a non-finite one is unspecified (the call does not fault).
+ *   - Errors: NB_ERR_INVALID (NULL handle or request -- checked before any device call --, wrong struct_size, m == 0, unknown flag
+ *     bits (2u included), list NULL, cap == 0 or cap > 4096, reserved != 0, neither radii nor radius > 0, radius negative or NaN,
+ *     points given with NB_NBR_AT_BODIES or missing without it, first_body + m > n), NB_ERR_STATE (nothing uploaded);
+ *     nb_last_error names the function and the field.
+ *   - Host pointers: the call blocks until the outputs are written; no pointer is kept.  NB_NBR_DEVICE: every pointer is device
+ *     memory on the handle's device, the work is enqueued on the handle's stream and the call returns at once.
+ *   - Memory: the partial rows of nb_neighbors (the same buffer, the same bound) plus 4 bytes per (point of a batch, j-chunk); a
+ *     host-pointer request stages `list` one batch at a time.  The batch of nb_neighbors is halved, in whole workgroups' worth of
+ *     points, until batch x cap x 4 <= 256 MiB (down to one workgroup's points); nb_neighbor_lists_shape reports it.  Nothing is
+ *     proportional to m x N. */
+typedef struct nb_neighbor_list_request {
+    uint32_t struct_size;   /* sizeof(nb_neighbor_list_request) */
+    uint32_t m;             /* number of points, >= 1 */
+    uint32_t flags;         /* NB_NBR_AT_BODIES | NB_NBR_DEVICE: the bits and the meaning they have for nb_neighbors */
+    uint32_t first_body;    /* NB_NBR_AT_BODIES only */
+    const void *points;     /* 4*m elements x, y, z, (ignored); NULL with NB_NBR_AT_BODIES */
+    const void *radii;      /* optional: m elements, one search radius per point (handle's precision) */
+    double radius;          /* used when radii == NULL; radii or radius > 0 is REQUIRED here */
+    uint32_t cap;           /* entries per point in `list`, 1 <= cap <= 4096 */
+    uint32_t reserved;      /* must be 0 */
+    uint32_t *list;         /* out, required: m * cap elements, row k = point k */
+    uint32_t *count;        /* out, optional: m elements, the TRUE number of bodies with d2 < h*h (may exceed cap) */
+    uint32_t *index;        /* out, optional: m elements, nearest body, as nb_neighbors */
+    void *dist2;            /* out, optional: m elements (handle's precision), its squared distance, as nb_neighbors */
+} nb_neighbor_list_request;
+int nb_neighbor_lists(nb_sim *s, const nb_neighbor_list_request *req);
+/* The same on a multi-shard system: evaluated on shard 0 against the caller's UNPADDED n rows, as nb_multi_neighbors -- a padding
+ * row is never listed and never counted. */
+int nb_multi_neighbor_lists(nb_multi *m, const nb_neighbor_list_request *req);
+/* The launch shape of an m-point request with rows of cap entries (no device call): as nb_neighbors_shape, the batch cut further
+ * as the memory rule above says.  For tests and tools; the results do not depend on it. */
+int nb_neighbor_lists_shape(nb_sim *s, uint32_t m, uint32_t cap, uint32_t *batch, uint32_t *chunks, uint32_t *j_per_chunk);
 
 #if defined(__GNUC__)
 #pragma GCC visibility pop

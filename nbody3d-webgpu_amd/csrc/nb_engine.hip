@@ -1092,7 +1092,7 @@ void nb_destroy(nb_sim* s)
     for (void* p : {s->jerk, s->hx, s->hv, s->fj_part, (void*)s->blk_lev, (void*)s->blk_due, (void*)s->blk_act, (void*)s->blk_hdr}) if (p) (void)hipFree(p);
     if (s->blk_hdr_host) (void)hipHostFree(s->blk_hdr_host);
     if (s->diag) (void)hipFree(s->diag);
-    for (auto* b : {&s->fld_pts, &s->fld_acc, &s->fld_phi, &s->fld_part, &s->nbr_rad, &s->nbr_idx, &s->nbr_d2, &s->nbr_cnt, &s->nbr_inf})
+    for (auto* b : {&s->fld_pts, &s->fld_acc, &s->fld_phi, &s->fld_part, &s->nbr_rad, &s->nbr_idx, &s->nbr_d2, &s->nbr_cnt, &s->nbr_inf, &s->nbl_off, &s->nbl_list})
         if (b->p) (void)hipFree(b->p);
     if (s->zero_row) (void)hipFree(s->zero_row);
     if (s->own_stream && s->stream) (void)hipStreamDestroy(s->stream);
@@ -1967,6 +1967,143 @@ int nb_neighbors_shape(nb_sim* s, uint32_t m, uint32_t* batch, uint32_t* chunks,
     if (m == 0) return fail(s, NB_ERR_INVALID, "nb_neighbors_shape: m must be >= 1");
     uint32_t b, c, per;
     nbr_shape(s, m, s->n, &b, &c, &per);
+    if (batch) *batch = b;
+    if (chunks) *chunks = c;
+    if (j_per_chunk) *j_per_chunk = per;
+    return NB_OK;
+}
+
+/* ---- neighbour lists ---------------------------------------------------------------------- */
+
+namespace {
+
+constexpr uint32_t kNblMaxCap = 4096;                   // most entries of one row
+constexpr uint64_t kNblListBytes = 256ull << 20;        // most bytes of `list` one batch writes (or one workgroup's points x cap, if that is more)
+
+// nbr_shape with the rows of `list` bounded too: the batch is halved in whole workgroups' worth of points until
+// batch x cap x 4 <= kNblListBytes (one workgroup's points is the floor), the chunks follow the batch as in nbr_shape.
+void nbl_shape(const nb_sim* s, uint32_t m, uint32_t cap, uint32_t rows, uint32_t* batch, uint32_t* chunks, uint32_t* per)
+{
+    const uint32_t prow = s->f64 ? nb::kNbrRows64 : nb::kNbrRows;
+    uint32_t mb;
+    nbr_shape(s, m, rows, &mb, chunks, per);
+    while ((uint64_t)mb * cap * 4 > kNblListBytes && mb > prow) {
+        const uint32_t half = std::max(prow, (mb / 2 + prow - 1) / prow * prow);
+        nbr_shape(s, half, rows, &mb, chunks, per);       // (never more than `half` points)
+    }
+    *batch = mb;
+}
+
+}  // namespace
+
+extern "C++" int nbi::neighbor_lists(nb_sim* s, const nb_neighbor_list_request* req, uint32_t rows, const char* who)
+{
+    const std::string w = std::string(who) + ": ";
+    if (!s) return fail(nullptr, NB_ERR_INVALID, w + "null handle");
+    if (!req) return fail(s, NB_ERR_INVALID, w + "null request");
+    if (req->struct_size != sizeof(nb_neighbor_list_request)) return fail(s, NB_ERR_INVALID, w + "struct_size must be sizeof(nb_neighbor_list_request)");
+    if (req->flags & ~(NB_NBR_AT_BODIES | NB_NBR_DEVICE)) return fail(s, NB_ERR_INVALID, w + "unknown bits in flags");
+    const bool at = (req->flags & NB_NBR_AT_BODIES) != 0, dev = (req->flags & NB_NBR_DEVICE) != 0;
+    if (at && req->points) return fail(s, NB_ERR_INVALID, w + "points must be NULL with NB_NBR_AT_BODIES");
+    if (!at && !req->points) return fail(s, NB_ERR_INVALID, w + "points is NULL (and NB_NBR_AT_BODIES is not set)");
+    if (req->m == 0) return fail(s, NB_ERR_INVALID, w + "m must be >= 1");
+    if (!req->list) return fail(s, NB_ERR_INVALID, w + "list is NULL");
+    if (req->cap == 0 || req->cap > kNblMaxCap) return fail(s, NB_ERR_INVALID, w + "cap must be in 1 .. 4096");
+    if (req->reserved != 0) return fail(s, NB_ERR_INVALID, w + "reserved must be 0");
+    if (!(req->radius >= 0.0)) return fail(s, NB_ERR_INVALID, w + "radius must be >= 0 (0: none given)");
+    if (!req->radii && !(req->radius > 0.0)) return fail(s, NB_ERR_INVALID, w + "the lists need radii or radius > 0");
+    if (at && (uint64_t)req->first_body + req->m > rows) return fail(s, NB_ERR_INVALID, w + "first_body + m exceeds n");
+    if (!s->uploaded) return fail(s, NB_ERR_STATE, w + "nothing uploaded yet");
+    NB_HIP(s, hipSetDevice(s->device));
+    if (int rc = finish_gather(s)) return rc;     // other ranks' rows must have landed
+
+    const size_t esz = s->esz, in_row = 4 * esz;
+    const uint32_t m = req->m, cap = req->cap;
+    const char* pts = at ? (const char*)s->bodies[s->cur] + in_row * req->first_body : (const char*)req->points;
+    const char* rad = (const char*)req->radii;
+    char* idx = (char*)req->index;
+    char* d2 = (char*)req->dist2;
+    char* cnt = (char*)req->count;
+    if (!dev) {
+        if (!at) {
+            if (int rc = field_reserve(s, s->fld_pts, in_row * m, who)) return rc;
+            NB_HIP(s, hipMemcpyAsync(s->fld_pts.p, req->points, in_row * m, hipMemcpyHostToDevice, s->stream));
+            pts = (const char*)s->fld_pts.p;
+        }
+        if (rad) {
+            if (int rc = field_reserve(s, s->nbr_rad, esz * m, who)) return rc;
+            NB_HIP(s, hipMemcpyAsync(s->nbr_rad.p, req->radii, esz * m, hipMemcpyHostToDevice, s->stream));
+            rad = (const char*)s->nbr_rad.p;
+        }
+        if (idx) { if (int rc = field_reserve(s, s->nbr_idx, 4 * (size_t)m, who)) return rc; idx = (char*)s->nbr_idx.p; }
+        if (d2) { if (int rc = field_reserve(s, s->nbr_d2, esz * m, who)) return rc; d2 = (char*)s->nbr_d2.p; }
+        if (cnt) { if (int rc = field_reserve(s, s->nbr_cnt, 4 * (size_t)m, who)) return rc; cnt = (char*)s->nbr_cnt.p; }
+    }
+    if (!s->f64 && !s->nbr_inf.p) {
+        static const float inf_row[4] = {HUGE_VALF, HUGE_VALF, HUGE_VALF, 0.0f};
+        if (int rc = field_reserve(s, s->nbr_inf, 64, who)) return rc;
+        NB_HIP(s, hipMemcpyAsync(s->nbr_inf.p, inf_row, sizeof inf_row, hipMemcpyHostToDevice, s->stream));
+    }
+
+    const uint32_t prow = s->f64 ? nb::kNbrRows64 : nb::kNbrRows;      // points per workgroup
+    const void* bodies = s->bodies[s->cur];
+    const void* inf_row = s->nbr_inf.p;
+    uint32_t n = rows, at_flag = at ? 1u : 0u, cap_arg = cap;
+    double rd = req->radius;
+    float rf = (float)req->radius;
+    for (uint32_t done = 0; done < m;) {
+        uint32_t mb, chunks, per;
+        nbl_shape(s, m - done, cap, rows, &mb, &chunks, &per);
+        const size_t list_bytes = (size_t)4 * cap * mb;
+        if (int rc = field_reserve(s, s->fld_part, (size_t)16 * chunks * mb, who)) return rc;
+        if (int rc = field_reserve(s, s->nbl_off, (size_t)4 * chunks * mb, who)) return rc;
+        if (!dev) { if (int rc = field_reserve(s, s->nbl_list, list_bytes, who)) return rc; }
+        const void* p = pts + in_row * done;
+        const void* r = rad ? rad + esz * done : nullptr;
+        void* part = s->fld_part.p;
+        void* off = s->nbl_off.p;
+        void* lst = dev ? (void*)(req->list + (size_t)cap * done) : s->nbl_list.p;
+        void* oi = idx ? idx + (size_t)4 * done : nullptr;
+        void* od = d2 ? d2 + esz * done : nullptr;
+        void* oc = cnt ? cnt + (size_t)4 * done : nullptr;
+        uint32_t self0 = req->first_body + done;
+        dim3 grid(ceil_div(mb, prow), chunks), block(nb::kBlock);
+        NB_HIP(s, hipMemsetAsync(lst, 0xff, list_bytes, s->stream));          // what pads the rows
+        void* oargs[] = {&part, &mb, &chunks, &off, &oi, &od, &oc};
+        if (s->f64) {
+            void* args[] = {&bodies, &p, &r, &part, &n, &mb, &per, &rd, &at_flag, &self0};
+            NB_HIP(s, hipLaunchKernel((const void*)&nb::nb_nbr64<double>, grid, block, args, 0, s->stream));
+            NB_HIP(s, hipLaunchKernel((const void*)&nb::nb_nbl_offsets<double>, dim3(ceil_div(mb, nb::kBlock)), block, oargs, 0, s->stream));
+            void* fargs[] = {&bodies, &p, &r, &off, &lst, &n, &mb, &per, &rd, &at_flag, &self0, &cap_arg};
+            NB_HIP(s, hipLaunchKernel((const void*)&nb::nb_nbl64<double>, grid, block, fargs, 0, s->stream));
+        } else {
+            void* args[] = {&bodies, &p, &r, &part, &n, &mb, &per, &rf, &at_flag, &self0, &inf_row};
+            NB_HIP(s, hipLaunchKernel((const void*)&nb::nb_nbr_pk<true>, grid, block, args, 0, s->stream));
+            NB_HIP(s, hipLaunchKernel((const void*)&nb::nb_nbl_offsets<float>, dim3(ceil_div(mb, nb::kBlock)), block, oargs, 0, s->stream));
+            void* fargs[] = {&bodies, &p, &r, &off, &lst, &n, &mb, &per, &rf, &at_flag, &self0, &cap_arg, &inf_row};
+            NB_HIP(s, hipLaunchKernel((const void*)&nb::nb_nbl_pk<>, grid, block, fargs, 0, s->stream));
+        }
+        if (!dev) NB_HIP(s, hipMemcpyAsync(req->list + (size_t)cap * done, lst, list_bytes, hipMemcpyDeviceToHost, s->stream));
+        done += mb;
+    }
+    if (!dev) {
+        if (req->index) NB_HIP(s, hipMemcpyAsync(req->index, idx, 4 * (size_t)m, hipMemcpyDeviceToHost, s->stream));
+        if (req->dist2) NB_HIP(s, hipMemcpyAsync(req->dist2, d2, esz * m, hipMemcpyDeviceToHost, s->stream));
+        if (req->count) NB_HIP(s, hipMemcpyAsync(req->count, cnt, 4 * (size_t)m, hipMemcpyDeviceToHost, s->stream));
+        NB_HIP(s, hipStreamSynchronize(s->stream));
+    }
+    return NB_OK;
+}
+
+int nb_neighbor_lists(nb_sim* s, const nb_neighbor_list_request* req) { return nbi::neighbor_lists(s, req, s ? s->n : 0u, "nb_neighbor_lists"); }
+
+int nb_neighbor_lists_shape(nb_sim* s, uint32_t m, uint32_t cap, uint32_t* batch, uint32_t* chunks, uint32_t* j_per_chunk)
+{
+    if (!s) return fail(nullptr, NB_ERR_INVALID, "nb_neighbor_lists_shape: null handle");
+    if (m == 0) return fail(s, NB_ERR_INVALID, "nb_neighbor_lists_shape: m must be >= 1");
+    if (cap == 0 || cap > kNblMaxCap) return fail(s, NB_ERR_INVALID, "nb_neighbor_lists_shape: cap must be in 1 .. 4096");
+    uint32_t b, c, per;
+    nbl_shape(s, m, cap, s->n, &b, &c, &per);
     if (batch) *batch = b;
     if (chunks) *chunks = c;
     if (j_per_chunk) *j_per_chunk = per;

@@ -157,6 +157,10 @@ struct nb_sim {
     // -- the two never overlap on the stream --; rad / idx / d2 / cnt stage a host-pointer request (O(m)); inf is one row at +inf, the
     // LDS-DMA source of nb_nbr_pk for j past the range
     field_buf nbr_rad, nbr_idx, nbr_d2, nbr_cnt, nbr_inf;
+    // nb_neighbor_lists: shares all of the above with nb_neighbors; off holds uint32 [j-chunk][point of a batch], the entries of a
+    // point's row that the chunks before hold (bounded as fld_part is); list stages one batch of a host-pointer request (<= 256 MiB,
+    // or one workgroup's points x cap)
+    field_buf nbl_off, nbl_list;
     // NB_INT_HERMITE4: bodies[0] / vel are the state at ONE instant, acc / jerk the derivatives derived from it.  None of the
     // leapfrog launch fields above is used: plain unpadded arrays, no planner, no graphs.
     bool hermite = false;
@@ -190,6 +194,8 @@ void set_create_error(const std::string& msg);
 // nb_neighbors on the first `rows` rows of the handle (nb_multi_neighbors: the caller's unpadded rows of shard 0); `who` names the
 // public function in the messages
 int neighbors(nb_sim* s, const nb_neighbor_request* req, uint32_t rows, const char* who);
+// nb_neighbor_lists likewise (nb_multi_neighbor_lists: the caller's unpadded rows of shard 0)
+int neighbor_lists(nb_sim* s, const nb_neighbor_list_request* req, uint32_t rows, const char* who);
 const std::string& create_error();
 
 // nb_comm.hip: called by nb_step after the integrate kernel when a communicator is attached.

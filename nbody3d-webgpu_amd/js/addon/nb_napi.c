@@ -67,6 +67,8 @@ static int (*p_download_levels)(nb_sim *, uint8_t *);
 static int (*p_upload_levels)(nb_sim *, const uint8_t *);
 static int (*p_neighbors)(nb_sim *, const nb_neighbor_request *);       /* neighbour queries, also within ABI 2.4: optional symbols */
 static int (*p_multi_neighbors)(nb_multi *, const nb_neighbor_request *);
+static int (*p_neighbor_lists)(nb_sim *, const nb_neighbor_list_request *);       /* neighbour lists, likewise: optional symbols */
+static int (*p_multi_neighbor_lists)(nb_multi *, const nb_neighbor_list_request *);
 static int (*p_eqm_info)(nb_sim *, int *);                              /* the equal-mass kernels' report, also within ABI 2.4: optional symbol */
 static int (*p_eqm_form)(nb_sim *, int *);                              /* which equal-mass form, likewise */
 
@@ -155,6 +157,8 @@ static napi_value js_load(napi_env env, napi_callback_info info)
         *(void **)(&p_upload_levels) = dlsym(h, "nb_upload_levels");
         *(void **)(&p_neighbors) = dlsym(h, "nb_neighbors");
         *(void **)(&p_multi_neighbors) = dlsym(h, "nb_multi_neighbors");
+        *(void **)(&p_neighbor_lists) = dlsym(h, "nb_neighbor_lists");
+        *(void **)(&p_multi_neighbor_lists) = dlsym(h, "nb_multi_neighbor_lists");
         *(void **)(&p_eqm_info) = dlsym(h, "nb_eqm_info");
         *(void **)(&p_eqm_form) = dlsym(h, "nb_eqm_form");
         g_lib = h;
@@ -728,6 +732,64 @@ static napi_value js_neighbors(napi_env env, napi_callback_info info)
     return undefined(env);
 }
 
+/* neighborLists(handle, points|null, firstBody, count, radii|null, radius, cap, listOut, countOut|null): nb_neighbor_lists /
+ * nb_multi_neighbor_lists.  points (4*m) / radii (m): typed arrays of the handle's precision; listOut: Uint32Array of m*cap
+ * elements, countOut: Uint32Array of m elements, written in place.  points null: the points are the bodies [firstBody,
+ * firstBody + count) themselves (NB_NBR_AT_BODIES). */
+static napi_value js_neighbor_lists(napi_env env, napi_callback_info info)
+{
+    size_t argc = 9; napi_value argv[9];
+    CHECK_NAPI(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    if (argc < 9) { napi_throw_type_error(env, NULL, "neighborLists(handle, points|null, firstBody, count, radii|null, radius, cap, listOut, countOut|null)"); return NULL; }
+    handle_t *h = get_handle(env, argv[0]); if (!h) return NULL;
+    if (!p_neighbor_lists || !p_multi_neighbor_lists) return throw_msg(env, NB_ERR_STATE, "the loaded library has no nb_neighbor_lists", "nb_neighbor_lists");
+    const napi_typedarray_type real = h->f64 ? napi_float64_array : napi_float32_array;
+    void *ptr[4] = {NULL, NULL, NULL, NULL}; size_t len[4] = {0, 0, 0, 0};
+    static const int arg_of[4] = {1, 4, 7, 8};
+    static const int is_u32[4] = {0, 0, 1, 1};
+    static const char *const what[4] = {"points", "radii", "listOut", "countOut"};
+    for (int k = 0; k < 4; ++k) {
+        napi_valuetype vt; napi_typeof(env, argv[arg_of[k]], &vt);
+        if (vt == napi_null || vt == napi_undefined) continue;
+        bool is_ta = false; napi_is_typedarray(env, argv[arg_of[k]], &is_ta);
+        napi_typedarray_type tt; napi_value ab; size_t off;
+        const napi_typedarray_type want = is_u32[k] ? napi_uint32_array : real;
+        if (!is_ta || napi_get_typedarray_info(env, argv[arg_of[k]], &tt, &len[k], &ptr[k], &ab, &off) != napi_ok || tt != want) {
+            char buf[160]; snprintf(buf, sizeof buf, "neighborLists: %s must be a %s or null", what[k], is_u32[k] ? "Uint32Array" : h->f64 ? "Float64Array" : "Float32Array");
+            napi_throw_type_error(env, NULL, buf); return NULL;
+        }
+    }
+    double first = 0, count = 0, radius = 0, cap = 0;
+    napi_get_value_double(env, argv[2], &first); napi_get_value_double(env, argv[3], &count); napi_get_value_double(env, argv[5], &radius);
+    napi_get_value_double(env, argv[6], &cap);
+    if (!(cap >= 0 && cap <= 4294967295.0)) { napi_throw_range_error(env, NULL, "neighborLists: cap out of range"); return NULL; }
+    nb_neighbor_list_request req;
+    memset(&req, 0, sizeof req);
+    req.struct_size = sizeof req;
+    if (ptr[0]) {
+        if (len[0] % 4 != 0 || len[0] / 4 > 0xffffffffu) { napi_throw_range_error(env, NULL, "neighborLists: points must hold 4*m elements"); return NULL; }
+        req.m = (uint32_t)(len[0] / 4);
+        req.points = ptr[0];
+    } else {
+        if (!(first >= 0 && first <= 4294967295.0 && count >= 0 && count <= 4294967295.0)) { napi_throw_range_error(env, NULL, "neighborLists: firstBody / count out of range"); return NULL; }
+        req.flags = NB_NBR_AT_BODIES;
+        req.first_body = (uint32_t)first; req.m = (uint32_t)count;
+    }
+    req.cap = (uint32_t)cap;
+    if ((ptr[1] && len[1] != (size_t)req.m) || (ptr[3] && len[3] != (size_t)req.m)) { napi_throw_range_error(env, NULL, "neighborLists: radii and countOut must hold m elements"); return NULL; }
+    if (ptr[2] && len[2] != (size_t)req.m * (size_t)req.cap) { napi_throw_range_error(env, NULL, "neighborLists: listOut must hold m * cap elements"); return NULL; }
+    req.radii = ptr[1]; req.radius = radius;
+    req.list = (uint32_t *)ptr[2]; req.count = (uint32_t *)ptr[3];
+    if (h->multi) {
+        int rcm = p_multi_neighbor_lists(h->multi, &req);
+        if (rcm != NB_OK) return throw_msg(env, rcm, p_multi_last_error(h->multi), "nb_multi_neighbor_lists");
+    } else {
+        int rc = p_neighbor_lists(h->sim, &req);
+        if (rc != NB_OK) return throw_nb(env, rc, h->sim, "nb_neighbor_lists");
+    }
+    return undefined(env);
+}
+
 /* downloadJerk(handle, jerkOut): nb_download_jerk -- 4*n elements (jx, jy, jz, 0) of a Hermite handle, written in place. */
 static napi_value js_download_jerk(napi_env env, napi_callback_info info)
 {
@@ -869,7 +931,7 @@ static napi_value init_module(napi_env env, napi_value exports)
         {"collectiveInfo", js_collective_info}, {"requestFrame", js_request_frame}, {"frame", js_frame}, {"planQuery", js_plan_query},
         {"fieldEval", js_field_eval}, {"downloadJerk", js_download_jerk}, {"uploadDerivs", js_upload_derivs},
         {"setBlockSteps", js_set_block_steps}, {"blockStats", js_block_stats}, {"downloadLevels", js_download_levels},
-        {"uploadLevels", js_upload_levels}, {"neighbors", js_neighbors},
+        {"uploadLevels", js_upload_levels}, {"neighbors", js_neighbors}, {"neighborLists", js_neighbor_lists},
     };
     for (size_t i = 0; i < sizeof fns / sizeof fns[0]; ++i) {
         napi_value f;

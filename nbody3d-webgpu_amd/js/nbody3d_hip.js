@@ -345,6 +345,38 @@ class Simulation {
     return out;
   }
 
+  /** Neighbour lists (nb_neighbor_lists; no reference analogue): WHICH bodies lie strictly inside options.radius (one for all) or
+   *  options.radii (one per point) of each of `points` -- 4*m elements x, y, z, (ignored) -- or, with options.bodies = [first, count]
+   *  (and points null), of each of those bodies, itself left out by index.  Returns {list: Uint32Array of m * cap elements, count:
+   *  Uint32Array of m elements, cap}: row k = list.subarray(k * cap, (k + 1) * cap) holds the members in ascending order, padded
+   *  with 0xffffffff; count[k] is the true number of members, and where it exceeds cap (options.cap, default 64, at most 4096) the
+   *  row holds the cap smallest indices.  The simulation state is not touched. */
+  neighborLists(points, options) {
+    this._need();
+    const o = options || {}, T = this.ArrayType;
+    let pts = null, first = 0, m;
+    if (o.bodies) { first = o.bodies[0] >>> 0; m = o.bodies[1] >>> 0; }
+    if (points !== null && points !== undefined) {
+      if (points instanceof T) pts = points;
+      else if (typeof points.length === 'number') pts = T.from(points);
+      else throw new TypeError('points: expected ' + T.name);
+      if (pts.length % 4 !== 0) throw new RangeError('points must hold 4*m elements (x, y, z, ignored)');
+      if (o.bodies) throw new RangeError('neighborLists(): give either points or options.bodies, not both');
+      m = pts.length / 4;
+    } else if (!o.bodies) throw new TypeError('neighborLists(): points, or options.bodies = [first, count], required');
+    let radii = null;
+    if (o.radii !== null && o.radii !== undefined) {
+      radii = o.radii instanceof T ? o.radii : T.from(o.radii);
+      if (radii.length !== m) throw new RangeError('options.radii must hold one radius per point');
+    }
+    const radius = o.radius === undefined || o.radius === null ? 0 : +o.radius;
+    const cap = o.cap === undefined || o.cap === null ? 64 : +o.cap;
+    if (!(Number.isInteger(cap) && cap >= 1 && cap <= 4096)) throw new RangeError('options.cap must be an integer in 1 .. 4096');
+    const out = { list: new Uint32Array(m * cap), count: new Uint32Array(m), cap: cap };
+    addon.neighborLists(this._h, pts, first, m, radii, radius, cap, out.list, out.count);
+    return out;
+  }
+
   /** The close pairs of the system: the MUTUAL nearest neighbours (i < j, each the other's nearest body) closer than `radius`, as
    *  {pairs: Uint32Array of 2*k elements i0, j0, i1, j1, ... sorted by i, dist2: k elements} -- one neighbors() call over all
    *  bodies and host code on its result. */

@@ -88,6 +88,13 @@ class nb_neighbor_request(C.Structure):     # include/nbody3d_hip.h (neighbour q
                 ("index", C.c_void_p), ("dist2", C.c_void_p), ("count", C.c_void_p)]
 
 
+class nb_neighbor_list_request(C.Structure):     # include/nbody3d_hip.h (neighbour lists, added within ABI 2.4)
+    _fields_ = [("struct_size", C.c_uint32), ("m", C.c_uint32), ("flags", C.c_uint32), ("first_body", C.c_uint32),
+                ("points", C.c_void_p), ("radii", C.c_void_p), ("radius", C.c_double),
+                ("cap", C.c_uint32), ("reserved", C.c_uint32),
+                ("list", C.c_void_p), ("count", C.c_void_p), ("index", C.c_void_p), ("dist2", C.c_void_p)]
+
+
 NB_BLOCK_FROZEN = 1
 
 
@@ -116,7 +123,8 @@ SYMBOLS = ["nb_abi_version", "nb_device_count", "nb_create", "nb_destroy", "nb_u
            "nb_step_times", "nb_step_times2", "nb_integrate_pass", "nb_force_pass", "nb_frame_request", "nb_frame_acquire", "nb_shape_info", "nb_plan_query",
            "nb_abi_minor", "nb_field_eval", "nb_multi_field_eval", "nb_download_jerk", "nb_upload_derivs",
            "nb_set_block_steps", "nb_block_stats", "nb_download_levels", "nb_upload_levels",
-           "nb_neighbors", "nb_multi_neighbors", "nb_neighbors_shape", "nb_eqm_info", "nb_eqm_form"]
+           "nb_neighbors", "nb_multi_neighbors", "nb_neighbors_shape", "nb_eqm_info", "nb_eqm_form",
+           "nb_neighbor_lists", "nb_multi_neighbor_lists", "nb_neighbor_lists_shape"]
 
 _lib = None
 
@@ -200,6 +208,10 @@ def load_library():
         L.nb_neighbors.argtypes = [vp, C.POINTER(nb_neighbor_request)]
         L.nb_multi_neighbors.argtypes = [vp, C.POINTER(nb_neighbor_request)]
         L.nb_neighbors_shape.argtypes = [vp, C.c_uint32] + [C.POINTER(C.c_uint32)] * 3
+    if hasattr(L, "nb_neighbor_lists"):     # neighbour lists, also within 2.4 and detected by the symbol
+        L.nb_neighbor_lists.argtypes = [vp, C.POINTER(nb_neighbor_list_request)]
+        L.nb_multi_neighbor_lists.argtypes = [vp, C.POINTER(nb_neighbor_list_request)]
+        L.nb_neighbor_lists_shape.argtypes = [vp, C.c_uint32, C.c_uint32] + [C.POINTER(C.c_uint32)] * 3
     if hasattr(L, "nb_eqm_info"):           # the equal-mass kernels' report, also within 2.4 and detected by the symbol
         L.nb_eqm_info.argtypes = [vp, C.POINTER(C.c_int)]
     if hasattr(L, "nb_eqm_form"):           # which of the equal-mass forms, likewise
@@ -314,6 +326,89 @@ def _neighbor_request(dtype, points, bodies, radius, radii):
     req.dist2 = _ptr(dist2) if req.m else None
     req.count = _ptr(count) if count is not None and req.m else None
     return req, (pts, rad), index, dist2, count
+
+
+def _need_neighbor_lists(what):
+    if not hasattr(load_library(), "nb_neighbor_lists"):
+        raise NBodyError(1, "%s: the loaded library has no nb_neighbor_lists" % what)
+
+
+def _neighbor_list_request(dtype, points, bodies, radius, radii, cap, nearest):
+    """The nb_neighbor_list_request of neighbor_lists(): (request, arrays kept alive, lists, count, index | None, dist2 | None)."""
+    _need_neighbor_lists("neighbor_lists()")
+    req = nb_neighbor_list_request()
+    req.struct_size = C.sizeof(nb_neighbor_list_request)
+    pts = rad = None
+    # (both or neither of points / bodies, a cap out of range: passed on as they are -- the engine's NB_ERR_INVALID names the field)
+    if bodies is not None:
+        first, count = int(bodies[0]), int(bodies[1])
+        if not (0 <= first < 2 ** 32 and 0 <= count < 2 ** 32):
+            raise ValueError("neighbor_lists(): bodies=(first, count) out of range")
+        req.flags |= NB_NBR_AT_BODIES
+        req.first_body, req.m = first, count
+    if points is not None:
+        pts = np.asarray(points, dtype=dtype)
+        if pts.ndim == 1:
+            pts = pts.reshape(-1, 3 if pts.size % 4 else 4)
+        if pts.ndim != 2 or pts.shape[1] not in (3, 4):
+            raise ValueError("neighbor_lists(): points must have shape (m, 3) or (m, 4)")
+        if pts.shape[1] == 3:
+            pts = np.concatenate([pts, np.zeros((len(pts), 1), dtype)], axis=1)
+        pts = np.ascontiguousarray(pts)
+        if bodies is None:
+            req.m = len(pts)
+        req.points = _ptr(pts) if len(pts) else None
+    if radii is not None:
+        rad = np.ascontiguousarray(radii, dtype=dtype).reshape(-1)
+        if len(rad) != req.m:
+            raise ValueError("neighbor_lists(): radii must hold one radius per point")
+        req.radii = _ptr(rad) if len(rad) else None
+    if radius is not None:
+        req.radius = float(radius)
+    cap = int(cap)
+    if not 0 <= cap < 2 ** 32:
+        raise ValueError("neighbor_lists(): cap out of range")
+    req.cap = cap
+    rows = cap if 1 <= cap <= 4096 else 1              # (an invalid cap is the engine's to refuse: nothing is written then)
+    lists = np.zeros((req.m, rows), np.uint32)
+    count = np.zeros((req.m,), np.uint32)
+    index = np.zeros((req.m,), np.uint32) if nearest else None
+    dist2 = np.zeros((req.m,), dtype) if nearest else None
+    req.list = _ptr(lists) if req.m else None
+    req.count = _ptr(count) if req.m else None
+    req.index = _ptr(index) if nearest and req.m else None
+    req.dist2 = _ptr(dist2) if nearest and req.m else None
+    return req, (pts, rad), lists, count, index, dist2
+
+
+def lists_to_csr(lists, count):
+    """The rows of a neighbor_lists() result without their padding: ``(offsets (m + 1,) int64, indices uint32, truncated (m,) bool)``
+    -- row k is ``indices[offsets[k]:offsets[k + 1]]``, its min(count[k], cap) entries in ascending order; ``truncated[k]`` says that
+    count[k] > cap, i.e. that the row holds only the cap smallest of its members."""
+    lists = np.asarray(lists, np.uint32)
+    count = np.asarray(count, np.uint32).astype(np.int64)
+    if lists.ndim != 2 or count.shape != (lists.shape[0],):
+        raise ValueError("lists_to_csr(): lists must be (m, cap) and count (m,)")
+    m, cap = lists.shape
+    kept = np.minimum(count, cap)
+    offsets = np.zeros(m + 1, np.int64)
+    np.cumsum(kept, out=offsets[1:])
+    mask = np.arange(cap, dtype=np.int64)[None, :] < kept[:, None]
+    return offsets, lists[mask], count > cap
+
+
+def pairs_from_lists(lists, count, first=0):
+    """Every unordered pair (i, j), i < j, of the rows of an all-bodies neighbor_lists() result (row k = body first + k):
+    ``(k, 2) uint32`` sorted by i, then j.  Membership is symmetric, so each pair is taken from the row of its smaller index.
+    Raises if a row was truncated."""
+    offsets, indices, truncated = lists_to_csr(lists, count)
+    if truncated.any():
+        raise ValueError("pairs_from_lists(): %d rows hold more members than cap (the largest count is %d): ask again with a larger cap"
+                         % (int(truncated.sum()), int(np.asarray(count).max())))
+    i = np.repeat(np.arange(len(offsets) - 1, dtype=np.int64) + int(first), np.diff(offsets))
+    j = indices.astype(np.int64)
+    ok = i < j
+    return np.stack([i[ok], j[ok]], axis=1).astype(np.uint32).reshape(-1, 2)
 
 
 def mutual_pairs(index, dist2, radius):
@@ -818,6 +913,55 @@ class Simulation:
         self._check(self._L.nb_neighbors_shape(self._h, int(m), *[C.byref(x) for x in v]))
         return dict(zip(("batch", "chunks", "j_per_chunk"), (x.value for x in v)))
 
+    def neighbor_lists(self, points=None, *, bodies=None, radius=None, radii=None, cap=64, nearest=False):
+        """nb_neighbor_lists: WHICH bodies lie strictly inside ``radius`` (one for all) or ``radii`` (one per point) of each of
+        ``points`` -- or, with ``bodies=(first, count)``, of each of those bodies, itself left out by index.  Returns ``(lists (m, cap)
+        uint32, count (m,) uint32)``, and with ``nearest`` also ``index`` and ``dist2`` as neighbors() returns them.  Row k holds the
+        members in ascending order, padded with NB_NBR_NONE; ``count`` is the true number of members (what neighbors() counts, bit
+        for bit): where it exceeds ``cap`` the row holds the cap smallest indices.  See lists_to_csr()."""
+        req, keep, lists, count, index, dist2 = _neighbor_list_request(self.dtype, points, bodies, radius, radii, cap, nearest)
+        self._check(self._L.nb_neighbor_lists(self._h, C.byref(req)))
+        return (lists, count, index, dist2) if nearest else (lists, count)
+
+    def neighbor_lists_device(self, points_ptr, m, list_ptr, cap, count_ptr=None, index_ptr=None, dist2_ptr=None, *, bodies=None,
+                              radius=None, radii_ptr=None):
+        """The device-pointer form (NB_NBR_DEVICE): device addresses on the handle's device (0 or None for what is not wanted);
+        ``list_ptr``: m * cap uint32.  Enqueued on the handle's stream, returns without waiting.  ``bodies=(first, count)`` selects the
+        bodies themselves (``points_ptr`` must then be None, ``m`` is ignored)."""
+        _need_neighbor_lists("neighbor_lists_device()")
+        req = nb_neighbor_list_request()
+        req.struct_size = C.sizeof(nb_neighbor_list_request)
+        req.flags = NB_NBR_DEVICE
+        if bodies is not None:
+            req.flags |= NB_NBR_AT_BODIES
+            req.first_body, req.m = int(bodies[0]), int(bodies[1])
+        else:
+            req.m = int(m)
+        req.points = points_ptr or None
+        req.radii = radii_ptr or None
+        req.radius = 0.0 if radius is None else float(radius)
+        req.cap = int(cap)
+        req.list = list_ptr or None
+        req.count = count_ptr or None
+        req.index = index_ptr or None
+        req.dist2 = dist2_ptr or None
+        self._check(self._L.nb_neighbor_lists(self._h, C.byref(req)))
+
+    def neighbor_lists_shape(self, m, cap):
+        """{batch, chunks, j_per_chunk}: the launch shape nb_neighbor_lists gives an m-point request with rows of ``cap`` entries (the
+        answers do not depend on it)."""
+        _need_neighbor_lists("neighbor_lists_shape()")
+        v = [C.c_uint32() for _ in range(3)]
+        self._check(self._L.nb_neighbor_lists_shape(self._h, int(m), int(cap), *[C.byref(x) for x in v]))
+        return dict(zip(("batch", "chunks", "j_per_chunk"), (x.value for x in v)))
+
+    def all_close_pairs(self, radius, cap=64):
+        """EVERY unordered pair i < j of bodies with d2 < radius^2 (close_pairs() gives the mutual-nearest ones only), as ``(k, 2)
+        uint32`` sorted by i, then j -- one neighbor_lists(bodies=(0, n)) call and host code on its result.  Raises ValueError if a
+        body has more than ``cap`` neighbours inside the radius."""
+        lists, count = self.neighbor_lists(bodies=(0, self.n), radius=radius, cap=cap)
+        return pairs_from_lists(lists, count)
+
     def close_pairs(self, radius):
         """The close pairs of the system: the MUTUAL nearest neighbours (i < j, each the other's nearest body) closer than ``radius``,
         as ``(pairs (k, 2) uint32 sorted by i, d2 (k,))`` -- one neighbors(bodies=(0, n)) call and host code on its result."""
@@ -974,6 +1118,13 @@ class MultiSimulation:
         req, keep, index, dist2, count = _neighbor_request(self.dtype, points, bodies, radius, radii)
         self._check(self._L.nb_multi_neighbors(self._h, C.byref(req)))
         return index, dist2, count
+
+    def neighbor_lists(self, points=None, *, bodies=None, radius=None, radii=None, cap=64, nearest=False):
+        """nb_multi_neighbor_lists: Simulation.neighbor_lists() on the whole system (evaluated on shard 0 against the caller's
+        unpadded rows: a padding row is never listed); ``bodies=(first, count)`` counts the caller's unpadded rows."""
+        req, keep, lists, count, index, dist2 = _neighbor_list_request(self.dtype, points, bodies, radius, radii, cap, nearest)
+        self._check(self._L.nb_multi_neighbor_lists(self._h, C.byref(req)))
+        return (lists, count, index, dist2) if nearest else (lists, count)
 
     @property
     def variant(self):
