@@ -57,7 +57,9 @@ extern "C" {
                              2.4 (round 11) likewise within 2.4: NB_FLAG_NO_EQM_POW2 (an older library ignores the bit: its equal-mass kernels keep
                                             their mass product anyway), nb_eqm_form.  Detected by the presence of the symbol nb_eqm_form
                              2.4 (round 12) likewise within 2.4: nb_neighbor_lists, nb_multi_neighbor_lists, nb_neighbor_lists_shape,
-                                            nb_neighbor_list_request.  Detected by the presence of the symbol nb_neighbor_lists */
+                                            nb_neighbor_list_request.  Detected by the presence of the symbol nb_neighbor_lists
+                             2.4 (round 13) likewise within 2.4: nb_knn, nb_multi_knn, nb_knn_shape, nb_knn_request.  Detected by the presence
+                                            of the symbol nb_knn */
 
 typedef struct nb_sim nb_sim; /* opaque */
 
@@ -632,8 +634,8 @@ int nb_neighbors_shape(nb_sim *s, uint32_t m, uint32_t *batch, uint32_t *chunks,
 
 /* ---- neighbour lists (added within ABI 2.4; no reference analogue) ----------------------------
  * For each of M points: WHICH of the handle's N bodies lie inside its radius -- the members nb_neighbors only counts --, as one
- * row of `cap` indices per point: the neighbour lists of an Ahmad-Cohen split, the k nearest bodies of a local-density estimate
- * (take a radius that holds them and select on the host), friends-of-friends links, all close pairs.
+ * row of `cap` indices per point: the neighbour lists of an Ahmad-Cohen split, friends-of-friends links, all close pairs (the k
+ * nearest bodies of a point, whatever their distance, are nb_knn's).
  *   - Membership: body j belongs to the row of point k iff d2(k, j) < h2, strictly, with d2 and h2 computed exactly as
  *     nb_neighbors computes them for its count: the same expression, the handle's precision, no softening, every row of the
  *     handle a body whatever its mass.  An NB_NBR_AT_BODIES point leaves ITSELF out by index; another body at the same position
@@ -681,6 +683,60 @@ int nb_multi_neighbor_lists(nb_multi *m, const nb_neighbor_list_request *req);
 /* The launch shape of an m-point request with rows of cap entries (no device call): as nb_neighbors_shape, the batch cut further
  * as the memory rule above says.  For tests and tools; the results do not depend on it. */
 int nb_neighbor_lists_shape(nb_sim *s, uint32_t m, uint32_t cap, uint32_t *batch, uint32_t *chunks, uint32_t *j_per_chunk);
+
+/* ---- k nearest neighbours (added within ABI 2.4; no reference analogue) -----------------------
+ * For each of M points: the K NEAREST of the handle's N bodies, nearest first -- what is defined by a number of neighbours and not
+ * by a radius: Casertano-Hut densities and the density centre, SPH-style smoothing lengths, k-th-neighbour time-step and
+ * softening criteria, Ahmad-Cohen neighbour spheres that hold a fixed number of members.  No radius has to be guessed, no row is
+ * longer than k, nothing is sorted on the host.
+ *   - Distance: exactly nb_neighbors' expression, d2 = fma(dz, dz, fma(dy, dy, dx * dx)) with dx = x_j - p_x, NO softening, in the
+ *     handle's precision; every row of the handle a body whatever its mass.  An NB_NBR_AT_BODIES point leaves ITSELF out by
+ *     index; another body at the same position is a neighbour at d2 = 0.
+ *   - Order: row r = index[r * k .. r * k + k) / dist2[r * k ..) holds the k smallest candidates under the TOTAL order (d2
+ *     ascending, then j ascending), in that order.  index[r * k] and dist2[r * k] are therefore the bytes nb_neighbors returns for
+ *     the same point.
+ *   - Short rows: with fewer than k candidates (n - 1 < k at the bodies, n < k otherwise) the remaining entries hold 0xffffffff
+ *     and +inf; a candidate whose d2 overflows to +inf is no candidate, as in nb_neighbors.  All m * k elements of an output are
+ *     defined, in host and in device mode.
+ *   - At least one of index / dist2 is non-NULL; an output that is not asked for is not written.
+ *   - Deterministic: no atomics; the order is total, so a point's row depends on that point and on the bodies ONLY -- not on m, not
+ *     on the batches, not on how the engine cuts j into chunks, not on k beyond its length: the row for k' < k is the first k'
+ *     entries of the row for k.  A sub-range request returns the bits of the same rows of a larger one.
+ *   - State read: that of nb_neighbors -- the positions behind every step enqueued so far, a shard handle finishes a pending
+ *     gather first; any handle kind, f32 and f64; nb_set_params is not required.  The simulation state, the engine's side copies,
+ *     the captured step graphs and the step counter are untouched: stepping after a call is bit-identical to stepping without it.
+ *   - Points and bodies must be finite; the result for a non-finite one is unspecified (the call does not fault).
+ *   - Errors: NB_ERR_INVALID (NULL handle or request -- checked before any device call --, wrong struct_size, m == 0, k == 0 or
+ *     k > 64, reserved != 0, unknown flag bits (2u included), both outputs NULL, points given with NB_NBR_AT_BODIES or missing
+ *     without it, first_body + m > n), NB_ERR_STATE (nothing uploaded); nb_last_error names the function and the field.
+ *   - Host pointers: the call blocks until the outputs are written; no pointer is kept.  NB_NBR_DEVICE: every pointer is device
+ *     memory on the handle's device, the work is enqueued on the handle's stream and the call returns at once.
+ *   - Memory: per (point of a batch, j-chunk) one partial row of k entries (d2, j), kept in an engine-owned working row of 2k
+ *     entries (k + 4 below k = 4) of 8 bytes (f32) or 16 bytes (f64); grown on demand, released by nb_destroy.  The shape is
+ *     derived ONCE per request: the batch and the j-chunks nb_neighbors would give m points (at most 512 chunks), the batch then
+ *     halved, in whole workgroups' worth of points and with the j-chunks kept, until chunks x batch x k x 8 <= 256 MiB (down to one
+ *     workgroup's points); every batch of the request, the last and shorter one included, runs against those chunks, and
+ *     nb_knn_shape reports them.  The working rows take 2 x that figure on f32 handles and 4 x on f64 handles (up to 1 GiB).  A
+ *     host-pointer request stages its outputs one batch at a time.  Nothing is proportional to m x N. */
+typedef struct nb_knn_request {
+    uint32_t struct_size;   /* sizeof(nb_knn_request) */
+    uint32_t m;             /* number of points, >= 1 */
+    uint32_t flags;         /* NB_NBR_AT_BODIES | NB_NBR_DEVICE: the bits and the meaning they have for nb_neighbors */
+    uint32_t first_body;    /* NB_NBR_AT_BODIES only */
+    const void *points;     /* 4*m elements x, y, z, (ignored); NULL with NB_NBR_AT_BODIES */
+    uint32_t k;             /* neighbours per point, 1 <= k <= 64 */
+    uint32_t reserved;      /* must be 0 */
+    uint32_t *index;        /* out, optional: m * k elements, row r = point r; 0xffffffff past the last candidate */
+    void *dist2;            /* out, optional: m * k elements (handle's precision); +inf past the last candidate */
+} nb_knn_request;
+int nb_knn(nb_sim *s, const nb_knn_request *req);
+/* The same on a multi-shard system: evaluated on shard 0 against the caller's UNPADDED n rows, as nb_multi_neighbors -- a padding
+ * row is never returned. */
+int nb_multi_knn(nb_multi *m, const nb_knn_request *req);
+/* The launch shape of an m-point request for k neighbours (no device call): the points of EVERY batch but the last (which takes
+ * what is left), the j-chunks and the bodies of one chunk, as the memory rule above says.  For tests and tools; the results do not
+ * depend on it. */
+int nb_knn_shape(nb_sim *s, uint32_t m, uint32_t k, uint32_t *batch, uint32_t *chunks, uint32_t *j_per_chunk);
 
 #if defined(__GNUC__)
 #pragma GCC visibility pop

@@ -727,6 +727,17 @@ int nb_multi_neighbor_lists(nb_multi* m, const nb_neighbor_list_request* req)
     return rc == NB_OK ? rc : mfail(m, rc, s->err);
 }
 
+int nb_multi_knn(nb_multi* m, const nb_knn_request* req)
+{
+    if (!m) return mfail(nullptr, NB_ERR_INVALID, "nb_multi_knn: null handle");
+    if (!req) return mfail(m, NB_ERR_INVALID, "nb_multi_knn: null request");
+    if (int rc = nb_multi_sync(m)) return rc;      // every shard's gather has landed: shard 0 holds all rows
+    // the caller's rows are the first n of the padded system: a padding row is never a neighbour
+    nb_sim* s = m->shard[0];
+    const int rc = nbi::knn(s, req, m->n, "nb_multi_knn");
+    return rc == NB_OK ? rc : mfail(m, rc, s->err);
+}
+
 int nb_multi_download(nb_multi* m, void* bodies, void* vel, void* accel)
 {
     if (!m) return NB_ERR_INVALID;

@@ -1092,7 +1092,7 @@ void nb_destroy(nb_sim* s)
     for (void* p : {s->jerk, s->hx, s->hv, s->fj_part, (void*)s->blk_lev, (void*)s->blk_due, (void*)s->blk_act, (void*)s->blk_hdr}) if (p) (void)hipFree(p);
     if (s->blk_hdr_host) (void)hipHostFree(s->blk_hdr_host);
     if (s->diag) (void)hipFree(s->diag);
-    for (auto* b : {&s->fld_pts, &s->fld_acc, &s->fld_phi, &s->fld_part, &s->nbr_rad, &s->nbr_idx, &s->nbr_d2, &s->nbr_cnt, &s->nbr_inf, &s->nbl_off, &s->nbl_list})
+    for (auto* b : {&s->fld_pts, &s->fld_acc, &s->fld_phi, &s->fld_part, &s->nbr_rad, &s->nbr_idx, &s->nbr_d2, &s->nbr_cnt, &s->nbr_inf, &s->nbl_off, &s->nbl_list, &s->knn_work, &s->knn_idx, &s->knn_d2, &s->knn_stat})
         if (b->p) (void)hipFree(b->p);
     if (s->zero_row) (void)hipFree(s->zero_row);
     if (s->own_stream && s->stream) (void)hipStreamDestroy(s->stream);
@@ -2104,6 +2104,162 @@ int nb_neighbor_lists_shape(nb_sim* s, uint32_t m, uint32_t cap, uint32_t* batch
     if (cap == 0 || cap > kNblMaxCap) return fail(s, NB_ERR_INVALID, "nb_neighbor_lists_shape: cap must be in 1 .. 4096");
     uint32_t b, c, per;
     nbl_shape(s, m, cap, s->n, &b, &c, &per);
+    if (batch) *batch = b;
+    if (chunks) *chunks = c;
+    if (j_per_chunk) *j_per_chunk = per;
+    return NB_OK;
+}
+
+/* ---- k nearest neighbours ----------------------------------------------------------------- */
+
+namespace {
+
+constexpr uint64_t kKnnRowBytes = kNblListBytes;        // most bytes of partial rows (chunks x batch x k x 8) one batch leaves
+constexpr uint32_t kKnnMaxChunks = 512;                 // most j-chunks: nb_knn_merge keeps 64 bytes of LDS per chunk (32 KiB)
+
+// The shape of a WHOLE m-point request: nbr_shape's batch and chunks for m points (at most kKnnMaxChunks chunks: few points against
+// millions of bodies would get more); the batch is then halved in whole workgroups' worth of points, the chunks kept, until
+// chunks x batch x k x 8 <= kKnnRowBytes (one workgroup's points is the floor).  Every batch of the request, the last and shorter
+// one included, runs against these chunks: fewer, longer chunks are what a k-nearest pass wants, since every chunk has to find its
+// own k candidates first.
+void knn_shape(const nb_sim* s, uint32_t m, uint32_t k, uint32_t rows, uint32_t* batch, uint32_t* chunks, uint32_t* per)
+{
+    const uint32_t prow = s->f64 ? nb::kNbrRows64 : nb::kNbrRows;
+    uint32_t mb;
+    nbr_shape(s, m, rows, &mb, chunks, per);
+    if (*chunks > kKnnMaxChunks) {
+        *per = ceil_div(ceil_div(rows, kKnnMaxChunks), (uint32_t)nb::kTile) * nb::kTile;
+        *chunks = ceil_div(rows, *per);
+    }
+    while ((uint64_t)*chunks * mb * k * 8 > kKnnRowBytes && mb > prow) mb = std::max(prow, (mb / 2 + prow - 1) / prow * prow);
+    *batch = mb;
+}
+
+#ifdef NB_TUNING    // calibration build only: what the passes did, summed over the calls since the last reset (tools/knn_bench.py --stats)
+uint64_t g_knn_stats[5];      // (point, chunk) rows, candidates appended, compactions before the end of a chunk, groups on the slow path, groups
+#endif
+
+}  // namespace
+
+#ifdef NB_TUNING
+extern "C" __attribute__((visibility("default"))) void nb_tuning_knn_stats(uint64_t* out, int reset)
+{
+    for (int q = 0; q < 5; ++q) { if (out) out[q] = g_knn_stats[q]; if (reset) g_knn_stats[q] = 0; }
+}
+#endif
+
+extern "C++" int nbi::knn(nb_sim* s, const nb_knn_request* req, uint32_t rows, const char* who)
+{
+    const std::string w = std::string(who) + ": ";
+    if (!s) return fail(nullptr, NB_ERR_INVALID, w + "null handle");
+    if (!req) return fail(s, NB_ERR_INVALID, w + "null request");
+    if (req->struct_size != sizeof(nb_knn_request)) return fail(s, NB_ERR_INVALID, w + "struct_size must be sizeof(nb_knn_request)");
+    if (req->flags & ~(NB_NBR_AT_BODIES | NB_NBR_DEVICE)) return fail(s, NB_ERR_INVALID, w + "unknown bits in flags");
+    const bool at = (req->flags & NB_NBR_AT_BODIES) != 0, dev = (req->flags & NB_NBR_DEVICE) != 0;
+    if (at && req->points) return fail(s, NB_ERR_INVALID, w + "points must be NULL with NB_NBR_AT_BODIES");
+    if (!at && !req->points) return fail(s, NB_ERR_INVALID, w + "points is NULL (and NB_NBR_AT_BODIES is not set)");
+    if (req->m == 0) return fail(s, NB_ERR_INVALID, w + "m must be >= 1");
+    if (req->k == 0 || req->k > nb::kKnnMaxK) return fail(s, NB_ERR_INVALID, w + "k must be in 1 .. 64");
+    if (req->reserved != 0) return fail(s, NB_ERR_INVALID, w + "reserved must be 0");
+    if (!req->index && !req->dist2) return fail(s, NB_ERR_INVALID, w + "index and dist2 are both NULL");
+    if (at && (uint64_t)req->first_body + req->m > rows) return fail(s, NB_ERR_INVALID, w + "first_body + m exceeds n");
+    if (!s->uploaded) return fail(s, NB_ERR_STATE, w + "nothing uploaded yet");
+    NB_HIP(s, hipSetDevice(s->device));
+    if (int rc = finish_gather(s)) return rc;     // other ranks' rows must have landed
+
+    const size_t esz = s->esz, in_row = 4 * esz, ent = s->f64 ? 16 : 8;
+    const uint32_t m = req->m, cap = nb::knn_cap(req->k);
+    const char* pts = at ? (const char*)s->bodies[s->cur] + in_row * req->first_body : (const char*)req->points;
+    if (!dev && !at) {
+        if (int rc = field_reserve(s, s->fld_pts, in_row * m, who)) return rc;
+        NB_HIP(s, hipMemcpyAsync(s->fld_pts.p, req->points, in_row * m, hipMemcpyHostToDevice, s->stream));
+        pts = (const char*)s->fld_pts.p;
+    }
+    if (!s->f64 && !s->nbr_inf.p) {
+        static const float inf_row[4] = {HUGE_VALF, HUGE_VALF, HUGE_VALF, 0.0f};
+        if (int rc = field_reserve(s, s->nbr_inf, 64, who)) return rc;
+        NB_HIP(s, hipMemcpyAsync(s->nbr_inf.p, inf_row, sizeof inf_row, hipMemcpyHostToDevice, s->stream));
+    }
+
+    const uint32_t prow = s->f64 ? nb::kNbrRows64 : nb::kNbrRows;      // points per workgroup
+    const void* bodies = s->bodies[s->cur];
+    const void* inf_row = s->nbr_inf.p;
+    uint32_t n = rows, at_flag = at ? 1u : 0u, k = req->k;
+    uint32_t batch, chunks, per;
+    knn_shape(s, m, k, rows, &batch, &chunks, &per);      // once: every batch runs against the same chunks
+    const size_t heads = (size_t)chunks * nb::kKnnMergeLanes;      // nb_knn_merge's dynamic LDS (chunks <= kKnnMaxChunks)
+    for (uint32_t done = 0; done < m;) {
+        uint32_t mb = std::min(batch, m - done);
+        if (int rc = field_reserve(s, s->knn_work, ent * cap * chunks * mb, who)) return rc;
+        if (!dev) {      // a host-pointer request stages its outputs batch by batch
+            if (req->index) { if (int rc = field_reserve(s, s->knn_idx, (size_t)4 * k * mb, who)) return rc; }
+            if (req->dist2) { if (int rc = field_reserve(s, s->knn_d2, esz * k * mb, who)) return rc; }
+        }
+        const void* p = pts + in_row * done;
+        void* work = s->knn_work.p;
+        void* oi = !req->index ? nullptr : dev ? (void*)(req->index + (size_t)k * done) : s->knn_idx.p;
+        void* od = !req->dist2 ? nullptr : dev ? (void*)((char*)req->dist2 + esz * k * done) : s->knn_d2.p;
+        uint32_t self0 = req->first_body + done;
+        dim3 grid(ceil_div(mb, prow), chunks), block(nb::kBlock);
+        void* margs[] = {&work, &mb, &chunks, &k, &oi, &od};
+        const dim3 mgrid(ceil_div(mb, nb::kKnnMergeLanes)), mblock(nb::kKnnMergeLanes);
+        void* stat_rows = nullptr;
+        void* stat_waves = nullptr;
+        const void* fn64 = (const void*)&nb::nb_knn64<double>;
+        const void* fn32 = (const void*)&nb::nb_knn_pk<>;
+#ifdef NB_TUNING
+        const size_t stat_n = (size_t)chunks * mb, wave_n = (size_t)chunks * grid.x * (nb::kBlock / 64);
+        const bool stats = getenv("NB_KNN_STATS") != nullptr;
+        if (stats) {
+            if (int rc = field_reserve(s, s->knn_stat, 8 * stat_n + 4 * wave_n, who)) return rc;
+            stat_rows = s->knn_stat.p;
+            stat_waves = (char*)s->knn_stat.p + 8 * stat_n;
+            fn64 = (const void*)&nb::nb_knn64<double, true>;
+            fn32 = (const void*)&nb::nb_knn_pk<true>;
+        }
+#endif
+        if (s->f64) {
+            void* args[] = {&bodies, &p, &work, &n, &mb, &per, &k, &at_flag, &self0, &stat_rows, &stat_waves};
+            NB_HIP(s, hipLaunchKernel(fn64, grid, block, args, 0, s->stream));
+            NB_HIP(s, hipLaunchKernel((const void*)&nb::nb_knn_merge<double>, mgrid, mblock, margs, heads, s->stream));
+        } else {
+            void* args[] = {&bodies, &p, &work, &n, &mb, &per, &k, &at_flag, &self0, &inf_row, &stat_rows, &stat_waves};
+            NB_HIP(s, hipLaunchKernel(fn32, grid, block, args, 0, s->stream));
+            NB_HIP(s, hipLaunchKernel((const void*)&nb::nb_knn_merge<float>, mgrid, mblock, margs, heads, s->stream));
+        }
+#ifdef NB_TUNING
+        if (stats) {
+            std::vector<uint32_t> h(2 * stat_n + wave_n);
+            NB_HIP(s, hipMemcpyAsync(h.data(), s->knn_stat.p, 4 * h.size(), hipMemcpyDeviceToHost, s->stream));
+            NB_HIP(s, hipStreamSynchronize(s->stream));
+            g_knn_stats[0] += stat_n;
+            for (size_t q = 0; q < stat_n; ++q) { g_knn_stats[1] += h[2 * q]; g_knn_stats[2] += h[2 * q + 1]; }
+            for (size_t q = 0; q < wave_n; ++q) g_knn_stats[3] += h[2 * stat_n + q];
+            for (uint32_t c = 0; c < chunks; ++c) {       // the groups a wave of chunk c walks: whole groups of 4 rows per tile
+                const uint32_t r = std::min(per, n - c * per);
+                g_knn_stats[4] += (uint64_t)grid.x * (nb::kBlock / 64) * ((r / nb::kTile) * (nb::kTile / nb::kKnnU) + (r % nb::kTile + nb::kKnnU - 1) / nb::kKnnU);
+            }
+        }
+#endif
+        if (!dev) {
+            if (req->index) NB_HIP(s, hipMemcpyAsync(req->index + (size_t)k * done, oi, (size_t)4 * k * mb, hipMemcpyDeviceToHost, s->stream));
+            if (req->dist2) NB_HIP(s, hipMemcpyAsync((char*)req->dist2 + esz * k * done, od, esz * k * mb, hipMemcpyDeviceToHost, s->stream));
+        }
+        done += mb;
+    }
+    if (!dev) NB_HIP(s, hipStreamSynchronize(s->stream));
+    return NB_OK;
+}
+
+int nb_knn(nb_sim* s, const nb_knn_request* req) { return nbi::knn(s, req, s ? s->n : 0u, "nb_knn"); }
+
+int nb_knn_shape(nb_sim* s, uint32_t m, uint32_t k, uint32_t* batch, uint32_t* chunks, uint32_t* j_per_chunk)
+{
+    if (!s) return fail(nullptr, NB_ERR_INVALID, "nb_knn_shape: null handle");
+    if (m == 0) return fail(s, NB_ERR_INVALID, "nb_knn_shape: m must be >= 1");
+    if (k == 0 || k > nb::kKnnMaxK) return fail(s, NB_ERR_INVALID, "nb_knn_shape: k must be in 1 .. 64");
+    uint32_t b, c, per;
+    knn_shape(s, m, k, s->n, &b, &c, &per);
     if (batch) *batch = b;
     if (chunks) *chunks = c;
     if (j_per_chunk) *j_per_chunk = per;

@@ -161,6 +161,10 @@ struct nb_sim {
     // point's row that the chunks before hold (bounded as fld_part is); list stages one batch of a host-pointer request (<= 256 MiB,
     // or one workgroup's points x cap)
     field_buf nbl_off, nbl_list;
+    // nb_knn: shares fld_pts and nbr_inf with nb_neighbors; work holds the working rows, knn_cap(k) entries of 8 (f32) or 16 (f64)
+    // bytes per (j-chunk, point of a batch) -- bounded by nb_knn's memory rule --; idx / d2 stage one batch of a host-pointer request
+    field_buf knn_work, knn_idx, knn_d2;
+    field_buf knn_stat;       // the calibration build's counters (NB_TUNING with NB_KNN_STATS set): never allocated otherwise
     // NB_INT_HERMITE4: bodies[0] / vel are the state at ONE instant, acc / jerk the derivatives derived from it.  None of the
     // leapfrog launch fields above is used: plain unpadded arrays, no planner, no graphs.
     bool hermite = false;
@@ -196,6 +200,8 @@ void set_create_error(const std::string& msg);
 int neighbors(nb_sim* s, const nb_neighbor_request* req, uint32_t rows, const char* who);
 // nb_neighbor_lists likewise (nb_multi_neighbor_lists: the caller's unpadded rows of shard 0)
 int neighbor_lists(nb_sim* s, const nb_neighbor_list_request* req, uint32_t rows, const char* who);
+// nb_knn likewise (nb_multi_knn: the caller's unpadded rows of shard 0)
+int knn(nb_sim* s, const nb_knn_request* req, uint32_t rows, const char* who);
 const std::string& create_error();
 
 // nb_comm.hip: called by nb_step after the integrate kernel when a communicator is attached.

@@ -69,6 +69,8 @@ static int (*p_neighbors)(nb_sim *, const nb_neighbor_request *);       /* neigh
 static int (*p_multi_neighbors)(nb_multi *, const nb_neighbor_request *);
 static int (*p_neighbor_lists)(nb_sim *, const nb_neighbor_list_request *);       /* neighbour lists, likewise: optional symbols */
 static int (*p_multi_neighbor_lists)(nb_multi *, const nb_neighbor_list_request *);
+static int (*p_knn)(nb_sim *, const nb_knn_request *);                              /* k nearest neighbours, likewise: optional symbols */
+static int (*p_multi_knn)(nb_multi *, const nb_knn_request *);
 static int (*p_eqm_info)(nb_sim *, int *);                              /* the equal-mass kernels' report, also within ABI 2.4: optional symbol */
 static int (*p_eqm_form)(nb_sim *, int *);                              /* which equal-mass form, likewise */
 
@@ -159,6 +161,8 @@ static napi_value js_load(napi_env env, napi_callback_info info)
         *(void **)(&p_multi_neighbors) = dlsym(h, "nb_multi_neighbors");
         *(void **)(&p_neighbor_lists) = dlsym(h, "nb_neighbor_lists");
         *(void **)(&p_multi_neighbor_lists) = dlsym(h, "nb_multi_neighbor_lists");
+        *(void **)(&p_knn) = dlsym(h, "nb_knn");
+        *(void **)(&p_multi_knn) = dlsym(h, "nb_multi_knn");
         *(void **)(&p_eqm_info) = dlsym(h, "nb_eqm_info");
         *(void **)(&p_eqm_form) = dlsym(h, "nb_eqm_form");
         g_lib = h;
@@ -790,6 +794,62 @@ static napi_value js_neighbor_lists(napi_env env, napi_callback_info info)
     return undefined(env);
 }
 
+/* knn(handle, points|null, firstBody, count, k, indexOut|null, dist2Out|null): nb_knn / nb_multi_knn.  points (4*m): a typed array
+ * of the handle's precision; indexOut: Uint32Array, dist2Out: typed array of the handle's precision, m*k elements each, written in
+ * place.  points null: the points are the bodies [firstBody, firstBody + count) themselves (NB_NBR_AT_BODIES). */
+static napi_value js_knn(napi_env env, napi_callback_info info)
+{
+    size_t argc = 7; napi_value argv[7];
+    CHECK_NAPI(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    if (argc < 7) { napi_throw_type_error(env, NULL, "knn(handle, points|null, firstBody, count, k, indexOut|null, dist2Out|null)"); return NULL; }
+    handle_t *h = get_handle(env, argv[0]); if (!h) return NULL;
+    if (!p_knn || !p_multi_knn) return throw_msg(env, NB_ERR_STATE, "the loaded library has no nb_knn", "nb_knn");
+    const napi_typedarray_type real = h->f64 ? napi_float64_array : napi_float32_array;
+    void *ptr[3] = {NULL, NULL, NULL}; size_t len[3] = {0, 0, 0};
+    static const int arg_of[3] = {1, 5, 6};
+    static const int is_u32[3] = {0, 1, 0};
+    static const char *const what[3] = {"points", "indexOut", "dist2Out"};
+    for (int k = 0; k < 3; ++k) {
+        napi_valuetype vt; napi_typeof(env, argv[arg_of[k]], &vt);
+        if (vt == napi_null || vt == napi_undefined) continue;
+        bool is_ta = false; napi_is_typedarray(env, argv[arg_of[k]], &is_ta);
+        napi_typedarray_type tt; napi_value ab; size_t off;
+        const napi_typedarray_type want = is_u32[k] ? napi_uint32_array : real;
+        if (!is_ta || napi_get_typedarray_info(env, argv[arg_of[k]], &tt, &len[k], &ptr[k], &ab, &off) != napi_ok || tt != want) {
+            char buf[160]; snprintf(buf, sizeof buf, "knn: %s must be a %s or null", what[k], is_u32[k] ? "Uint32Array" : h->f64 ? "Float64Array" : "Float32Array");
+            napi_throw_type_error(env, NULL, buf); return NULL;
+        }
+    }
+    double first = 0, count = 0, kk = 0;
+    napi_get_value_double(env, argv[2], &first); napi_get_value_double(env, argv[3], &count); napi_get_value_double(env, argv[4], &kk);
+    if (!(kk >= 0 && kk <= 4294967295.0)) { napi_throw_range_error(env, NULL, "knn: k out of range"); return NULL; }
+    nb_knn_request req;
+    memset(&req, 0, sizeof req);
+    req.struct_size = sizeof req;
+    if (ptr[0]) {
+        if (len[0] % 4 != 0 || len[0] / 4 > 0xffffffffu) { napi_throw_range_error(env, NULL, "knn: points must hold 4*m elements"); return NULL; }
+        req.m = (uint32_t)(len[0] / 4);
+        req.points = ptr[0];
+    } else {
+        if (!(first >= 0 && first <= 4294967295.0 && count >= 0 && count <= 4294967295.0)) { napi_throw_range_error(env, NULL, "knn: firstBody / count out of range"); return NULL; }
+        req.flags = NB_NBR_AT_BODIES;
+        req.first_body = (uint32_t)first; req.m = (uint32_t)count;
+    }
+    req.k = (uint32_t)kk;
+    if ((ptr[1] && len[1] != (size_t)req.m * (size_t)req.k) || (ptr[2] && len[2] != (size_t)req.m * (size_t)req.k)) {
+        napi_throw_range_error(env, NULL, "knn: indexOut and dist2Out must hold m * k elements"); return NULL;
+    }
+    req.index = (uint32_t *)ptr[1]; req.dist2 = ptr[2];
+    if (h->multi) {
+        int rcm = p_multi_knn(h->multi, &req);
+        if (rcm != NB_OK) return throw_msg(env, rcm, p_multi_last_error(h->multi), "nb_multi_knn");
+    } else {
+        int rc = p_knn(h->sim, &req);
+        if (rc != NB_OK) return throw_nb(env, rc, h->sim, "nb_knn");
+    }
+    return undefined(env);
+}
+
 /* downloadJerk(handle, jerkOut): nb_download_jerk -- 4*n elements (jx, jy, jz, 0) of a Hermite handle, written in place. */
 static napi_value js_download_jerk(napi_env env, napi_callback_info info)
 {
@@ -932,6 +992,7 @@ static napi_value init_module(napi_env env, napi_value exports)
         {"fieldEval", js_field_eval}, {"downloadJerk", js_download_jerk}, {"uploadDerivs", js_upload_derivs},
         {"setBlockSteps", js_set_block_steps}, {"blockStats", js_block_stats}, {"downloadLevels", js_download_levels},
         {"uploadLevels", js_upload_levels}, {"neighbors", js_neighbors}, {"neighborLists", js_neighbor_lists},
+        {"knn", js_knn},
     };
     for (size_t i = 0; i < sizeof fns / sizeof fns[0]; ++i) {
         napi_value f;

@@ -377,6 +377,51 @@ class Simulation {
     return out;
   }
 
+  /** The k nearest bodies (nb_knn; no reference analogue) of each of `points` -- 4*m elements x, y, z, (ignored) -- or, with
+   *  options.bodies = [first, count] (and points null), of each of those bodies, itself left out by index.  options.k: 1 .. 64,
+   *  default 6.  Returns {index: Uint32Array, dist2: Float32Array | Float64Array, k}, m * k elements each: row r =
+   *  index.subarray(r * k, (r + 1) * k) holds the k smallest candidates in the order (dist2 ascending, then index ascending), padded
+   *  with 0xffffffff / Infinity where there are fewer than k.  options.dist2 === false leaves dist2 out.  Column 0 is what
+   *  neighbors() returns.  The simulation state is not touched. */
+  knn(points, options) {
+    this._need();
+    const o = options || {}, T = this.ArrayType;
+    let pts = null, first = 0, m;
+    if (o.bodies) { first = o.bodies[0] >>> 0; m = o.bodies[1] >>> 0; }
+    if (points !== null && points !== undefined) {
+      if (points instanceof T) pts = points;
+      else if (typeof points.length === 'number') pts = T.from(points);
+      else throw new TypeError('points: expected ' + T.name);
+      if (pts.length % 4 !== 0) throw new RangeError('points must hold 4*m elements (x, y, z, ignored)');
+      if (o.bodies) throw new RangeError('knn(): give either points or options.bodies, not both');
+      m = pts.length / 4;
+    } else if (!o.bodies) throw new TypeError('knn(): points, or options.bodies = [first, count], required');
+    const k = o.k === undefined || o.k === null ? 6 : +o.k;
+    if (!(Number.isInteger(k) && k >= 1 && k <= 64)) throw new RangeError('options.k must be an integer in 1 .. 64');
+    const out = { index: new Uint32Array(m * k), dist2: o.dist2 === false ? null : new T(m * k), k: k };
+    addon.knn(this._h, pts, first, m, k, out.index, out.dist2);
+    return out;
+  }
+
+  /** The Casertano-Hut local density at every body, a Float64Array of nBodies elements: one knn() call over all bodies, then per
+   *  body the masses of its first k - 1 neighbours over the volume of the sphere that reaches the k-th (k >= 2, default 6); NaN
+   *  where a body has fewer than k neighbours. */
+  localDensity(k) {
+    this._need();
+    k = k === undefined || k === null ? 6 : +k;
+    if (!(Number.isInteger(k) && k >= 2 && k <= 64)) throw new RangeError('localDensity(k): k must be an integer in 2 .. 64');
+    const n = this.nBodies, nn = this.knn(null, { bodies: [0, n], k: k }), b = this.readBodies();
+    const rho = new Float64Array(n);
+    for (let i = 0; i < n; i++) {
+      const row = i * k;
+      if (nn.index[row + k - 1] === 0xffffffff) { rho[i] = NaN; continue; }
+      let msum = 0;
+      for (let t = 0; t < k - 1; t++) msum += b[4 * nn.index[row + t] + 3];
+      rho[i] = msum / (4 * Math.PI / 3 * Math.pow(nn.dist2[row + k - 1], 1.5));
+    }
+    return rho;
+  }
+
   /** The close pairs of the system: the MUTUAL nearest neighbours (i < j, each the other's nearest body) closer than `radius`, as
    *  {pairs: Uint32Array of 2*k elements i0, j0, i1, j1, ... sorted by i, dist2: k elements} -- one neighbors() call over all
    *  bodies and host code on its result. */

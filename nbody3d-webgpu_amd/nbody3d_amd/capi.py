@@ -95,6 +95,12 @@ class nb_neighbor_list_request(C.Structure):     # include/nbody3d_hip.h (neighb
                 ("list", C.c_void_p), ("count", C.c_void_p), ("index", C.c_void_p), ("dist2", C.c_void_p)]
 
 
+class nb_knn_request(C.Structure):          # include/nbody3d_hip.h (k nearest neighbours, added within ABI 2.4)
+    _fields_ = [("struct_size", C.c_uint32), ("m", C.c_uint32), ("flags", C.c_uint32), ("first_body", C.c_uint32),
+                ("points", C.c_void_p), ("k", C.c_uint32), ("reserved", C.c_uint32),
+                ("index", C.c_void_p), ("dist2", C.c_void_p)]
+
+
 NB_BLOCK_FROZEN = 1
 
 
@@ -124,7 +130,8 @@ SYMBOLS = ["nb_abi_version", "nb_device_count", "nb_create", "nb_destroy", "nb_u
            "nb_abi_minor", "nb_field_eval", "nb_multi_field_eval", "nb_download_jerk", "nb_upload_derivs",
            "nb_set_block_steps", "nb_block_stats", "nb_download_levels", "nb_upload_levels",
            "nb_neighbors", "nb_multi_neighbors", "nb_neighbors_shape", "nb_eqm_info", "nb_eqm_form",
-           "nb_neighbor_lists", "nb_multi_neighbor_lists", "nb_neighbor_lists_shape"]
+           "nb_neighbor_lists", "nb_multi_neighbor_lists", "nb_neighbor_lists_shape",
+           "nb_knn", "nb_multi_knn", "nb_knn_shape"]
 
 _lib = None
 
@@ -212,6 +219,10 @@ def load_library():
         L.nb_neighbor_lists.argtypes = [vp, C.POINTER(nb_neighbor_list_request)]
         L.nb_multi_neighbor_lists.argtypes = [vp, C.POINTER(nb_neighbor_list_request)]
         L.nb_neighbor_lists_shape.argtypes = [vp, C.c_uint32, C.c_uint32] + [C.POINTER(C.c_uint32)] * 3
+    if hasattr(L, "nb_knn"):                # k nearest neighbours, also within 2.4 and detected by the symbol
+        L.nb_knn.argtypes = [vp, C.POINTER(nb_knn_request)]
+        L.nb_multi_knn.argtypes = [vp, C.POINTER(nb_knn_request)]
+        L.nb_knn_shape.argtypes = [vp, C.c_uint32, C.c_uint32] + [C.POINTER(C.c_uint32)] * 3
     if hasattr(L, "nb_eqm_info"):           # the equal-mass kernels' report, also within 2.4 and detected by the symbol
         L.nb_eqm_info.argtypes = [vp, C.POINTER(C.c_int)]
     if hasattr(L, "nb_eqm_form"):           # which of the equal-mass forms, likewise
@@ -379,6 +390,70 @@ def _neighbor_list_request(dtype, points, bodies, radius, radii, cap, nearest):
     req.index = _ptr(index) if nearest and req.m else None
     req.dist2 = _ptr(dist2) if nearest and req.m else None
     return req, (pts, rad), lists, count, index, dist2
+
+
+def _need_knn(what):
+    if not hasattr(load_library(), "nb_knn"):
+        raise NBodyError(1, "%s: the loaded library has no nb_knn" % what)
+
+
+def _knn_request(dtype, points, bodies, k, want_dist2):
+    """The nb_knn_request of knn(): (request, arrays kept alive, index, dist2 | None)."""
+    _need_knn("knn()")
+    req = nb_knn_request()
+    req.struct_size = C.sizeof(nb_knn_request)
+    pts = None
+    # (both or neither of points / bodies, a k out of range: passed on as they are -- the engine's NB_ERR_INVALID names the field)
+    if bodies is not None:
+        first, count = int(bodies[0]), int(bodies[1])
+        if not (0 <= first < 2 ** 32 and 0 <= count < 2 ** 32):
+            raise ValueError("knn(): bodies=(first, count) out of range")
+        req.flags |= NB_NBR_AT_BODIES
+        req.first_body, req.m = first, count
+    if points is not None:
+        pts = np.asarray(points, dtype=dtype)
+        if pts.ndim == 1:
+            pts = pts.reshape(-1, 3 if pts.size % 4 else 4)
+        if pts.ndim != 2 or pts.shape[1] not in (3, 4):
+            raise ValueError("knn(): points must have shape (m, 3) or (m, 4)")
+        if pts.shape[1] == 3:
+            pts = np.concatenate([pts, np.zeros((len(pts), 1), dtype)], axis=1)
+        pts = np.ascontiguousarray(pts)
+        if bodies is None:
+            req.m = len(pts)
+        req.points = _ptr(pts) if len(pts) else None
+    k = int(k)
+    if not 0 <= k < 2 ** 32:
+        raise ValueError("knn(): k out of range")
+    req.k = k
+    cols = k if 1 <= k <= 64 else 1                    # (an invalid k is the engine's to refuse: nothing is written then)
+    index = np.zeros((req.m, cols), np.uint32)
+    dist2 = np.zeros((req.m, cols), dtype) if want_dist2 else None
+    req.index = _ptr(index) if req.m else None
+    req.dist2 = _ptr(dist2) if want_dist2 and req.m else None
+    return req, (pts,), index, dist2
+
+
+def density_from_knn(bodies, index, dist2):
+    """The Casertano-Hut local density of each row of a knn() result, in float64: the masses of the first k - 1 neighbours over the
+    volume of the sphere that reaches the k-th, ``rho = sum(m[index[:, :k-1]]) / (4 pi / 3 * dist2[:, k-1] ** 1.5)`` -- the point
+    itself and the k-th neighbour left out.  ``bodies``: (n, 4) rows (x, y, z, m) or the n masses; k >= 2.  ``nan`` where the row
+    holds fewer than k neighbours."""
+    b = np.asarray(bodies, np.float64)
+    mass = b[:, 3] if b.ndim == 2 else b
+    index = np.asarray(index, np.uint32)
+    d2 = np.asarray(dist2, np.float64)
+    if index.ndim != 2 or d2.shape != index.shape:
+        raise ValueError("density_from_knn(): index and dist2 must both be (m, k)")
+    k = index.shape[1]
+    if k < 2:
+        raise ValueError("density_from_knn(): k must be >= 2")
+    full = index[:, k - 1] != NB_NBR_NONE
+    inner = np.where(full[:, None], index[:, :k - 1].astype(np.int64), 0)
+    msum = mass[inner].sum(axis=1)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        rho = msum / (4.0 * np.pi / 3.0 * np.where(full, d2[:, k - 1], 1.0) ** 1.5)
+    return np.where(full, rho, np.nan)
 
 
 def lists_to_csr(lists, count):
@@ -955,6 +1030,59 @@ class Simulation:
         self._check(self._L.nb_neighbor_lists_shape(self._h, int(m), int(cap), *[C.byref(x) for x in v]))
         return dict(zip(("batch", "chunks", "j_per_chunk"), (x.value for x in v)))
 
+    def knn(self, points=None, *, bodies=None, k=6, dist2=True):
+        """nb_knn: the ``k`` nearest bodies (1 <= k <= 64) of each of ``points`` ((m, 3) or (m, 4); the fourth column is ignored) --
+        or, with ``bodies=(first, count)``, of each of those bodies, itself left out by index.  Returns ``(index (m, k) uint32,
+        dist2 (m, k) | None)``: row r holds the k smallest candidates in the order (d2 ascending, then index ascending), d2 the
+        plain squared distance of neighbors(); with fewer than k candidates the rest of the row is NB_NBR_NONE / +inf.  Column 0
+        is what neighbors() returns, bit for bit; the row for a smaller k is the start of the row for a larger one."""
+        req, keep, index, d2 = _knn_request(self.dtype, points, bodies, k, dist2)
+        self._check(self._L.nb_knn(self._h, C.byref(req)))
+        return index, d2
+
+    def knn_device(self, points_ptr, m, k, index_ptr, dist2_ptr=None, *, bodies=None):
+        """The device-pointer form (NB_NBR_DEVICE): device addresses on the handle's device (0 or None for what is not wanted);
+        ``index_ptr``: m * k uint32, ``dist2_ptr``: m * k elements of the handle's precision.  Enqueued on the handle's stream, returns
+        without waiting.  ``bodies=(first, count)`` selects the bodies themselves (``points_ptr`` must then be None, ``m`` is ignored)."""
+        _need_knn("knn_device()")
+        req = nb_knn_request()
+        req.struct_size = C.sizeof(nb_knn_request)
+        req.flags = NB_NBR_DEVICE
+        if bodies is not None:
+            req.flags |= NB_NBR_AT_BODIES
+            req.first_body, req.m = int(bodies[0]), int(bodies[1])
+        else:
+            req.m = int(m)
+        req.points = points_ptr or None
+        req.k = int(k)
+        req.index = index_ptr or None
+        req.dist2 = dist2_ptr or None
+        self._check(self._L.nb_knn(self._h, C.byref(req)))
+
+    def knn_shape(self, m, k):
+        """{batch, chunks, j_per_chunk}: the launch shape nb_knn gives an m-point request for k neighbours (the answers do not depend
+        on it)."""
+        _need_knn("knn_shape()")
+        v = [C.c_uint32() for _ in range(3)]
+        self._check(self._L.nb_knn_shape(self._h, int(m), int(k), *[C.byref(x) for x in v]))
+        return dict(zip(("batch", "chunks", "j_per_chunk"), (x.value for x in v)))
+
+    def local_density(self, k=6):
+        """The Casertano-Hut density at every body, (n,) float64: one knn(bodies=(0, n), k=k) call and density_from_knn() on its
+        result (``nan`` for every body when n - 1 < k)."""
+        return self._local_density(k)[1]
+
+    def _local_density(self, k):
+        index, d2 = self.knn(bodies=(0, self.n), k=k)
+        b = self.read(vel=False, accel=False)[0]
+        return b, density_from_knn(b, index, d2)
+
+    def density_center(self, k=6):
+        """The density centre of the system, (3,) float64: sum(rho x) / sum(rho) over the bodies with a density (local_density(k))."""
+        b, rho = self._local_density(k)
+        ok = np.isfinite(rho)
+        return (rho[ok, None] * b[ok, :3].astype(np.float64)).sum(axis=0) / rho[ok].sum()
+
     def all_close_pairs(self, radius, cap=64):
         """EVERY unordered pair i < j of bodies with d2 < radius^2 (close_pairs() gives the mutual-nearest ones only), as ``(k, 2)
         uint32`` sorted by i, then j -- one neighbor_lists(bodies=(0, n)) call and host code on its result.  Raises ValueError if a
@@ -1125,6 +1253,13 @@ class MultiSimulation:
         req, keep, lists, count, index, dist2 = _neighbor_list_request(self.dtype, points, bodies, radius, radii, cap, nearest)
         self._check(self._L.nb_multi_neighbor_lists(self._h, C.byref(req)))
         return (lists, count, index, dist2) if nearest else (lists, count)
+
+    def knn(self, points=None, *, bodies=None, k=6, dist2=True):
+        """nb_multi_knn: Simulation.knn() on the whole system (evaluated on shard 0 against the caller's unpadded rows: a padding
+        row is never returned); ``bodies=(first, count)`` counts the caller's unpadded rows."""
+        req, keep, index, d2 = _knn_request(self.dtype, points, bodies, k, dist2)
+        self._check(self._L.nb_multi_knn(self._h, C.byref(req)))
+        return index, d2
 
     @property
     def variant(self):
