@@ -59,7 +59,9 @@ extern "C" {
                              2.4 (round 12) likewise within 2.4: nb_neighbor_lists, nb_multi_neighbor_lists, nb_neighbor_lists_shape,
                                             nb_neighbor_list_request.  Detected by the presence of the symbol nb_neighbor_lists
                              2.4 (round 13) likewise within 2.4: nb_knn, nb_multi_knn, nb_knn_shape, nb_knn_request.  Detected by the presence
-                                            of the symbol nb_knn */
+                                            of the symbol nb_knn
+                             2.4 (round 14) likewise within 2.4: nb_list_force, nb_multi_list_force, nb_list_force_shape,
+                                            nb_list_force_request.  Detected by the presence of the symbol nb_list_force */
 
 typedef struct nb_sim nb_sim; /* opaque */
 
@@ -737,6 +739,73 @@ int nb_multi_knn(nb_multi *m, const nb_knn_request *req);
  * what is left), the j-chunks and the bodies of one chunk, as the memory rule above says.  For tests and tools; the results do not
  * depend on it. */
 int nb_knn_shape(nb_sim *s, uint32_t m, uint32_t k, uint32_t *batch, uint32_t *chunks, uint32_t *j_per_chunk);
+
+/* ---- forces over neighbour rows (added within ABI 2.4; no reference analogue) -----------------
+ * For each of M rows of body indices -- the rows nb_neighbor_lists and nb_knn write, or any a caller builds --: acceleration, jerk
+ * and potential summed over THE ENTRIES OF THE ROW ONLY, at the row's point or body.  This is the irregular force of an
+ * Ahmad-Cohen split, the sum a collisional code evaluates many times per regular step; its cost is the entries, not M x N.
+ *   - The sums, for row k, with p, u the position and velocity of its point (or of body first_body + k):
+ *         a    =   sum_j G m_j dr / rho^3
+ *         jerk =   sum_j G m_j [ dv / rho^3 - 3 (dr.dv) dr / rho^5 ]
+ *         phi  = - sum_j G m_j / rho          dr = x_j - p,  dv = v_j - u,  rho^2 = |dr|^2 + eps2
+ *     over the entries j of the row, with the handle's eps2 and the G of the last nb_set_params, read from the positions as they
+ *     stand behind every step enqueued so far (the state nb_field_eval reads; a shard handle finishes a pending gather first).
+ *     accel.w and jerk.w are 0.  Outputs have the handle's precision; at least one of accel / jerk / phi is non-NULL and an
+ *     output that is not asked for is not written.
+ *   - Entries: row k is list[k * cap .. k * cap + cap); with count, only its first min(count[k], cap) entries are read.  An entry
+ *     >= n adds nothing -- the padding 0xffffffff wherever it stands in the row, or any other value past the rows; the call does
+ *     not fault.  With NB_LISTF_AT_BODIES an entry equal to the row's own index first_body + k adds nothing (its dr is 0, but its
+ *     m / sqrt(eps2) would count in phi).  A duplicated entry is added twice.  The order of a row does not have to ascend:
+ *     nb_knn's index rows are valid input.  A row without a valid entry gives exact +0 in every output.
+ *   - Jerk: needs velocities at the positions' instant, so it is available on Hermite handles only (block-step handles included);
+ *     jerk != NULL on a leapfrog handle is NB_ERR_STATE, as for nb_download_jerk.  accel and phi work on every handle kind (shard,
+ *     fused, symmetric, Hermite).  On nb_multi jerk != NULL is NB_ERR_INVALID; nb_multi_list_force evaluates on shard 0 against
+ *     the caller's UNPADDED n rows, as the other nb_multi_* queries (an entry that names a padding row adds nothing).
+ *   - Deterministic, and more than nb_field_eval promises: no atomics, and the order of additions is a function of an entry's
+ *     POSITION IN ITS ROW alone.  Entry e goes to lane e mod LS of the row's group of LS lanes; a lane adds its entries in ascending
+ *     e (in the handle's precision, the per-pair arithmetic of the force+jerk pass); the LS lane sums are combined in fp64 in a
+ *     fixed tree; G multiplies the total once, in fp64, and the product is rounded once (nb_field_eval's rule).  LS is one build
+ *     constant per precision (nb_list_force_shape reports it).  A row's outputs therefore depend on that row's entries, its point
+ *     and the bodies ONLY: not on m, not on the batches, not on cap -- the same entries re-packed at another cap give the same
+ *     bits --, and not on whether count was passed, provided the tail it skips is padding.
+ *   - State: the simulation state, the engine's side copies, the captured step graphs and the step counter are untouched: stepping
+ *     after a call is bit-identical to stepping without it.
+ *   - Points, point velocities and bodies must be finite and eps2 > 0; otherwise the result is unspecified (the call does not fault).
+ *   - Errors: NB_ERR_INVALID (NULL handle or request -- checked before any device call --, wrong struct_size, m == 0, unknown flag
+ *     bits (2u included), list NULL, cap outside 1 .. 4096, reserved != 0, all three outputs NULL, points / point_vel given with
+ *     NB_LISTF_AT_BODIES, points missing without it, point_vel missing with a jerk at points or given without one,
+ *     first_body + m > n), NB_ERR_STATE (nothing uploaded, nb_set_params not called, jerk on a leapfrog handle); nb_last_error
+ *     names the function and the field.
+ *   - Host pointers: the call blocks until the outputs are written; no pointer is kept.  NB_LISTF_DEVICE: every pointer is device
+ *     memory on the handle's device, the arrays are read and written in place, the work is enqueued on the handle's stream and the
+ *     call returns at once.
+ *   - Memory: a host-pointer request stages list, count, the points and the outputs one batch at a time, the batch halved in
+ *     whole workgroups' worth of rows until batch x cap x 4 <= 256 MiB (nb_neighbor_lists' rule and its staging buffer).  Nothing
+ *     is proportional to m x N. */
+#define NB_LISTF_AT_BODIES 1u   /* row k belongs to body first_body + k; an entry equal to that index is skipped */
+#define NB_LISTF_DEVICE    4u   /* every pointer is device memory on the handle's device; enqueued on the handle's stream, returns at once */
+typedef struct nb_list_force_request {
+    uint32_t struct_size;   /* sizeof(nb_list_force_request) */
+    uint32_t m;             /* number of rows, >= 1 */
+    uint32_t flags;         /* NB_LISTF_AT_BODIES | NB_LISTF_DEVICE */
+    uint32_t first_body;    /* NB_LISTF_AT_BODIES only */
+    const void *points;     /* 4*m elements x, y, z, (ignored); NULL with NB_LISTF_AT_BODIES */
+    const void *point_vel;  /* 4*m elements vx, vy, vz, (ignored); required iff jerk != NULL and NB_LISTF_AT_BODIES is not set, else must be NULL */
+    const uint32_t *list;   /* required: m * cap entries, row k = list[k*cap .. k*cap+cap) */
+    const uint32_t *count;  /* optional: m elements; only the first min(count[k], cap) entries of row k are read */
+    uint32_t cap;           /* entries per row, 1 <= cap <= 4096 */
+    uint32_t reserved;      /* must be 0 */
+    void *accel;            /* out, optional: 4*m elements (ax, ay, az, 0) of the handle's precision */
+    void *jerk;             /* out, optional: 4*m elements (jx, jy, jz, 0); Hermite handles only */
+    void *phi;              /* out, optional: m elements */
+} nb_list_force_request;    /* 80 bytes */
+int nb_list_force(nb_sim *s, const nb_list_force_request *req);
+/* The same on a multi-shard system: evaluated on shard 0 against the caller's UNPADDED n rows; jerk must be NULL. */
+int nb_multi_list_force(nb_multi *m, const nb_list_force_request *req);
+/* The shape of an m-row request at `cap` entries per row (no device call): the rows of EVERY batch but the last of a host-pointer
+ * request (a device-pointer request is one batch), and LS, the lanes that share a row.  For tests and tools; the results do not
+ * depend on the batch. */
+int nb_list_force_shape(nb_sim *s, uint32_t m, uint32_t cap, uint32_t *batch, uint32_t *lanes_per_row);
 
 #if defined(__GNUC__)
 #pragma GCC visibility pop

@@ -1092,7 +1092,7 @@ void nb_destroy(nb_sim* s)
     for (void* p : {s->jerk, s->hx, s->hv, s->fj_part, (void*)s->blk_lev, (void*)s->blk_due, (void*)s->blk_act, (void*)s->blk_hdr}) if (p) (void)hipFree(p);
     if (s->blk_hdr_host) (void)hipHostFree(s->blk_hdr_host);
     if (s->diag) (void)hipFree(s->diag);
-    for (auto* b : {&s->fld_pts, &s->fld_acc, &s->fld_phi, &s->fld_part, &s->nbr_rad, &s->nbr_idx, &s->nbr_d2, &s->nbr_cnt, &s->nbr_inf, &s->nbl_off, &s->nbl_list, &s->knn_work, &s->knn_idx, &s->knn_d2, &s->knn_stat})
+    for (auto* b : {&s->fld_pts, &s->fld_acc, &s->fld_phi, &s->fld_part, &s->nbr_rad, &s->nbr_idx, &s->nbr_d2, &s->nbr_cnt, &s->nbr_inf, &s->nbl_off, &s->nbl_list, &s->knn_work, &s->knn_idx, &s->knn_d2, &s->knn_stat, &s->lf_pvel, &s->lf_jerk})
         if (b->p) (void)hipFree(b->p);
     if (s->zero_row) (void)hipFree(s->zero_row);
     if (s->own_stream && s->stream) (void)hipStreamDestroy(s->stream);
@@ -2263,6 +2263,134 @@ int nb_knn_shape(nb_sim* s, uint32_t m, uint32_t k, uint32_t* batch, uint32_t* c
     if (batch) *batch = b;
     if (chunks) *chunks = c;
     if (j_per_chunk) *j_per_chunk = per;
+    return NB_OK;
+}
+
+/* ---- forces over neighbour rows ------------------------------------------------------------- */
+
+namespace {
+
+// The rows of every batch but the last of a host-pointer request: nbl_shape's rule for the staged rows -- halved in whole workgroups'
+// worth of rows until batch x cap x 4 <= kNblListBytes (one workgroup's rows is the floor).
+uint32_t lf_batch(const nb_sim* s, uint32_t m, uint32_t cap)
+{
+    const uint32_t prow = nb::lf_rows(s->f64);
+    uint32_t mb = m;
+    while ((uint64_t)mb * cap * 4 > kNblListBytes && mb > prow) mb = std::max(prow, (mb / 2 + prow - 1) / prow * prow);
+    return mb;
+}
+
+#define NB_LF_TABLE(K) {nullptr, (const void*)&nb::K<false, false, true>, (const void*)&nb::K<false, true, false>, (const void*)&nb::K<false, true, true>, \
+                        (const void*)&nb::K<true, false, false>, (const void*)&nb::K<true, false, true>, (const void*)&nb::K<true, true, false>,    \
+                        (const void*)&nb::K<true, true, true>}
+// the kernel for the outputs asked for: [accel << 2 | jerk << 1 | phi]
+const void* lf_kernel(bool f64, bool a, bool j, bool p)
+{
+    static const void* const k32[8] = NB_LF_TABLE(nb_lf32);
+    static const void* const k64[8] = NB_LF_TABLE(nb_lf64);
+    return (f64 ? k64 : k32)[(a ? 4 : 0) | (j ? 2 : 0) | (p ? 1 : 0)];
+}
+#undef NB_LF_TABLE
+
+}  // namespace
+
+extern "C++" int nbi::list_force(nb_sim* s, const nb_list_force_request* req, uint32_t rows, const char* who)
+{
+    const std::string w = std::string(who) + ": ";
+    if (!s) return fail(nullptr, NB_ERR_INVALID, w + "null handle");
+    if (!req) return fail(s, NB_ERR_INVALID, w + "null request");
+    if (req->struct_size != sizeof(nb_list_force_request)) return fail(s, NB_ERR_INVALID, w + "struct_size must be sizeof(nb_list_force_request)");
+    if (req->m == 0) return fail(s, NB_ERR_INVALID, w + "m must be >= 1");
+    if (req->flags & ~(NB_LISTF_AT_BODIES | NB_LISTF_DEVICE)) return fail(s, NB_ERR_INVALID, w + "unknown bits in flags");
+    const bool at = (req->flags & NB_LISTF_AT_BODIES) != 0, dev = (req->flags & NB_LISTF_DEVICE) != 0;
+    if (!req->list) return fail(s, NB_ERR_INVALID, w + "list is NULL");
+    if (req->cap == 0 || req->cap > kNblMaxCap) return fail(s, NB_ERR_INVALID, w + "cap must be in 1 .. 4096");
+    if (req->reserved != 0) return fail(s, NB_ERR_INVALID, w + "reserved must be 0");
+    if (!req->accel && !req->jerk && !req->phi) return fail(s, NB_ERR_INVALID, w + "accel, jerk and phi are all NULL");
+    if (at && req->points) return fail(s, NB_ERR_INVALID, w + "points must be NULL with NB_LISTF_AT_BODIES");
+    if (at && req->point_vel) return fail(s, NB_ERR_INVALID, w + "point_vel must be NULL with NB_LISTF_AT_BODIES");
+    if (!at && !req->points) return fail(s, NB_ERR_INVALID, w + "points is NULL (and NB_LISTF_AT_BODIES is not set)");
+    if (!at && req->jerk && !req->point_vel) return fail(s, NB_ERR_INVALID, w + "point_vel is NULL (the jerk at points needs their velocities)");
+    if (!at && !req->jerk && req->point_vel) return fail(s, NB_ERR_INVALID, w + "point_vel must be NULL when jerk is NULL");
+    if (at && (uint64_t)req->first_body + req->m > rows) return fail(s, NB_ERR_INVALID, w + "first_body + m exceeds n");
+    if (!s->uploaded) return fail(s, NB_ERR_STATE, w + "nothing uploaded yet");
+    if (!s->params_set) return fail(s, NB_ERR_STATE, w + "nb_set_params has not been called (G)");
+    if (req->jerk && !s->hermite) return fail(s, NB_ERR_STATE, w + "jerk needs a Hermite handle (nb_config.integrator = NB_INT_HERMITE4)");
+    NB_HIP(s, hipSetDevice(s->device));
+    if (int rc = finish_gather(s)) return rc;     // other ranks' rows must have landed
+
+    const size_t esz = s->esz, row4 = 4 * esz;
+    const uint32_t m = req->m;
+    const bool wa = req->accel != nullptr, wj = req->jerk != nullptr, wp = req->phi != nullptr;
+    const void* fn = lf_kernel(s->f64, wa, wj, wp);
+    const void* bodies = s->bodies[s->cur];
+    const void* vel = wj ? s->vel : nullptr;
+    uint32_t n = rows, cap = req->cap, at_flag = at ? 1u : 0u;
+    double G = s->G, eps2d = s->eps2;
+    float eps2f = (float)s->eps2;
+    const uint32_t batch = dev ? m : lf_batch(s, m, cap);        // device pointers are read in place: one launch
+    for (uint32_t done = 0; done < m;) {
+        uint32_t mb = std::min(batch, m - done);
+        const void* pts = at ? (const char*)bodies + row4 * (req->first_body + done) : (const char*)req->points + row4 * done;
+        const void* pv = !wj ? nullptr : at ? (const char*)s->vel + row4 * (req->first_body + done) : (const char*)req->point_vel + row4 * done;
+        const void* lst = req->list + (size_t)cap * done;
+        const void* cnt = req->count ? req->count + done : nullptr;
+        void* oa = wa ? (char*)req->accel + row4 * done : nullptr;
+        void* oj = wj ? (char*)req->jerk + row4 * done : nullptr;
+        void* op = wp ? (char*)req->phi + esz * done : nullptr;
+        if (!dev) {      // a host-pointer request stages its rows and its outputs batch by batch
+            const size_t list_bytes = (size_t)4 * cap * mb;
+            if (int rc = field_reserve(s, s->nbl_list, list_bytes, who)) return rc;
+            NB_HIP(s, hipMemcpyAsync(s->nbl_list.p, lst, list_bytes, hipMemcpyHostToDevice, s->stream));
+            lst = s->nbl_list.p;
+            if (cnt) {
+                if (int rc = field_reserve(s, s->nbr_cnt, (size_t)4 * mb, who)) return rc;
+                NB_HIP(s, hipMemcpyAsync(s->nbr_cnt.p, cnt, (size_t)4 * mb, hipMemcpyHostToDevice, s->stream));
+                cnt = s->nbr_cnt.p;
+            }
+            if (!at) {
+                if (int rc = field_reserve(s, s->fld_pts, row4 * mb, who)) return rc;
+                NB_HIP(s, hipMemcpyAsync(s->fld_pts.p, pts, row4 * mb, hipMemcpyHostToDevice, s->stream));
+                pts = s->fld_pts.p;
+                if (wj) {
+                    if (int rc = field_reserve(s, s->lf_pvel, row4 * mb, who)) return rc;
+                    NB_HIP(s, hipMemcpyAsync(s->lf_pvel.p, pv, row4 * mb, hipMemcpyHostToDevice, s->stream));
+                    pv = s->lf_pvel.p;
+                }
+            }
+            if (wa) { if (int rc = field_reserve(s, s->fld_acc, row4 * mb, who)) return rc; oa = s->fld_acc.p; }
+            if (wj) { if (int rc = field_reserve(s, s->lf_jerk, row4 * mb, who)) return rc; oj = s->lf_jerk.p; }
+            if (wp) { if (int rc = field_reserve(s, s->fld_phi, esz * mb, who)) return rc; op = s->fld_phi.p; }
+        }
+        uint32_t self0 = req->first_body + done;
+        const dim3 grid(ceil_div(mb, nb::lf_rows(s->f64))), block(nb::kBlock);
+        if (s->f64) {
+            void* args[] = {&bodies, &vel, &pts, &pv, &lst, &cnt, &n, &mb, &cap, &eps2d, &G, &at_flag, &self0, &oa, &oj, &op};
+            NB_HIP(s, hipLaunchKernel(fn, grid, block, args, 0, s->stream));
+        } else {
+            void* args[] = {&bodies, &vel, &pts, &pv, &lst, &cnt, &n, &mb, &cap, &eps2f, &G, &at_flag, &self0, &oa, &oj, &op};
+            NB_HIP(s, hipLaunchKernel(fn, grid, block, args, 0, s->stream));
+        }
+        if (!dev) {
+            if (wa) NB_HIP(s, hipMemcpyAsync((char*)req->accel + row4 * done, oa, row4 * mb, hipMemcpyDeviceToHost, s->stream));
+            if (wj) NB_HIP(s, hipMemcpyAsync((char*)req->jerk + row4 * done, oj, row4 * mb, hipMemcpyDeviceToHost, s->stream));
+            if (wp) NB_HIP(s, hipMemcpyAsync((char*)req->phi + esz * done, op, esz * mb, hipMemcpyDeviceToHost, s->stream));
+        }
+        done += mb;
+    }
+    if (!dev) NB_HIP(s, hipStreamSynchronize(s->stream));
+    return NB_OK;
+}
+
+int nb_list_force(nb_sim* s, const nb_list_force_request* req) { return nbi::list_force(s, req, s ? s->n : 0u, "nb_list_force"); }
+
+int nb_list_force_shape(nb_sim* s, uint32_t m, uint32_t cap, uint32_t* batch, uint32_t* lanes_per_row)
+{
+    if (!s) return fail(nullptr, NB_ERR_INVALID, "nb_list_force_shape: null handle");
+    if (m == 0) return fail(s, NB_ERR_INVALID, "nb_list_force_shape: m must be >= 1");
+    if (cap == 0 || cap > kNblMaxCap) return fail(s, NB_ERR_INVALID, "nb_list_force_shape: cap must be in 1 .. 4096");
+    if (batch) *batch = lf_batch(s, m, cap);
+    if (lanes_per_row) *lanes_per_row = nb::lf_lanes(s->f64);
     return NB_OK;
 }
 

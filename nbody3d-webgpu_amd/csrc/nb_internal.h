@@ -165,6 +165,9 @@ struct nb_sim {
     // bytes per (j-chunk, point of a batch) -- bounded by nb_knn's memory rule --; idx / d2 stage one batch of a host-pointer request
     field_buf knn_work, knn_idx, knn_d2;
     field_buf knn_stat;       // the calibration build's counters (NB_TUNING with NB_KNN_STATS set): never allocated otherwise
+    // nb_list_force: a host-pointer request stages one batch at a time -- its rows in nbl_list, its counts in nbr_cnt, its points in
+    // fld_pts, accel / phi in fld_acc / fld_phi (none of those calls overlaps another on the stream); pvel / jerk are its own
+    field_buf lf_pvel, lf_jerk;
     // NB_INT_HERMITE4: bodies[0] / vel are the state at ONE instant, acc / jerk the derivatives derived from it.  None of the
     // leapfrog launch fields above is used: plain unpadded arrays, no planner, no graphs.
     bool hermite = false;
@@ -202,6 +205,8 @@ int neighbors(nb_sim* s, const nb_neighbor_request* req, uint32_t rows, const ch
 int neighbor_lists(nb_sim* s, const nb_neighbor_list_request* req, uint32_t rows, const char* who);
 // nb_knn likewise (nb_multi_knn: the caller's unpadded rows of shard 0)
 int knn(nb_sim* s, const nb_knn_request* req, uint32_t rows, const char* who);
+// nb_list_force likewise (nb_multi_list_force: entries >= the caller's unpadded n add nothing)
+int list_force(nb_sim* s, const nb_list_force_request* req, uint32_t rows, const char* who);
 const std::string& create_error();
 
 // nb_comm.hip: called by nb_step after the integrate kernel when a communicator is attached.

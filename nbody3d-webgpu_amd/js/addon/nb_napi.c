@@ -71,6 +71,8 @@ static int (*p_neighbor_lists)(nb_sim *, const nb_neighbor_list_request *);     
 static int (*p_multi_neighbor_lists)(nb_multi *, const nb_neighbor_list_request *);
 static int (*p_knn)(nb_sim *, const nb_knn_request *);                              /* k nearest neighbours, likewise: optional symbols */
 static int (*p_multi_knn)(nb_multi *, const nb_knn_request *);
+static int (*p_list_force)(nb_sim *, const nb_list_force_request *);                /* forces over neighbour rows, likewise: optional symbols */
+static int (*p_multi_list_force)(nb_multi *, const nb_list_force_request *);
 static int (*p_eqm_info)(nb_sim *, int *);                              /* the equal-mass kernels' report, also within ABI 2.4: optional symbol */
 static int (*p_eqm_form)(nb_sim *, int *);                              /* which equal-mass form, likewise */
 
@@ -163,6 +165,8 @@ static napi_value js_load(napi_env env, napi_callback_info info)
         *(void **)(&p_multi_neighbor_lists) = dlsym(h, "nb_multi_neighbor_lists");
         *(void **)(&p_knn) = dlsym(h, "nb_knn");
         *(void **)(&p_multi_knn) = dlsym(h, "nb_multi_knn");
+        *(void **)(&p_list_force) = dlsym(h, "nb_list_force");
+        *(void **)(&p_multi_list_force) = dlsym(h, "nb_multi_list_force");
         *(void **)(&p_eqm_info) = dlsym(h, "nb_eqm_info");
         *(void **)(&p_eqm_form) = dlsym(h, "nb_eqm_form");
         g_lib = h;
@@ -850,6 +854,63 @@ static napi_value js_knn(napi_env env, napi_callback_info info)
     return undefined(env);
 }
 
+/* listForce(handle, list, cap, points|null, pointVel|null, firstBody, count|null, accelOut|null, jerkOut|null, phiOut|null):
+ * nb_list_force / nb_multi_list_force.  list: Uint32Array of m * cap entries, count: Uint32Array of m elements or null; points / pointVel
+ * (4*m) and the outputs (4*m, 4*m, m elements): typed arrays of the handle's precision, the outputs written in place.  points null:
+ * row k belongs to body firstBody + k (NB_LISTF_AT_BODIES). */
+static napi_value js_list_force(napi_env env, napi_callback_info info)
+{
+    size_t argc = 10; napi_value argv[10];
+    CHECK_NAPI(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    if (argc < 10) { napi_throw_type_error(env, NULL, "listForce(handle, list, cap, points|null, pointVel|null, firstBody, count|null, accelOut|null, jerkOut|null, phiOut|null)"); return NULL; }
+    handle_t *h = get_handle(env, argv[0]); if (!h) return NULL;
+    if (!p_list_force || !p_multi_list_force) return throw_msg(env, NB_ERR_STATE, "the loaded library has no nb_list_force", "nb_list_force");
+    const napi_typedarray_type real = h->f64 ? napi_float64_array : napi_float32_array;
+    void *ptr[7] = {NULL, NULL, NULL, NULL, NULL, NULL, NULL}; size_t len[7] = {0, 0, 0, 0, 0, 0, 0};
+    static const int arg_of[7] = {1, 3, 4, 6, 7, 8, 9};
+    static const int is_u32[7] = {1, 0, 0, 1, 0, 0, 0};
+    static const char *const what[7] = {"list", "points", "pointVel", "count", "accelOut", "jerkOut", "phiOut"};
+    for (int k = 0; k < 7; ++k) {
+        napi_valuetype vt; napi_typeof(env, argv[arg_of[k]], &vt);
+        if (vt == napi_null || vt == napi_undefined) continue;
+        bool is_ta = false; napi_is_typedarray(env, argv[arg_of[k]], &is_ta);
+        napi_typedarray_type tt; napi_value ab; size_t off;
+        const napi_typedarray_type want = is_u32[k] ? napi_uint32_array : real;
+        if (!is_ta || napi_get_typedarray_info(env, argv[arg_of[k]], &tt, &len[k], &ptr[k], &ab, &off) != napi_ok || tt != want) {
+            char buf[160]; snprintf(buf, sizeof buf, "listForce: %s must be a %s or null", what[k], is_u32[k] ? "Uint32Array" : h->f64 ? "Float64Array" : "Float32Array");
+            napi_throw_type_error(env, NULL, buf); return NULL;
+        }
+    }
+    double cap = 0, first = 0;
+    napi_get_value_double(env, argv[2], &cap); napi_get_value_double(env, argv[5], &first);
+    if (!ptr[0] || !(cap >= 1 && cap <= 4294967295.0) || len[0] % (size_t)cap != 0 || len[0] / (size_t)cap > 0xffffffffu || len[0] == 0) {
+        napi_throw_range_error(env, NULL, "listForce: list must hold m * cap entries, m >= 1"); return NULL;
+    }
+    if (!(first >= 0 && first <= 4294967295.0)) { napi_throw_range_error(env, NULL, "listForce: firstBody out of range"); return NULL; }
+    nb_list_force_request req;
+    memset(&req, 0, sizeof req);
+    req.struct_size = sizeof req;
+    req.cap = (uint32_t)cap;
+    req.m = (uint32_t)(len[0] / (size_t)cap);
+    const size_t m = req.m;
+    if ((ptr[1] && len[1] != 4 * m) || (ptr[2] && len[2] != 4 * m) || (ptr[3] && len[3] != m) || (ptr[4] && len[4] != 4 * m) ||
+        (ptr[5] && len[5] != 4 * m) || (ptr[6] && len[6] != m)) {
+        napi_throw_range_error(env, NULL, "listForce: points, pointVel, accelOut and jerkOut must hold 4*m elements, count and phiOut m"); return NULL;
+    }
+    if (!ptr[1]) { req.flags = NB_LISTF_AT_BODIES; req.first_body = (uint32_t)first; }
+    req.points = ptr[1]; req.point_vel = ptr[2];
+    req.list = (const uint32_t *)ptr[0]; req.count = (const uint32_t *)ptr[3];
+    req.accel = ptr[4]; req.jerk = ptr[5]; req.phi = ptr[6];
+    if (h->multi) {
+        int rcm = p_multi_list_force(h->multi, &req);
+        if (rcm != NB_OK) return throw_msg(env, rcm, p_multi_last_error(h->multi), "nb_multi_list_force");
+    } else {
+        int rc = p_list_force(h->sim, &req);
+        if (rc != NB_OK) return throw_nb(env, rc, h->sim, "nb_list_force");
+    }
+    return undefined(env);
+}
+
 /* downloadJerk(handle, jerkOut): nb_download_jerk -- 4*n elements (jx, jy, jz, 0) of a Hermite handle, written in place. */
 static napi_value js_download_jerk(napi_env env, napi_callback_info info)
 {
@@ -992,7 +1053,7 @@ static napi_value init_module(napi_env env, napi_value exports)
         {"fieldEval", js_field_eval}, {"downloadJerk", js_download_jerk}, {"uploadDerivs", js_upload_derivs},
         {"setBlockSteps", js_set_block_steps}, {"blockStats", js_block_stats}, {"downloadLevels", js_download_levels},
         {"uploadLevels", js_upload_levels}, {"neighbors", js_neighbors}, {"neighborLists", js_neighbor_lists},
-        {"knn", js_knn},
+        {"knn", js_knn}, {"listForce", js_list_force},
     };
     for (size_t i = 0; i < sizeof fns / sizeof fns[0]; ++i) {
         napi_value f;

@@ -403,6 +403,43 @@ class Simulation {
     return out;
   }
 
+  /** Acceleration, jerk and potential summed over the entries of neighbour rows (nb_list_force; no reference analogue): `lists` is a
+   *  Uint32Array of m * options.cap entries -- the rows neighborLists() or knn() return, or any other --, row k belonging to
+   *  options.points[k] (4*m elements x, y, z, ignored) or, with options.bodies = [first, m], to body first + k, an entry equal to
+   *  that index skipped.  An entry >= nBodies (the padding 0xffffffff, wherever it stands) adds nothing.  options.count
+   *  (Uint32Array, m): only the first min(count, cap) entries of a row are read.  options.accel (default true), options.jerk
+   *  (default false: needs a 'hermite4' simulation and, at points, options.pointVel), options.phi (default false) choose the
+   *  outputs.  Returns {accel, jerk, phi}: 4*m, 4*m, m elements, null for what was not asked for.  A row's outputs depend on its
+   *  entries, its point and the bodies only, bit for bit.  The simulation state is not touched. */
+  listForce(lists, options) {
+    this._need();
+    const o = options || {}, T = this.ArrayType;
+    if (!(lists instanceof Uint32Array)) throw new TypeError('lists: expected Uint32Array');
+    const cap = o.cap === undefined || o.cap === null ? NaN : +o.cap;
+    if (!(Number.isInteger(cap) && cap >= 1 && cap <= 4096)) throw new RangeError('options.cap must be an integer in 1 .. 4096');
+    if (lists.length === 0 || lists.length % cap !== 0) throw new RangeError('lists must hold m * cap entries, m >= 1');
+    const m = lists.length / cap;
+    const real = function (a, name) {
+      if (a === null || a === undefined) return null;
+      if (a instanceof T) return a;
+      if (typeof a.length === 'number') return T.from(a);
+      throw new TypeError(name + ': expected ' + T.name);
+    };
+    const pts = real(o.points, 'points'), pv = real(o.pointVel, 'pointVel');
+    let first = 0;
+    if (o.bodies) {
+      if (pts) throw new RangeError('listForce(): give either options.points or options.bodies, not both');
+      first = o.bodies[0] >>> 0;
+      if ((o.bodies[1] >>> 0) !== m) throw new RangeError('options.bodies = [first, count]: count must be the number of rows');
+    } else if (!pts) throw new TypeError('listForce(): options.points, or options.bodies = [first, count], required');
+    let count = null;
+    if (o.count !== null && o.count !== undefined) count = o.count instanceof Uint32Array ? o.count : Uint32Array.from(o.count);
+    const out = { accel: o.accel === false ? null : new T(4 * m), jerk: o.jerk ? new T(4 * m) : null, phi: o.phi ? new T(m) : null };
+    addon.setParams(this._h, this.dt, this.G);   // the sums carry G
+    addon.listForce(this._h, lists, cap, pts, pv, first, count, out.accel, out.jerk, out.phi);
+    return out;
+  }
+
   /** The Casertano-Hut local density at every body, a Float64Array of nBodies elements: one knn() call over all bodies, then per
    *  body the masses of its first k - 1 neighbours over the volume of the sphere that reaches the k-th (k >= 2, default 6); NaN
    *  where a body has fewer than k neighbours. */

@@ -101,6 +101,15 @@ class nb_knn_request(C.Structure):          # include/nbody3d_hip.h (k nearest n
                 ("index", C.c_void_p), ("dist2", C.c_void_p)]
 
 
+class nb_list_force_request(C.Structure):   # include/nbody3d_hip.h (forces over neighbour rows, added within ABI 2.4)
+    _fields_ = [("struct_size", C.c_uint32), ("m", C.c_uint32), ("flags", C.c_uint32), ("first_body", C.c_uint32),
+                ("points", C.c_void_p), ("point_vel", C.c_void_p), ("list", C.c_void_p), ("count", C.c_void_p),
+                ("cap", C.c_uint32), ("reserved", C.c_uint32),
+                ("accel", C.c_void_p), ("jerk", C.c_void_p), ("phi", C.c_void_p)]
+
+
+NB_LISTF_AT_BODIES, NB_LISTF_DEVICE = 1, 4
+
 NB_BLOCK_FROZEN = 1
 
 
@@ -131,7 +140,8 @@ SYMBOLS = ["nb_abi_version", "nb_device_count", "nb_create", "nb_destroy", "nb_u
            "nb_set_block_steps", "nb_block_stats", "nb_download_levels", "nb_upload_levels",
            "nb_neighbors", "nb_multi_neighbors", "nb_neighbors_shape", "nb_eqm_info", "nb_eqm_form",
            "nb_neighbor_lists", "nb_multi_neighbor_lists", "nb_neighbor_lists_shape",
-           "nb_knn", "nb_multi_knn", "nb_knn_shape"]
+           "nb_knn", "nb_multi_knn", "nb_knn_shape",
+           "nb_list_force", "nb_multi_list_force", "nb_list_force_shape"]
 
 _lib = None
 
@@ -223,6 +233,10 @@ def load_library():
         L.nb_knn.argtypes = [vp, C.POINTER(nb_knn_request)]
         L.nb_multi_knn.argtypes = [vp, C.POINTER(nb_knn_request)]
         L.nb_knn_shape.argtypes = [vp, C.c_uint32, C.c_uint32] + [C.POINTER(C.c_uint32)] * 3
+    if hasattr(L, "nb_list_force"):         # forces over neighbour rows, also within 2.4 and detected by the symbol
+        L.nb_list_force.argtypes = [vp, C.POINTER(nb_list_force_request)]
+        L.nb_multi_list_force.argtypes = [vp, C.POINTER(nb_list_force_request)]
+        L.nb_list_force_shape.argtypes = [vp, C.c_uint32, C.c_uint32] + [C.POINTER(C.c_uint32)] * 2
     if hasattr(L, "nb_eqm_info"):           # the equal-mass kernels' report, also within 2.4 and detected by the symbol
         L.nb_eqm_info.argtypes = [vp, C.POINTER(C.c_int)]
     if hasattr(L, "nb_eqm_form"):           # which of the equal-mass forms, likewise
@@ -390,6 +404,70 @@ def _neighbor_list_request(dtype, points, bodies, radius, radii, cap, nearest):
     req.index = _ptr(index) if nearest and req.m else None
     req.dist2 = _ptr(dist2) if nearest and req.m else None
     return req, (pts, rad), lists, count, index, dist2
+
+
+def _need_list_force(what):
+    if not hasattr(load_library(), "nb_list_force"):
+        raise NBodyError(1, "%s: the loaded library has no nb_list_force" % what)
+
+
+def _rows4(a, dtype, what):
+    a = np.asarray(a, dtype=dtype)
+    if a.ndim == 1:
+        a = a.reshape(-1, 3 if a.size % 4 else 4)
+    if a.ndim != 2 or a.shape[1] not in (3, 4):
+        raise ValueError("list_force(): %s must have shape (m, 3) or (m, 4)" % what)
+    if a.shape[1] == 3:
+        a = np.concatenate([a, np.zeros((len(a), 1), dtype)], axis=1)
+    return np.ascontiguousarray(a)
+
+
+def _list_force_request(dtype, lists, bodies, points, point_vel, count, accel, jerk, phi):
+    """The nb_list_force_request of list_force(): (request, arrays kept alive, accel | None, jerk | None, phi | None)."""
+    _need_list_force("list_force()")
+    req = nb_list_force_request()
+    req.struct_size = C.sizeof(nb_list_force_request)
+    lists = np.ascontiguousarray(lists, dtype=np.uint32)
+    if lists.ndim != 2:
+        raise ValueError("list_force(): lists must have shape (m, cap)")
+    m, cap = lists.shape
+    if not (m < 2 ** 32 and cap < 2 ** 32):
+        raise ValueError("list_force(): lists out of range")
+    req.m, req.cap = m, cap
+    pts = pv = cnt = None
+    # (both or neither of points / bodies, point_vel without a jerk, a cap out of range: passed on as they are -- the engine's
+    # NB_ERR_INVALID names the field)
+    if bodies is not None:
+        first, nb = int(bodies[0]), int(bodies[1])
+        if not (0 <= first < 2 ** 32 and 0 <= nb < 2 ** 32):
+            raise ValueError("list_force(): bodies=(first, count) out of range")
+        if nb != m:
+            raise ValueError("list_force(): bodies=(first, count) must name one body per row of lists")
+        req.flags |= NB_LISTF_AT_BODIES
+        req.first_body = first
+    if points is not None:
+        pts = _rows4(points, dtype, "points")
+        if len(pts) != m:
+            raise ValueError("list_force(): points must hold one point per row of lists")
+        req.points = _ptr(pts) if m else None
+    if point_vel is not None:
+        pv = _rows4(point_vel, dtype, "point_vel")
+        if len(pv) != m:
+            raise ValueError("list_force(): point_vel must hold one velocity per row of lists")
+        req.point_vel = _ptr(pv) if m else None
+    if count is not None:
+        cnt = np.ascontiguousarray(count, dtype=np.uint32).reshape(-1)
+        if len(cnt) != m:
+            raise ValueError("list_force(): count must hold one length per row of lists")
+        req.count = _ptr(cnt) if m else None
+    req.list = _ptr(lists) if lists.size else None
+    a = np.zeros((m, 4), dtype) if accel else None
+    j = np.zeros((m, 4), dtype) if jerk else None
+    f = np.zeros((m,), dtype) if phi else None
+    req.accel = _ptr(a) if accel and m else None
+    req.jerk = _ptr(j) if jerk and m else None
+    req.phi = _ptr(f) if phi and m else None
+    return req, (lists, pts, pv, cnt), a, j, f
 
 
 def _need_knn(what):
@@ -608,6 +686,7 @@ class Simulation:
         cfg.tile = tile
         cfg.eps2 = 0.0 if eps2 is None else float(eps2)
         cfg.device = device
+        self._device = int(device)
         self.shard_begin, self.shard_count = (0, self.n) if shard is None else (int(shard[0]), int(shard[1]))
         if shard is not None:      # shard_count = 0 means "whole system, not a shard" (eligible for the fused step)
             cfg.shard_begin, cfg.shard_count = self.shard_begin, self.shard_count
@@ -1030,6 +1109,79 @@ class Simulation:
         self._check(self._L.nb_neighbor_lists_shape(self._h, int(m), int(cap), *[C.byref(x) for x in v]))
         return dict(zip(("batch", "chunks", "j_per_chunk"), (x.value for x in v)))
 
+    def list_force(self, lists, *, bodies=None, points=None, point_vel=None, count=None, accel=True, jerk=False, phi=False):
+        """nb_list_force: acceleration, jerk and potential summed over the entries of each row of ``lists`` ((m, cap) uint32: the
+        rows neighbor_lists() or knn() return, or any other) at ``points`` ((m, 3) or (m, 4)) -- or, with ``bodies=(first, m)``, at
+        those bodies, an entry equal to the row's own body skipped.  ``count`` ((m,) uint32): only the first min(count, cap) entries
+        of a row are read.  An entry >= n (the padding NB_NBR_NONE, wherever it stands) adds nothing.  ``jerk`` needs a Hermite handle
+        and, at points, ``point_vel``.  Returns ``(accel (m, 4) | None, jerk (m, 4) | None, phi (m,) | None)``.  A row's outputs depend
+        on its entries, its point and the bodies only -- bit for bit, whatever m, cap and count are."""
+        req, keep, a, j, f = _list_force_request(self.dtype, lists, bodies, points, point_vel, count, accel, jerk, phi)
+        self._check(self._L.nb_list_force(self._h, C.byref(req)))
+        return a, j, f
+
+    def list_force_device(self, list_ptr, m, cap, *, bodies=None, points_ptr=None, point_vel_ptr=None, count_ptr=None,
+                          accel_ptr=None, jerk_ptr=None, phi_ptr=None):
+        """The device-pointer form (NB_LISTF_DEVICE): device addresses on the handle's device (0 or None for what is not wanted);
+        ``list_ptr``: m * cap uint32, ``count_ptr``: m uint32, the outputs as list_force() returns them.  Read and written in place,
+        enqueued on the handle's stream, returns without waiting.  ``bodies=(first, count)`` selects the bodies themselves
+        (``points_ptr`` must then be None, ``m`` is ignored)."""
+        _need_list_force("list_force_device()")
+        req = nb_list_force_request()
+        req.struct_size = C.sizeof(nb_list_force_request)
+        req.flags = NB_LISTF_DEVICE
+        if bodies is not None:
+            req.flags |= NB_LISTF_AT_BODIES
+            req.first_body, req.m = int(bodies[0]), int(bodies[1])
+        else:
+            req.m = int(m)
+        req.points = points_ptr or None
+        req.point_vel = point_vel_ptr or None
+        req.list = list_ptr or None
+        req.count = count_ptr or None
+        req.cap = int(cap)
+        req.accel = accel_ptr or None
+        req.jerk = jerk_ptr or None
+        req.phi = phi_ptr or None
+        self._check(self._L.nb_list_force(self._h, C.byref(req)))
+
+    def list_force_shape(self, m, cap):
+        """{batch, lanes_per_row}: the rows of every batch but the last that a host-pointer nb_list_force request of m rows at ``cap``
+        entries is staged in, and the lanes that share one row (the answers depend on neither m nor the batch)."""
+        _need_list_force("list_force_shape()")
+        v = [C.c_uint32() for _ in range(2)]
+        self._check(self._L.nb_list_force_shape(self._h, int(m), int(cap), *[C.byref(x) for x in v]))
+        return dict(zip(("batch", "lanes_per_row"), (x.value for x in v)))
+
+    def irregular_force(self, radius, cap=128, *, jerk=None, phi=False):
+        """The irregular force of an Ahmad-Cohen split at every body: nb_neighbor_lists with ``radius`` and rows of ``cap`` entries,
+        then nb_list_force over those rows, both with device pointers on the handle's stream -- the rows never visit the host.
+        ``jerk`` defaults to what the handle can give (Hermite handles: True).  Returns ``(accel (n, 4), jerk (n, 4) | None, phi (n,) |
+        None, count (n,) uint32)``; where count exceeds cap the sums run over the cap members with the smallest indices."""
+        _need_list_force("irregular_force()")
+        import torch
+        jerk = (self.integrator != "leapfrog") if jerk is None else bool(jerk)
+        n, cap = self.n, int(cap)
+        if not 1 <= cap <= 4096:
+            raise ValueError("irregular_force(): cap must be in 1 .. 4096")
+        dev = torch.device("cuda", torch.cuda.current_device() if self._device < 0 else self._device)
+        tt = torch.float64 if self.dtype == np.float64 else torch.float32
+        lst = torch.empty((n, cap), dtype=torch.int32, device=dev)
+        cnt = torch.empty((n,), dtype=torch.int32, device=dev)
+        a = torch.empty((n, 4), dtype=tt, device=dev)
+        j = torch.empty((n, 4), dtype=tt, device=dev) if jerk else None
+        f = torch.empty((n,), dtype=tt, device=dev) if phi else None
+        # The buffers come from torch's allocator on torch's CURRENT stream and are used on the HANDLE's stream.  Two waits make that
+        # safe, and both are needed: this one (whatever torch still runs on a recycled block has finished before the engine writes
+        # it) and self.sync() below (the engine has finished before torch reads the buffers or takes them back).
+        torch.cuda.current_stream(dev).synchronize()
+        self.neighbor_lists_device(None, 0, lst.data_ptr(), cap, cnt.data_ptr(), bodies=(0, n), radius=radius)
+        self.list_force_device(lst.data_ptr(), 0, cap, bodies=(0, n), count_ptr=cnt.data_ptr(), accel_ptr=a.data_ptr(),
+                               jerk_ptr=j.data_ptr() if jerk else None, phi_ptr=f.data_ptr() if phi else None)
+        self.sync()
+        host = lambda t: None if t is None else t.cpu().numpy()
+        return host(a), host(j), host(f), cnt.cpu().numpy().view(np.uint32)
+
     def knn(self, points=None, *, bodies=None, k=6, dist2=True):
         """nb_knn: the ``k`` nearest bodies (1 <= k <= 64) of each of ``points`` ((m, 3) or (m, 4); the fourth column is ignored) --
         or, with ``bodies=(first, count)``, of each of those bodies, itself left out by index.  Returns ``(index (m, k) uint32,
@@ -1253,6 +1405,13 @@ class MultiSimulation:
         req, keep, lists, count, index, dist2 = _neighbor_list_request(self.dtype, points, bodies, radius, radii, cap, nearest)
         self._check(self._L.nb_multi_neighbor_lists(self._h, C.byref(req)))
         return (lists, count, index, dist2) if nearest else (lists, count)
+
+    def list_force(self, lists, *, bodies=None, points=None, point_vel=None, count=None, accel=True, jerk=False, phi=False):
+        """nb_multi_list_force: Simulation.list_force() on the whole system (evaluated on shard 0 against the caller's unpadded
+        rows); ``jerk`` is refused (NB_ERR_INVALID): the shards are leapfrog handles."""
+        req, keep, a, j, f = _list_force_request(self.dtype, lists, bodies, points, point_vel, count, accel, jerk, phi)
+        self._check(self._L.nb_multi_list_force(self._h, C.byref(req)))
+        return a, j, f
 
     def knn(self, points=None, *, bodies=None, k=6, dist2=True):
         """nb_multi_knn: Simulation.knn() on the whole system (evaluated on shard 0 against the caller's unpadded rows: a padding
