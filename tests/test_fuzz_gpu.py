@@ -132,3 +132,11 @@ def test_random_api_call_sequence(seed):
     and on the oracle side by side (tests/api_sequence.py; tools/fuzz_api.py runs the long campaign)."""
     from api_sequence import run_sequence
     run_sequence(seed, n_max=1500)
+
+
+@pytest.mark.parametrize("seed", range(41000, 41032))
+def test_random_api_call_sequence_with_queries(seed):
+    """The same sequences with every query mixed in (field, neighbours, lists, k nearest, list forces, diagnostics, frame): asked on the
+    handle as it stands, then compared with a twin loaded with the state read() returns (tests/query_state.py)."""
+    from api_sequence import run_sequence
+    run_sequence(seed, n_max=1500, queries=True)
