@@ -61,7 +61,9 @@ extern "C" {
                              2.4 (round 13) likewise within 2.4: nb_knn, nb_multi_knn, nb_knn_shape, nb_knn_request.  Detected by the presence
                                             of the symbol nb_knn
                              2.4 (round 14) likewise within 2.4: nb_list_force, nb_multi_list_force, nb_list_force_shape,
-                                            nb_list_force_request.  Detected by the presence of the symbol nb_list_force */
+                                            nb_list_force_request.  Detected by the presence of the symbol nb_list_force
+                             2.4 (round 15) likewise within 2.4: nb_split_force, nb_multi_split_force, nb_split_force_shape,
+                                            nb_split_force_request, NB_SPLIT_*.  Detected by the presence of the symbol nb_split_force */
 
 typedef struct nb_sim nb_sim; /* opaque */
 
@@ -806,6 +808,74 @@ int nb_multi_list_force(nb_multi *m, const nb_list_force_request *req);
  * request (a device-pointer request is one batch), and LS, the lanes that share a row.  For tests and tools; the results do not
  * depend on the batch. */
 int nb_list_force_shape(nb_sim *s, uint32_t m, uint32_t cap, uint32_t *batch, uint32_t *lanes_per_row);
+
+/* ---- regular and irregular force+jerk in one pass (added within ABI 2.4; no reference analogue) ----
+ * For each of M points (or bodies): the acceleration and the jerk of ALL N rows of the handle, every pair's term added to exactly
+ * one of TWO sums -- the irregular sum over the bodies inside the point's radius, the regular sum over every other row.  This
+ * is the regular-force pass of an Ahmad-Cohen scheme: one comparison per pair decides which accumulators take the term.  Nothing
+ * is subtracted, so the small sum of a point with a close neighbour does not carry the rounding error of the large one (what
+ * "full pass minus nb_list_force" does), and the two sums are cut by the same comparison in the same pass.
+ *   - Membership: body j is a MEMBER of point k iff d2 < h2, strictly, with d2 = fma(dz, dz, fma(dy, dy, dx * dx)), dx = x_j - p_x,
+ *     and h2 = h * h, h = radii[k] or radius, all in the handle's precision: nb_neighbors' expression and rule, letter for letter
+ *     (a body exactly on the sphere is no member).  Every row of the handle is a body whatever its mass.  *_irr sums the members,
+ *     *_reg sums every other row.
+ *   - Pair arithmetic: the force+jerk pass's terms
+ *         a    = sum_j G m_j dr / rho^3
+ *         jerk = sum_j G m_j [ dv / rho^3 - 3 (dr.dv) dr / rho^5 ]          dr = x_j - p,  dv = v_j - u
+ *     with rho^2 = d2 + eps2 -- one rounding more than the force+jerk pass's fused chain, so *_irr + *_reg is NOT bit-comparable
+ *     with what nb_force_pass / nb_step leave in accel and jerk --, then that pass's sequence (reciprocal root, s3 = (m y) y^2, the
+ *     jerk as ONE sum of s3 (dv - 3 q dr)).  A pair's term goes to exactly one of the two sums: its weight is s3 in that sum and 0
+ *     in the other.  Never a subtraction.
+ *   - Own row: with NB_SPLIT_AT_BODIES point k is body first_body + k; its own row needs no mask (dr = dv = 0 and eps2 > 0 give an
+ *     exact 0 in whichever sum it lands).  Another body at the same position is a member (d2 = 0): it adds 0 to a and its dv term
+ *     to the jerk.
+ *   - Empty sides: a point without a member (radii[k] = 0 included) gets exactly 0 (== 0) in both irregular rows; a point whose
+ *     radius covers every row gets exactly 0 in both regular rows.  .w of every row is 0.
+ *   - Summation: as the force+jerk pass -- on f32 handles binary32 in two levels inside a j-chunk (a register takes at most 1,024
+ *     terms), fp64 across the j-chunks in ascending order, G multiplied in once in fp64 and the product rounded once.  No atomics:
+ *     the same request on the same state gives the same bits, and a scalar radius and a radii array filled with that value give
+ *     the same bits.  Nothing more is promised (the order may depend on m, as for nb_field_eval).
+ *   - Handles: accel_irr / accel_reg work on every handle kind (whole, shard after its gather, fused, symmetric, Hermite,
+ *     block-step), f32 and f64.  The jerk pair needs velocities at the positions' instant: Hermite handles only (block-step
+ *     included); on a leapfrog handle it is NB_ERR_STATE, as for nb_list_force.  There is no fp64 audit mode: 2u is an unknown flag.
+ *     On nb_multi a jerk pointer is NB_ERR_INVALID; nb_multi_split_force evaluates on shard 0 against the caller's UNPADDED n rows
+ *     (the zero-mass padding rows add exactly nothing to either sum).
+ *   - Positions read: as they stand behind every step enqueued so far (the state nb_field_eval reads).  The simulation state,
+ *     the side copies, the captured graphs and the step counter are untouched: stepping after a call is bit-identical to stepping
+ *     without it.  nb_set_params is required (G).
+ *   - Points, velocities and bodies must be finite and eps2 > 0; otherwise the result is unspecified (the call does not fault).
+ *   - Errors: NB_ERR_INVALID (NULL handle or request -- checked before any device call --, wrong struct_size, m == 0, unknown flag
+ *     bits, all four outputs NULL, points / point_vel given with NB_SPLIT_AT_BODIES, points missing without it, point_vel missing
+ *     with a jerk at points or given without one, first_body + m > n, neither radii nor radius > 0, radius negative or NaN; on
+ *     nb_multi a non-NULL jerk pointer), NB_ERR_STATE (nothing uploaded, nb_set_params not called, a jerk on a leapfrog handle);
+ *     nb_last_error names the function and the field.
+ *   - Host pointers: the call blocks until the outputs are written; no pointer is kept.  NB_SPLIT_DEVICE: every pointer is device
+ *     memory on the handle's device, read and written in place, enqueued on the handle's stream; the call returns at once.
+ *   - Memory: up to four partial rows per (point of a batch, j-chunk) in the buffer nb_field_eval and nb_neighbors share, under
+ *     its bound (the j-chunks are made longer, then the batch is halved, until it fits); a host-pointer request is staged as
+ *     those calls stage theirs.  Nothing is proportional to m x N. */
+#define NB_SPLIT_AT_BODIES 1u   /* point k is body first_body + k */
+#define NB_SPLIT_DEVICE    4u   /* every pointer is device memory; enqueued on the handle's stream, returns at once */
+typedef struct nb_split_force_request {
+    uint32_t struct_size;   /* sizeof(nb_split_force_request) */
+    uint32_t m;             /* number of points, >= 1 */
+    uint32_t flags;         /* NB_SPLIT_AT_BODIES | NB_SPLIT_DEVICE */
+    uint32_t first_body;    /* NB_SPLIT_AT_BODIES only */
+    const void *points;     /* 4*m elements x, y, z, (ignored); NULL with NB_SPLIT_AT_BODIES */
+    const void *point_vel;  /* 4*m elements vx, vy, vz, (ignored); required iff a jerk is asked for at points, else NULL */
+    const void *radii;      /* optional: m elements of the handle's precision; an element may be 0 */
+    double radius;          /* used when radii == NULL; radii or radius > 0 is required */
+    void *accel_irr;        /* out, optional: 4*m elements (ax, ay, az, 0) over the members */
+    void *accel_reg;        /* out, optional: 4*m elements over every other row */
+    void *jerk_irr;         /* out, optional: 4*m elements (jx, jy, jz, 0); Hermite handles only */
+    void *jerk_reg;         /* out, optional: likewise */
+} nb_split_force_request;   /* 80 bytes */
+int nb_split_force(nb_sim *s, const nb_split_force_request *req);
+/* The same on a multi-shard system: evaluated on shard 0 against the caller's UNPADDED n rows; the jerk pointers must be NULL. */
+int nb_multi_split_force(nb_multi *m, const nb_split_force_request *req);
+/* The shape of an m-point request (no device call): the points of the first batch, its j-chunks, the bodies per chunk and the
+ * points one workgroup takes.  For tests and tools. */
+int nb_split_force_shape(nb_sim *s, uint32_t m, uint32_t *batch, uint32_t *chunks, uint32_t *j_per_chunk, uint32_t *rows_per_workgroup);
 
 #if defined(__GNUC__)
 #pragma GCC visibility pop

@@ -751,6 +751,19 @@ int nb_multi_list_force(nb_multi* m, const nb_list_force_request* req)
     return rc == NB_OK ? rc : mfail(m, rc, s->err);
 }
 
+int nb_multi_split_force(nb_multi* m, const nb_split_force_request* req)
+{
+    if (!m) return mfail(nullptr, NB_ERR_INVALID, "nb_multi_split_force: null handle");
+    if (!req) return mfail(m, NB_ERR_INVALID, "nb_multi_split_force: null request");
+    if (req->struct_size == sizeof(nb_split_force_request) && (req->jerk_irr || req->jerk_reg))
+        return mfail(m, NB_ERR_INVALID, "nb_multi_split_force: jerk_irr and jerk_reg must be NULL (the shards are leapfrog handles)");
+    if (int rc = nb_multi_sync(m)) return rc;      // every shard's gather has landed: shard 0 holds all rows
+    // the caller's rows are the first n of the padded system: the padding rows (zero mass) would add exactly nothing to either sum
+    nb_sim* s = m->shard[0];
+    const int rc = nbi::split_force(s, req, m->n, "nb_multi_split_force");
+    return rc == NB_OK ? rc : mfail(m, rc, s->err);
+}
+
 int nb_multi_download(nb_multi* m, void* bodies, void* vel, void* accel)
 {
     if (!m) return NB_ERR_INVALID;

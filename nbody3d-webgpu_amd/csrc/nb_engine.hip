@@ -1092,7 +1092,7 @@ void nb_destroy(nb_sim* s)
     for (void* p : {s->jerk, s->hx, s->hv, s->fj_part, (void*)s->blk_lev, (void*)s->blk_due, (void*)s->blk_act, (void*)s->blk_hdr}) if (p) (void)hipFree(p);
     if (s->blk_hdr_host) (void)hipHostFree(s->blk_hdr_host);
     if (s->diag) (void)hipFree(s->diag);
-    for (auto* b : {&s->fld_pts, &s->fld_acc, &s->fld_phi, &s->fld_part, &s->nbr_rad, &s->nbr_idx, &s->nbr_d2, &s->nbr_cnt, &s->nbr_inf, &s->nbl_off, &s->nbl_list, &s->knn_work, &s->knn_idx, &s->knn_d2, &s->knn_stat, &s->lf_pvel, &s->lf_jerk})
+    for (auto* b : {&s->fld_pts, &s->fld_acc, &s->fld_phi, &s->fld_part, &s->nbr_rad, &s->nbr_idx, &s->nbr_d2, &s->nbr_cnt, &s->nbr_inf, &s->nbl_off, &s->nbl_list, &s->knn_work, &s->knn_idx, &s->knn_d2, &s->knn_stat, &s->lf_pvel, &s->lf_jerk, &s->split_out})
         if (b->p) (void)hipFree(b->p);
     if (s->zero_row) (void)hipFree(s->zero_row);
     if (s->own_stream && s->stream) (void)hipStreamDestroy(s->stream);
@@ -2391,6 +2391,146 @@ int nb_list_force_shape(nb_sim* s, uint32_t m, uint32_t cap, uint32_t* batch, ui
     if (cap == 0 || cap > kNblMaxCap) return fail(s, NB_ERR_INVALID, "nb_list_force_shape: cap must be in 1 .. 4096");
     if (batch) *batch = lf_batch(s, m, cap);
     if (lanes_per_row) *lanes_per_row = nb::lf_lanes(s->f64);
+    return NB_OK;
+}
+
+/* ---- regular and irregular force+jerk in one pass -------------------------------------------- */
+
+namespace {
+
+// The first batch of an m-point request against `rows` bodies: nbr_shape's rule for nb_split_pk's rows per workgroup, with
+// `planes` partial rows per (point, j-chunk) counted against nb_field_eval's bound of fld_part (the same bytes).  Where the j-chunks
+// field_shape cuts for a batch do not fit, the chunks are made LONGER first (down to what kFieldMaxChunk allows: a workgroup's
+// prologue, epilogue and its rows in nb_split_reduce are paid per chunk, and 2,048 workgroups are wanted, not 2,048-body chunks),
+// and only then is the batch halved (measured: profiles/r15/split_force.md §3).
+void split_shape(const nb_sim* s, uint32_t m, uint32_t rows, uint32_t planes, uint32_t* batch, uint32_t* chunks, uint32_t* per)
+{
+    const uint32_t prow = s->f64 ? nb::kSplitRows64 : nb::kSplitRows;
+    const uint64_t part_rows = std::max<uint64_t>(kFieldPartRows, (uint64_t)2 * field_blocks_wanted(s) * (s->f64 ? nb::kFieldRows64 : nb::kFieldRows)) / planes;
+    auto cut = [&](uint32_t mb) {
+        field_shape(s, ceil_div(mb, prow), chunks, per);
+        const uint64_t room = part_rows / mb;                       // the chunks the bound leaves a batch of mb points
+        if (*chunks > room && room >= std::max(1u, ceil_div(s->n, kFieldMaxChunk))) {
+            *per = ceil_div(ceil_div(s->n, (uint32_t)room), (uint32_t)nb::kTile) * nb::kTile;
+            *chunks = ceil_div(s->n, *per);
+        }
+    };
+    uint32_t mb = std::min(m, s->f64 ? 65536u : 262144u);
+    cut(mb);
+    while ((uint64_t)*chunks * mb > part_rows && mb > prow) {       // fewer points at once: the partial rows stay bounded
+        mb = std::max(prow, (mb / 2 + prow - 1) / prow * prow);
+        cut(mb);
+    }
+    *chunks = std::max(1u, std::min(*chunks, ceil_div(rows, *per)));      // chunks that start past the last row hold nothing
+    *batch = mb;
+}
+
+}  // namespace
+
+extern "C++" int nbi::split_force(nb_sim* s, const nb_split_force_request* req, uint32_t rows, const char* who)
+{
+    const std::string w = std::string(who) + ": ";
+    if (!s) return fail(nullptr, NB_ERR_INVALID, w + "null handle");
+    if (!req) return fail(s, NB_ERR_INVALID, w + "null request");
+    if (req->struct_size != sizeof(nb_split_force_request)) return fail(s, NB_ERR_INVALID, w + "struct_size must be sizeof(nb_split_force_request)");
+    if (req->m == 0) return fail(s, NB_ERR_INVALID, w + "m must be >= 1");
+    if (req->flags & ~(NB_SPLIT_AT_BODIES | NB_SPLIT_DEVICE)) return fail(s, NB_ERR_INVALID, w + "unknown bits in flags");
+    const bool at = (req->flags & NB_SPLIT_AT_BODIES) != 0, dev = (req->flags & NB_SPLIT_DEVICE) != 0;
+    const bool wj = req->jerk_irr || req->jerk_reg;
+    if (!req->accel_irr && !req->accel_reg && !wj) return fail(s, NB_ERR_INVALID, w + "accel_irr, accel_reg, jerk_irr and jerk_reg are all NULL");
+    if (at && req->points) return fail(s, NB_ERR_INVALID, w + "points must be NULL with NB_SPLIT_AT_BODIES");
+    if (at && req->point_vel) return fail(s, NB_ERR_INVALID, w + "point_vel must be NULL with NB_SPLIT_AT_BODIES");
+    if (!at && !req->points) return fail(s, NB_ERR_INVALID, w + "points is NULL (and NB_SPLIT_AT_BODIES is not set)");
+    if (!at && wj && !req->point_vel) return fail(s, NB_ERR_INVALID, w + "point_vel is NULL (the jerk at points needs their velocities)");
+    if (!at && !wj && req->point_vel) return fail(s, NB_ERR_INVALID, w + "point_vel must be NULL when jerk_irr and jerk_reg are NULL");
+    if (at && (uint64_t)req->first_body + req->m > rows) return fail(s, NB_ERR_INVALID, w + "first_body + m exceeds n");
+    if (!(req->radius >= 0.0)) return fail(s, NB_ERR_INVALID, w + "radius must be >= 0 (0: none given)");
+    if (!req->radii && !(req->radius > 0.0)) return fail(s, NB_ERR_INVALID, w + "radii is NULL and radius is not > 0");
+    if (!s->uploaded) return fail(s, NB_ERR_STATE, w + "nothing uploaded yet");
+    if (!s->params_set) return fail(s, NB_ERR_STATE, w + "nb_set_params has not been called (G)");
+    if (wj && !s->hermite) return fail(s, NB_ERR_STATE, w + "jerk_irr / jerk_reg need a Hermite handle (nb_config.integrator = NB_INT_HERMITE4)");
+    NB_HIP(s, hipSetDevice(s->device));
+    if (int rc = finish_gather(s)) return rc;     // other ranks' rows must have landed
+
+    const size_t esz = s->esz, row4 = 4 * esz;
+    const uint32_t m = req->m;
+    const void* bodies = s->bodies[s->cur];
+    const void* vel = wj ? s->vel : nullptr;
+    const char* pts = at ? (const char*)bodies + row4 * req->first_body : (const char*)req->points;
+    const char* pvel = !wj ? nullptr : at ? (const char*)s->vel + row4 * req->first_body : (const char*)req->point_vel;
+    const char* rad = (const char*)req->radii;
+    void* const user[4] = {req->accel_irr, req->accel_reg, req->jerk_irr, req->jerk_reg};
+    char* out[4] = {(char*)user[0], (char*)user[1], (char*)user[2], (char*)user[3]};
+    if (!dev) {      // a host-pointer request is staged whole, as nb_field_eval stages its own: O(m)
+        if (!at) {
+            if (int rc = field_reserve(s, s->fld_pts, row4 * m, who)) return rc;
+            NB_HIP(s, hipMemcpyAsync(s->fld_pts.p, req->points, row4 * m, hipMemcpyHostToDevice, s->stream));
+            pts = (const char*)s->fld_pts.p;
+            if (wj) {
+                if (int rc = field_reserve(s, s->lf_pvel, row4 * m, who)) return rc;
+                NB_HIP(s, hipMemcpyAsync(s->lf_pvel.p, req->point_vel, row4 * m, hipMemcpyHostToDevice, s->stream));
+                pvel = (const char*)s->lf_pvel.p;
+            }
+        }
+        if (rad) {
+            if (int rc = field_reserve(s, s->nbr_rad, esz * m, who)) return rc;
+            NB_HIP(s, hipMemcpyAsync(s->nbr_rad.p, req->radii, esz * m, hipMemcpyHostToDevice, s->stream));
+            rad = (const char*)s->nbr_rad.p;
+        }
+        if (int rc = field_reserve(s, s->split_out, 4 * row4 * m, who)) return rc;
+        for (int p = 0; p < 4; ++p) out[p] = user[p] ? (char*)s->split_out.p + (size_t)p * row4 * m : nullptr;
+    }
+
+    const uint32_t prow = s->f64 ? nb::kSplitRows64 : nb::kSplitRows;      // points per workgroup
+    const void* zero_row = s->zero_row;
+    uint32_t n = rows, planes = wj ? 4u : 2u;
+    double G = s->G, eps2d = s->eps2, rd = req->radius;
+    float eps2f = (float)s->eps2, rf = (float)req->radius;
+    for (uint32_t done = 0; done < m;) {
+        uint32_t mb, chunks, per;
+        split_shape(s, m - done, rows, planes, &mb, &chunks, &per);
+        if (int rc = field_reserve(s, s->fld_part, row4 * planes * chunks * mb, who)) return rc;
+        const void* p = pts + row4 * done;
+        const void* pv = pvel ? pvel + row4 * done : nullptr;
+        const void* r = rad ? rad + esz * done : nullptr;
+        void* part = s->fld_part.p;
+        void* o[4];
+        for (int q = 0; q < 4; ++q) o[q] = out[q] ? out[q] + row4 * done : nullptr;
+        dim3 grid(ceil_div(mb, prow), chunks), block(nb::kBlock);
+        void* rargs[] = {&part, &mb, &chunks, &planes, &G, &o[0], &o[1], &o[2], &o[3]};
+        if (s->f64) {
+            void* args[] = {&bodies, &vel, &p, &pv, &r, &part, &n, &mb, &per, &eps2d, &rd};
+            const void* fn = wj ? (const void*)&nb::nb_split64<double, true> : (const void*)&nb::nb_split64<double, false>;
+            NB_HIP(s, hipLaunchKernel(fn, grid, block, args, 0, s->stream));
+            NB_HIP(s, hipLaunchKernel((const void*)&nb::nb_split_reduce<double, double>, dim3(ceil_div(mb, nb::kBlock)), block, rargs, 0, s->stream));
+        } else {
+            void* args[] = {&bodies, &vel, &p, &pv, &r, &part, &n, &mb, &per, &eps2f, &rf, &zero_row};
+            const void* fn = wj ? (const void*)&nb::nb_split_pk<nb::kSplitNG, true> : (const void*)&nb::nb_split_pk<nb::kSplitNG, false>;
+            NB_HIP(s, hipLaunchKernel(fn, grid, block, args, 0, s->stream));
+            NB_HIP(s, hipLaunchKernel((const void*)&nb::nb_split_reduce<float, float>, dim3(ceil_div(mb, nb::kBlock)), block, rargs, 0, s->stream));
+        }
+        done += mb;
+    }
+    if (!dev) {
+        for (int q = 0; q < 4; ++q)
+            if (user[q]) NB_HIP(s, hipMemcpyAsync(user[q], out[q], row4 * m, hipMemcpyDeviceToHost, s->stream));
+        NB_HIP(s, hipStreamSynchronize(s->stream));
+    }
+    return NB_OK;
+}
+
+int nb_split_force(nb_sim* s, const nb_split_force_request* req) { return nbi::split_force(s, req, s ? s->n : 0u, "nb_split_force"); }
+
+int nb_split_force_shape(nb_sim* s, uint32_t m, uint32_t* batch, uint32_t* chunks, uint32_t* j_per_chunk, uint32_t* rows_per_workgroup)
+{
+    if (!s) return fail(nullptr, NB_ERR_INVALID, "nb_split_force_shape: null handle");
+    if (m == 0) return fail(s, NB_ERR_INVALID, "nb_split_force_shape: m must be >= 1");
+    uint32_t b, c, per;
+    split_shape(s, m, s->n, s->hermite ? 4u : 2u, &b, &c, &per);      // (a Hermite handle: the shape of a request with the jerk pair)
+    if (batch) *batch = b;
+    if (chunks) *chunks = c;
+    if (j_per_chunk) *j_per_chunk = per;
+    if (rows_per_workgroup) *rows_per_workgroup = s->f64 ? nb::kSplitRows64 : nb::kSplitRows;
     return NB_OK;
 }
 

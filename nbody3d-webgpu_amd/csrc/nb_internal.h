@@ -168,6 +168,9 @@ struct nb_sim {
     // nb_list_force: a host-pointer request stages one batch at a time -- its rows in nbl_list, its counts in nbr_cnt, its points in
     // fld_pts, accel / phi in fld_acc / fld_phi (none of those calls overlaps another on the stream); pvel / jerk are its own
     field_buf lf_pvel, lf_jerk;
+    // nb_split_force: shares fld_pts / lf_pvel / nbr_rad (a host-pointer request's points, their velocities, radii) and fld_part (up
+    // to four partial rows per (j-chunk, point of a batch), under the same bound) with the calls above; out stages its four outputs
+    field_buf split_out;
     // NB_INT_HERMITE4: bodies[0] / vel are the state at ONE instant, acc / jerk the derivatives derived from it.  None of the
     // leapfrog launch fields above is used: plain unpadded arrays, no planner, no graphs.
     bool hermite = false;
@@ -207,6 +210,8 @@ int neighbor_lists(nb_sim* s, const nb_neighbor_list_request* req, uint32_t rows
 int knn(nb_sim* s, const nb_knn_request* req, uint32_t rows, const char* who);
 // nb_list_force likewise (nb_multi_list_force: entries >= the caller's unpadded n add nothing)
 int list_force(nb_sim* s, const nb_list_force_request* req, uint32_t rows, const char* who);
+// nb_split_force likewise (nb_multi_split_force: the caller's unpadded rows of shard 0)
+int split_force(nb_sim* s, const nb_split_force_request* req, uint32_t rows, const char* who);
 const std::string& create_error();
 
 // nb_comm.hip: called by nb_step after the integrate kernel when a communicator is attached.

@@ -66,4 +66,5 @@
 #include "kernels/knn.hip.h"         // nb_knn_pk, nb_knn64, nb_knn_merge (nb_knn: the k nearest bodies of every point)
 #include "kernels/list_force.hip.h"  // nb_lf32, nb_lf64 (nb_list_force: acceleration, jerk and potential over neighbour rows)
 #include "kernels/hermite.hip.h"     // nb_fj_pk, nb_fj64, nb_fj_reduce, nb_hermite_predict, nb_hermite_correct (NB_INT_HERMITE4)
+#include "kernels/split_force.hip.h" // nb_split_pk, nb_split64, nb_split_reduce (nb_split_force: regular and irregular force+jerk in one pass)
 #include "kernels/block.hip.h"       // nb_blk_start, nb_blk_sched, nb_blk_predict, nb_blk_fj_pk, nb_blk_fj64, nb_blk_correct (nb_set_block_steps)

@@ -73,6 +73,8 @@ static int (*p_knn)(nb_sim *, const nb_knn_request *);                          
 static int (*p_multi_knn)(nb_multi *, const nb_knn_request *);
 static int (*p_list_force)(nb_sim *, const nb_list_force_request *);                /* forces over neighbour rows, likewise: optional symbols */
 static int (*p_multi_list_force)(nb_multi *, const nb_list_force_request *);
+static int (*p_split_force)(nb_sim *, const nb_split_force_request *);              /* regular + irregular force+jerk in one pass, likewise */
+static int (*p_multi_split_force)(nb_multi *, const nb_split_force_request *);
 static int (*p_eqm_info)(nb_sim *, int *);                              /* the equal-mass kernels' report, also within ABI 2.4: optional symbol */
 static int (*p_eqm_form)(nb_sim *, int *);                              /* which equal-mass form, likewise */
 
@@ -167,6 +169,8 @@ static napi_value js_load(napi_env env, napi_callback_info info)
         *(void **)(&p_multi_knn) = dlsym(h, "nb_multi_knn");
         *(void **)(&p_list_force) = dlsym(h, "nb_list_force");
         *(void **)(&p_multi_list_force) = dlsym(h, "nb_multi_list_force");
+        *(void **)(&p_split_force) = dlsym(h, "nb_split_force");
+        *(void **)(&p_multi_split_force) = dlsym(h, "nb_multi_split_force");
         *(void **)(&p_eqm_info) = dlsym(h, "nb_eqm_info");
         *(void **)(&p_eqm_form) = dlsym(h, "nb_eqm_form");
         g_lib = h;
@@ -911,6 +915,55 @@ static napi_value js_list_force(napi_env env, napi_callback_info info)
     return undefined(env);
 }
 
+/* splitForce(handle, points|null, pointVel|null, firstBody, m, radii|null, radius, accelIrrOut|null, accelRegOut|null, jerkIrrOut|null,
+ * jerkRegOut|null): nb_split_force / nb_multi_split_force.  points / pointVel and the outputs (4*m elements), radii (m elements): typed
+ * arrays of the handle's precision, the outputs written in place.  points null: point k is body firstBody + k (NB_SPLIT_AT_BODIES). */
+static napi_value js_split_force(napi_env env, napi_callback_info info)
+{
+    size_t argc = 11; napi_value argv[11];
+    CHECK_NAPI(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    if (argc < 11) { napi_throw_type_error(env, NULL, "splitForce(handle, points|null, pointVel|null, firstBody, m, radii|null, radius, accelIrrOut|null, accelRegOut|null, jerkIrrOut|null, jerkRegOut|null)"); return NULL; }
+    handle_t *h = get_handle(env, argv[0]); if (!h) return NULL;
+    if (!p_split_force || !p_multi_split_force) return throw_msg(env, NB_ERR_STATE, "the loaded library has no nb_split_force", "nb_split_force");
+    const napi_typedarray_type real = h->f64 ? napi_float64_array : napi_float32_array;
+    void *ptr[7] = {NULL, NULL, NULL, NULL, NULL, NULL, NULL}; size_t len[7] = {0, 0, 0, 0, 0, 0, 0};
+    static const int arg_of[7] = {1, 2, 5, 7, 8, 9, 10};
+    static const char *const what[7] = {"points", "pointVel", "radii", "accelIrrOut", "accelRegOut", "jerkIrrOut", "jerkRegOut"};
+    for (int k = 0; k < 7; ++k) {
+        napi_valuetype vt; napi_typeof(env, argv[arg_of[k]], &vt);
+        if (vt == napi_null || vt == napi_undefined) continue;
+        bool is_ta = false; napi_is_typedarray(env, argv[arg_of[k]], &is_ta);
+        napi_typedarray_type tt; napi_value ab; size_t off;
+        if (!is_ta || napi_get_typedarray_info(env, argv[arg_of[k]], &tt, &len[k], &ptr[k], &ab, &off) != napi_ok || tt != real) {
+            char buf[160]; snprintf(buf, sizeof buf, "splitForce: %s must be a %s or null", what[k], h->f64 ? "Float64Array" : "Float32Array");
+            napi_throw_type_error(env, NULL, buf); return NULL;
+        }
+    }
+    double first = 0, count = 0, radius = 0;
+    napi_get_value_double(env, argv[3], &first); napi_get_value_double(env, argv[4], &count); napi_get_value_double(env, argv[6], &radius);
+    if (!(first >= 0 && first <= 4294967295.0) || !(count >= 0 && count <= 4294967295.0)) { napi_throw_range_error(env, NULL, "splitForce: firstBody / m out of range"); return NULL; }
+    nb_split_force_request req;
+    memset(&req, 0, sizeof req);
+    req.struct_size = sizeof req;
+    req.m = (uint32_t)count;
+    const size_t m = req.m;
+    if ((ptr[0] && len[0] != 4 * m) || (ptr[1] && len[1] != 4 * m) || (ptr[2] && len[2] != m) || (ptr[3] && len[3] != 4 * m) ||
+        (ptr[4] && len[4] != 4 * m) || (ptr[5] && len[5] != 4 * m) || (ptr[6] && len[6] != 4 * m)) {
+        napi_throw_range_error(env, NULL, "splitForce: points, pointVel and the outputs must hold 4*m elements, radii m"); return NULL;
+    }
+    if (!ptr[0]) { req.flags = NB_SPLIT_AT_BODIES; req.first_body = (uint32_t)first; }
+    req.points = ptr[0]; req.point_vel = ptr[1]; req.radii = ptr[2]; req.radius = radius;
+    req.accel_irr = ptr[3]; req.accel_reg = ptr[4]; req.jerk_irr = ptr[5]; req.jerk_reg = ptr[6];
+    if (h->multi) {
+        int rcm = p_multi_split_force(h->multi, &req);
+        if (rcm != NB_OK) return throw_msg(env, rcm, p_multi_last_error(h->multi), "nb_multi_split_force");
+    } else {
+        int rc = p_split_force(h->sim, &req);
+        if (rc != NB_OK) return throw_nb(env, rc, h->sim, "nb_split_force");
+    }
+    return undefined(env);
+}
+
 /* downloadJerk(handle, jerkOut): nb_download_jerk -- 4*n elements (jx, jy, jz, 0) of a Hermite handle, written in place. */
 static napi_value js_download_jerk(napi_env env, napi_callback_info info)
 {
@@ -1053,7 +1106,7 @@ static napi_value init_module(napi_env env, napi_value exports)
         {"fieldEval", js_field_eval}, {"downloadJerk", js_download_jerk}, {"uploadDerivs", js_upload_derivs},
         {"setBlockSteps", js_set_block_steps}, {"blockStats", js_block_stats}, {"downloadLevels", js_download_levels},
         {"uploadLevels", js_upload_levels}, {"neighbors", js_neighbors}, {"neighborLists", js_neighbor_lists},
-        {"knn", js_knn}, {"listForce", js_list_force},
+        {"knn", js_knn}, {"listForce", js_list_force}, {"splitForce", js_split_force},
     };
     for (size_t i = 0; i < sizeof fns / sizeof fns[0]; ++i) {
         napi_value f;

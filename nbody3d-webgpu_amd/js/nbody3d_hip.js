@@ -440,6 +440,37 @@ class Simulation {
     return out;
   }
 
+  /** The regular and the irregular force+jerk of every point in ONE pass (nb_split_force; no reference analogue): at `points` (4*m
+   *  elements x, y, z, ignored) -- or, with options.bodies = [first, m], at those bodies -- the acceleration of ALL bodies, every
+   *  pair's term added to exactly one of two sums: *Irr over the bodies with d2 < h^2 (options.radius, or one of options.radii per
+   *  point; the strict rule of neighbors()), *Reg over every other row.  Nothing is subtracted.  options.jerk (default: true on a
+   *  'hermite4' simulation, which it needs) adds the two jerk sums and wants, at points, options.pointVel.  Returns {accelIrr,
+   *  accelReg, jerkIrr, jerkReg}: 4*m elements each, the jerks null when not asked for.  The simulation state is not touched. */
+  splitForce(points, options) {
+    this._need();
+    const o = options || {}, T = this.ArrayType;
+    const real = function (a, name) {
+      if (a === null || a === undefined) return null;
+      if (a instanceof T) return a;
+      if (typeof a.length === 'number') return T.from(a);
+      throw new TypeError(name + ': expected ' + T.name);
+    };
+    const pts = real(points, 'points'), pv = real(o.pointVel, 'pointVel'), radii = real(o.radii, 'radii');
+    let first = 0, m = 0;
+    if (pts) {
+      if (pts.length % 4 !== 0) throw new RangeError('points must hold 4*m elements (x, y, z, ignored)');
+      if (o.bodies) throw new RangeError('splitForce(): give either points or options.bodies, not both');
+      m = pts.length / 4;
+    } else if (o.bodies) { first = o.bodies[0] >>> 0; m = o.bodies[1] >>> 0; }
+    else throw new TypeError('splitForce(): points, or options.bodies = [first, count], required');
+    const jerk = o.jerk === undefined || o.jerk === null ? this.integrator !== 'leapfrog' : !!o.jerk;
+    const radius = o.radius === undefined || o.radius === null ? 0 : +o.radius;
+    const out = { accelIrr: new T(4 * m), accelReg: new T(4 * m), jerkIrr: jerk ? new T(4 * m) : null, jerkReg: jerk ? new T(4 * m) : null };
+    addon.setParams(this._h, this.dt, this.G);   // the sums carry G
+    addon.splitForce(this._h, pts, pv, first, m, radii, radius, out.accelIrr, out.accelReg, out.jerkIrr, out.jerkReg);
+    return out;
+  }
+
   /** The Casertano-Hut local density at every body, a Float64Array of nBodies elements: one knn() call over all bodies, then per
    *  body the masses of its first k - 1 neighbours over the volume of the sphere that reaches the k-th (k >= 2, default 6); NaN
    *  where a body has fewer than k neighbours. */

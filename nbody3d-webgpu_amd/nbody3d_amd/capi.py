@@ -110,6 +110,15 @@ class nb_list_force_request(C.Structure):   # include/nbody3d_hip.h (forces over
 
 NB_LISTF_AT_BODIES, NB_LISTF_DEVICE = 1, 4
 
+
+class nb_split_force_request(C.Structure):  # include/nbody3d_hip.h (regular and irregular force+jerk in one pass, added within ABI 2.4)
+    _fields_ = [("struct_size", C.c_uint32), ("m", C.c_uint32), ("flags", C.c_uint32), ("first_body", C.c_uint32),
+                ("points", C.c_void_p), ("point_vel", C.c_void_p), ("radii", C.c_void_p), ("radius", C.c_double),
+                ("accel_irr", C.c_void_p), ("accel_reg", C.c_void_p), ("jerk_irr", C.c_void_p), ("jerk_reg", C.c_void_p)]
+
+
+NB_SPLIT_AT_BODIES, NB_SPLIT_DEVICE = 1, 4
+
 NB_BLOCK_FROZEN = 1
 
 
@@ -141,7 +150,8 @@ SYMBOLS = ["nb_abi_version", "nb_device_count", "nb_create", "nb_destroy", "nb_u
            "nb_neighbors", "nb_multi_neighbors", "nb_neighbors_shape", "nb_eqm_info", "nb_eqm_form",
            "nb_neighbor_lists", "nb_multi_neighbor_lists", "nb_neighbor_lists_shape",
            "nb_knn", "nb_multi_knn", "nb_knn_shape",
-           "nb_list_force", "nb_multi_list_force", "nb_list_force_shape"]
+           "nb_list_force", "nb_multi_list_force", "nb_list_force_shape",
+           "nb_split_force", "nb_multi_split_force", "nb_split_force_shape"]
 
 _lib = None
 
@@ -237,6 +247,10 @@ def load_library():
         L.nb_list_force.argtypes = [vp, C.POINTER(nb_list_force_request)]
         L.nb_multi_list_force.argtypes = [vp, C.POINTER(nb_list_force_request)]
         L.nb_list_force_shape.argtypes = [vp, C.c_uint32, C.c_uint32] + [C.POINTER(C.c_uint32)] * 2
+    if hasattr(L, "nb_split_force"):        # regular and irregular force+jerk in one pass, also within 2.4 and detected by the symbol
+        L.nb_split_force.argtypes = [vp, C.POINTER(nb_split_force_request)]
+        L.nb_multi_split_force.argtypes = [vp, C.POINTER(nb_split_force_request)]
+        L.nb_split_force_shape.argtypes = [vp, C.c_uint32] + [C.POINTER(C.c_uint32)] * 4
     if hasattr(L, "nb_eqm_info"):           # the equal-mass kernels' report, also within 2.4 and detected by the symbol
         L.nb_eqm_info.argtypes = [vp, C.POINTER(C.c_int)]
     if hasattr(L, "nb_eqm_form"):           # which of the equal-mass forms, likewise
@@ -468,6 +482,54 @@ def _list_force_request(dtype, lists, bodies, points, point_vel, count, accel, j
     req.jerk = _ptr(j) if jerk and m else None
     req.phi = _ptr(f) if phi and m else None
     return req, (lists, pts, pv, cnt), a, j, f
+
+
+def _need_split_force(what):
+    if not hasattr(load_library(), "nb_split_force"):
+        raise NBodyError(1, "%s: the loaded library has no nb_split_force" % what)
+
+
+SPLIT_OUTPUTS = ("accel_irr", "accel_reg", "jerk_irr", "jerk_reg")
+
+
+def _split_force_request(dtype, points, bodies, point_vel, radius, radii, jerk):
+    """The nb_split_force_request of split_force(): (request, arrays kept alive, {output name: (m, 4) array})."""
+    _need_split_force("split_force()")
+    req = nb_split_force_request()
+    req.struct_size = C.sizeof(nb_split_force_request)
+    pts = pv = rad = None
+    m = None
+    # (both or neither of points / bodies, point_vel without a jerk, no radius at all: passed on as they are -- the engine's
+    # NB_ERR_INVALID names the field)
+    if bodies is not None:
+        first, m = int(bodies[0]), int(bodies[1])
+        if not (0 <= first < 2 ** 32 and 0 <= m < 2 ** 32):
+            raise ValueError("split_force(): bodies=(first, count) out of range")
+        req.flags |= NB_SPLIT_AT_BODIES
+        req.first_body = first
+    if points is not None:
+        pts = _rows4(points, dtype, "points")
+        m = len(pts) if m is None else m
+        req.points = _ptr(pts) if len(pts) else None
+    if m is None:
+        raise ValueError("split_force(): give points or bodies=(first, count)")
+    if point_vel is not None:
+        pv = _rows4(point_vel, dtype, "point_vel")
+        if len(pv) != m:
+            raise ValueError("split_force(): point_vel must hold one velocity per point")
+        req.point_vel = _ptr(pv) if m else None
+    if radii is not None:
+        rad = np.ascontiguousarray(radii, dtype=dtype).reshape(-1)
+        if len(rad) != m:
+            raise ValueError("split_force(): radii must hold one radius per point")
+        req.radii = _ptr(rad) if m else None
+    req.radius = 0.0 if radius is None else float(radius)
+    req.m = m
+    out = {}
+    for name in SPLIT_OUTPUTS[:4 if jerk else 2]:
+        out[name] = np.zeros((m, 4), dtype)
+        setattr(req, name, _ptr(out[name]) if m else None)
+    return req, (pts, pv, rad), out
 
 
 def _need_knn(what):
@@ -1182,6 +1244,49 @@ class Simulation:
         host = lambda t: None if t is None else t.cpu().numpy()
         return host(a), host(j), host(f), cnt.cpu().numpy().view(np.uint32)
 
+    def split_force(self, points=None, *, bodies=None, point_vel=None, radius=None, radii=None, jerk=None):
+        """nb_split_force: the acceleration (and, on Hermite handles, the jerk) of ALL bodies at ``points`` ((m, 3) or (m, 4)) -- or,
+        with ``bodies=(first, m)``, at those bodies --, every pair's term added to exactly one of two sums: ``*_irr`` over the bodies
+        with d2 < h^2 (``radius``, or one of ``radii`` per point; nb_neighbors' strict rule), ``*_reg`` over every other row.  One
+        pass, nothing subtracted.  ``jerk`` defaults to what the handle can give (Hermite handles: True) and needs, at points,
+        ``point_vel``.  Returns a dict of (m, 4) arrays: accel_irr, accel_reg[, jerk_irr, jerk_reg]."""
+        jerk = (self.integrator != "leapfrog") if jerk is None else bool(jerk)
+        req, keep, out = _split_force_request(self.dtype, points, bodies, point_vel, radius, radii, jerk)
+        self._check(self._L.nb_split_force(self._h, C.byref(req)))
+        return out
+
+    def split_force_device(self, m, *, bodies=None, points_ptr=None, point_vel_ptr=None, radius=None, radii_ptr=None,
+                           accel_irr_ptr=None, accel_reg_ptr=None, jerk_irr_ptr=None, jerk_reg_ptr=None):
+        """The device-pointer form (NB_SPLIT_DEVICE): device addresses on the handle's device (0 or None for what is not wanted), the
+        outputs as split_force() returns them.  Read and written in place, enqueued on the handle's stream, returns without
+        waiting.  ``bodies=(first, count)`` selects the bodies themselves (``points_ptr`` must then be None, ``m`` is ignored)."""
+        _need_split_force("split_force_device()")
+        req = nb_split_force_request()
+        req.struct_size = C.sizeof(nb_split_force_request)
+        req.flags = NB_SPLIT_DEVICE
+        if bodies is not None:
+            req.flags |= NB_SPLIT_AT_BODIES
+            req.first_body, req.m = int(bodies[0]), int(bodies[1])
+        else:
+            req.m = int(m)
+        req.points = points_ptr or None
+        req.point_vel = point_vel_ptr or None
+        req.radii = radii_ptr or None
+        req.radius = 0.0 if radius is None else float(radius)
+        req.accel_irr = accel_irr_ptr or None
+        req.accel_reg = accel_reg_ptr or None
+        req.jerk_irr = jerk_irr_ptr or None
+        req.jerk_reg = jerk_reg_ptr or None
+        self._check(self._L.nb_split_force(self._h, C.byref(req)))
+
+    def split_force_shape(self, m):
+        """{batch, chunks, j_per_chunk, rows_per_workgroup}: the launch shape nb_split_force gives an m-point request (on a Hermite
+        handle: one with the jerk pair)."""
+        _need_split_force("split_force_shape()")
+        v = [C.c_uint32() for _ in range(4)]
+        self._check(self._L.nb_split_force_shape(self._h, int(m), *[C.byref(x) for x in v]))
+        return dict(zip(("batch", "chunks", "j_per_chunk", "rows_per_workgroup"), (x.value for x in v)))
+
     def knn(self, points=None, *, bodies=None, k=6, dist2=True):
         """nb_knn: the ``k`` nearest bodies (1 <= k <= 64) of each of ``points`` ((m, 3) or (m, 4); the fourth column is ignored) --
         or, with ``bodies=(first, count)``, of each of those bodies, itself left out by index.  Returns ``(index (m, k) uint32,
@@ -1412,6 +1517,13 @@ class MultiSimulation:
         req, keep, a, j, f = _list_force_request(self.dtype, lists, bodies, points, point_vel, count, accel, jerk, phi)
         self._check(self._L.nb_multi_list_force(self._h, C.byref(req)))
         return a, j, f
+
+    def split_force(self, points=None, *, bodies=None, point_vel=None, radius=None, radii=None, jerk=False):
+        """nb_multi_split_force: Simulation.split_force() on the whole system (evaluated on shard 0 against the caller's unpadded
+        rows); ``jerk`` is refused (NB_ERR_INVALID): the shards are leapfrog handles."""
+        req, keep, out = _split_force_request(self.dtype, points, bodies, point_vel, radius, radii, jerk)
+        self._check(self._L.nb_multi_split_force(self._h, C.byref(req)))
+        return out
 
     def knn(self, points=None, *, bodies=None, k=6, dist2=True):
         """nb_multi_knn: Simulation.knn() on the whole system (evaluated on shard 0 against the caller's unpadded rows: a padding
