@@ -63,7 +63,9 @@ extern "C" {
                              2.4 (round 14) likewise within 2.4: nb_list_force, nb_multi_list_force, nb_list_force_shape,
                                             nb_list_force_request.  Detected by the presence of the symbol nb_list_force
                              2.4 (round 15) likewise within 2.4: nb_split_force, nb_multi_split_force, nb_split_force_shape,
-                                            nb_split_force_request, NB_SPLIT_*.  Detected by the presence of the symbol nb_split_force */
+                                            nb_split_force_request, NB_SPLIT_*.  Detected by the presence of the symbol nb_split_force
+                             2.4 (round 16) likewise within 2.4: nb_set_neighbor_scheme, nb_neighbor_scheme_stats, nb_download_neighbor_scheme,
+                                            nb_neighbor_scheme.  Detected by the presence of the symbol nb_set_neighbor_scheme */
 
 typedef struct nb_sim nb_sim; /* opaque */
 
@@ -876,6 +878,96 @@ int nb_multi_split_force(nb_multi *m, const nb_split_force_request *req);
 /* The shape of an m-point request (no device call): the points of the first batch, its j-chunks, the bodies per chunk and the
  * points one workgroup takes.  For tests and tools. */
 int nb_split_force_shape(nb_sim *s, uint32_t m, uint32_t *batch, uint32_t *chunks, uint32_t *j_per_chunk, uint32_t *rows_per_workgroup);
+
+/* ---- Ahmad-Cohen neighbour scheme with two shared step levels (added within ABI 2.4; no reference analogue) ----
+ * A collisional system on a Hermite handle otherwise puts every body on the step its closest encounters need.  With the scheme
+ * (Ahmad & Cohen 1973) a body's force is kept as two parts: the IRREGULAR part over the bodies inside its neighbour radius, which
+ * changes fast and is re-evaluated every hs = dt / N_sub, and the REGULAR part over every other row, which is evaluated once per dt
+ * and extrapolated in between.  Only the list sums -- the entries of the lists, not N x N pairs -- run at the fine step.  Both step
+ * levels are shared by all bodies, the radius is fixed (a scalar, or one per body), a list that does not fit its row is a reported
+ * error.  Hermite handles only.
+ *   - Quantities: per body x, v at one instant; the irregular derivatives (ai, ji) over the body's list; the regular derivatives
+ *     (ar0, jr0) over every other row, valid at the last regular time t0; the body's row of the list L, of `cap` entries, with its
+ *     true count.  Membership is nb_neighbors' rule letter for letter: d2 = fma(dz, dz, fma(dy, dy, dx * dx)) < h * h, strictly, in
+ *     the handle's precision, no softening, the own row left out by index.
+ *   - Start.  Runs when the scheme's state is not current: after nb_set_neighbor_scheme and after everything that stales a Hermite
+ *     handle's derivatives (nb_upload, nb_upload_derivs, nb_device_ptr(NB_BODIES / NB_VEL), a changed G), and after a changed dt
+ *     (so that a handle whose dt changes continues exactly as a fresh handle given its (x, v) would), at the next nb_step,
+ *     nb_download (accel), nb_download_jerk, nb_device_ptr(NB_ACCEL / NB_JERK) or nb_download_neighbor_scheme.  On (x, v) as they
+ *     stand: (ai, ji, ar0, jr0) = the four outputs of nb_split_force at the bodies; L and count = nb_neighbor_lists at the bodies
+ *     with the same radius or radii.  Both bit for bit what the public calls return.
+ *   - Substeps.  One regular step runs s = 0 .. N_sub - 1 with tau = s hs; all polynomial arithmetic is fp64 on the stored values,
+ *     each stored value rounded once to the handle's precision, with the expressions of the shared step's predictor and corrector:
+ *       1. a = ai + (ar0 + tau jr0), j = ji + jr0;
+ *       2. (xp, vp) = the Hermite predictor over hs from (x, v, a, j), for ALL bodies;
+ *       3. (ai1, ji1) = the sums of nb_list_force over the body's row of L at the predicted state: points (xp_i, vp_i), entries
+ *          gathered from (xp, vp), with its rules (entry e to lane e mod LS, a lane adds in ascending e, the lane sums combined in
+ *          the fixed fp64 tree, G multiplied in once, invalid and own entries load row 0 with mass 0);
+ *       4. a1 = ai1 + (ar0 + (tau + hs) jr0), j1 = ji1 + jr0;
+ *       5. (x, v) <- the Hermite corrector over hs with (a, j, a1, j1);
+ *       6. (ai, ji) <- (ai1, ji1).
+ *   - Regular time, after the last substep, on the arrived state (x, v):
+ *       1. (aio, jio) = the list sums over the OLD list at (x, v);
+ *       2. (ai', ji', ar', jr') = nb_split_force at the bodies;
+ *       3. L', count' = nb_neighbor_lists at the bodies (the same state as 2: the same membership);
+ *       4. aro = (ar' + ai') - aio, jro = (jr' + ji') - jio, in fp64: the regular force with respect to the old list;
+ *       5. v += dt/2 (aro - ar0) - dt^2/12 (5 jr0 + jro);
+ *       6. x += dt^2/6 (aro - ar0) - dt^3/24 (3 jr0 + jro);
+ *       7. (ai, ji, ar0, jr0, L, count) <- the primed values.
+ *     5 and 6 are the difference between the Hermite corrector and the Hermite predictor over dt: with every row empty a regular step
+ *     is a plain Hermite step of dt in exact arithmetic, with every row holding every other body the substeps are Hermite steps of hs.
+ *   - Overflow.  If some count' > cap at a regular time, the state at that time is complete and is kept and steps_done counts the
+ *     step, but the next interval would have no consistent list: nb_step returns NB_ERR_STATE (the message names the number of
+ *     overflowed rows, the largest count and cap), and so does every later nb_step until nb_set_neighbor_scheme is called again --
+ *     a larger cap, a smaller radius or NULL all clear it.  An overflow at the start fails the triggering call with the state
+ *     untouched (and every later one, until the scheme is set again or the state changes).
+ *   - HOST SYNCHRONISATION.  nb_step with the scheme on synchronises with the device ONCE PER REGULAR STEP: the host reads a small
+ *     header (overflowed rows, largest count, entries) from pinned memory.  Such a step cannot be captured into a caller's graph;
+ *     ext_stream keeps working otherwise.
+ *   - nb_step(k) equals k x nb_step(1) bit for bit, and two handles give the same bits.  dt may change between steps: the first
+ *     prediction of a regular step is made at its start, never at the end of the previous one, and the step after a change runs
+ *     the start first (the components a regular time leaves were evaluated in front of its correction 5-6; the start's belong to
+ *     the corrected state).  dt <= 0 is a no-op.
+ *   - nb_download's accel and nb_download_jerk return ai + ar0 and ji + jr0, summed in fp64 and rounded once.  Every query reads the
+ *     state at the regular time (nb_field_eval, nb_neighbors, nb_neighbor_lists, nb_knn, nb_list_force, nb_split_force,
+ *     nb_diagnostics, frames).  nb_force_pass is unchanged.  nb_enable_timing / nb_step_times2 report one regular step per launch:
+ *     force_ms is its span, integrate_ms = 0 (as for block handles).
+ *   - NO bit-exact checkpoint: a restore through nb_upload (+ nb_upload_derivs) re-runs the start -- the uploaded totals are replaced
+ *     by the start's components -- and continues within the scheme's accuracy, NOT bit-identically: the components a running handle
+ *     carries (the irregular sums come from the list kernel's order of additions, the start's from nb_split_force's) are not part
+ *     of any download that can be uploaded again.
+ *   - Switching the scheme off (NULL) leaves a plain Hermite handle whose derivatives are re-evaluated at the next step.
+ *   - Errors.  Leapfrog handle: NB_ERR_STATE.  Block steps and the scheme exclude each other: switching either on while the other is
+ *     on is NB_ERR_STATE, the message naming both.  NULL handle, wrong struct_size, substeps not a power of two or > 1024,
+ *     cap > 4096, flags != 0, radius <= 0 or NaN without radii, a negative or non-finite radii element: NB_ERR_INVALID, checked
+ *     before any device call; the message names the function and the field.
+ *   - Memory: allocated by nb_set_neighbor_scheme, released by NULL or nb_destroy -- the four component arrays, a second predicted
+ *     pair, the list (n x cap x 4 bytes), the counts, a copy of radii, the pinned header.  nb_multi has no counterpart. */
+typedef struct nb_neighbor_scheme {
+    uint32_t struct_size;  /* sizeof(nb_neighbor_scheme) */
+    uint32_t substeps;     /* N_sub: a power of two, 1 .. 1024; 0 -> 8 */
+    uint32_t cap;          /* entries per row, 1 .. 4096; 0 -> 128 */
+    uint32_t flags;        /* none defined: must be 0 */
+    double   radius;       /* used when radii == NULL; must then be > 0 */
+    const void *radii;     /* optional: n elements of the handle's precision, >= 0, finite; COPIED by the call */
+} nb_neighbor_scheme;      /* 32 bytes */
+int nb_set_neighbor_scheme(nb_sim *s, const nb_neighbor_scheme *cfg /* NULL: back to plain Hermite steps */);
+
+/* (a struct TAG without a typedef, as nb_block_stats) */
+struct nb_neighbor_scheme_stats {
+    uint32_t struct_size, enabled;
+    uint64_t regular_steps, substeps, entries;   /* entries = sum of min(count, cap) over the list builds (start included) */
+    uint64_t builds;
+    uint32_t max_count, overflowed;              /* of the LAST build */
+};                                               /* 48 bytes */
+/* The counters since the scheme was set or last reset (set out->struct_size).  A Hermite handle without the scheme reports
+ * enabled = 0 and zeros. */
+int nb_neighbor_scheme_stats(nb_sim *s, struct nb_neighbor_scheme_stats *out, int reset);
+
+/* The scheme's own arrays at the handle's instant (runs the start first if they are not current); any pointer may be NULL.  Blocks.
+ * NB_ERR_STATE on a handle without the scheme. */
+int nb_download_neighbor_scheme(nb_sim *s, void *accel_irr, void *jerk_irr, void *accel_reg, void *jerk_reg,
+                                uint32_t *list /* n * cap */, uint32_t *count /* n */);
 
 #if defined(__GNUC__)
 #pragma GCC visibility pop

@@ -569,6 +569,18 @@ int get_events(nb_sim* s, nb_events* out)
     return 0;
 }
 
+// Releases what nb_set_neighbor_scheme allocated, switches the scheme off and zeroes its counters.
+void ac_release(nb_sim* s)
+{
+    for (void** p : {&s->ac_ai, &s->ac_ji, &s->ac_ar, &s->ac_jr, &s->ac_px, &s->ac_pv, &s->ac_radii, (void**)&s->ac_list, (void**)&s->ac_count, (void**)&s->ac_hdr})
+        if (*p) { (void)hipFree(*p); *p = nullptr; }
+    if (s->ac_hdr_host) { (void)hipHostFree(s->ac_hdr_host); s->ac_hdr_host = nullptr; }
+    s->ac = s->ac_ok = s->ac_over = false;
+    s->ac_msg.clear();
+    s->ac_regular = s->ac_substeps = s->ac_entries = s->ac_builds = 0;
+    s->ac_max_count = s->ac_overflowed = 0;
+}
+
 void free_frames(nb_sim* s)
 {
     for (auto& f : s->frame) {
@@ -623,9 +635,13 @@ void launch_fj(nb_sim* s, const void* pos, const void* vel, void* acc_out, void*
     }
 }
 
-// Makes acc / jerk the derivatives of (bodies, vel) for the G in force (a no-op while they are current).
+int ensure_scheme(nb_sim* s, const char* who);
+
+// Makes acc / jerk the derivatives of (bodies, vel) for the G in force (a no-op while they are current).  With the neighbour scheme
+// on they are the scheme's totals and come from its start.
 int ensure_derivs(nb_sim* s, const char* who)
 {
+    if (s->ac) return ensure_scheme(s, who);
     if (!s->params_set) return fail(s, NB_ERR_STATE, std::string(who) + ": nb_set_params has not been called (G)");
     if (s->derivs_ok && s->derivs_any_G) { s->derivs_any_G = false; s->derivs_G = s->G; }
     if (s->derivs_ok && s->derivs_G == s->G) return NB_OK;
@@ -765,6 +781,125 @@ int block_step(nb_sim* s, uint32_t nsteps)
         NB_HIP(s, hipGetLastError());
         ++s->blk_outer;
         ++s->steps_done;
+    }
+    return NB_OK;
+}
+
+// ---- the Ahmad-Cohen neighbour scheme (nb_set_neighbor_scheme; kernels/ac_scheme.hip.h) ----------
+// One list build at the bodies: nb_split_force's four outputs into (ai, ji, ar, jr) and nb_neighbor_lists' rows and counts into
+// ac_list / ac_count, both through the engine's own entry points with device pointers, on the handle's stream.
+int ac_build(nb_sim* s, void* ai, void* ji, void* ar, void* jr, const char* who)
+{
+    nb_split_force_request sq;
+    memset(&sq, 0, sizeof sq);
+    sq.struct_size = sizeof sq; sq.m = s->n; sq.flags = NB_SPLIT_AT_BODIES | NB_SPLIT_DEVICE;
+    sq.radii = s->ac_radii; sq.radius = s->ac_radii ? 0.0 : s->ac_radius;
+    sq.accel_irr = ai; sq.jerk_irr = ji; sq.accel_reg = ar; sq.jerk_reg = jr;
+    if (int rc = nbi::split_force(s, &sq, s->n, who)) return rc;
+    nb_neighbor_list_request lq;
+    memset(&lq, 0, sizeof lq);
+    lq.struct_size = sizeof lq; lq.m = s->n; lq.flags = NB_NBR_AT_BODIES | NB_NBR_DEVICE;
+    lq.radii = s->ac_radii; lq.radius = s->ac_radii ? 0.0 : s->ac_radius;
+    lq.cap = s->ac_cap; lq.list = s->ac_list; lq.count = s->ac_count;
+    if (int rc = nbi::neighbor_lists(s, &lq, s->n, who)) return rc;
+    NB_HIP(s, hipMemsetAsync(s->ac_hdr, 0, sizeof(unsigned long long) * nb::kAcHdrWords, s->stream));
+    return NB_OK;
+}
+
+// HOST SYNCHRONISATION: the header of a build (rows over cap, largest count, entries) is read here, after one wait for the stream.
+// Returns true when some row holds more than cap members; *msg then names the numbers.
+int ac_read_header(nb_sim* s, bool* over, std::string* msg)
+{
+    NB_HIP(s, hipMemcpyAsync(s->ac_hdr_host, s->ac_hdr, sizeof(unsigned long long) * nb::kAcHdrWords, hipMemcpyDeviceToHost, s->stream));
+    NB_HIP(s, hipStreamSynchronize(s->stream));
+    const unsigned long long rows = s->ac_hdr_host[nb::kAcOver], mx = s->ac_hdr_host[nb::kAcMax];
+    ++s->ac_builds;
+    s->ac_entries += s->ac_hdr_host[nb::kAcEntries];
+    s->ac_max_count = (uint32_t)mx;
+    s->ac_overflowed = (uint32_t)rows;
+    *over = rows != 0;
+    if (*over) *msg = "neighbour list overflow: " + std::to_string(rows) + " rows hold more than cap members (largest count " + std::to_string(mx) + ", cap " + std::to_string(s->ac_cap) + "); call nb_set_neighbor_scheme with a larger cap or a smaller radius";
+    return NB_OK;
+}
+
+// The start: makes the scheme's arrays current for (bodies, vel) and the G in force (a no-op while they are).
+int ensure_scheme(nb_sim* s, const char* who)
+{
+    if (!s->params_set) return fail(s, NB_ERR_STATE, std::string(who) + ": nb_set_params has not been called (G)");
+    if (s->ac_ok && s->derivs_ok && s->derivs_any_G) { s->derivs_any_G = false; s->derivs_G = s->G; }      // (never set while the scheme is on)
+    if (s->ac_ok && s->derivs_ok && s->derivs_G == s->G) return NB_OK;
+    s->ac_ok = false; s->derivs_ok = false;
+    if (int rc = ac_build(s, s->ac_ai, s->ac_ji, s->ac_ar, s->ac_jr, who)) return rc;
+    uint32_t n = s->n, cap = s->ac_cap;
+    void* args[] = {&s->ac_ai, &s->ac_ji, &s->ac_ar, &s->ac_jr, &s->acc, &s->jerk, &s->ac_count, &s->ac_hdr, &n, &cap};
+    const void* fn = s->f64 ? (const void*)&nb::nb_ac_start<double> : (const void*)&nb::nb_ac_start<float>;
+    NB_HIP(s, hipLaunchKernel(fn, dim3(ceil_div(n, nb::kBlock)), dim3(nb::kBlock), args, 0, s->stream));
+    bool over = false;
+    std::string msg;
+    if (int rc = ac_read_header(s, &over, &msg)) return rc;
+    if (over) return fail(s, NB_ERR_STATE, std::string(who) + ": " + msg);      // the state is untouched; every later call starts again
+    s->ac_ok = true; s->ac_over = false;
+    s->derivs_ok = true; s->derivs_any_G = false; s->derivs_G = s->G;
+    return NB_OK;
+}
+
+// nb_step of a handle with the neighbour scheme: nsteps regular steps of dt.  Per regular step: the first prediction, N_sub substep
+// launches, the sums over the old list, the split pass and the list build at the arrived state, the regular correction, and ONE
+// host wait for the header of the build.  Timed steps record e[0] .. e[1] around the regular step (as block steps).
+int ac_step(nb_sim* s, uint32_t nsteps)
+{
+    if (s->ac_over) return fail(s, NB_ERR_STATE, "nb_step: " + s->ac_msg);
+    if (int rc = ensure_scheme(s, "nb_step")) return rc;
+    uint32_t n = s->n, cap = s->ac_cap;
+    const uint32_t nsub = s->ac_nsub;
+    double dt = s->dt, hs = s->dt / (double)nsub, G = s->G, eps2d = s->eps2;
+    float eps2f = (float)s->eps2;
+    void *x = s->bodies[0], *v = s->vel;
+    void* P[2][2] = {{s->hx, s->hv}, {s->ac_px, s->ac_pv}};
+    const dim3 rows_grid(ceil_div(n, nb::kBlock)), sub_grid(ceil_div(n, nb::lf_rows(s->f64))), block(nb::kBlock);
+    for (uint32_t k = 0; k < nsteps; ++k) {
+        nb_events ev;
+        const bool rec = s->timing && get_events(s, &ev) == 0;
+        if (rec) NB_HIP(s, hipEventRecord(ev.e[0], s->stream));
+        {
+            void* args[] = {&x, &v, &s->ac_ai, &s->ac_ji, &s->ac_ar, &s->ac_jr, &P[0][0], &P[0][1], &n, &hs};
+            const void* fn = s->f64 ? (const void*)&nb::nb_ac_predict0<double> : (const void*)&nb::nb_ac_predict0<float>;
+            NB_HIP(s, hipLaunchKernel(fn, rows_grid, block, args, 0, s->stream));
+        }
+        for (uint32_t q = 0; q < nsub; ++q) {
+            double tau0 = (double)q * hs, tau1 = tau0 + hs;
+            void **pr = P[q & 1], **pw = P[(q + 1) & 1];
+            void *wx = q + 1 < nsub ? pw[0] : nullptr, *wv = q + 1 < nsub ? pw[1] : nullptr;
+            if (s->f64) {
+                void* args[] = {&pr[0], &pr[1], &s->ac_list, &s->ac_count, &n, &cap, &eps2d, &G, &x, &v, &s->ac_ai, &s->ac_ji, &s->ac_ar, &s->ac_jr, &tau0, &tau1, &hs, &wx, &wv};
+                NB_HIP(s, hipLaunchKernel((const void*)&nb::nb_ac_sub64<nb::kLfLanes64>, sub_grid, block, args, 0, s->stream));
+            } else {
+                void* args[] = {&pr[0], &pr[1], &s->ac_list, &s->ac_count, &n, &cap, &eps2f, &G, &x, &v, &s->ac_ai, &s->ac_ji, &s->ac_ar, &s->ac_jr, &tau0, &tau1, &hs, &wx, &wv};
+                NB_HIP(s, hipLaunchKernel((const void*)&nb::nb_ac_sub32<nb::kLfLanes32>, sub_grid, block, args, 0, s->stream));
+            }
+        }
+        // the regular time: (aio, jio) over the OLD list into the first predicted pair, (ar', jr') into the second, (ai', ji') in
+        // place (the old ones are not read again), the new list over the old one (the old-list sums are enqueued in front of it)
+        nb_list_force_request fq;
+        memset(&fq, 0, sizeof fq);
+        fq.struct_size = sizeof fq; fq.m = n; fq.flags = NB_LISTF_AT_BODIES | NB_LISTF_DEVICE;
+        fq.list = s->ac_list; fq.count = s->ac_count; fq.cap = cap; fq.accel = s->hx; fq.jerk = s->hv;
+        if (int rc = nbi::list_force(s, &fq, n, "nb_step")) return rc;
+        if (int rc = ac_build(s, s->ac_ai, s->ac_ji, s->ac_px, s->ac_pv, "nb_step")) return rc;
+        {
+            void* args[] = {&x, &v, &s->ac_ai, &s->ac_ji, &s->ac_px, &s->ac_pv, &s->hx, &s->hv, &s->ac_ar, &s->ac_jr, &s->acc, &s->jerk, &s->ac_count, &s->ac_hdr, &n, &cap, &dt};
+            const void* fn = s->f64 ? (const void*)&nb::nb_ac_regular<double> : (const void*)&nb::nb_ac_regular<float>;
+            NB_HIP(s, hipLaunchKernel(fn, rows_grid, block, args, 0, s->stream));
+        }
+        if (rec) { NB_HIP(s, hipEventRecord(ev.e[1], s->stream)); ev.blk = true; s->pending.push_back(ev); }
+        bool over = false;
+        if (int rc = ac_read_header(s, &over, &s->ac_msg)) return rc;
+        ++s->ac_regular; s->ac_substeps += nsub;
+        ++s->steps_done;
+        if (over) {      // this step's state is complete and kept; the next interval has no consistent list
+            s->ac_over = true;
+            return fail(s, NB_ERR_STATE, "nb_step: " + s->ac_msg);
+        }
     }
     return NB_OK;
 }
@@ -1091,6 +1226,7 @@ void nb_destroy(nb_sim* s)
     if (s->sym_A) (void)hipFree(s->sym_A);
     for (void* p : {s->jerk, s->hx, s->hv, s->fj_part, (void*)s->blk_lev, (void*)s->blk_due, (void*)s->blk_act, (void*)s->blk_hdr}) if (p) (void)hipFree(p);
     if (s->blk_hdr_host) (void)hipHostFree(s->blk_hdr_host);
+    ac_release(s);
     if (s->diag) (void)hipFree(s->diag);
     for (auto* b : {&s->fld_pts, &s->fld_acc, &s->fld_phi, &s->fld_part, &s->nbr_rad, &s->nbr_idx, &s->nbr_d2, &s->nbr_cnt, &s->nbr_inf, &s->nbl_off, &s->nbl_list, &s->knn_work, &s->knn_idx, &s->knn_d2, &s->knn_stat, &s->lf_pvel, &s->lf_jerk, &s->split_out})
         if (b->p) (void)hipFree(b->p);
@@ -1116,6 +1252,7 @@ int nb_upload(nb_sim* s, const void* bodies, const void* vel, const void* accel)
     if (s->hermite) {          // accel is a derived array here: ignored, re-evaluated with the jerk when next needed
         s->uploaded = true;
         s->derivs_ok = false;
+        s->ac_ok = false;
         s->levels = 0;
         return NB_OK;
     }
@@ -1152,6 +1289,7 @@ int nb_set_params(nb_sim* s, double dt, double G)
     if (!s) return NB_ERR_INVALID;
     if (!(dt == dt) || !(G == G)) return fail(s, NB_ERR_INVALID, "nb_set_params: NaN");
     if (s->params_set && (dt != s->dt || G != s->G)) s->levels = 0;      // block steps: the levels belong to (dt, G)
+    if (s->params_set && dt != s->dt) s->ac_ok = false;                  // the neighbour scheme starts again from (x, v) (a changed G: ensure_scheme)
     s->dt = dt; s->G = G; s->params_set = true;
     return NB_OK;
 }
@@ -1163,7 +1301,7 @@ int nb_step(nb_sim* s, uint32_t nsteps)
     if (!s->params_set) return fail(s, NB_ERR_STATE, "nb_step: nb_set_params has not been called");
     if (!(s->dt > 0.0)) return NB_OK;   // `if (dt > 0)` gate, nbody3d.js:474
     NB_HIP(s, hipSetDevice(s->device));
-    if (s->hermite) return s->blk ? block_step(s, nsteps) : hermite_step(s, nsteps);
+    if (s->hermite) return s->ac ? ac_step(s, nsteps) : s->blk ? block_step(s, nsteps) : hermite_step(s, nsteps);
     const bool exchange = s->xfn || s->rccl;
     ensure_pairs(s);      // the j-packed step's position copy, if something outside the step rewrote the positions or G
     if (gm_active(s) && !s->gm_ok) { if (int rc = finish_gather(s)) return rc; }
@@ -1296,8 +1434,8 @@ int nb_device_ptr(nb_sim* s, int which, void** out)
         if (int rc = ensure_derivs(s, "nb_device_ptr")) return rc;
     }
     switch (which) {
-        case NB_BODIES: *out = s->bodies[s->cur]; s->pairs_ok = false; s->gm_ok = false; s->derivs_ok = false; s->levels = 0; s->eqm = nb_sim::kEqmUnknown; break;   // the caller may write through it
-        case NB_VEL: *out = s->vel; s->derivs_ok = false; s->levels = 0; s->eqm = nb_sim::kEqmUnknown; break;      // (the w lanes: see ensure_eqm)
+        case NB_BODIES: *out = s->bodies[s->cur]; s->pairs_ok = false; s->gm_ok = false; s->derivs_ok = false; s->ac_ok = false; s->levels = 0; s->eqm = nb_sim::kEqmUnknown; break;   // the caller may write through it
+        case NB_VEL: *out = s->vel; s->derivs_ok = false; s->ac_ok = false; s->levels = 0; s->eqm = nb_sim::kEqmUnknown; break;      // (the w lanes: see ensure_eqm)
         case NB_ACCEL: *out = s->acc; s->eqm = nb_sim::kEqmUnknown; break;
         case NB_JERK: *out = s->jerk; break;
         default: return fail(s, NB_ERR_INVALID, "nb_device_ptr: unknown array");
@@ -1331,6 +1469,7 @@ int nb_upload_derivs(nb_sim* s, const void* accel, const void* jerk)
     s->derivs_ok = true;
     s->derivs_any_G = !s->params_set;
     s->derivs_G = s->G;
+    s->ac_ok = false;      // the neighbour scheme keeps its own components: its start runs again (the uploaded totals are replaced)
     return NB_OK;
 }
 
@@ -1339,6 +1478,7 @@ int nb_set_block_steps(nb_sim* s, const nb_block_steps* cfg)
     if (!s) return fail(nullptr, NB_ERR_INVALID, "nb_set_block_steps: null handle");
     if (!s->hermite) return fail(s, NB_ERR_STATE, "nb_set_block_steps: needs a Hermite handle (nb_config.integrator = NB_INT_HERMITE4)");
     if (!cfg) { s->blk = false; s->levels = 0; return NB_OK; }
+    if (s->ac) return fail(s, NB_ERR_STATE, "nb_set_block_steps: the neighbour scheme is switched on (nb_set_neighbor_scheme): block steps and the neighbour scheme exclude each other");
     if (cfg->struct_size != sizeof(nb_block_steps)) return fail(s, NB_ERR_INVALID, "nb_set_block_steps: struct_size must be sizeof(nb_block_steps)");
     const uint32_t L = cfg->max_level ? cfg->max_level : 20u;
     if (cfg->max_level > 30) return fail(s, NB_ERR_INVALID, "nb_set_block_steps: max_level is at most 30");
@@ -1414,6 +1554,87 @@ int nb_upload_levels(nb_sim* s, const uint8_t* levels)
     NB_HIP(s, hipStreamSynchronize(s->stream));
     NB_HIP(s, hipMemcpy(s->blk_lev, levels, s->n, hipMemcpyHostToDevice));
     s->levels = 1;      // the start kernel keeps these levels and starts the clock (due_i = s_i)
+    return NB_OK;
+}
+
+int nb_set_neighbor_scheme(nb_sim* s, const nb_neighbor_scheme* cfg)
+{
+    if (!s) return fail(nullptr, NB_ERR_INVALID, "nb_set_neighbor_scheme: null handle");
+    if (!s->hermite) return fail(s, NB_ERR_STATE, "nb_set_neighbor_scheme: needs a Hermite handle (nb_config.integrator = NB_INT_HERMITE4)");
+    if (!cfg) {
+        if (s->ac) { NB_HIP(s, hipSetDevice(s->device)); NB_HIP(s, hipStreamSynchronize(s->stream)); s->derivs_ok = false; }      // acc / jerk held the scheme's totals
+        ac_release(s);
+        return NB_OK;
+    }
+    if (cfg->struct_size != sizeof(nb_neighbor_scheme)) return fail(s, NB_ERR_INVALID, "nb_set_neighbor_scheme: struct_size must be sizeof(nb_neighbor_scheme)");
+    const uint32_t nsub = cfg->substeps ? cfg->substeps : 8u, cap = cfg->cap ? cfg->cap : 128u;
+    if (nsub > 1024 || (nsub & (nsub - 1))) return fail(s, NB_ERR_INVALID, "nb_set_neighbor_scheme: substeps must be a power of two in 1 .. 1024 (0: the default 8)");
+    if (cap > 4096) return fail(s, NB_ERR_INVALID, "nb_set_neighbor_scheme: cap must be in 1 .. 4096 (0: the default 128)");
+    if (cfg->flags != 0) return fail(s, NB_ERR_INVALID, "nb_set_neighbor_scheme: flags must be 0");
+    if (!cfg->radii && !(cfg->radius > 0.0)) return fail(s, NB_ERR_INVALID, "nb_set_neighbor_scheme: radius must be > 0 when radii is NULL");
+    if (cfg->radii) {
+        for (uint32_t i = 0; i < s->n; ++i) {
+            const double h = s->f64 ? ((const double*)cfg->radii)[i] : (double)((const float*)cfg->radii)[i];
+            if (!(h >= 0.0) || std::isinf(h)) return fail(s, NB_ERR_INVALID, "nb_set_neighbor_scheme: radii[" + std::to_string(i) + "] must be finite and >= 0");
+        }
+    }
+    if (s->blk) return fail(s, NB_ERR_STATE, "nb_set_neighbor_scheme: block steps are switched on (nb_set_block_steps): block steps and the neighbour scheme exclude each other");
+    NB_HIP(s, hipSetDevice(s->device));
+    NB_HIP(s, hipStreamSynchronize(s->stream));
+    if (s->ac) s->derivs_ok = false;
+    ac_release(s);
+    const size_t rows = 4 * s->esz * s->n;
+    hipError_t e = hipSuccess;
+    for (void** p : {&s->ac_ai, &s->ac_ji, &s->ac_ar, &s->ac_jr, &s->ac_px, &s->ac_pv})
+        if (e == hipSuccess) e = hipMalloc(p, rows);
+    if (e == hipSuccess) e = hipMalloc((void**)&s->ac_list, sizeof(uint32_t) * (size_t)s->n * cap);
+    if (e == hipSuccess) e = hipMalloc((void**)&s->ac_count, sizeof(uint32_t) * s->n);
+    if (e == hipSuccess) e = hipMalloc((void**)&s->ac_hdr, sizeof(unsigned long long) * nb::kAcHdrWords);
+    if (e == hipSuccess) e = hipHostMalloc((void**)&s->ac_hdr_host, sizeof(unsigned long long) * nb::kAcHdrWords, hipHostMallocDefault);
+    if (e == hipSuccess && cfg->radii) {
+        e = hipMalloc(&s->ac_radii, s->esz * s->n);
+        if (e == hipSuccess) e = hipMemcpy(s->ac_radii, cfg->radii, s->esz * s->n, hipMemcpyHostToDevice);      // copied: the pointer is not kept
+    }
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        ac_release(s);
+        return fail(s, e == hipErrorOutOfMemory ? NB_ERR_NOMEM : NB_ERR_HIP, std::string("nb_set_neighbor_scheme: cannot allocate the scheme's arrays: ") + hipGetErrorString(e));
+    }
+    s->ac = true; s->ac_ok = false; s->ac_over = false;
+    s->ac_nsub = nsub; s->ac_cap = cap; s->ac_radius = cfg->radius;
+    return NB_OK;
+}
+
+int nb_neighbor_scheme_stats(nb_sim* s, struct nb_neighbor_scheme_stats* out, int reset)
+{
+    if (!s) return fail(nullptr, NB_ERR_INVALID, "nb_neighbor_scheme_stats: null handle");
+    if (!s->hermite) return fail(s, NB_ERR_STATE, "nb_neighbor_scheme_stats: needs a Hermite handle (nb_config.integrator = NB_INT_HERMITE4)");
+    if (!out || out->struct_size != sizeof(struct nb_neighbor_scheme_stats)) return fail(s, NB_ERR_INVALID, "nb_neighbor_scheme_stats: set out->struct_size to sizeof(nb_neighbor_scheme_stats)");
+    std::memset(out, 0, sizeof(*out));
+    out->struct_size = sizeof(*out);
+    if (!s->ac) return NB_OK;
+    out->enabled = 1u;
+    out->regular_steps = s->ac_regular; out->substeps = s->ac_substeps; out->entries = s->ac_entries; out->builds = s->ac_builds;
+    out->max_count = s->ac_max_count; out->overflowed = s->ac_overflowed;
+    if (reset) s->ac_regular = s->ac_substeps = s->ac_entries = s->ac_builds = 0;
+    return NB_OK;
+}
+
+int nb_download_neighbor_scheme(nb_sim* s, void* accel_irr, void* jerk_irr, void* accel_reg, void* jerk_reg, uint32_t* list, uint32_t* count)
+{
+    if (!s) return fail(nullptr, NB_ERR_INVALID, "nb_download_neighbor_scheme: null handle");
+    if (!s->ac) return fail(s, NB_ERR_STATE, "nb_download_neighbor_scheme: the neighbour scheme is not switched on (nb_set_neighbor_scheme)");
+    if (!s->uploaded) return fail(s, NB_ERR_STATE, "nb_download_neighbor_scheme: nothing uploaded yet");
+    NB_HIP(s, hipSetDevice(s->device));
+    if (int rc = ensure_scheme(s, "nb_download_neighbor_scheme")) return rc;
+    NB_HIP(s, hipStreamSynchronize(s->stream));
+    const size_t rows = 4 * s->esz * s->n;
+    if (accel_irr) NB_HIP(s, hipMemcpy(accel_irr, s->ac_ai, rows, hipMemcpyDeviceToHost));
+    if (jerk_irr) NB_HIP(s, hipMemcpy(jerk_irr, s->ac_ji, rows, hipMemcpyDeviceToHost));
+    if (accel_reg) NB_HIP(s, hipMemcpy(accel_reg, s->ac_ar, rows, hipMemcpyDeviceToHost));
+    if (jerk_reg) NB_HIP(s, hipMemcpy(jerk_reg, s->ac_jr, rows, hipMemcpyDeviceToHost));
+    if (list) NB_HIP(s, hipMemcpy(list, s->ac_list, sizeof(uint32_t) * (size_t)s->n * s->ac_cap, hipMemcpyDeviceToHost));
+    if (count) NB_HIP(s, hipMemcpy(count, s->ac_count, sizeof(uint32_t) * s->n, hipMemcpyDeviceToHost));
     return NB_OK;
 }
 

@@ -195,6 +195,27 @@ struct nb_sim {
     int levels = 0;                  // 0: stale; 1: blk_lev came from nb_upload_levels, the outer step's clock (blk_due) is not started yet;
                                      // 2: blk_lev / blk_due belong to the state, dt, G and the configuration
     uint64_t blk_outer = 0, blk_steps = 0, blk_body_steps = 0;
+    // nb_set_neighbor_scheme: the Ahmad-Cohen neighbour scheme with two shared step levels (kernels/ac_scheme.hip.h).  Allocated
+    // by the call, released by NULL or nb_destroy.  While it is on, acc / jerk hold the totals ai + ar0, ji + jr0.
+    bool ac = false;
+    bool ac_ok = false;              // the scheme's arrays belong to (bodies, vel) and derivs_G (together with derivs_ok)
+    bool ac_over = false;            // a build at a regular time overflowed: nb_step fails with ac_msg until the scheme is set again
+    std::string ac_msg;
+    uint32_t ac_nsub = 8, ac_cap = 128;
+    double ac_radius = 0.0;
+    void* ac_radii = nullptr;        // device copy of the caller's radii (n elements), or null
+    void* ac_ai = nullptr;           // the irregular derivatives, over the body's row of ac_list
+    void* ac_ji = nullptr;
+    void* ac_ar = nullptr;           // the regular derivatives at the last regular time
+    void* ac_jr = nullptr;
+    void* ac_px = nullptr;           // the second predicted pair (the first is hx / hv)
+    void* ac_pv = nullptr;
+    uint32_t* ac_list = nullptr;     // n x ac_cap
+    uint32_t* ac_count = nullptr;    // n, the true counts
+    unsigned long long* ac_hdr = nullptr;        // device: nb::kAcHdrWords words, zeroed in front of every build
+    unsigned long long* ac_hdr_host = nullptr;   // pinned host copy the step loop reads after its wait
+    uint64_t ac_regular = 0, ac_substeps = 0, ac_entries = 0, ac_builds = 0;
+    uint32_t ac_max_count = 0, ac_overflowed = 0;      // of the last build
 };
 
 namespace nbi {

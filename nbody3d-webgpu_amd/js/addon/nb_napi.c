@@ -75,11 +75,14 @@ static int (*p_list_force)(nb_sim *, const nb_list_force_request *);            
 static int (*p_multi_list_force)(nb_multi *, const nb_list_force_request *);
 static int (*p_split_force)(nb_sim *, const nb_split_force_request *);              /* regular + irregular force+jerk in one pass, likewise */
 static int (*p_multi_split_force)(nb_multi *, const nb_split_force_request *);
+static int (*p_set_neighbor_scheme)(nb_sim *, const nb_neighbor_scheme *);          /* the Ahmad-Cohen neighbour scheme, likewise: optional symbols */
+static int (*p_neighbor_scheme_stats)(nb_sim *, struct nb_neighbor_scheme_stats *, int);
+static int (*p_download_neighbor_scheme)(nb_sim *, void *, void *, void *, void *, uint32_t *, uint32_t *);
 static int (*p_eqm_info)(nb_sim *, int *);                              /* the equal-mass kernels' report, also within ABI 2.4: optional symbol */
 static int (*p_eqm_form)(nb_sim *, int *);                              /* which equal-mass form, likewise */
 
 /* one JS handle = a single-device nb_sim or a single-process multi-device nb_multi */
-typedef struct { nb_sim *sim; nb_multi *multi; uint32_t n; int f64; } handle_t;
+typedef struct { nb_sim *sim; nb_multi *multi; uint32_t n; int f64; uint32_t ac_cap; /* entries per row of the neighbour scheme, 0: off */ } handle_t;
 
 #define CHECK_NAPI(env, call)                                                        \
     do {                                                                             \
@@ -171,6 +174,9 @@ static napi_value js_load(napi_env env, napi_callback_info info)
         *(void **)(&p_multi_list_force) = dlsym(h, "nb_multi_list_force");
         *(void **)(&p_split_force) = dlsym(h, "nb_split_force");
         *(void **)(&p_multi_split_force) = dlsym(h, "nb_multi_split_force");
+        *(void **)(&p_set_neighbor_scheme) = dlsym(h, "nb_set_neighbor_scheme");
+        *(void **)(&p_neighbor_scheme_stats) = dlsym(h, "nb_neighbor_scheme_stats");
+        *(void **)(&p_download_neighbor_scheme) = dlsym(h, "nb_download_neighbor_scheme");
         *(void **)(&p_eqm_info) = dlsym(h, "nb_eqm_info");
         *(void **)(&p_eqm_form) = dlsym(h, "nb_eqm_form");
         g_lib = h;
@@ -301,7 +307,7 @@ static napi_value js_create(napi_env env, napi_callback_info info)
     }
     handle_t *h = (handle_t *)calloc(1, sizeof *h);
     if (!h) { if (sim) p_destroy(sim); if (multi) p_multi_destroy(multi); napi_throw_error(env, NULL, "out of memory"); return NULL; }
-    h->sim = sim; h->multi = multi; h->n = cfg.n; h->f64 = cfg.precision == NB_F64;
+    h->sim = sim; h->multi = multi; h->n = cfg.n; h->f64 = cfg.precision == NB_F64; h->ac_cap = 0;
     napi_value ext;
     if (napi_create_external(env, h, finalize_handle, NULL, &ext) != napi_ok) {
         finalize_handle(env, h, NULL); napi_throw_error(env, NULL, "napi_create_external failed"); return NULL;
@@ -1095,6 +1101,103 @@ static napi_value js_upload_levels(napi_env env, napi_callback_info info)
     return undefined(env);
 }
 
+/* the single-device handle of a neighbour-scheme call, or NULL with an exception pending */
+static handle_t *scheme_handle(napi_env env, napi_value v, const void *sym, const char *where)
+{
+    handle_t *h = get_handle(env, v); if (!h) return NULL;
+    if (h->multi || !sym) { throw_msg(env, NB_ERR_STATE, "needs a single-device Hermite handle and a library with nb_set_neighbor_scheme", where); return NULL; }
+    return h;
+}
+
+/* a typed array of `want` elements of the given type, or null when nullable */
+static int get_typed(napi_env env, napi_value v, napi_typedarray_type type, size_t want, int nullable, void **out, const char *name)
+{
+    napi_valuetype t; napi_typeof(env, v, &t);
+    *out = NULL;
+    if (t == napi_null || t == napi_undefined) {
+        if (nullable) return 1;
+        napi_throw_type_error(env, NULL, name); return 0;
+    }
+    bool is_ta = false; napi_is_typedarray(env, v, &is_ta);
+    napi_typedarray_type tt = napi_int8_array; size_t len = 0; void *data = NULL; napi_value ab; size_t off;
+    if (!is_ta || napi_get_typedarray_info(env, v, &tt, &len, &data, &ab, &off) != napi_ok || tt != type) { napi_throw_type_error(env, NULL, name); return 0; }
+    if (len != want) { napi_throw_range_error(env, NULL, name); return 0; }
+    *out = data; return 1;
+}
+
+/* setNeighborScheme(handle, null) | setNeighborScheme(handle, radius, radii | null, substeps, cap): nb_set_neighbor_scheme (substeps 0 /
+ * cap 0: the defaults 8 / 128); radii: n elements of the handle's precision, copied by the call */
+static napi_value js_set_neighbor_scheme(napi_env env, napi_callback_info info)
+{
+    size_t argc = 5; napi_value argv[5];
+    CHECK_NAPI(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    if (argc < 2) { napi_throw_type_error(env, NULL, "setNeighborScheme(handle, null | radius, radii, substeps, cap)"); return NULL; }
+    handle_t *h = scheme_handle(env, argv[0], *(void **)&p_set_neighbor_scheme, "nb_set_neighbor_scheme"); if (!h) return NULL;
+    napi_valuetype t; napi_typeof(env, argv[1], &t);
+    int rc;
+    if (argc < 5 && (t == napi_null || t == napi_undefined)) { rc = p_set_neighbor_scheme(h->sim, NULL); if (rc == NB_OK) h->ac_cap = 0; }
+    else {
+        if (argc < 5) { napi_throw_type_error(env, NULL, "setNeighborScheme(handle, radius, radii, substeps, cap)"); return NULL; }
+        nb_neighbor_scheme cfg;
+        memset(&cfg, 0, sizeof cfg);
+        cfg.struct_size = sizeof cfg;
+        uint32_t u = 0; void *radii = NULL;
+        CHECK_NAPI(env, napi_get_value_double(env, argv[1], &cfg.radius));
+        if (!get_typed(env, argv[2], h->f64 ? napi_float64_array : napi_float32_array, h->n, 1, &radii, "radii must be null or a typed array of n elements of the simulation's precision")) return NULL;
+        cfg.radii = radii;
+        CHECK_NAPI(env, napi_get_value_uint32(env, argv[3], &u)); cfg.substeps = u;
+        CHECK_NAPI(env, napi_get_value_uint32(env, argv[4], &u)); cfg.cap = u;
+        rc = p_set_neighbor_scheme(h->sim, &cfg);
+        if (rc == NB_OK) h->ac_cap = cfg.cap ? cfg.cap : 128u;
+    }
+    if (rc != NB_OK) return throw_nb(env, rc, h->sim, "nb_set_neighbor_scheme");
+    return undefined(env);
+}
+
+/* neighborSchemeStats(handle, reset) -> {enabled, regularSteps, substeps, entries, builds, maxCount, overflowed} (counts as doubles) */
+static napi_value js_neighbor_scheme_stats(napi_env env, napi_callback_info info)
+{
+    size_t argc = 2; napi_value argv[2];
+    CHECK_NAPI(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    if (argc < 1) { napi_throw_type_error(env, NULL, "neighborSchemeStats(handle, reset)"); return NULL; }
+    handle_t *h = scheme_handle(env, argv[0], *(void **)&p_neighbor_scheme_stats, "nb_neighbor_scheme_stats"); if (!h) return NULL;
+    bool reset = false;
+    if (argc > 1) napi_get_value_bool(env, argv[1], &reset);
+    struct nb_neighbor_scheme_stats st;
+    memset(&st, 0, sizeof st);
+    st.struct_size = sizeof st;
+    int rc = p_neighbor_scheme_stats(h->sim, &st, reset ? 1 : 0);
+    if (rc != NB_OK) return throw_nb(env, rc, h->sim, "nb_neighbor_scheme_stats");
+    napi_value o, v;
+    CHECK_NAPI(env, napi_create_object(env, &o));
+    napi_get_boolean(env, st.enabled != 0, &v); napi_set_named_property(env, o, "enabled", v);
+    napi_create_double(env, (double)st.regular_steps, &v); napi_set_named_property(env, o, "regularSteps", v);
+    napi_create_double(env, (double)st.substeps, &v); napi_set_named_property(env, o, "substeps", v);
+    napi_create_double(env, (double)st.entries, &v); napi_set_named_property(env, o, "entries", v);
+    napi_create_double(env, (double)st.builds, &v); napi_set_named_property(env, o, "builds", v);
+    napi_create_uint32(env, st.max_count, &v); napi_set_named_property(env, o, "maxCount", v);
+    napi_create_uint32(env, st.overflowed, &v); napi_set_named_property(env, o, "overflowed", v);
+    return o;
+}
+
+/* downloadNeighborScheme(handle, accelIrr, jerkIrr, accelReg, jerkReg, list, count): nb_download_neighbor_scheme, written in place; any
+ * of the six may be null.  list: Uint32Array of n * cap (the cap the scheme was set with), count: Uint32Array of n */
+static napi_value js_download_neighbor_scheme(napi_env env, napi_callback_info info)
+{
+    size_t argc = 7; napi_value argv[7];
+    CHECK_NAPI(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    if (argc < 7) { napi_throw_type_error(env, NULL, "downloadNeighborScheme(handle, accelIrr, jerkIrr, accelReg, jerkReg, list, count)"); return NULL; }
+    handle_t *h = scheme_handle(env, argv[0], *(void **)&p_download_neighbor_scheme, "nb_download_neighbor_scheme"); if (!h) return NULL;
+    void *row[4], *list, *count;
+    for (int k = 0; k < 4; ++k)
+        if (!get_array(env, argv[1 + k], h, 1, &row[k], "accelIrr / jerkIrr / accelReg / jerkReg must be null or typed arrays of 4*n elements")) return NULL;
+    if (!get_typed(env, argv[5], napi_uint32_array, (size_t)h->n * h->ac_cap, 1, &list, "list must be null or a Uint32Array of n * cap elements")) return NULL;
+    if (!get_typed(env, argv[6], napi_uint32_array, h->n, 1, &count, "count must be null or a Uint32Array of n elements")) return NULL;
+    int rc = p_download_neighbor_scheme(h->sim, row[0], row[1], row[2], row[3], (uint32_t *)list, (uint32_t *)count);
+    if (rc != NB_OK) return throw_nb(env, rc, h->sim, "nb_download_neighbor_scheme");
+    return undefined(env);
+}
+
 static napi_value init_module(napi_env env, napi_value exports)
 {
     static const struct { const char *name; napi_callback fn; } fns[] = {
@@ -1107,6 +1210,8 @@ static napi_value init_module(napi_env env, napi_value exports)
         {"setBlockSteps", js_set_block_steps}, {"blockStats", js_block_stats}, {"downloadLevels", js_download_levels},
         {"uploadLevels", js_upload_levels}, {"neighbors", js_neighbors}, {"neighborLists", js_neighbor_lists},
         {"knn", js_knn}, {"listForce", js_list_force}, {"splitForce", js_split_force},
+        {"setNeighborScheme", js_set_neighbor_scheme}, {"neighborSchemeStats", js_neighbor_scheme_stats},
+        {"downloadNeighborScheme", js_download_neighbor_scheme},
     };
     for (size_t i = 0; i < sizeof fns / sizeof fns[0]; ++i) {
         napi_value f;

@@ -224,6 +224,40 @@ class Simulation {
     return this;
   }
 
+  /** The Ahmad-Cohen neighbour scheme of a 'hermite4' simulation (nb_set_neighbor_scheme; no reference analogue): a body's force is
+   *  split at its neighbour radius; the sums over its neighbour list run every dt / substeps, the rest once per dt.  {radius | radii,
+   *  substeps, cap}: one radius for all or one per body (copied), substeps a power of two (default 8), cap the entries of a list row
+   *  (default 128).  A list that does not fit its row makes step() throw NB_4 until the scheme is set again.
+   *  setNeighborScheme(null) switches back to plain Hermite steps. */
+  setNeighborScheme(options) {
+    this._need();
+    if (options === null || options === undefined) { addon.setNeighborScheme(this._h, null); this._acCap = 0; return this; }
+    const T = this.ArrayType, r = options.radii;
+    const radii = r === null || r === undefined ? null : (r instanceof T ? r : T.from(r));
+    addon.setParams(this._h, this.dt, this.G);
+    addon.setNeighborScheme(this._h, options.radius === undefined || options.radius === null ? 0 : +options.radius, radii,
+      (options.substeps || 0) >>> 0, (options.cap || 0) >>> 0);
+    this._acCap = (options.cap || 0) >>> 0 || 128;
+    return this;
+  }
+
+  /** {enabled, regularSteps, substeps, entries, builds, maxCount, overflowed} (nb_neighbor_scheme_stats): entries is the sum of
+   *  min(count, cap) over the list builds, the start included; maxCount and overflowed belong to the last build. */
+  neighborSchemeStats(reset) { this._need(); return addon.neighborSchemeStats(this._h, !!reset); }
+
+  /** The scheme's own arrays at the simulation's instant (nb_download_neighbor_scheme; runs the scheme's start first if they are
+   *  not current): {accelIrr, jerkIrr, accelReg, jerkReg (4*N each), list (Uint32Array N * cap), count (Uint32Array N), cap}. */
+  downloadNeighborScheme() {
+    this._need();
+    if (!this._acCap) throw new Error('downloadNeighborScheme(): the neighbour scheme is not switched on (setNeighborScheme)');
+    const T = this.ArrayType, n = this.nBodies;
+    const out = { accelIrr: new T(4 * n), jerkIrr: new T(4 * n), accelReg: new T(4 * n), jerkReg: new T(4 * n),
+      list: new Uint32Array(n * this._acCap), count: new Uint32Array(n), cap: this._acCap };
+    addon.setParams(this._h, this.dt, this.G);
+    addon.downloadNeighborScheme(this._h, out.accelIrr, out.jerkIrr, out.accelReg, out.jerkReg, out.list, out.count);
+    return out;
+  }
+
   /** util.js:230-244: write the three arrays into the EXISTING buffers (N must match).  A 'hermite4' simulation ignores accel on its
    *  own (a derived array); with BOTH state.accel and state.jerk it takes them as its derivatives (nb_upload_derivs). */
   restore(state) {

@@ -132,6 +132,16 @@ class nb_block_stats(C.Structure):
                 ("body_steps", C.c_uint64), ("clamped", C.c_uint64), ("finest_level", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+class nb_neighbor_scheme(C.Structure):      # include/nbody3d_hip.h (the Ahmad-Cohen neighbour scheme of a Hermite handle)
+    _fields_ = [("struct_size", C.c_uint32), ("substeps", C.c_uint32), ("cap", C.c_uint32), ("flags", C.c_uint32),
+                ("radius", C.c_double), ("radii", C.c_void_p)]
+
+
+class nb_neighbor_scheme_stats(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("enabled", C.c_uint32), ("regular_steps", C.c_uint64), ("substeps", C.c_uint64),
+                ("entries", C.c_uint64), ("builds", C.c_uint64), ("max_count", C.c_uint32), ("overflowed", C.c_uint32)]
+
+
 EXCHANGE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p)
 EXCHANGE_WAIT_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p)
 
@@ -151,7 +161,8 @@ SYMBOLS = ["nb_abi_version", "nb_device_count", "nb_create", "nb_destroy", "nb_u
            "nb_neighbor_lists", "nb_multi_neighbor_lists", "nb_neighbor_lists_shape",
            "nb_knn", "nb_multi_knn", "nb_knn_shape",
            "nb_list_force", "nb_multi_list_force", "nb_list_force_shape",
-           "nb_split_force", "nb_multi_split_force", "nb_split_force_shape"]
+           "nb_split_force", "nb_multi_split_force", "nb_split_force_shape",
+           "nb_set_neighbor_scheme", "nb_neighbor_scheme_stats", "nb_download_neighbor_scheme"]
 
 _lib = None
 
@@ -251,6 +262,10 @@ def load_library():
         L.nb_split_force.argtypes = [vp, C.POINTER(nb_split_force_request)]
         L.nb_multi_split_force.argtypes = [vp, C.POINTER(nb_split_force_request)]
         L.nb_split_force_shape.argtypes = [vp, C.c_uint32] + [C.POINTER(C.c_uint32)] * 4
+    if hasattr(L, "nb_set_neighbor_scheme"):    # the Ahmad-Cohen neighbour scheme, also within 2.4 and detected by the symbol
+        L.nb_set_neighbor_scheme.argtypes = [vp, C.POINTER(nb_neighbor_scheme)]
+        L.nb_neighbor_scheme_stats.argtypes = [vp, C.POINTER(nb_neighbor_scheme_stats), C.c_int]
+        L.nb_download_neighbor_scheme.argtypes = [vp] * 7
     if hasattr(L, "nb_eqm_info"):           # the equal-mass kernels' report, also within 2.4 and detected by the symbol
         L.nb_eqm_info.argtypes = [vp, C.POINTER(C.c_int)]
     if hasattr(L, "nb_eqm_form"):           # which of the equal-mass forms, likewise
@@ -904,6 +919,59 @@ class Simulation:
             raise ValueError("levels must have shape (%d,)" % self.n)
         self._check(self._L.nb_upload_levels(self._h, _ptr(lv)))
         return self
+
+    # -- the Ahmad-Cohen neighbour scheme of a Hermite handle -------------------
+    def _need_scheme(self, what):
+        if not hasattr(self._L, "nb_set_neighbor_scheme"):
+            raise NBodyError(1, "%s: the loaded library has no nb_set_neighbor_scheme" % what)
+
+    def set_neighbor_scheme(self, *args, **kw):
+        """set_neighbor_scheme(radius=None, radii=None, substeps=None, cap=None): nb_set_neighbor_scheme -- a body's force is
+        split at its neighbour radius; the sums over its neighbour list run every dt / substeps, the rest once per dt.  ``radius``
+        is one number, ``radii`` one per body (copied by the call); substeps a power of two (None: the library's 8), cap the
+        entries of a list row (None: 128).  A list that does not fit its row makes step() raise NB_ERR_STATE until the scheme is
+        set again.  set_neighbor_scheme(None) switches back to plain Hermite steps."""
+        self._need_scheme("set_neighbor_scheme()")
+        if args == (None,) and not kw:
+            self._check(self._L.nb_set_neighbor_scheme(self._h, None))
+            return self
+
+        def bind(radius=None, radii=None, substeps=None, cap=None):
+            return radius, radii, substeps, cap
+        radius, radii, substeps, cap = bind(*args, **kw)
+        cfg = nb_neighbor_scheme()
+        cfg.struct_size = C.sizeof(nb_neighbor_scheme)
+        cfg.substeps = 0 if substeps is None else int(substeps)
+        cfg.cap = 0 if cap is None else int(cap)
+        cfg.flags = 0
+        cfg.radius = 0.0 if radius is None else float(radius)
+        keep = None
+        if radii is not None:
+            keep = np.ascontiguousarray(radii, dtype=self.dtype)
+            if keep.shape != (self.n,):
+                raise ValueError("radii must have shape (%d,)" % self.n)
+            cfg.radii = _ptr(keep)
+        self._check(self._L.nb_set_neighbor_scheme(self._h, C.byref(cfg)))
+        return self
+
+    def neighbor_scheme_stats(self, reset=False):
+        """nb_neighbor_scheme_stats: {enabled, regular_steps, substeps, entries, builds, max_count, overflowed}; entries is the
+        sum of min(count, cap) over the list builds (the start included), max_count and overflowed belong to the last build."""
+        self._need_scheme("neighbor_scheme_stats()")
+        st = nb_neighbor_scheme_stats()
+        st.struct_size = C.sizeof(nb_neighbor_scheme_stats)
+        self._check(self._L.nb_neighbor_scheme_stats(self._h, C.byref(st), 1 if reset else 0))
+        return {k: int(getattr(st, k)) for k in ("enabled", "regular_steps", "substeps", "entries", "builds", "max_count", "overflowed")}
+
+    def download_neighbor_scheme(self, cap):
+        """nb_download_neighbor_scheme: {accel_irr, jerk_irr, accel_reg, jerk_reg ((N, 4)), list ((N, cap), uint32), count ((N,),
+        uint32)} at the handle's instant; runs the scheme's start first if they are not current.  ``cap`` is the scheme's."""
+        self._need_scheme("download_neighbor_scheme()")
+        out = {k: np.zeros((self.n, 4), self.dtype) for k in ("accel_irr", "jerk_irr", "accel_reg", "jerk_reg")}
+        out["list"] = np.zeros((self.n, int(cap)), np.uint32)
+        out["count"] = np.zeros(self.n, np.uint32)
+        self._check(self._L.nb_download_neighbor_scheme(self._h, *[_ptr(out[k]) for k in ("accel_irr", "jerk_irr", "accel_reg", "jerk_reg", "list", "count")]))
+        return out
 
     # -- multi-GPU / measurement / diagnostics ------------------------------
     def device_ptr(self, which):
