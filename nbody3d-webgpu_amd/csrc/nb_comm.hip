@@ -324,6 +324,23 @@ void drop_comms(nb_multi* m)
     m->comms.clear();
 }
 
+// What the nb_multi_* queries share.  Once every shard's gather has landed, shard 0 holds all rows; the caller's rows are the first
+// n of the padded system, so its indices are shard 0's and only the bound is the multi handle's: the padding rows (zero mass, at
+// the origin) are no bodies to a query -- never a neighbour, never listed or counted, and they would add exactly nothing to a sum.
+// refused(): the text of what the wrapper itself turns down (null: nothing), asked once the handle and the request are there.
+template <class R, class Pre>
+int multi_query(nb_multi* m, const R* req, const char* who, int (*query)(nb_sim*, const R*, uint32_t, const char*), Pre&& refused)
+{
+    if (!m) return mfail(nullptr, NB_ERR_INVALID, std::string(who) + ": null handle");
+    if (!req) return mfail(m, NB_ERR_INVALID, std::string(who) + ": null request");
+    if (const char* why = refused()) return mfail(m, NB_ERR_INVALID, std::string(who) + ": " + why);
+    if (int rc = nb_multi_sync(m)) return rc;
+    nb_sim* s = m->shard[0];
+    const int rc = query(s, req, m->n, who);
+    return rc == NB_OK ? rc : mfail(m, rc, s->err);
+}
+const char* nothing_refused() { return nullptr; }
+
 }  // namespace
 
 extern "C" {
@@ -694,74 +711,27 @@ int nb_multi_diagnostics(nb_multi* m, double out[5])
 
 int nb_multi_field_eval(nb_multi* m, const nb_field_request* req)
 {
-    if (!m) return mfail(nullptr, NB_ERR_INVALID, "nb_multi_field_eval: null handle");
-    if (!req) return mfail(m, NB_ERR_INVALID, "nb_multi_field_eval: null request");
-    // the caller's rows are the first n of the padded system: its indices are shard 0's, only the bound is the multi handle's
-    if (req->struct_size == sizeof(nb_field_request) && (req->flags & NB_FIELD_AT_BODIES) && (uint64_t)req->first_body + req->m > m->n)
-        return mfail(m, NB_ERR_INVALID, "nb_multi_field_eval: first_body + m exceeds n");
-    if (int rc = nb_multi_sync(m)) return rc;      // every shard's gather has landed: shard 0 holds all rows (padding: zero mass)
-    nb_sim* s = m->shard[0];
-    const int rc = nb_field_eval(s, req);
-    return rc == NB_OK ? rc : mfail(m, rc, s->err);
+    return multi_query(m, req, "nb_multi_field_eval", +[](nb_sim* s, const nb_field_request* r, uint32_t, const char*) { return nb_field_eval(s, r); }, [&] {
+        const bool past = req->struct_size == sizeof(nb_field_request) && (req->flags & NB_FIELD_AT_BODIES) && (uint64_t)req->first_body + req->m > m->n;
+        return past ? "first_body + m exceeds n" : nullptr; });
 }
 
-int nb_multi_neighbors(nb_multi* m, const nb_neighbor_request* req)
-{
-    if (!m) return mfail(nullptr, NB_ERR_INVALID, "nb_multi_neighbors: null handle");
-    if (!req) return mfail(m, NB_ERR_INVALID, "nb_multi_neighbors: null request");
-    if (int rc = nb_multi_sync(m)) return rc;      // every shard's gather has landed: shard 0 holds all rows
-    // the caller's rows are the first n of the padded system: the padding rows (zero mass, at the origin) are no bodies here
-    nb_sim* s = m->shard[0];
-    const int rc = nbi::neighbors(s, req, m->n, "nb_multi_neighbors");
-    return rc == NB_OK ? rc : mfail(m, rc, s->err);
-}
+int nb_multi_neighbors(nb_multi* m, const nb_neighbor_request* req) { return multi_query(m, req, "nb_multi_neighbors", nbi::neighbors, nothing_refused); }
 
-int nb_multi_neighbor_lists(nb_multi* m, const nb_neighbor_list_request* req)
-{
-    if (!m) return mfail(nullptr, NB_ERR_INVALID, "nb_multi_neighbor_lists: null handle");
-    if (!req) return mfail(m, NB_ERR_INVALID, "nb_multi_neighbor_lists: null request");
-    if (int rc = nb_multi_sync(m)) return rc;      // every shard's gather has landed: shard 0 holds all rows
-    // the caller's rows are the first n of the padded system: the padding rows are never listed and never counted
-    nb_sim* s = m->shard[0];
-    const int rc = nbi::neighbor_lists(s, req, m->n, "nb_multi_neighbor_lists");
-    return rc == NB_OK ? rc : mfail(m, rc, s->err);
-}
+int nb_multi_neighbor_lists(nb_multi* m, const nb_neighbor_list_request* req) { return multi_query(m, req, "nb_multi_neighbor_lists", nbi::neighbor_lists, nothing_refused); }
 
-int nb_multi_knn(nb_multi* m, const nb_knn_request* req)
-{
-    if (!m) return mfail(nullptr, NB_ERR_INVALID, "nb_multi_knn: null handle");
-    if (!req) return mfail(m, NB_ERR_INVALID, "nb_multi_knn: null request");
-    if (int rc = nb_multi_sync(m)) return rc;      // every shard's gather has landed: shard 0 holds all rows
-    // the caller's rows are the first n of the padded system: a padding row is never a neighbour
-    nb_sim* s = m->shard[0];
-    const int rc = nbi::knn(s, req, m->n, "nb_multi_knn");
-    return rc == NB_OK ? rc : mfail(m, rc, s->err);
-}
+int nb_multi_knn(nb_multi* m, const nb_knn_request* req) { return multi_query(m, req, "nb_multi_knn", nbi::knn, nothing_refused); }
 
 int nb_multi_list_force(nb_multi* m, const nb_list_force_request* req)
 {
-    if (!m) return mfail(nullptr, NB_ERR_INVALID, "nb_multi_list_force: null handle");
-    if (!req) return mfail(m, NB_ERR_INVALID, "nb_multi_list_force: null request");
-    if (req->struct_size == sizeof(nb_list_force_request) && req->jerk)
-        return mfail(m, NB_ERR_INVALID, "nb_multi_list_force: jerk must be NULL (the shards are leapfrog handles)");
-    if (int rc = nb_multi_sync(m)) return rc;      // every shard's gather has landed: shard 0 holds all rows
-    // the caller's rows are the first n of the padded system: an entry that names a padding row adds nothing
-    nb_sim* s = m->shard[0];
-    const int rc = nbi::list_force(s, req, m->n, "nb_multi_list_force");
-    return rc == NB_OK ? rc : mfail(m, rc, s->err);
+    return multi_query(m, req, "nb_multi_list_force", nbi::list_force, [&] {
+        return req->struct_size == sizeof(nb_list_force_request) && req->jerk ? "jerk must be NULL (the shards are leapfrog handles)" : nullptr; });
 }
 
 int nb_multi_split_force(nb_multi* m, const nb_split_force_request* req)
 {
-    if (!m) return mfail(nullptr, NB_ERR_INVALID, "nb_multi_split_force: null handle");
-    if (!req) return mfail(m, NB_ERR_INVALID, "nb_multi_split_force: null request");
-    if (req->struct_size == sizeof(nb_split_force_request) && (req->jerk_irr || req->jerk_reg))
-        return mfail(m, NB_ERR_INVALID, "nb_multi_split_force: jerk_irr and jerk_reg must be NULL (the shards are leapfrog handles)");
-    if (int rc = nb_multi_sync(m)) return rc;      // every shard's gather has landed: shard 0 holds all rows
-    // the caller's rows are the first n of the padded system: the padding rows (zero mass) would add exactly nothing to either sum
-    nb_sim* s = m->shard[0];
-    const int rc = nbi::split_force(s, req, m->n, "nb_multi_split_force");
-    return rc == NB_OK ? rc : mfail(m, rc, s->err);
+    return multi_query(m, req, "nb_multi_split_force", nbi::split_force, [&] {
+        return req->struct_size == sizeof(nb_split_force_request) && (req->jerk_irr || req->jerk_reg) ? "jerk_irr and jerk_reg must be NULL (the shards are leapfrog handles)" : nullptr; });
 }
 
 int nb_multi_download(nb_multi* m, void* bodies, void* vel, void* accel)

@@ -1228,7 +1228,7 @@ void nb_destroy(nb_sim* s)
     if (s->blk_hdr_host) (void)hipHostFree(s->blk_hdr_host);
     ac_release(s);
     if (s->diag) (void)hipFree(s->diag);
-    for (auto* b : {&s->fld_pts, &s->fld_acc, &s->fld_phi, &s->fld_part, &s->nbr_rad, &s->nbr_idx, &s->nbr_d2, &s->nbr_cnt, &s->nbr_inf, &s->nbl_off, &s->nbl_list, &s->knn_work, &s->knn_idx, &s->knn_d2, &s->knn_stat, &s->lf_pvel, &s->lf_jerk, &s->split_out})
+    for (auto* b : {&s->q_in[0], &s->q_in[1], &s->q_in[2], &s->q_in[3], &s->q_out[0], &s->q_out[1], &s->q_out[2], &s->q_out[3], &s->q_part, &s->q_off, &s->q_work, &s->q_inf, &s->knn_stat})
         if (b->p) (void)hipFree(b->p);
     if (s->zero_row) (void)hipFree(s->zero_row);
     if (s->own_stream && s->stream) (void)hipStreamDestroy(s->stream);
@@ -1941,11 +1941,12 @@ int nb_diagnostics(nb_sim* s, double out[5])
 
 /* ---- field queries ------------------------------------------------------------------------ */
 
+extern "C++" {      // (templates below)
 namespace {
 
 // Makes an engine-owned buffer hold at least `bytes` (a grown buffer is a new allocation: whatever the stream still runs on the
 // old one is waited for first).
-int field_reserve(nb_sim* s, nb_sim::field_buf& b, size_t bytes, const char* who = "nb_field_eval")
+int field_reserve(nb_sim* s, nb_sim::field_buf& b, size_t bytes, const char* who)
 {
     if (bytes <= b.cap) return NB_OK;
     if (b.p) { NB_HIP(s, hipStreamSynchronize(s->stream)); (void)hipFree(b.p); b.p = nullptr; b.cap = 0; }
@@ -1990,61 +1991,171 @@ void field_shape(const nb_sim* s, uint32_t pblocks, uint32_t* chunks, uint32_t* 
     *chunks = ceil_div(s->n, per);
 }
 
+// ---- what the six queries share: one prologue, one staging path, one batch rule ----
+
+// The six request structs open with the same fields (struct_size, m, flags, first_body, points) and the four flag families
+// use the same bits.
+constexpr uint32_t kQueryAtBodies = 1u, kQueryDevice = 4u;
+static_assert(NB_FIELD_AT_BODIES == kQueryAtBodies && NB_NBR_AT_BODIES == kQueryAtBodies && NB_LISTF_AT_BODIES == kQueryAtBodies && NB_SPLIT_AT_BODIES == kQueryAtBodies, "one *_AT_BODIES bit");
+static_assert(NB_FIELD_DEVICE == kQueryDevice && NB_NBR_DEVICE == kQueryDevice && NB_LISTF_DEVICE == kQueryDevice && NB_SPLIT_DEVICE == kQueryDevice, "one *_DEVICE bit");
+
+// What the prologue has to know of a query: the names its messages carry, the flag bits it takes, whether its sums need G.
+struct query_kind { const char* request; const char* at_bodies; uint32_t flags; bool needs_G; };
+constexpr query_kind kQField = {"nb_field_request", "NB_FIELD_AT_BODIES", NB_FIELD_AT_BODIES | NB_FIELD_F64 | NB_FIELD_DEVICE, true};
+constexpr query_kind kQNbr = {"nb_neighbor_request", "NB_NBR_AT_BODIES", NB_NBR_AT_BODIES | NB_NBR_DEVICE, false};
+constexpr query_kind kQNbl = {"nb_neighbor_list_request", "NB_NBR_AT_BODIES", NB_NBR_AT_BODIES | NB_NBR_DEVICE, false};
+constexpr query_kind kQKnn = {"nb_knn_request", "NB_NBR_AT_BODIES", NB_NBR_AT_BODIES | NB_NBR_DEVICE, false};
+constexpr query_kind kQListF = {"nb_list_force_request", "NB_LISTF_AT_BODIES", NB_LISTF_AT_BODIES | NB_LISTF_DEVICE, true};
+constexpr query_kind kQSplit = {"nb_split_force_request", "NB_SPLIT_AT_BODIES", NB_SPLIT_AT_BODIES | NB_SPLIT_DEVICE, true};
+
+// (the text is only put together when a call fails: the Ahmad-Cohen scheme goes through these functions in every regular step)
+int qfail(nb_sim* s, int code, const char* who, const std::string& what) { return fail(s, code, std::string(who) + ": " + what); }
+
+// The prologue of every query against the first `rows` rows of the handle: the request's head, then `specific` (the checks of the
+// fields only this query has: the text of the first one missed, or null), then the handle's state; every NB_ERR_INVALID comes
+// before every NB_ERR_STATE.  `who` names the public function in the messages.
+template <class R, class F>
+int query_begin(nb_sim* s, const R* req, const query_kind& k, uint32_t rows, const char* who, F&& specific)
+{
+    if (!s) return qfail(nullptr, NB_ERR_INVALID, who, "null handle");
+    if (!req) return qfail(s, NB_ERR_INVALID, who, "null request");
+    if (req->struct_size != sizeof(R)) return qfail(s, NB_ERR_INVALID, who, std::string("struct_size must be sizeof(") + k.request + ")");
+    if (req->flags & ~k.flags) return qfail(s, NB_ERR_INVALID, who, "unknown bits in flags");
+    const bool at = (req->flags & kQueryAtBodies) != 0;
+    if (at && req->points) return qfail(s, NB_ERR_INVALID, who, std::string("points must be NULL with ") + k.at_bodies);
+    if (!at && !req->points) return qfail(s, NB_ERR_INVALID, who, std::string("points is NULL (and ") + k.at_bodies + " is not set)");
+    if (req->m == 0) return qfail(s, NB_ERR_INVALID, who, "m must be >= 1");
+    if (const char* bad = specific()) return qfail(s, NB_ERR_INVALID, who, bad);
+    if (at && (uint64_t)req->first_body + req->m > rows) return qfail(s, NB_ERR_INVALID, who, "first_body + m exceeds n");
+    if (!s->uploaded) return qfail(s, NB_ERR_STATE, who, "nothing uploaded yet");
+    if (k.needs_G && !s->params_set) return qfail(s, NB_ERR_STATE, who, "nb_set_params has not been called (G)");
+    NB_HIP(s, hipSetDevice(s->device));
+    return finish_gather(s);     // other ranks' rows must have landed
+}
+
+// One array of a request: where the caller has it (null: not asked for), its bytes per point, its direction, the engine buffer
+// that stages it for a host-pointer request (null: it is on the device whatever the request says -- the handle's own rows) and
+// whether it is staged whole, ahead of the first batch, or batch by batch.
+struct q_array {
+    const void* user;
+    size_t stride;
+    bool out;
+    nb_sim::field_buf* buf;
+    bool whole;
+    char* dev = nullptr;      // stage_in: the device address of point `first`
+    size_t first = 0;
+    char* at(size_t point) const { return dev ? dev + stride * (point - first) : nullptr; }
+};
+
+// The points of a request: the caller's, or with *_AT_BODIES the handle's own rows from first_body on.
+template <class R>
+q_array query_points(nb_sim* s, const R* req, bool whole = true)
+{
+    const size_t row = 4 * s->esz;
+    if (req->flags & kQueryAtBodies) return {(const char*)s->bodies[s->cur] + row * req->first_body, row, false, nullptr, whole};
+    return {req->points, row, false, &s->q_in[0], whole};
+}
+
+// Resolves points [first, first + count) of every array staged as `whole` says to device addresses: a device-pointer request's
+// (`dev`) are the caller's own; a host-pointer request's get room in their engine buffer, the inputs copied in.
+int stage_in(nb_sim* s, bool dev, std::initializer_list<q_array*> arrays, bool whole, size_t first, size_t count, const char* who)
+{
+    for (q_array* a : arrays) {
+        if (!a->user || a->whole != whole) continue;
+        if (dev || !a->buf) { a->dev = (char*)a->user; a->first = 0; continue; }
+        if (int rc = field_reserve(s, *a->buf, a->stride * count, who)) return rc;
+        a->dev = (char*)a->buf->p;
+        a->first = first;
+        if (!a->out) NB_HIP(s, hipMemcpyAsync(a->dev, (const char*)a->user + a->stride * first, a->stride * count, hipMemcpyHostToDevice, s->stream));
+    }
+    return NB_OK;
+}
+
+// The other way: copies the outputs that stage_in gave room back to a host-pointer request's arrays and, behind the arrays that
+// are staged whole -- the end of the request --, waits for the stream.  A device-pointer request returns without waiting.
+int stage_out(nb_sim* s, bool dev, std::initializer_list<q_array*> arrays, bool whole, size_t first, size_t count)
+{
+    if (dev) return NB_OK;
+    for (q_array* a : arrays)
+        if (a->user && a->out && a->buf && a->whole == whole)
+            NB_HIP(s, hipMemcpyAsync((char*)a->user + a->stride * first, a->dev, a->stride * count, hipMemcpyDeviceToHost, s->stream));
+    if (whole) NB_HIP(s, hipStreamSynchronize(s->stream));
+    return NB_OK;
+}
+
+// One row at +inf: the LDS-DMA source of the f32 neighbour kernels for j past the range.  Written once per handle.
+int ensure_inf_row(nb_sim* s, const char* who)
+{
+    if (s->f64 || s->q_inf.p) return NB_OK;
+    static const float inf_row[4] = {HUGE_VALF, HUGE_VALF, HUGE_VALF, 0.0f};
+    if (int rc = field_reserve(s, s->q_inf, 64, who)) return rc;
+    NB_HIP(s, hipMemcpyAsync(s->q_inf.p, inf_row, sizeof inf_row, hipMemcpyHostToDevice, s->stream));
+    return NB_OK;
+}
+
+// The batch rule: fewer points at once -- half as many, in whole workgroups' worth (prow) of points, one workgroup's being the
+// floor -- while the batch is too big.  cut(mb) lays out a batch of mb points and returns the points it really takes.
+template <class Cut, class Big>
+uint32_t fit_batch(uint32_t mb, uint32_t prow, Cut&& cut, Big&& too_big)
+{
+    for (mb = cut(mb); too_big(mb) && mb > prow;) mb = cut(std::max(prow, (mb / 2 + prow - 1) / prow * prow));
+    return mb;
+}
+uint32_t as_it_is(uint32_t mb) { return mb; }      // a cut that leaves the chunks alone
+
+// The first batch of an m-point request whose kernel takes prow points per workgroup, under nb_field_eval's rule: at most 262,144
+// points (65,536 in fp64), field_shape's j-chunks for them, halved until chunks x batch partial rows fit the bound of q_part.
+uint32_t part_shape(const nb_sim* s, uint32_t m, uint32_t prow, bool wide, uint32_t* chunks, uint32_t* per)
+{
+    const uint64_t part_rows = std::max<uint64_t>(kFieldPartRows, (uint64_t)2 * field_blocks_wanted(s) * prow);
+    return fit_batch(std::min(m, wide ? 65536u : 262144u), prow,
+                     [&](uint32_t mb) { field_shape(s, ceil_div(mb, prow), chunks, per); return mb; },
+                     [&](uint32_t mb) { return (uint64_t)*chunks * mb > part_rows; });
+}
+
+// What the *_shape getters share: the checks in front (`bad`: the text of a cap or k out of range, or null) and the outputs behind.
+int shape_begin(nb_sim* s, const char* who, uint32_t m, const char* bad = nullptr)
+{
+    if (!s) return qfail(nullptr, NB_ERR_INVALID, who, "null handle");
+    if (m == 0) return qfail(s, NB_ERR_INVALID, who, "m must be >= 1");
+    return bad ? qfail(s, NB_ERR_INVALID, who, bad) : NB_OK;
+}
+int shape_put(uint32_t b, uint32_t c, uint32_t per, uint32_t* batch, uint32_t* chunks, uint32_t* j_per_chunk)
+{
+    if (batch) *batch = b;
+    if (chunks) *chunks = c;
+    if (j_per_chunk) *j_per_chunk = per;
+    return NB_OK;
+}
+
 }  // namespace
+}  // extern "C++"
 
 int nb_field_eval(nb_sim* s, const nb_field_request* req)
 {
-    if (!s) return fail(nullptr, NB_ERR_INVALID, "nb_field_eval: null handle");
-    if (!req) return fail(s, NB_ERR_INVALID, "nb_field_eval: null request");
-    if (req->struct_size != sizeof(nb_field_request)) return fail(s, NB_ERR_INVALID, "nb_field_eval: struct_size must be sizeof(nb_field_request)");
-    if (req->flags & ~(NB_FIELD_AT_BODIES | NB_FIELD_F64 | NB_FIELD_DEVICE)) return fail(s, NB_ERR_INVALID, "nb_field_eval: unknown bits in flags");
+    const char* who = "nb_field_eval";
+    if (int rc = query_begin(s, req, kQField, s ? s->n : 0u, who, [&]() -> const char* {
+            return !req->accel && !req->phi ? "accel and phi are both NULL" : nullptr; })) return rc;
     const bool at = (req->flags & NB_FIELD_AT_BODIES) != 0, dev = (req->flags & NB_FIELD_DEVICE) != 0;
-    if (at && req->points) return fail(s, NB_ERR_INVALID, "nb_field_eval: points must be NULL with NB_FIELD_AT_BODIES");
-    if (!at && !req->points) return fail(s, NB_ERR_INVALID, "nb_field_eval: points is NULL (and NB_FIELD_AT_BODIES is not set)");
-    if (req->m == 0) return fail(s, NB_ERR_INVALID, "nb_field_eval: m must be >= 1");
-    if (!req->accel && !req->phi) return fail(s, NB_ERR_INVALID, "nb_field_eval: accel and phi are both NULL");
-    if (at && (uint64_t)req->first_body + req->m > s->n) return fail(s, NB_ERR_INVALID, "nb_field_eval: first_body + m exceeds n");
-    if (!s->uploaded) return fail(s, NB_ERR_STATE, "nb_field_eval: nothing uploaded yet");
-    if (!s->params_set) return fail(s, NB_ERR_STATE, "nb_field_eval: nb_set_params has not been called (G)");
-    NB_HIP(s, hipSetDevice(s->device));
-    if (int rc = finish_gather(s)) return rc;     // other ranks' rows must have landed
-
     const bool wide = s->f64 || (req->flags & NB_FIELD_F64);      // fp64 arithmetic and outputs
-    const size_t in_row = 4 * s->esz, out_esz = wide ? 8 : 4;
+    const size_t out_esz = wide ? 8 : 4;
     const uint32_t m = req->m;
-    const char* pts = at ? (const char*)s->bodies[s->cur] + in_row * req->first_body : (const char*)req->points;
-    char* acc = (char*)req->accel;
-    char* phi = (char*)req->phi;
-    if (!dev) {
-        if (!at) {
-            if (int rc = field_reserve(s, s->fld_pts, in_row * m)) return rc;
-            NB_HIP(s, hipMemcpyAsync(s->fld_pts.p, req->points, in_row * m, hipMemcpyHostToDevice, s->stream));
-            pts = (const char*)s->fld_pts.p;
-        }
-        if (req->accel) { if (int rc = field_reserve(s, s->fld_acc, 4 * out_esz * m)) return rc; acc = (char*)s->fld_acc.p; }
-        if (req->phi) { if (int rc = field_reserve(s, s->fld_phi, out_esz * m)) return rc; phi = (char*)s->fld_phi.p; }
-    }
+    q_array pts = query_points(s, req), acc = {req->accel, 4 * out_esz, true, &s->q_out[0], true}, phi = {req->phi, out_esz, true, &s->q_out[1], true};
+    if (int rc = stage_in(s, dev, {&pts, &acc, &phi}, true, 0, m, who)) return rc;
 
     const uint32_t rows = wide ? nb::kFieldRows64 : nb::kFieldRows;      // points per workgroup
-    const uint32_t batch_max = wide ? 65536u : 262144u;
-    const uint64_t part_rows = std::max<uint64_t>(kFieldPartRows, (uint64_t)2 * field_blocks_wanted(s) * rows);
     const void* bodies = s->bodies[s->cur];
     const void* zero_row = s->zero_row;
     uint32_t n = s->n, at_flag = at ? 1u : 0u;
     double G = s->G, eps2d = s->eps2;
     float eps2f = (float)s->eps2;
     for (uint32_t done = 0; done < m;) {
-        uint32_t mb = std::min(m - done, batch_max), chunks, per;
-        field_shape(s, ceil_div(mb, rows), &chunks, &per);
-        while ((uint64_t)chunks * mb > part_rows && mb > rows) {     // fewer points at once: the partial sums stay bounded
-            mb = std::max(rows, (mb / 2 + rows - 1) / rows * rows);
-            field_shape(s, ceil_div(mb, rows), &chunks, &per);
-        }
-        if (int rc = field_reserve(s, s->fld_part, (size_t)4 * out_esz * chunks * mb)) return rc;
-        const void* p = pts + in_row * done;
-        void* part = s->fld_part.p;
-        void* a = acc ? acc + 4 * out_esz * done : nullptr;
-        void* f = phi ? phi + out_esz * done : nullptr;
+        uint32_t chunks, per, mb = part_shape(s, m - done, rows, wide, &chunks, &per);
+        if (int rc = field_reserve(s, s->q_part, (size_t)4 * out_esz * chunks * mb, who)) return rc;
+        const void* p = pts.at(done);
+        void* part = s->q_part.p;
+        void* a = acc.at(done);
+        void* f = phi.at(done);
         uint32_t self0 = req->first_body + done;
         dim3 grid(ceil_div(mb, rows), chunks), block(nb::kBlock);
         if (wide) {
@@ -2063,99 +2174,58 @@ int nb_field_eval(nb_sim* s, const nb_field_request* req)
         }
         done += mb;
     }
-    if (!dev) {
-        if (req->accel) NB_HIP(s, hipMemcpyAsync(req->accel, acc, 4 * out_esz * m, hipMemcpyDeviceToHost, s->stream));
-        if (req->phi) NB_HIP(s, hipMemcpyAsync(req->phi, phi, out_esz * m, hipMemcpyDeviceToHost, s->stream));
-        NB_HIP(s, hipStreamSynchronize(s->stream));
-    }
-    return NB_OK;
+    return stage_out(s, dev, {&acc, &phi}, true, 0, m);
 }
 
 /* ---- neighbour queries -------------------------------------------------------------------- */
 
 namespace {
 
+uint32_t nbr_rows(const nb_sim* s) { return s->f64 ? nb::kNbrRows64 : nb::kNbrRows; }      // points per workgroup
+
 // The first batch of an m-point request against `rows` bodies: its points, j-chunks and bodies per chunk -- nb_field_eval's rule
 // (field_shape on the handle's n: the answer does not depend on the cut, and rows <= n only ever leaves chunks at the end empty).
 void nbr_shape(const nb_sim* s, uint32_t m, uint32_t rows, uint32_t* batch, uint32_t* chunks, uint32_t* per)
 {
-    const uint32_t prow = s->f64 ? nb::kNbrRows64 : nb::kNbrRows;
-    const uint64_t part_rows = std::max<uint64_t>(kFieldPartRows, (uint64_t)2 * field_blocks_wanted(s) * prow);
-    uint32_t mb = std::min(m, s->f64 ? 65536u : 262144u);
-    field_shape(s, ceil_div(mb, prow), chunks, per);
-    while ((uint64_t)*chunks * mb > part_rows && mb > prow) {       // fewer points at once: the partial rows stay bounded
-        mb = std::max(prow, (mb / 2 + prow - 1) / prow * prow);
-        field_shape(s, ceil_div(mb, prow), chunks, per);
-    }
+    *batch = part_shape(s, m, nbr_rows(s), s->f64, chunks, per);
     *chunks = std::max(1u, std::min(*chunks, ceil_div(rows, *per)));      // chunks that start past the last row hold nothing
-    *batch = mb;
 }
+
+// the radius checks that nb_neighbor_lists and nb_split_force share with nb_neighbors
+const char* bad_radius(double radius) { return radius >= 0.0 ? nullptr : "radius must be >= 0 (0: none given)"; }
 
 }  // namespace
 
 extern "C++" int nbi::neighbors(nb_sim* s, const nb_neighbor_request* req, uint32_t rows, const char* who)
 {
-    const std::string w = std::string(who) + ": ";
-    if (!s) return fail(nullptr, NB_ERR_INVALID, w + "null handle");
-    if (!req) return fail(s, NB_ERR_INVALID, w + "null request");
-    if (req->struct_size != sizeof(nb_neighbor_request)) return fail(s, NB_ERR_INVALID, w + "struct_size must be sizeof(nb_neighbor_request)");
-    if (req->flags & ~(NB_NBR_AT_BODIES | NB_NBR_DEVICE)) return fail(s, NB_ERR_INVALID, w + "unknown bits in flags");
+    if (int rc = query_begin(s, req, kQNbr, rows, who, [&]() -> const char* {
+            if (!req->index && !req->dist2 && !req->count) return "index, dist2 and count are all NULL";
+            if (bad_radius(req->radius)) return bad_radius(req->radius);
+            return req->count && !req->radii && !(req->radius > 0.0) ? "count needs radii or radius > 0" : nullptr; })) return rc;
     const bool at = (req->flags & NB_NBR_AT_BODIES) != 0, dev = (req->flags & NB_NBR_DEVICE) != 0;
-    if (at && req->points) return fail(s, NB_ERR_INVALID, w + "points must be NULL with NB_NBR_AT_BODIES");
-    if (!at && !req->points) return fail(s, NB_ERR_INVALID, w + "points is NULL (and NB_NBR_AT_BODIES is not set)");
-    if (req->m == 0) return fail(s, NB_ERR_INVALID, w + "m must be >= 1");
-    if (!req->index && !req->dist2 && !req->count) return fail(s, NB_ERR_INVALID, w + "index, dist2 and count are all NULL");
-    if (!(req->radius >= 0.0)) return fail(s, NB_ERR_INVALID, w + "radius must be >= 0 (0: none given)");
-    if (req->count && !req->radii && !(req->radius > 0.0)) return fail(s, NB_ERR_INVALID, w + "count needs radii or radius > 0");
-    if (at && (uint64_t)req->first_body + req->m > rows) return fail(s, NB_ERR_INVALID, w + "first_body + m exceeds n");
-    if (!s->uploaded) return fail(s, NB_ERR_STATE, w + "nothing uploaded yet");
-    NB_HIP(s, hipSetDevice(s->device));
-    if (int rc = finish_gather(s)) return rc;     // other ranks' rows must have landed
-
-    const size_t esz = s->esz, in_row = 4 * esz;
+    const size_t esz = s->esz;
     const uint32_t m = req->m;
-    const char* pts = at ? (const char*)s->bodies[s->cur] + in_row * req->first_body : (const char*)req->points;
-    const char* rad = req->count ? (const char*)req->radii : nullptr;      // the radius only enters the count
-    char* idx = (char*)req->index;
-    char* d2 = (char*)req->dist2;
-    char* cnt = (char*)req->count;
-    if (!dev) {
-        if (!at) {
-            if (int rc = field_reserve(s, s->fld_pts, in_row * m, who)) return rc;
-            NB_HIP(s, hipMemcpyAsync(s->fld_pts.p, req->points, in_row * m, hipMemcpyHostToDevice, s->stream));
-            pts = (const char*)s->fld_pts.p;
-        }
-        if (rad) {
-            if (int rc = field_reserve(s, s->nbr_rad, esz * m, who)) return rc;
-            NB_HIP(s, hipMemcpyAsync(s->nbr_rad.p, req->radii, esz * m, hipMemcpyHostToDevice, s->stream));
-            rad = (const char*)s->nbr_rad.p;
-        }
-        if (idx) { if (int rc = field_reserve(s, s->nbr_idx, 4 * (size_t)m, who)) return rc; idx = (char*)s->nbr_idx.p; }
-        if (d2) { if (int rc = field_reserve(s, s->nbr_d2, esz * m, who)) return rc; d2 = (char*)s->nbr_d2.p; }
-        if (cnt) { if (int rc = field_reserve(s, s->nbr_cnt, 4 * (size_t)m, who)) return rc; cnt = (char*)s->nbr_cnt.p; }
-    }
-    if (!s->f64 && !s->nbr_inf.p) {
-        static const float inf_row[4] = {HUGE_VALF, HUGE_VALF, HUGE_VALF, 0.0f};
-        if (int rc = field_reserve(s, s->nbr_inf, 64, who)) return rc;
-        NB_HIP(s, hipMemcpyAsync(s->nbr_inf.p, inf_row, sizeof inf_row, hipMemcpyHostToDevice, s->stream));
-    }
+    q_array pts = query_points(s, req), rad = {req->count ? req->radii : nullptr, esz, false, &s->q_in[1], true};      // the radius only enters the count
+    q_array idx = {req->index, 4, true, &s->q_out[0], true}, d2 = {req->dist2, esz, true, &s->q_out[1], true}, cnt = {req->count, 4, true, &s->q_out[2], true};
+    if (int rc = stage_in(s, dev, {&pts, &rad, &idx, &d2, &cnt}, true, 0, m, who)) return rc;
+    if (int rc = ensure_inf_row(s, who)) return rc;
 
-    const uint32_t prow = s->f64 ? nb::kNbrRows64 : nb::kNbrRows;      // points per workgroup
+    const uint32_t prow = nbr_rows(s);
     const void* bodies = s->bodies[s->cur];
-    const void* inf_row = s->nbr_inf.p;
+    const void* inf_row = s->q_inf.p;
     uint32_t n = rows, at_flag = at ? 1u : 0u;
     double rd = req->radius;
     float rf = (float)req->radius;
     for (uint32_t done = 0; done < m;) {
         uint32_t mb, chunks, per;
         nbr_shape(s, m - done, rows, &mb, &chunks, &per);
-        if (int rc = field_reserve(s, s->fld_part, (size_t)16 * chunks * mb, who)) return rc;
-        const void* p = pts + in_row * done;
-        const void* r = rad ? rad + esz * done : nullptr;
-        void* part = s->fld_part.p;
-        void* oi = idx ? idx + (size_t)4 * done : nullptr;
-        void* od = d2 ? d2 + esz * done : nullptr;
-        void* oc = cnt ? cnt + (size_t)4 * done : nullptr;
+        if (int rc = field_reserve(s, s->q_part, (size_t)16 * chunks * mb, who)) return rc;
+        const void* p = pts.at(done);
+        const void* r = rad.at(done);
+        void* part = s->q_part.p;
+        void* oi = idx.at(done);
+        void* od = d2.at(done);
+        void* oc = cnt.at(done);
         uint32_t self0 = req->first_body + done;
         dim3 grid(ceil_div(mb, prow), chunks), block(nb::kBlock);
         void* rargs[] = {&part, &mb, &chunks, &oi, &od, &oc};
@@ -2171,27 +2241,17 @@ extern "C++" int nbi::neighbors(nb_sim* s, const nb_neighbor_request* req, uint3
         }
         done += mb;
     }
-    if (!dev) {
-        if (req->index) NB_HIP(s, hipMemcpyAsync(req->index, idx, 4 * (size_t)m, hipMemcpyDeviceToHost, s->stream));
-        if (req->dist2) NB_HIP(s, hipMemcpyAsync(req->dist2, d2, esz * m, hipMemcpyDeviceToHost, s->stream));
-        if (req->count) NB_HIP(s, hipMemcpyAsync(req->count, cnt, 4 * (size_t)m, hipMemcpyDeviceToHost, s->stream));
-        NB_HIP(s, hipStreamSynchronize(s->stream));
-    }
-    return NB_OK;
+    return stage_out(s, dev, {&idx, &d2, &cnt}, true, 0, m);
 }
 
 int nb_neighbors(nb_sim* s, const nb_neighbor_request* req) { return nbi::neighbors(s, req, s ? s->n : 0u, "nb_neighbors"); }
 
 int nb_neighbors_shape(nb_sim* s, uint32_t m, uint32_t* batch, uint32_t* chunks, uint32_t* j_per_chunk)
 {
-    if (!s) return fail(nullptr, NB_ERR_INVALID, "nb_neighbors_shape: null handle");
-    if (m == 0) return fail(s, NB_ERR_INVALID, "nb_neighbors_shape: m must be >= 1");
+    if (int rc = shape_begin(s, "nb_neighbors_shape", m)) return rc;
     uint32_t b, c, per;
     nbr_shape(s, m, s->n, &b, &c, &per);
-    if (batch) *batch = b;
-    if (chunks) *chunks = c;
-    if (j_per_chunk) *j_per_chunk = per;
-    return NB_OK;
+    return shape_put(b, c, per, batch, chunks, j_per_chunk);
 }
 
 /* ---- neighbour lists ---------------------------------------------------------------------- */
@@ -2201,134 +2261,85 @@ namespace {
 constexpr uint32_t kNblMaxCap = 4096;                   // most entries of one row
 constexpr uint64_t kNblListBytes = 256ull << 20;        // most bytes of `list` one batch writes (or one workgroup's points x cap, if that is more)
 
-// nbr_shape with the rows of `list` bounded too: the batch is halved in whole workgroups' worth of points until
-// batch x cap x 4 <= kNblListBytes (one workgroup's points is the floor), the chunks follow the batch as in nbr_shape.
+const char* bad_cap(uint32_t cap) { return cap == 0 || cap > kNblMaxCap ? "cap must be in 1 .. 4096" : nullptr; }
+
+// nbr_shape with the rows of `list` bounded too: the batch is halved until batch x cap x 4 <= kNblListBytes, the chunks follow the
+// batch as in nbr_shape (which never takes more points than it is given).
 void nbl_shape(const nb_sim* s, uint32_t m, uint32_t cap, uint32_t rows, uint32_t* batch, uint32_t* chunks, uint32_t* per)
 {
-    const uint32_t prow = s->f64 ? nb::kNbrRows64 : nb::kNbrRows;
-    uint32_t mb;
-    nbr_shape(s, m, rows, &mb, chunks, per);
-    while ((uint64_t)mb * cap * 4 > kNblListBytes && mb > prow) {
-        const uint32_t half = std::max(prow, (mb / 2 + prow - 1) / prow * prow);
-        nbr_shape(s, half, rows, &mb, chunks, per);       // (never more than `half` points)
-    }
-    *batch = mb;
+    *batch = fit_batch(m, nbr_rows(s), [&](uint32_t mb) { nbr_shape(s, mb, rows, &mb, chunks, per); return mb; },
+                       [&](uint32_t mb) { return (uint64_t)mb * cap * 4 > kNblListBytes; });
 }
 
 }  // namespace
 
 extern "C++" int nbi::neighbor_lists(nb_sim* s, const nb_neighbor_list_request* req, uint32_t rows, const char* who)
 {
-    const std::string w = std::string(who) + ": ";
-    if (!s) return fail(nullptr, NB_ERR_INVALID, w + "null handle");
-    if (!req) return fail(s, NB_ERR_INVALID, w + "null request");
-    if (req->struct_size != sizeof(nb_neighbor_list_request)) return fail(s, NB_ERR_INVALID, w + "struct_size must be sizeof(nb_neighbor_list_request)");
-    if (req->flags & ~(NB_NBR_AT_BODIES | NB_NBR_DEVICE)) return fail(s, NB_ERR_INVALID, w + "unknown bits in flags");
+    if (int rc = query_begin(s, req, kQNbl, rows, who, [&]() -> const char* {
+            if (!req->list) return "list is NULL";
+            if (bad_cap(req->cap)) return bad_cap(req->cap);
+            if (req->reserved != 0) return "reserved must be 0";
+            if (bad_radius(req->radius)) return bad_radius(req->radius);
+            return !req->radii && !(req->radius > 0.0) ? "the lists need radii or radius > 0" : nullptr; })) return rc;
     const bool at = (req->flags & NB_NBR_AT_BODIES) != 0, dev = (req->flags & NB_NBR_DEVICE) != 0;
-    if (at && req->points) return fail(s, NB_ERR_INVALID, w + "points must be NULL with NB_NBR_AT_BODIES");
-    if (!at && !req->points) return fail(s, NB_ERR_INVALID, w + "points is NULL (and NB_NBR_AT_BODIES is not set)");
-    if (req->m == 0) return fail(s, NB_ERR_INVALID, w + "m must be >= 1");
-    if (!req->list) return fail(s, NB_ERR_INVALID, w + "list is NULL");
-    if (req->cap == 0 || req->cap > kNblMaxCap) return fail(s, NB_ERR_INVALID, w + "cap must be in 1 .. 4096");
-    if (req->reserved != 0) return fail(s, NB_ERR_INVALID, w + "reserved must be 0");
-    if (!(req->radius >= 0.0)) return fail(s, NB_ERR_INVALID, w + "radius must be >= 0 (0: none given)");
-    if (!req->radii && !(req->radius > 0.0)) return fail(s, NB_ERR_INVALID, w + "the lists need radii or radius > 0");
-    if (at && (uint64_t)req->first_body + req->m > rows) return fail(s, NB_ERR_INVALID, w + "first_body + m exceeds n");
-    if (!s->uploaded) return fail(s, NB_ERR_STATE, w + "nothing uploaded yet");
-    NB_HIP(s, hipSetDevice(s->device));
-    if (int rc = finish_gather(s)) return rc;     // other ranks' rows must have landed
-
-    const size_t esz = s->esz, in_row = 4 * esz;
+    const size_t esz = s->esz;
     const uint32_t m = req->m, cap = req->cap;
-    const char* pts = at ? (const char*)s->bodies[s->cur] + in_row * req->first_body : (const char*)req->points;
-    const char* rad = (const char*)req->radii;
-    char* idx = (char*)req->index;
-    char* d2 = (char*)req->dist2;
-    char* cnt = (char*)req->count;
-    if (!dev) {
-        if (!at) {
-            if (int rc = field_reserve(s, s->fld_pts, in_row * m, who)) return rc;
-            NB_HIP(s, hipMemcpyAsync(s->fld_pts.p, req->points, in_row * m, hipMemcpyHostToDevice, s->stream));
-            pts = (const char*)s->fld_pts.p;
-        }
-        if (rad) {
-            if (int rc = field_reserve(s, s->nbr_rad, esz * m, who)) return rc;
-            NB_HIP(s, hipMemcpyAsync(s->nbr_rad.p, req->radii, esz * m, hipMemcpyHostToDevice, s->stream));
-            rad = (const char*)s->nbr_rad.p;
-        }
-        if (idx) { if (int rc = field_reserve(s, s->nbr_idx, 4 * (size_t)m, who)) return rc; idx = (char*)s->nbr_idx.p; }
-        if (d2) { if (int rc = field_reserve(s, s->nbr_d2, esz * m, who)) return rc; d2 = (char*)s->nbr_d2.p; }
-        if (cnt) { if (int rc = field_reserve(s, s->nbr_cnt, 4 * (size_t)m, who)) return rc; cnt = (char*)s->nbr_cnt.p; }
-    }
-    if (!s->f64 && !s->nbr_inf.p) {
-        static const float inf_row[4] = {HUGE_VALF, HUGE_VALF, HUGE_VALF, 0.0f};
-        if (int rc = field_reserve(s, s->nbr_inf, 64, who)) return rc;
-        NB_HIP(s, hipMemcpyAsync(s->nbr_inf.p, inf_row, sizeof inf_row, hipMemcpyHostToDevice, s->stream));
-    }
+    q_array pts = query_points(s, req), rad = {req->radii, esz, false, &s->q_in[1], true}, lst = {req->list, (size_t)4 * cap, true, &s->q_out[3], false};
+    q_array idx = {req->index, 4, true, &s->q_out[0], true}, d2 = {req->dist2, esz, true, &s->q_out[1], true}, cnt = {req->count, 4, true, &s->q_out[2], true};
+    if (int rc = stage_in(s, dev, {&pts, &rad, &idx, &d2, &cnt}, true, 0, m, who)) return rc;
+    if (int rc = ensure_inf_row(s, who)) return rc;
 
-    const uint32_t prow = s->f64 ? nb::kNbrRows64 : nb::kNbrRows;      // points per workgroup
+    const uint32_t prow = nbr_rows(s);
     const void* bodies = s->bodies[s->cur];
-    const void* inf_row = s->nbr_inf.p;
+    const void* inf_row = s->q_inf.p;
     uint32_t n = rows, at_flag = at ? 1u : 0u, cap_arg = cap;
     double rd = req->radius;
     float rf = (float)req->radius;
     for (uint32_t done = 0; done < m;) {
         uint32_t mb, chunks, per;
         nbl_shape(s, m - done, cap, rows, &mb, &chunks, &per);
-        const size_t list_bytes = (size_t)4 * cap * mb;
-        if (int rc = field_reserve(s, s->fld_part, (size_t)16 * chunks * mb, who)) return rc;
-        if (int rc = field_reserve(s, s->nbl_off, (size_t)4 * chunks * mb, who)) return rc;
-        if (!dev) { if (int rc = field_reserve(s, s->nbl_list, list_bytes, who)) return rc; }
-        const void* p = pts + in_row * done;
-        const void* r = rad ? rad + esz * done : nullptr;
-        void* part = s->fld_part.p;
-        void* off = s->nbl_off.p;
-        void* lst = dev ? (void*)(req->list + (size_t)cap * done) : s->nbl_list.p;
-        void* oi = idx ? idx + (size_t)4 * done : nullptr;
-        void* od = d2 ? d2 + esz * done : nullptr;
-        void* oc = cnt ? cnt + (size_t)4 * done : nullptr;
+        if (int rc = field_reserve(s, s->q_part, (size_t)16 * chunks * mb, who)) return rc;
+        if (int rc = field_reserve(s, s->q_off, (size_t)4 * chunks * mb, who)) return rc;
+        if (int rc = stage_in(s, dev, {&lst}, false, done, mb, who)) return rc;      // a host-pointer request stages its rows batch by batch
+        const void* p = pts.at(done);
+        const void* r = rad.at(done);
+        void* part = s->q_part.p;
+        void* off = s->q_off.p;
+        void* l = lst.at(done);
+        void* oi = idx.at(done);
+        void* od = d2.at(done);
+        void* oc = cnt.at(done);
         uint32_t self0 = req->first_body + done;
         dim3 grid(ceil_div(mb, prow), chunks), block(nb::kBlock);
-        NB_HIP(s, hipMemsetAsync(lst, 0xff, list_bytes, s->stream));          // what pads the rows
+        NB_HIP(s, hipMemsetAsync(l, 0xff, (size_t)4 * cap * mb, s->stream));          // what pads the rows
         void* oargs[] = {&part, &mb, &chunks, &off, &oi, &od, &oc};
         if (s->f64) {
             void* args[] = {&bodies, &p, &r, &part, &n, &mb, &per, &rd, &at_flag, &self0};
             NB_HIP(s, hipLaunchKernel((const void*)&nb::nb_nbr64<double>, grid, block, args, 0, s->stream));
             NB_HIP(s, hipLaunchKernel((const void*)&nb::nb_nbl_offsets<double>, dim3(ceil_div(mb, nb::kBlock)), block, oargs, 0, s->stream));
-            void* fargs[] = {&bodies, &p, &r, &off, &lst, &n, &mb, &per, &rd, &at_flag, &self0, &cap_arg};
+            void* fargs[] = {&bodies, &p, &r, &off, &l, &n, &mb, &per, &rd, &at_flag, &self0, &cap_arg};
             NB_HIP(s, hipLaunchKernel((const void*)&nb::nb_nbl64<double>, grid, block, fargs, 0, s->stream));
         } else {
             void* args[] = {&bodies, &p, &r, &part, &n, &mb, &per, &rf, &at_flag, &self0, &inf_row};
             NB_HIP(s, hipLaunchKernel((const void*)&nb::nb_nbr_pk<true>, grid, block, args, 0, s->stream));
             NB_HIP(s, hipLaunchKernel((const void*)&nb::nb_nbl_offsets<float>, dim3(ceil_div(mb, nb::kBlock)), block, oargs, 0, s->stream));
-            void* fargs[] = {&bodies, &p, &r, &off, &lst, &n, &mb, &per, &rf, &at_flag, &self0, &cap_arg, &inf_row};
+            void* fargs[] = {&bodies, &p, &r, &off, &l, &n, &mb, &per, &rf, &at_flag, &self0, &cap_arg, &inf_row};
             NB_HIP(s, hipLaunchKernel((const void*)&nb::nb_nbl_pk<>, grid, block, fargs, 0, s->stream));
         }
-        if (!dev) NB_HIP(s, hipMemcpyAsync(req->list + (size_t)cap * done, lst, list_bytes, hipMemcpyDeviceToHost, s->stream));
+        if (int rc = stage_out(s, dev, {&lst}, false, done, mb)) return rc;
         done += mb;
     }
-    if (!dev) {
-        if (req->index) NB_HIP(s, hipMemcpyAsync(req->index, idx, 4 * (size_t)m, hipMemcpyDeviceToHost, s->stream));
-        if (req->dist2) NB_HIP(s, hipMemcpyAsync(req->dist2, d2, esz * m, hipMemcpyDeviceToHost, s->stream));
-        if (req->count) NB_HIP(s, hipMemcpyAsync(req->count, cnt, 4 * (size_t)m, hipMemcpyDeviceToHost, s->stream));
-        NB_HIP(s, hipStreamSynchronize(s->stream));
-    }
-    return NB_OK;
+    return stage_out(s, dev, {&idx, &d2, &cnt}, true, 0, m);
 }
 
 int nb_neighbor_lists(nb_sim* s, const nb_neighbor_list_request* req) { return nbi::neighbor_lists(s, req, s ? s->n : 0u, "nb_neighbor_lists"); }
 
 int nb_neighbor_lists_shape(nb_sim* s, uint32_t m, uint32_t cap, uint32_t* batch, uint32_t* chunks, uint32_t* j_per_chunk)
 {
-    if (!s) return fail(nullptr, NB_ERR_INVALID, "nb_neighbor_lists_shape: null handle");
-    if (m == 0) return fail(s, NB_ERR_INVALID, "nb_neighbor_lists_shape: m must be >= 1");
-    if (cap == 0 || cap > kNblMaxCap) return fail(s, NB_ERR_INVALID, "nb_neighbor_lists_shape: cap must be in 1 .. 4096");
+    if (int rc = shape_begin(s, "nb_neighbor_lists_shape", m, bad_cap(cap))) return rc;
     uint32_t b, c, per;
     nbl_shape(s, m, cap, s->n, &b, &c, &per);
-    if (batch) *batch = b;
-    if (chunks) *chunks = c;
-    if (j_per_chunk) *j_per_chunk = per;
-    return NB_OK;
+    return shape_put(b, c, per, batch, chunks, j_per_chunk);
 }
 
 /* ---- k nearest neighbours ----------------------------------------------------------------- */
@@ -2338,22 +2349,21 @@ namespace {
 constexpr uint64_t kKnnRowBytes = kNblListBytes;        // most bytes of partial rows (chunks x batch x k x 8) one batch leaves
 constexpr uint32_t kKnnMaxChunks = 512;                 // most j-chunks: nb_knn_merge keeps 64 bytes of LDS per chunk (32 KiB)
 
+const char* bad_k(uint32_t k) { return k == 0 || k > nb::kKnnMaxK ? "k must be in 1 .. 64" : nullptr; }
+
 // The shape of a WHOLE m-point request: nbr_shape's batch and chunks for m points (at most kKnnMaxChunks chunks: few points against
-// millions of bodies would get more); the batch is then halved in whole workgroups' worth of points, the chunks kept, until
-// chunks x batch x k x 8 <= kKnnRowBytes (one workgroup's points is the floor).  Every batch of the request, the last and shorter
-// one included, runs against these chunks: fewer, longer chunks are what a k-nearest pass wants, since every chunk has to find its
-// own k candidates first.
+// millions of bodies would get more); the batch is then halved, the chunks kept, until chunks x batch x k x 8 <= kKnnRowBytes.
+// Every batch of the request, the last and shorter one included, runs against these chunks: fewer, longer chunks are what a
+// k-nearest pass wants, since every chunk has to find its own k candidates first.
 void knn_shape(const nb_sim* s, uint32_t m, uint32_t k, uint32_t rows, uint32_t* batch, uint32_t* chunks, uint32_t* per)
 {
-    const uint32_t prow = s->f64 ? nb::kNbrRows64 : nb::kNbrRows;
     uint32_t mb;
     nbr_shape(s, m, rows, &mb, chunks, per);
     if (*chunks > kKnnMaxChunks) {
         *per = ceil_div(ceil_div(rows, kKnnMaxChunks), (uint32_t)nb::kTile) * nb::kTile;
         *chunks = ceil_div(rows, *per);
     }
-    while ((uint64_t)*chunks * mb * k * 8 > kKnnRowBytes && mb > prow) mb = std::max(prow, (mb / 2 + prow - 1) / prow * prow);
-    *batch = mb;
+    *batch = fit_batch(mb, nbr_rows(s), as_it_is, [&](uint32_t b) { return (uint64_t)*chunks * b * k * 8 > kKnnRowBytes; });
 }
 
 #ifdef NB_TUNING    // calibration build only: what the passes did, summed over the calls since the last reset (tools/knn_bench.py --stats)
@@ -2371,55 +2381,32 @@ extern "C" __attribute__((visibility("default"))) void nb_tuning_knn_stats(uint6
 
 extern "C++" int nbi::knn(nb_sim* s, const nb_knn_request* req, uint32_t rows, const char* who)
 {
-    const std::string w = std::string(who) + ": ";
-    if (!s) return fail(nullptr, NB_ERR_INVALID, w + "null handle");
-    if (!req) return fail(s, NB_ERR_INVALID, w + "null request");
-    if (req->struct_size != sizeof(nb_knn_request)) return fail(s, NB_ERR_INVALID, w + "struct_size must be sizeof(nb_knn_request)");
-    if (req->flags & ~(NB_NBR_AT_BODIES | NB_NBR_DEVICE)) return fail(s, NB_ERR_INVALID, w + "unknown bits in flags");
+    if (int rc = query_begin(s, req, kQKnn, rows, who, [&]() -> const char* {
+            if (bad_k(req->k)) return bad_k(req->k);
+            if (req->reserved != 0) return "reserved must be 0";
+            return !req->index && !req->dist2 ? "index and dist2 are both NULL" : nullptr; })) return rc;
     const bool at = (req->flags & NB_NBR_AT_BODIES) != 0, dev = (req->flags & NB_NBR_DEVICE) != 0;
-    if (at && req->points) return fail(s, NB_ERR_INVALID, w + "points must be NULL with NB_NBR_AT_BODIES");
-    if (!at && !req->points) return fail(s, NB_ERR_INVALID, w + "points is NULL (and NB_NBR_AT_BODIES is not set)");
-    if (req->m == 0) return fail(s, NB_ERR_INVALID, w + "m must be >= 1");
-    if (req->k == 0 || req->k > nb::kKnnMaxK) return fail(s, NB_ERR_INVALID, w + "k must be in 1 .. 64");
-    if (req->reserved != 0) return fail(s, NB_ERR_INVALID, w + "reserved must be 0");
-    if (!req->index && !req->dist2) return fail(s, NB_ERR_INVALID, w + "index and dist2 are both NULL");
-    if (at && (uint64_t)req->first_body + req->m > rows) return fail(s, NB_ERR_INVALID, w + "first_body + m exceeds n");
-    if (!s->uploaded) return fail(s, NB_ERR_STATE, w + "nothing uploaded yet");
-    NB_HIP(s, hipSetDevice(s->device));
-    if (int rc = finish_gather(s)) return rc;     // other ranks' rows must have landed
-
-    const size_t esz = s->esz, in_row = 4 * esz, ent = s->f64 ? 16 : 8;
+    const size_t esz = s->esz, ent = s->f64 ? 16 : 8;
     const uint32_t m = req->m, cap = nb::knn_cap(req->k);
-    const char* pts = at ? (const char*)s->bodies[s->cur] + in_row * req->first_body : (const char*)req->points;
-    if (!dev && !at) {
-        if (int rc = field_reserve(s, s->fld_pts, in_row * m, who)) return rc;
-        NB_HIP(s, hipMemcpyAsync(s->fld_pts.p, req->points, in_row * m, hipMemcpyHostToDevice, s->stream));
-        pts = (const char*)s->fld_pts.p;
-    }
-    if (!s->f64 && !s->nbr_inf.p) {
-        static const float inf_row[4] = {HUGE_VALF, HUGE_VALF, HUGE_VALF, 0.0f};
-        if (int rc = field_reserve(s, s->nbr_inf, 64, who)) return rc;
-        NB_HIP(s, hipMemcpyAsync(s->nbr_inf.p, inf_row, sizeof inf_row, hipMemcpyHostToDevice, s->stream));
-    }
-
-    const uint32_t prow = s->f64 ? nb::kNbrRows64 : nb::kNbrRows;      // points per workgroup
-    const void* bodies = s->bodies[s->cur];
-    const void* inf_row = s->nbr_inf.p;
     uint32_t n = rows, at_flag = at ? 1u : 0u, k = req->k;
+    q_array pts = query_points(s, req), idx = {req->index, (size_t)4 * k, true, &s->q_out[0], false}, d2 = {req->dist2, esz * k, true, &s->q_out[1], false};
+    if (int rc = stage_in(s, dev, {&pts}, true, 0, m, who)) return rc;
+    if (int rc = ensure_inf_row(s, who)) return rc;
+
+    const uint32_t prow = nbr_rows(s);
+    const void* bodies = s->bodies[s->cur];
+    const void* inf_row = s->q_inf.p;
     uint32_t batch, chunks, per;
     knn_shape(s, m, k, rows, &batch, &chunks, &per);      // once: every batch runs against the same chunks
     const size_t heads = (size_t)chunks * nb::kKnnMergeLanes;      // nb_knn_merge's dynamic LDS (chunks <= kKnnMaxChunks)
     for (uint32_t done = 0; done < m;) {
         uint32_t mb = std::min(batch, m - done);
-        if (int rc = field_reserve(s, s->knn_work, ent * cap * chunks * mb, who)) return rc;
-        if (!dev) {      // a host-pointer request stages its outputs batch by batch
-            if (req->index) { if (int rc = field_reserve(s, s->knn_idx, (size_t)4 * k * mb, who)) return rc; }
-            if (req->dist2) { if (int rc = field_reserve(s, s->knn_d2, esz * k * mb, who)) return rc; }
-        }
-        const void* p = pts + in_row * done;
-        void* work = s->knn_work.p;
-        void* oi = !req->index ? nullptr : dev ? (void*)(req->index + (size_t)k * done) : s->knn_idx.p;
-        void* od = !req->dist2 ? nullptr : dev ? (void*)((char*)req->dist2 + esz * k * done) : s->knn_d2.p;
+        if (int rc = field_reserve(s, s->q_work, ent * cap * chunks * mb, who)) return rc;
+        if (int rc = stage_in(s, dev, {&idx, &d2}, false, done, mb, who)) return rc;      // a host-pointer request stages its outputs batch by batch
+        const void* p = pts.at(done);
+        void* work = s->q_work.p;
+        void* oi = idx.at(done);
+        void* od = d2.at(done);
         uint32_t self0 = req->first_body + done;
         dim3 grid(ceil_div(mb, prow), chunks), block(nb::kBlock);
         void* margs[] = {&work, &mb, &chunks, &k, &oi, &od};
@@ -2462,43 +2449,30 @@ extern "C++" int nbi::knn(nb_sim* s, const nb_knn_request* req, uint32_t rows, c
             }
         }
 #endif
-        if (!dev) {
-            if (req->index) NB_HIP(s, hipMemcpyAsync(req->index + (size_t)k * done, oi, (size_t)4 * k * mb, hipMemcpyDeviceToHost, s->stream));
-            if (req->dist2) NB_HIP(s, hipMemcpyAsync((char*)req->dist2 + esz * k * done, od, esz * k * mb, hipMemcpyDeviceToHost, s->stream));
-        }
+        if (int rc = stage_out(s, dev, {&idx, &d2}, false, done, mb)) return rc;
         done += mb;
     }
-    if (!dev) NB_HIP(s, hipStreamSynchronize(s->stream));
-    return NB_OK;
+    return stage_out(s, dev, {}, true, 0, m);
 }
 
 int nb_knn(nb_sim* s, const nb_knn_request* req) { return nbi::knn(s, req, s ? s->n : 0u, "nb_knn"); }
 
 int nb_knn_shape(nb_sim* s, uint32_t m, uint32_t k, uint32_t* batch, uint32_t* chunks, uint32_t* j_per_chunk)
 {
-    if (!s) return fail(nullptr, NB_ERR_INVALID, "nb_knn_shape: null handle");
-    if (m == 0) return fail(s, NB_ERR_INVALID, "nb_knn_shape: m must be >= 1");
-    if (k == 0 || k > nb::kKnnMaxK) return fail(s, NB_ERR_INVALID, "nb_knn_shape: k must be in 1 .. 64");
+    if (int rc = shape_begin(s, "nb_knn_shape", m, bad_k(k))) return rc;
     uint32_t b, c, per;
     knn_shape(s, m, k, s->n, &b, &c, &per);
-    if (batch) *batch = b;
-    if (chunks) *chunks = c;
-    if (j_per_chunk) *j_per_chunk = per;
-    return NB_OK;
+    return shape_put(b, c, per, batch, chunks, j_per_chunk);
 }
 
 /* ---- forces over neighbour rows ------------------------------------------------------------- */
 
 namespace {
 
-// The rows of every batch but the last of a host-pointer request: nbl_shape's rule for the staged rows -- halved in whole workgroups'
-// worth of rows until batch x cap x 4 <= kNblListBytes (one workgroup's rows is the floor).
+// The rows of every batch but the last of a host-pointer request: nbl_shape's bound for the staged rows, batch x cap x 4 <= kNblListBytes.
 uint32_t lf_batch(const nb_sim* s, uint32_t m, uint32_t cap)
 {
-    const uint32_t prow = nb::lf_rows(s->f64);
-    uint32_t mb = m;
-    while ((uint64_t)mb * cap * 4 > kNblListBytes && mb > prow) mb = std::max(prow, (mb / 2 + prow - 1) / prow * prow);
-    return mb;
+    return fit_batch(m, nb::lf_rows(s->f64), as_it_is, [&](uint32_t mb) { return (uint64_t)mb * cap * 4 > kNblListBytes; });
 }
 
 #define NB_LF_TABLE(K) {nullptr, (const void*)&nb::K<false, false, true>, (const void*)&nb::K<false, true, false>, (const void*)&nb::K<false, true, true>, \
@@ -2517,99 +2491,61 @@ const void* lf_kernel(bool f64, bool a, bool j, bool p)
 
 extern "C++" int nbi::list_force(nb_sim* s, const nb_list_force_request* req, uint32_t rows, const char* who)
 {
-    const std::string w = std::string(who) + ": ";
-    if (!s) return fail(nullptr, NB_ERR_INVALID, w + "null handle");
-    if (!req) return fail(s, NB_ERR_INVALID, w + "null request");
-    if (req->struct_size != sizeof(nb_list_force_request)) return fail(s, NB_ERR_INVALID, w + "struct_size must be sizeof(nb_list_force_request)");
-    if (req->m == 0) return fail(s, NB_ERR_INVALID, w + "m must be >= 1");
-    if (req->flags & ~(NB_LISTF_AT_BODIES | NB_LISTF_DEVICE)) return fail(s, NB_ERR_INVALID, w + "unknown bits in flags");
+    if (int rc = query_begin(s, req, kQListF, rows, who, [&]() -> const char* {
+            const bool at = (req->flags & NB_LISTF_AT_BODIES) != 0;
+            if (!req->list) return "list is NULL";
+            if (bad_cap(req->cap)) return bad_cap(req->cap);
+            if (req->reserved != 0) return "reserved must be 0";
+            if (!req->accel && !req->jerk && !req->phi) return "accel, jerk and phi are all NULL";
+            if (at && req->point_vel) return "point_vel must be NULL with NB_LISTF_AT_BODIES";
+            if (!at && req->jerk && !req->point_vel) return "point_vel is NULL (the jerk at points needs their velocities)";
+            return !at && !req->jerk && req->point_vel ? "point_vel must be NULL when jerk is NULL" : nullptr; })) return rc;
+    if (req->jerk && !s->hermite) return qfail(s, NB_ERR_STATE, who, "jerk needs a Hermite handle (nb_config.integrator = NB_INT_HERMITE4)");
     const bool at = (req->flags & NB_LISTF_AT_BODIES) != 0, dev = (req->flags & NB_LISTF_DEVICE) != 0;
-    if (!req->list) return fail(s, NB_ERR_INVALID, w + "list is NULL");
-    if (req->cap == 0 || req->cap > kNblMaxCap) return fail(s, NB_ERR_INVALID, w + "cap must be in 1 .. 4096");
-    if (req->reserved != 0) return fail(s, NB_ERR_INVALID, w + "reserved must be 0");
-    if (!req->accel && !req->jerk && !req->phi) return fail(s, NB_ERR_INVALID, w + "accel, jerk and phi are all NULL");
-    if (at && req->points) return fail(s, NB_ERR_INVALID, w + "points must be NULL with NB_LISTF_AT_BODIES");
-    if (at && req->point_vel) return fail(s, NB_ERR_INVALID, w + "point_vel must be NULL with NB_LISTF_AT_BODIES");
-    if (!at && !req->points) return fail(s, NB_ERR_INVALID, w + "points is NULL (and NB_LISTF_AT_BODIES is not set)");
-    if (!at && req->jerk && !req->point_vel) return fail(s, NB_ERR_INVALID, w + "point_vel is NULL (the jerk at points needs their velocities)");
-    if (!at && !req->jerk && req->point_vel) return fail(s, NB_ERR_INVALID, w + "point_vel must be NULL when jerk is NULL");
-    if (at && (uint64_t)req->first_body + req->m > rows) return fail(s, NB_ERR_INVALID, w + "first_body + m exceeds n");
-    if (!s->uploaded) return fail(s, NB_ERR_STATE, w + "nothing uploaded yet");
-    if (!s->params_set) return fail(s, NB_ERR_STATE, w + "nb_set_params has not been called (G)");
-    if (req->jerk && !s->hermite) return fail(s, NB_ERR_STATE, w + "jerk needs a Hermite handle (nb_config.integrator = NB_INT_HERMITE4)");
-    NB_HIP(s, hipSetDevice(s->device));
-    if (int rc = finish_gather(s)) return rc;     // other ranks' rows must have landed
-
     const size_t esz = s->esz, row4 = 4 * esz;
     const uint32_t m = req->m;
-    const bool wa = req->accel != nullptr, wj = req->jerk != nullptr, wp = req->phi != nullptr;
-    const void* fn = lf_kernel(s->f64, wa, wj, wp);
+    const bool wj = req->jerk != nullptr;
+    const void* fn = lf_kernel(s->f64, req->accel != nullptr, wj, req->phi != nullptr);
     const void* bodies = s->bodies[s->cur];
     const void* vel = wj ? s->vel : nullptr;
     uint32_t n = rows, cap = req->cap, at_flag = at ? 1u : 0u;
     double G = s->G, eps2d = s->eps2;
     float eps2f = (float)s->eps2;
+    // a host-pointer request stages its rows and its outputs batch by batch
+    q_array lst = {req->list, (size_t)4 * cap, false, &s->q_in[3], false}, cnt = {req->count, 4, false, &s->q_in[1], false}, pts = query_points(s, req, false);
+    q_array pvel = {!wj ? nullptr : at ? (const char*)s->vel + row4 * req->first_body : req->point_vel, row4, false, at ? nullptr : &s->q_in[2], false};
+    q_array acc = {req->accel, row4, true, &s->q_out[0], false}, jerk = {req->jerk, row4, true, &s->q_out[1], false}, phi = {req->phi, esz, true, &s->q_out[2], false};
     const uint32_t batch = dev ? m : lf_batch(s, m, cap);        // device pointers are read in place: one launch
     for (uint32_t done = 0; done < m;) {
         uint32_t mb = std::min(batch, m - done);
-        const void* pts = at ? (const char*)bodies + row4 * (req->first_body + done) : (const char*)req->points + row4 * done;
-        const void* pv = !wj ? nullptr : at ? (const char*)s->vel + row4 * (req->first_body + done) : (const char*)req->point_vel + row4 * done;
-        const void* lst = req->list + (size_t)cap * done;
-        const void* cnt = req->count ? req->count + done : nullptr;
-        void* oa = wa ? (char*)req->accel + row4 * done : nullptr;
-        void* oj = wj ? (char*)req->jerk + row4 * done : nullptr;
-        void* op = wp ? (char*)req->phi + esz * done : nullptr;
-        if (!dev) {      // a host-pointer request stages its rows and its outputs batch by batch
-            const size_t list_bytes = (size_t)4 * cap * mb;
-            if (int rc = field_reserve(s, s->nbl_list, list_bytes, who)) return rc;
-            NB_HIP(s, hipMemcpyAsync(s->nbl_list.p, lst, list_bytes, hipMemcpyHostToDevice, s->stream));
-            lst = s->nbl_list.p;
-            if (cnt) {
-                if (int rc = field_reserve(s, s->nbr_cnt, (size_t)4 * mb, who)) return rc;
-                NB_HIP(s, hipMemcpyAsync(s->nbr_cnt.p, cnt, (size_t)4 * mb, hipMemcpyHostToDevice, s->stream));
-                cnt = s->nbr_cnt.p;
-            }
-            if (!at) {
-                if (int rc = field_reserve(s, s->fld_pts, row4 * mb, who)) return rc;
-                NB_HIP(s, hipMemcpyAsync(s->fld_pts.p, pts, row4 * mb, hipMemcpyHostToDevice, s->stream));
-                pts = s->fld_pts.p;
-                if (wj) {
-                    if (int rc = field_reserve(s, s->lf_pvel, row4 * mb, who)) return rc;
-                    NB_HIP(s, hipMemcpyAsync(s->lf_pvel.p, pv, row4 * mb, hipMemcpyHostToDevice, s->stream));
-                    pv = s->lf_pvel.p;
-                }
-            }
-            if (wa) { if (int rc = field_reserve(s, s->fld_acc, row4 * mb, who)) return rc; oa = s->fld_acc.p; }
-            if (wj) { if (int rc = field_reserve(s, s->lf_jerk, row4 * mb, who)) return rc; oj = s->lf_jerk.p; }
-            if (wp) { if (int rc = field_reserve(s, s->fld_phi, esz * mb, who)) return rc; op = s->fld_phi.p; }
-        }
+        if (int rc = stage_in(s, dev, {&lst, &cnt, &pts, &pvel, &acc, &jerk, &phi}, false, done, mb, who)) return rc;
+        const void* p = pts.at(done);
+        const void* pv = pvel.at(done);
+        const void* l = lst.at(done);
+        const void* c = cnt.at(done);
+        void* oa = acc.at(done);
+        void* oj = jerk.at(done);
+        void* op = phi.at(done);
         uint32_t self0 = req->first_body + done;
         const dim3 grid(ceil_div(mb, nb::lf_rows(s->f64))), block(nb::kBlock);
         if (s->f64) {
-            void* args[] = {&bodies, &vel, &pts, &pv, &lst, &cnt, &n, &mb, &cap, &eps2d, &G, &at_flag, &self0, &oa, &oj, &op};
+            void* args[] = {&bodies, &vel, &p, &pv, &l, &c, &n, &mb, &cap, &eps2d, &G, &at_flag, &self0, &oa, &oj, &op};
             NB_HIP(s, hipLaunchKernel(fn, grid, block, args, 0, s->stream));
         } else {
-            void* args[] = {&bodies, &vel, &pts, &pv, &lst, &cnt, &n, &mb, &cap, &eps2f, &G, &at_flag, &self0, &oa, &oj, &op};
+            void* args[] = {&bodies, &vel, &p, &pv, &l, &c, &n, &mb, &cap, &eps2f, &G, &at_flag, &self0, &oa, &oj, &op};
             NB_HIP(s, hipLaunchKernel(fn, grid, block, args, 0, s->stream));
         }
-        if (!dev) {
-            if (wa) NB_HIP(s, hipMemcpyAsync((char*)req->accel + row4 * done, oa, row4 * mb, hipMemcpyDeviceToHost, s->stream));
-            if (wj) NB_HIP(s, hipMemcpyAsync((char*)req->jerk + row4 * done, oj, row4 * mb, hipMemcpyDeviceToHost, s->stream));
-            if (wp) NB_HIP(s, hipMemcpyAsync((char*)req->phi + esz * done, op, esz * mb, hipMemcpyDeviceToHost, s->stream));
-        }
+        if (int rc = stage_out(s, dev, {&acc, &jerk, &phi}, false, done, mb)) return rc;
         done += mb;
     }
-    if (!dev) NB_HIP(s, hipStreamSynchronize(s->stream));
-    return NB_OK;
+    return stage_out(s, dev, {}, true, 0, m);
 }
 
 int nb_list_force(nb_sim* s, const nb_list_force_request* req) { return nbi::list_force(s, req, s ? s->n : 0u, "nb_list_force"); }
 
 int nb_list_force_shape(nb_sim* s, uint32_t m, uint32_t cap, uint32_t* batch, uint32_t* lanes_per_row)
 {
-    if (!s) return fail(nullptr, NB_ERR_INVALID, "nb_list_force_shape: null handle");
-    if (m == 0) return fail(s, NB_ERR_INVALID, "nb_list_force_shape: m must be >= 1");
-    if (cap == 0 || cap > kNblMaxCap) return fail(s, NB_ERR_INVALID, "nb_list_force_shape: cap must be in 1 .. 4096");
+    if (int rc = shape_begin(s, "nb_list_force_shape", m, bad_cap(cap))) return rc;
     if (batch) *batch = lf_batch(s, m, cap);
     if (lanes_per_row) *lanes_per_row = nb::lf_lanes(s->f64);
     return NB_OK;
@@ -2619,14 +2555,16 @@ int nb_list_force_shape(nb_sim* s, uint32_t m, uint32_t cap, uint32_t* batch, ui
 
 namespace {
 
+uint32_t split_rows(const nb_sim* s) { return s->f64 ? nb::kSplitRows64 : nb::kSplitRows; }      // points per workgroup
+
 // The first batch of an m-point request against `rows` bodies: nbr_shape's rule for nb_split_pk's rows per workgroup, with
-// `planes` partial rows per (point, j-chunk) counted against nb_field_eval's bound of fld_part (the same bytes).  Where the j-chunks
+// `planes` partial rows per (point, j-chunk) counted against nb_field_eval's bound of q_part (the same bytes).  Where the j-chunks
 // field_shape cuts for a batch do not fit, the chunks are made LONGER first (down to what kFieldMaxChunk allows: a workgroup's
 // prologue, epilogue and its rows in nb_split_reduce are paid per chunk, and 2,048 workgroups are wanted, not 2,048-body chunks),
 // and only then is the batch halved (measured: profiles/r15/split_force.md §3).
 void split_shape(const nb_sim* s, uint32_t m, uint32_t rows, uint32_t planes, uint32_t* batch, uint32_t* chunks, uint32_t* per)
 {
-    const uint32_t prow = s->f64 ? nb::kSplitRows64 : nb::kSplitRows;
+    const uint32_t prow = split_rows(s);
     const uint64_t part_rows = std::max<uint64_t>(kFieldPartRows, (uint64_t)2 * field_blocks_wanted(s) * (s->f64 ? nb::kFieldRows64 : nb::kFieldRows)) / planes;
     auto cut = [&](uint32_t mb) {
         field_shape(s, ceil_div(mb, prow), chunks, per);
@@ -2635,74 +2573,39 @@ void split_shape(const nb_sim* s, uint32_t m, uint32_t rows, uint32_t planes, ui
             *per = ceil_div(ceil_div(s->n, (uint32_t)room), (uint32_t)nb::kTile) * nb::kTile;
             *chunks = ceil_div(s->n, *per);
         }
+        return mb;
     };
-    uint32_t mb = std::min(m, s->f64 ? 65536u : 262144u);
-    cut(mb);
-    while ((uint64_t)*chunks * mb > part_rows && mb > prow) {       // fewer points at once: the partial rows stay bounded
-        mb = std::max(prow, (mb / 2 + prow - 1) / prow * prow);
-        cut(mb);
-    }
+    *batch = fit_batch(std::min(m, s->f64 ? 65536u : 262144u), prow, cut, [&](uint32_t mb) { return (uint64_t)*chunks * mb > part_rows; });
     *chunks = std::max(1u, std::min(*chunks, ceil_div(rows, *per)));      // chunks that start past the last row hold nothing
-    *batch = mb;
 }
 
 }  // namespace
 
 extern "C++" int nbi::split_force(nb_sim* s, const nb_split_force_request* req, uint32_t rows, const char* who)
 {
-    const std::string w = std::string(who) + ": ";
-    if (!s) return fail(nullptr, NB_ERR_INVALID, w + "null handle");
-    if (!req) return fail(s, NB_ERR_INVALID, w + "null request");
-    if (req->struct_size != sizeof(nb_split_force_request)) return fail(s, NB_ERR_INVALID, w + "struct_size must be sizeof(nb_split_force_request)");
-    if (req->m == 0) return fail(s, NB_ERR_INVALID, w + "m must be >= 1");
-    if (req->flags & ~(NB_SPLIT_AT_BODIES | NB_SPLIT_DEVICE)) return fail(s, NB_ERR_INVALID, w + "unknown bits in flags");
+    if (int rc = query_begin(s, req, kQSplit, rows, who, [&]() -> const char* {
+            const bool at = (req->flags & NB_SPLIT_AT_BODIES) != 0, wj = req->jerk_irr || req->jerk_reg;
+            if (!req->accel_irr && !req->accel_reg && !wj) return "accel_irr, accel_reg, jerk_irr and jerk_reg are all NULL";
+            if (at && req->point_vel) return "point_vel must be NULL with NB_SPLIT_AT_BODIES";
+            if (!at && wj && !req->point_vel) return "point_vel is NULL (the jerk at points needs their velocities)";
+            if (!at && !wj && req->point_vel) return "point_vel must be NULL when jerk_irr and jerk_reg are NULL";
+            if (bad_radius(req->radius)) return bad_radius(req->radius);
+            return !req->radii && !(req->radius > 0.0) ? "radii is NULL and radius is not > 0" : nullptr; })) return rc;
     const bool at = (req->flags & NB_SPLIT_AT_BODIES) != 0, dev = (req->flags & NB_SPLIT_DEVICE) != 0;
     const bool wj = req->jerk_irr || req->jerk_reg;
-    if (!req->accel_irr && !req->accel_reg && !wj) return fail(s, NB_ERR_INVALID, w + "accel_irr, accel_reg, jerk_irr and jerk_reg are all NULL");
-    if (at && req->points) return fail(s, NB_ERR_INVALID, w + "points must be NULL with NB_SPLIT_AT_BODIES");
-    if (at && req->point_vel) return fail(s, NB_ERR_INVALID, w + "point_vel must be NULL with NB_SPLIT_AT_BODIES");
-    if (!at && !req->points) return fail(s, NB_ERR_INVALID, w + "points is NULL (and NB_SPLIT_AT_BODIES is not set)");
-    if (!at && wj && !req->point_vel) return fail(s, NB_ERR_INVALID, w + "point_vel is NULL (the jerk at points needs their velocities)");
-    if (!at && !wj && req->point_vel) return fail(s, NB_ERR_INVALID, w + "point_vel must be NULL when jerk_irr and jerk_reg are NULL");
-    if (at && (uint64_t)req->first_body + req->m > rows) return fail(s, NB_ERR_INVALID, w + "first_body + m exceeds n");
-    if (!(req->radius >= 0.0)) return fail(s, NB_ERR_INVALID, w + "radius must be >= 0 (0: none given)");
-    if (!req->radii && !(req->radius > 0.0)) return fail(s, NB_ERR_INVALID, w + "radii is NULL and radius is not > 0");
-    if (!s->uploaded) return fail(s, NB_ERR_STATE, w + "nothing uploaded yet");
-    if (!s->params_set) return fail(s, NB_ERR_STATE, w + "nb_set_params has not been called (G)");
-    if (wj && !s->hermite) return fail(s, NB_ERR_STATE, w + "jerk_irr / jerk_reg need a Hermite handle (nb_config.integrator = NB_INT_HERMITE4)");
-    NB_HIP(s, hipSetDevice(s->device));
-    if (int rc = finish_gather(s)) return rc;     // other ranks' rows must have landed
-
+    if (wj && !s->hermite) return qfail(s, NB_ERR_STATE, who, "jerk_irr / jerk_reg need a Hermite handle (nb_config.integrator = NB_INT_HERMITE4)");
     const size_t esz = s->esz, row4 = 4 * esz;
     const uint32_t m = req->m;
     const void* bodies = s->bodies[s->cur];
     const void* vel = wj ? s->vel : nullptr;
-    const char* pts = at ? (const char*)bodies + row4 * req->first_body : (const char*)req->points;
-    const char* pvel = !wj ? nullptr : at ? (const char*)s->vel + row4 * req->first_body : (const char*)req->point_vel;
-    const char* rad = (const char*)req->radii;
-    void* const user[4] = {req->accel_irr, req->accel_reg, req->jerk_irr, req->jerk_reg};
-    char* out[4] = {(char*)user[0], (char*)user[1], (char*)user[2], (char*)user[3]};
-    if (!dev) {      // a host-pointer request is staged whole, as nb_field_eval stages its own: O(m)
-        if (!at) {
-            if (int rc = field_reserve(s, s->fld_pts, row4 * m, who)) return rc;
-            NB_HIP(s, hipMemcpyAsync(s->fld_pts.p, req->points, row4 * m, hipMemcpyHostToDevice, s->stream));
-            pts = (const char*)s->fld_pts.p;
-            if (wj) {
-                if (int rc = field_reserve(s, s->lf_pvel, row4 * m, who)) return rc;
-                NB_HIP(s, hipMemcpyAsync(s->lf_pvel.p, req->point_vel, row4 * m, hipMemcpyHostToDevice, s->stream));
-                pvel = (const char*)s->lf_pvel.p;
-            }
-        }
-        if (rad) {
-            if (int rc = field_reserve(s, s->nbr_rad, esz * m, who)) return rc;
-            NB_HIP(s, hipMemcpyAsync(s->nbr_rad.p, req->radii, esz * m, hipMemcpyHostToDevice, s->stream));
-            rad = (const char*)s->nbr_rad.p;
-        }
-        if (int rc = field_reserve(s, s->split_out, 4 * row4 * m, who)) return rc;
-        for (int p = 0; p < 4; ++p) out[p] = user[p] ? (char*)s->split_out.p + (size_t)p * row4 * m : nullptr;
-    }
+    // a host-pointer request is staged whole, as nb_field_eval stages its own: O(m)
+    q_array pts = query_points(s, req), rad = {req->radii, esz, false, &s->q_in[1], true};
+    q_array pvel = {!wj ? nullptr : at ? (const char*)s->vel + row4 * req->first_body : req->point_vel, row4, false, at ? nullptr : &s->q_in[2], true};
+    q_array out[4] = {{req->accel_irr, row4, true, &s->q_out[0], true}, {req->accel_reg, row4, true, &s->q_out[1], true},
+                      {req->jerk_irr, row4, true, &s->q_out[2], true}, {req->jerk_reg, row4, true, &s->q_out[3], true}};
+    if (int rc = stage_in(s, dev, {&pts, &pvel, &rad, &out[0], &out[1], &out[2], &out[3]}, true, 0, m, who)) return rc;
 
-    const uint32_t prow = s->f64 ? nb::kSplitRows64 : nb::kSplitRows;      // points per workgroup
+    const uint32_t prow = split_rows(s);
     const void* zero_row = s->zero_row;
     uint32_t n = rows, planes = wj ? 4u : 2u;
     double G = s->G, eps2d = s->eps2, rd = req->radius;
@@ -2710,13 +2613,12 @@ extern "C++" int nbi::split_force(nb_sim* s, const nb_split_force_request* req, 
     for (uint32_t done = 0; done < m;) {
         uint32_t mb, chunks, per;
         split_shape(s, m - done, rows, planes, &mb, &chunks, &per);
-        if (int rc = field_reserve(s, s->fld_part, row4 * planes * chunks * mb, who)) return rc;
-        const void* p = pts + row4 * done;
-        const void* pv = pvel ? pvel + row4 * done : nullptr;
-        const void* r = rad ? rad + esz * done : nullptr;
-        void* part = s->fld_part.p;
-        void* o[4];
-        for (int q = 0; q < 4; ++q) o[q] = out[q] ? out[q] + row4 * done : nullptr;
+        if (int rc = field_reserve(s, s->q_part, row4 * planes * chunks * mb, who)) return rc;
+        const void* p = pts.at(done);
+        const void* pv = pvel.at(done);
+        const void* r = rad.at(done);
+        void* part = s->q_part.p;
+        void* o[4] = {out[0].at(done), out[1].at(done), out[2].at(done), out[3].at(done)};
         dim3 grid(ceil_div(mb, prow), chunks), block(nb::kBlock);
         void* rargs[] = {&part, &mb, &chunks, &planes, &G, &o[0], &o[1], &o[2], &o[3]};
         if (s->f64) {
@@ -2732,27 +2634,18 @@ extern "C++" int nbi::split_force(nb_sim* s, const nb_split_force_request* req, 
         }
         done += mb;
     }
-    if (!dev) {
-        for (int q = 0; q < 4; ++q)
-            if (user[q]) NB_HIP(s, hipMemcpyAsync(user[q], out[q], row4 * m, hipMemcpyDeviceToHost, s->stream));
-        NB_HIP(s, hipStreamSynchronize(s->stream));
-    }
-    return NB_OK;
+    return stage_out(s, dev, {&out[0], &out[1], &out[2], &out[3]}, true, 0, m);
 }
 
 int nb_split_force(nb_sim* s, const nb_split_force_request* req) { return nbi::split_force(s, req, s ? s->n : 0u, "nb_split_force"); }
 
 int nb_split_force_shape(nb_sim* s, uint32_t m, uint32_t* batch, uint32_t* chunks, uint32_t* j_per_chunk, uint32_t* rows_per_workgroup)
 {
-    if (!s) return fail(nullptr, NB_ERR_INVALID, "nb_split_force_shape: null handle");
-    if (m == 0) return fail(s, NB_ERR_INVALID, "nb_split_force_shape: m must be >= 1");
+    if (int rc = shape_begin(s, "nb_split_force_shape", m)) return rc;
     uint32_t b, c, per;
     split_shape(s, m, s->n, s->hermite ? 4u : 2u, &b, &c, &per);      // (a Hermite handle: the shape of a request with the jerk pair)
-    if (batch) *batch = b;
-    if (chunks) *chunks = c;
-    if (j_per_chunk) *j_per_chunk = per;
-    if (rows_per_workgroup) *rows_per_workgroup = s->f64 ? nb::kSplitRows64 : nb::kSplitRows;
-    return NB_OK;
+    if (rows_per_workgroup) *rows_per_workgroup = split_rows(s);
+    return shape_put(b, c, per, batch, chunks, j_per_chunk);
 }
 
 /* ---- viewer frame feed -------------------------------------------------------------------- */

@@ -149,28 +149,16 @@ struct nb_sim {
     nb_frame_slot frame[kFrameSlots];
     int frame_next = 0;              // slot the next request writes
     int frame_latest = -1;           // most recently requested slot
-    // nb_field_eval: engine-owned buffers, grown on demand, released by nb_destroy.  pts / acc / phi stage a host-pointer request
-    // (O(m)); part holds one (ax, ay, az, sum m/r) row per (j-chunk, point of a batch): a bounded number of rows whatever m and n are
+    // The queries (nb_field_eval, nb_neighbors, nb_neighbor_lists, nb_knn, nb_list_force, nb_split_force): engine-owned buffers by
+    // role, grown on demand, released by nb_destroy.  The six share them: no two requests overlap on the stream, and within one
+    // request no two arrays take the same slot.  q_in / q_out stage a host-pointer request's inputs ([0] points, [1] radii or counts,
+    // [2] point velocities, [3] list rows) and its outputs, whole (O(m)) or one batch at a time; q_part holds the partial rows per
+    // (j-chunk, point of a batch) and q_off nb_neighbor_lists' uint32 offsets per (j-chunk, point of a batch): a bounded number of
+    // rows whatever m and n are; q_work holds nb_knn's working rows, bounded by its memory rule; q_inf is one row at +inf, the LDS-DMA
+    // source of the f32 neighbour kernels for j past the range: written once, never used for anything else.
     int n_cu = 256;
-    struct field_buf { void* p = nullptr; size_t cap = 0; } fld_pts, fld_acc, fld_phi, fld_part;
-    // nb_neighbors: shares fld_pts (points) and fld_part (16-byte rows (d2, index, count) per (j-chunk, point of a batch)) with nb_field_eval
-    // -- the two never overlap on the stream --; rad / idx / d2 / cnt stage a host-pointer request (O(m)); inf is one row at +inf, the
-    // LDS-DMA source of nb_nbr_pk for j past the range
-    field_buf nbr_rad, nbr_idx, nbr_d2, nbr_cnt, nbr_inf;
-    // nb_neighbor_lists: shares all of the above with nb_neighbors; off holds uint32 [j-chunk][point of a batch], the entries of a
-    // point's row that the chunks before hold (bounded as fld_part is); list stages one batch of a host-pointer request (<= 256 MiB,
-    // or one workgroup's points x cap)
-    field_buf nbl_off, nbl_list;
-    // nb_knn: shares fld_pts and nbr_inf with nb_neighbors; work holds the working rows, knn_cap(k) entries of 8 (f32) or 16 (f64)
-    // bytes per (j-chunk, point of a batch) -- bounded by nb_knn's memory rule --; idx / d2 stage one batch of a host-pointer request
-    field_buf knn_work, knn_idx, knn_d2;
+    struct field_buf { void* p = nullptr; size_t cap = 0; } q_in[4], q_out[4], q_part, q_off, q_work, q_inf;
     field_buf knn_stat;       // the calibration build's counters (NB_TUNING with NB_KNN_STATS set): never allocated otherwise
-    // nb_list_force: a host-pointer request stages one batch at a time -- its rows in nbl_list, its counts in nbr_cnt, its points in
-    // fld_pts, accel / phi in fld_acc / fld_phi (none of those calls overlaps another on the stream); pvel / jerk are its own
-    field_buf lf_pvel, lf_jerk;
-    // nb_split_force: shares fld_pts / lf_pvel / nbr_rad (a host-pointer request's points, their velocities, radii) and fld_part (up
-    // to four partial rows per (j-chunk, point of a batch), under the same bound) with the calls above; out stages its four outputs
-    field_buf split_out;
     // NB_INT_HERMITE4: bodies[0] / vel are the state at ONE instant, acc / jerk the derivatives derived from it.  None of the
     // leapfrog launch fields above is used: plain unpadded arrays, no planner, no graphs.
     bool hermite = false;

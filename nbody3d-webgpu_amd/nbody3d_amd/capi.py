@@ -300,32 +300,74 @@ def _ptr(a):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
 
 
+def _need(symbol, what):
+    """``what`` (the caller's name) needs ``symbol``: the queries after nb_field_eval were added within ABI 2.4, one by one."""
+    if not hasattr(load_library(), symbol):
+        raise NBodyError(1, "%s: the loaded library has no %s" % (what, symbol))
+
+
+def _rows4(a, dtype, who, what="points"):
+    """``a`` as contiguous (m, 4) rows of ``dtype``: (m, 3) gets a fourth column of zeros, a flat array is read as rows."""
+    a = np.asarray(a, dtype=dtype)
+    if a.ndim == 1:
+        a = a.reshape(-1, 3 if a.size % 4 else 4)
+    if a.ndim != 2 or a.shape[1] not in (3, 4):
+        raise ValueError("%s: %s must have shape (m, 3) or (m, 4)" % (who, what))
+    if a.shape[1] == 3:
+        a = np.concatenate([a, np.zeros((len(a), 1), dtype)], axis=1)
+    return np.ascontiguousarray(a)
+
+
+def _targets(who, req, dtype, points, bodies, at_bodies):
+    """The "``bodies=(first, count)`` or ``points``" part of ``who``'s request: sets flags, first_body, points and m (the count of
+    the bodies if they are given, else the number of points).  Returns (points array to keep alive | None, count | None).  Both or
+    neither of the two: passed on as they are -- the engine's NB_ERR_INVALID names the field."""
+    pts = count = None
+    if bodies is not None:
+        first, count = int(bodies[0]), int(bodies[1])
+        if not (0 <= first < 2 ** 32 and 0 <= count < 2 ** 32):
+            raise ValueError("%s: bodies=(first, count) out of range" % who)
+        req.flags |= at_bodies
+        req.first_body, req.m = first, count
+    if points is not None:
+        pts = _rows4(points, dtype, who)
+        if bodies is None:
+            req.m = len(pts)
+        req.points = _ptr(pts) if len(pts) else None
+    return pts, count
+
+
+def _radii(who, req, dtype, radii):
+    """The ``radii`` part of ``who``'s request (after _targets: one radius per point): the array to keep alive, or None."""
+    if radii is None:
+        return None
+    rad = np.ascontiguousarray(radii, dtype=dtype).reshape(-1)
+    if len(rad) != req.m:
+        raise ValueError("%s: radii must hold one radius per point" % who)
+    req.radii = _ptr(rad) if len(rad) else None
+    return rad
+
+
+def _new_request(cls):
+    req = cls()
+    req.struct_size = C.sizeof(cls)
+    return req
+
+
+def _device_request(cls, flags, at_bodies, m, bodies, points_ptr):
+    """What the ``*_device`` methods share: ``bodies=(first, count)`` selects the bodies themselves (``m`` is ignored then)."""
+    # (the head of every request, in the structs' order: struct_size, m, flags, first_body, points)
+    if bodies is not None:
+        return cls(C.sizeof(cls), int(bodies[1]), flags | at_bodies, int(bodies[0]), points_ptr or None)
+    return cls(C.sizeof(cls), int(m), flags, 0, points_ptr or None)
+
+
 def _field_request(n, dtype, points, bodies, accel, phi, f64):
     """The nb_field_request of field(): (request, points array kept alive, accel array | None, phi array | None)."""
     if load_library().nb_abi_minor() < 4:
         raise NBodyError(1, "field(): the loaded library is ABI %d.%d; nb_field_eval needs 2.4" % (abi_version(), abi_minor()))
-    req = nb_field_request()
-    req.struct_size = C.sizeof(nb_field_request)
-    pts = None
-    # (both or neither of points / bodies: passed on as they are -- the engine's NB_ERR_INVALID names the field)
-    if bodies is not None:
-        first, count = int(bodies[0]), int(bodies[1])
-        if not (0 <= first < 2 ** 32 and 0 <= count < 2 ** 32):
-            raise ValueError("field(): bodies=(first, count) out of range")
-        req.flags |= NB_FIELD_AT_BODIES
-        req.first_body, req.m = first, count
-    if points is not None:
-        pts = np.asarray(points, dtype=dtype)
-        if pts.ndim == 1:
-            pts = pts.reshape(-1, 3 if pts.size % 4 else 4)
-        if pts.ndim != 2 or pts.shape[1] not in (3, 4):
-            raise ValueError("field(): points must have shape (m, 3) or (m, 4)")
-        if pts.shape[1] == 3:
-            pts = np.concatenate([pts, np.zeros((len(pts), 1), dtype)], axis=1)
-        pts = np.ascontiguousarray(pts)
-        if bodies is None:
-            req.m = len(pts)
-        req.points = _ptr(pts) if len(pts) else None
+    req = _new_request(nb_field_request)
+    pts, _ = _targets("field()", req, dtype, points, bodies, NB_FIELD_AT_BODIES)
     out_t = np.float64 if (f64 or dtype == np.float64) else np.float32
     if f64:
         req.flags |= NB_FIELD_F64
@@ -336,41 +378,12 @@ def _field_request(n, dtype, points, bodies, accel, phi, f64):
     return req, pts, a, f
 
 
-def _need_neighbors(what):
-    if not hasattr(load_library(), "nb_neighbors"):
-        raise NBodyError(1, "%s: the loaded library has no nb_neighbors" % what)
-
-
 def _neighbor_request(dtype, points, bodies, radius, radii):
     """The nb_neighbor_request of neighbors(): (request, arrays kept alive, index, dist2, count | None)."""
-    _need_neighbors("neighbors()")
-    req = nb_neighbor_request()
-    req.struct_size = C.sizeof(nb_neighbor_request)
-    pts = rad = None
-    # (both or neither of points / bodies: passed on as they are -- the engine's NB_ERR_INVALID names the field)
-    if bodies is not None:
-        first, count = int(bodies[0]), int(bodies[1])
-        if not (0 <= first < 2 ** 32 and 0 <= count < 2 ** 32):
-            raise ValueError("neighbors(): bodies=(first, count) out of range")
-        req.flags |= NB_NBR_AT_BODIES
-        req.first_body, req.m = first, count
-    if points is not None:
-        pts = np.asarray(points, dtype=dtype)
-        if pts.ndim == 1:
-            pts = pts.reshape(-1, 3 if pts.size % 4 else 4)
-        if pts.ndim != 2 or pts.shape[1] not in (3, 4):
-            raise ValueError("neighbors(): points must have shape (m, 3) or (m, 4)")
-        if pts.shape[1] == 3:
-            pts = np.concatenate([pts, np.zeros((len(pts), 1), dtype)], axis=1)
-        pts = np.ascontiguousarray(pts)
-        if bodies is None:
-            req.m = len(pts)
-        req.points = _ptr(pts) if len(pts) else None
-    if radii is not None:
-        rad = np.ascontiguousarray(radii, dtype=dtype).reshape(-1)
-        if len(rad) != req.m:
-            raise ValueError("neighbors(): radii must hold one radius per point")
-        req.radii = _ptr(rad) if len(rad) else None
+    _need("nb_neighbors", "neighbors()")
+    req = _new_request(nb_neighbor_request)
+    pts, _ = _targets("neighbors()", req, dtype, points, bodies, NB_NBR_AT_BODIES)
+    rad = _radii("neighbors()", req, dtype, radii)
     if radius is not None:
         req.radius = float(radius)
     index = np.zeros((req.m,), np.uint32)
@@ -382,41 +395,12 @@ def _neighbor_request(dtype, points, bodies, radius, radii):
     return req, (pts, rad), index, dist2, count
 
 
-def _need_neighbor_lists(what):
-    if not hasattr(load_library(), "nb_neighbor_lists"):
-        raise NBodyError(1, "%s: the loaded library has no nb_neighbor_lists" % what)
-
-
 def _neighbor_list_request(dtype, points, bodies, radius, radii, cap, nearest):
     """The nb_neighbor_list_request of neighbor_lists(): (request, arrays kept alive, lists, count, index | None, dist2 | None)."""
-    _need_neighbor_lists("neighbor_lists()")
-    req = nb_neighbor_list_request()
-    req.struct_size = C.sizeof(nb_neighbor_list_request)
-    pts = rad = None
-    # (both or neither of points / bodies, a cap out of range: passed on as they are -- the engine's NB_ERR_INVALID names the field)
-    if bodies is not None:
-        first, count = int(bodies[0]), int(bodies[1])
-        if not (0 <= first < 2 ** 32 and 0 <= count < 2 ** 32):
-            raise ValueError("neighbor_lists(): bodies=(first, count) out of range")
-        req.flags |= NB_NBR_AT_BODIES
-        req.first_body, req.m = first, count
-    if points is not None:
-        pts = np.asarray(points, dtype=dtype)
-        if pts.ndim == 1:
-            pts = pts.reshape(-1, 3 if pts.size % 4 else 4)
-        if pts.ndim != 2 or pts.shape[1] not in (3, 4):
-            raise ValueError("neighbor_lists(): points must have shape (m, 3) or (m, 4)")
-        if pts.shape[1] == 3:
-            pts = np.concatenate([pts, np.zeros((len(pts), 1), dtype)], axis=1)
-        pts = np.ascontiguousarray(pts)
-        if bodies is None:
-            req.m = len(pts)
-        req.points = _ptr(pts) if len(pts) else None
-    if radii is not None:
-        rad = np.ascontiguousarray(radii, dtype=dtype).reshape(-1)
-        if len(rad) != req.m:
-            raise ValueError("neighbor_lists(): radii must hold one radius per point")
-        req.radii = _ptr(rad) if len(rad) else None
+    _need("nb_neighbor_lists", "neighbor_lists()")
+    req = _new_request(nb_neighbor_list_request)
+    pts, _ = _targets("neighbor_lists()", req, dtype, points, bodies, NB_NBR_AT_BODIES)
+    rad = _radii("neighbor_lists()", req, dtype, radii)
     if radius is not None:
         req.radius = float(radius)
     cap = int(cap)
@@ -435,52 +419,26 @@ def _neighbor_list_request(dtype, points, bodies, radius, radii, cap, nearest):
     return req, (pts, rad), lists, count, index, dist2
 
 
-def _need_list_force(what):
-    if not hasattr(load_library(), "nb_list_force"):
-        raise NBodyError(1, "%s: the loaded library has no nb_list_force" % what)
-
-
-def _rows4(a, dtype, what):
-    a = np.asarray(a, dtype=dtype)
-    if a.ndim == 1:
-        a = a.reshape(-1, 3 if a.size % 4 else 4)
-    if a.ndim != 2 or a.shape[1] not in (3, 4):
-        raise ValueError("list_force(): %s must have shape (m, 3) or (m, 4)" % what)
-    if a.shape[1] == 3:
-        a = np.concatenate([a, np.zeros((len(a), 1), dtype)], axis=1)
-    return np.ascontiguousarray(a)
-
-
 def _list_force_request(dtype, lists, bodies, points, point_vel, count, accel, jerk, phi):
     """The nb_list_force_request of list_force(): (request, arrays kept alive, accel | None, jerk | None, phi | None)."""
-    _need_list_force("list_force()")
-    req = nb_list_force_request()
-    req.struct_size = C.sizeof(nb_list_force_request)
+    _need("nb_list_force", "list_force()")
+    req = _new_request(nb_list_force_request)
     lists = np.ascontiguousarray(lists, dtype=np.uint32)
     if lists.ndim != 2:
         raise ValueError("list_force(): lists must have shape (m, cap)")
     m, cap = lists.shape
     if not (m < 2 ** 32 and cap < 2 ** 32):
         raise ValueError("list_force(): lists out of range")
+    pv = cnt = None
+    # (point_vel without a jerk, a cap out of range: passed on as they are -- the engine's NB_ERR_INVALID names the field)
+    pts, nb = _targets("list_force()", req, dtype, points, bodies, NB_LISTF_AT_BODIES)
+    if nb is not None and nb != m:
+        raise ValueError("list_force(): bodies=(first, count) must name one body per row of lists")
+    if pts is not None and len(pts) != m:
+        raise ValueError("list_force(): points must hold one point per row of lists")
     req.m, req.cap = m, cap
-    pts = pv = cnt = None
-    # (both or neither of points / bodies, point_vel without a jerk, a cap out of range: passed on as they are -- the engine's
-    # NB_ERR_INVALID names the field)
-    if bodies is not None:
-        first, nb = int(bodies[0]), int(bodies[1])
-        if not (0 <= first < 2 ** 32 and 0 <= nb < 2 ** 32):
-            raise ValueError("list_force(): bodies=(first, count) out of range")
-        if nb != m:
-            raise ValueError("list_force(): bodies=(first, count) must name one body per row of lists")
-        req.flags |= NB_LISTF_AT_BODIES
-        req.first_body = first
-    if points is not None:
-        pts = _rows4(points, dtype, "points")
-        if len(pts) != m:
-            raise ValueError("list_force(): points must hold one point per row of lists")
-        req.points = _ptr(pts) if m else None
     if point_vel is not None:
-        pv = _rows4(point_vel, dtype, "point_vel")
+        pv = _rows4(point_vel, dtype, "list_force()", "point_vel")
         if len(pv) != m:
             raise ValueError("list_force(): point_vel must hold one velocity per row of lists")
         req.point_vel = _ptr(pv) if m else None
@@ -499,47 +457,27 @@ def _list_force_request(dtype, lists, bodies, points, point_vel, count, accel, j
     return req, (lists, pts, pv, cnt), a, j, f
 
 
-def _need_split_force(what):
-    if not hasattr(load_library(), "nb_split_force"):
-        raise NBodyError(1, "%s: the loaded library has no nb_split_force" % what)
-
-
 SPLIT_OUTPUTS = ("accel_irr", "accel_reg", "jerk_irr", "jerk_reg")
 
 
 def _split_force_request(dtype, points, bodies, point_vel, radius, radii, jerk):
     """The nb_split_force_request of split_force(): (request, arrays kept alive, {output name: (m, 4) array})."""
-    _need_split_force("split_force()")
-    req = nb_split_force_request()
-    req.struct_size = C.sizeof(nb_split_force_request)
-    pts = pv = rad = None
-    m = None
-    # (both or neither of points / bodies, point_vel without a jerk, no radius at all: passed on as they are -- the engine's
-    # NB_ERR_INVALID names the field)
-    if bodies is not None:
-        first, m = int(bodies[0]), int(bodies[1])
-        if not (0 <= first < 2 ** 32 and 0 <= m < 2 ** 32):
-            raise ValueError("split_force(): bodies=(first, count) out of range")
-        req.flags |= NB_SPLIT_AT_BODIES
-        req.first_body = first
-    if points is not None:
-        pts = _rows4(points, dtype, "points")
-        m = len(pts) if m is None else m
-        req.points = _ptr(pts) if len(pts) else None
-    if m is None:
+    _need("nb_split_force", "split_force()")
+    req = _new_request(nb_split_force_request)
+    if points is None and bodies is None:
         raise ValueError("split_force(): give points or bodies=(first, count)")
+    # (both of points / bodies, point_vel without a jerk, no radius at all: passed on as they are -- the engine's NB_ERR_INVALID
+    # names the field)
+    pts, _ = _targets("split_force()", req, dtype, points, bodies, NB_SPLIT_AT_BODIES)
+    m = req.m
+    pv = None
     if point_vel is not None:
-        pv = _rows4(point_vel, dtype, "point_vel")
+        pv = _rows4(point_vel, dtype, "split_force()", "point_vel")
         if len(pv) != m:
             raise ValueError("split_force(): point_vel must hold one velocity per point")
         req.point_vel = _ptr(pv) if m else None
-    if radii is not None:
-        rad = np.ascontiguousarray(radii, dtype=dtype).reshape(-1)
-        if len(rad) != m:
-            raise ValueError("split_force(): radii must hold one radius per point")
-        req.radii = _ptr(rad) if m else None
+    rad = _radii("split_force()", req, dtype, radii)
     req.radius = 0.0 if radius is None else float(radius)
-    req.m = m
     out = {}
     for name in SPLIT_OUTPUTS[:4 if jerk else 2]:
         out[name] = np.zeros((m, 4), dtype)
@@ -547,36 +485,11 @@ def _split_force_request(dtype, points, bodies, point_vel, radius, radii, jerk):
     return req, (pts, pv, rad), out
 
 
-def _need_knn(what):
-    if not hasattr(load_library(), "nb_knn"):
-        raise NBodyError(1, "%s: the loaded library has no nb_knn" % what)
-
-
 def _knn_request(dtype, points, bodies, k, want_dist2):
     """The nb_knn_request of knn(): (request, arrays kept alive, index, dist2 | None)."""
-    _need_knn("knn()")
-    req = nb_knn_request()
-    req.struct_size = C.sizeof(nb_knn_request)
-    pts = None
-    # (both or neither of points / bodies, a k out of range: passed on as they are -- the engine's NB_ERR_INVALID names the field)
-    if bodies is not None:
-        first, count = int(bodies[0]), int(bodies[1])
-        if not (0 <= first < 2 ** 32 and 0 <= count < 2 ** 32):
-            raise ValueError("knn(): bodies=(first, count) out of range")
-        req.flags |= NB_NBR_AT_BODIES
-        req.first_body, req.m = first, count
-    if points is not None:
-        pts = np.asarray(points, dtype=dtype)
-        if pts.ndim == 1:
-            pts = pts.reshape(-1, 3 if pts.size % 4 else 4)
-        if pts.ndim != 2 or pts.shape[1] not in (3, 4):
-            raise ValueError("knn(): points must have shape (m, 3) or (m, 4)")
-        if pts.shape[1] == 3:
-            pts = np.concatenate([pts, np.zeros((len(pts), 1), dtype)], axis=1)
-        pts = np.ascontiguousarray(pts)
-        if bodies is None:
-            req.m = len(pts)
-        req.points = _ptr(pts) if len(pts) else None
+    _need("nb_knn", "knn()")
+    req = _new_request(nb_knn_request)
+    pts, _ = _targets("knn()", req, dtype, points, bodies, NB_NBR_AT_BODIES)
     k = int(k)
     if not 0 <= k < 2 ** 32:
         raise ValueError("knn(): k out of range")
@@ -1128,6 +1041,12 @@ class Simulation:
         self._check(self._L.nb_diagnostics(self._h, out))
         return out[0], out[1], np.array(out[2:5])
 
+    def _shape(self, getter, names, *args):
+        """What the ``*_shape`` methods share: {name: value} of the uint32 outputs of an nb_*_shape getter."""
+        v = [C.c_uint32() for _ in names]
+        self._check(getter(self._h, *args, *[C.byref(x) for x in v]))
+        return dict(zip(names, (x.value for x in v)))
+
     def field(self, points=None, *, bodies=None, accel=True, phi=True, f64=False):
         """nb_field_eval: acceleration and potential of the system at ``points`` ((m, 3) or (m, 4); the fourth column is ignored)
         or, with ``bodies=(first, count)``, at the current positions of those bodies, each leaving itself out of its sums.
@@ -1145,15 +1064,7 @@ class Simulation:
         positions (``points_ptr`` must then be None and ``m`` is ignored)."""
         if self._L.nb_abi_minor() < 4:
             raise NBodyError(1, "field_device(): the loaded library is ABI %d.%d; nb_field_eval needs 2.4" % (abi_version(), abi_minor()))
-        req = nb_field_request()
-        req.struct_size = C.sizeof(nb_field_request)
-        req.flags = NB_FIELD_DEVICE | (NB_FIELD_F64 if f64 else 0)
-        if bodies is not None:
-            req.flags |= NB_FIELD_AT_BODIES
-            req.first_body, req.m = int(bodies[0]), int(bodies[1])
-        else:
-            req.m = int(m)
-        req.points = points_ptr or None
+        req = _device_request(nb_field_request, NB_FIELD_DEVICE | (NB_FIELD_F64 if f64 else 0), NB_FIELD_AT_BODIES, m, bodies, points_ptr)
         req.accel = accel_ptr or None
         req.phi = phi_ptr or None
         self._check(self._L.nb_field_eval(self._h, C.byref(req)))
@@ -1173,16 +1084,8 @@ class Simulation:
         """The device-pointer form (NB_NBR_DEVICE): device addresses on the handle's device (e.g. ``tensor.data_ptr()``; 0 or None for
         what is not wanted), element types as for neighbors().  The work is enqueued on the handle's stream and the call returns
         without waiting.  ``bodies=(first, count)`` selects the bodies themselves (``points_ptr`` must then be None, ``m`` is ignored)."""
-        _need_neighbors("neighbors_device()")
-        req = nb_neighbor_request()
-        req.struct_size = C.sizeof(nb_neighbor_request)
-        req.flags = NB_NBR_DEVICE
-        if bodies is not None:
-            req.flags |= NB_NBR_AT_BODIES
-            req.first_body, req.m = int(bodies[0]), int(bodies[1])
-        else:
-            req.m = int(m)
-        req.points = points_ptr or None
+        _need("nb_neighbors", "neighbors_device()")
+        req = _device_request(nb_neighbor_request, NB_NBR_DEVICE, NB_NBR_AT_BODIES, m, bodies, points_ptr)
         req.radii = radii_ptr or None
         req.radius = 0.0 if radius is None else float(radius)
         req.index = index_ptr or None
@@ -1192,10 +1095,8 @@ class Simulation:
 
     def neighbors_shape(self, m):
         """{batch, chunks, j_per_chunk}: the launch shape nb_neighbors gives an m-point request (the answers do not depend on it)."""
-        _need_neighbors("neighbors_shape()")
-        v = [C.c_uint32() for _ in range(3)]
-        self._check(self._L.nb_neighbors_shape(self._h, int(m), *[C.byref(x) for x in v]))
-        return dict(zip(("batch", "chunks", "j_per_chunk"), (x.value for x in v)))
+        _need("nb_neighbors", "neighbors_shape()")
+        return self._shape(self._L.nb_neighbors_shape, ("batch", "chunks", "j_per_chunk"), int(m))
 
     def neighbor_lists(self, points=None, *, bodies=None, radius=None, radii=None, cap=64, nearest=False):
         """nb_neighbor_lists: WHICH bodies lie strictly inside ``radius`` (one for all) or ``radii`` (one per point) of each of
@@ -1212,16 +1113,8 @@ class Simulation:
         """The device-pointer form (NB_NBR_DEVICE): device addresses on the handle's device (0 or None for what is not wanted);
         ``list_ptr``: m * cap uint32.  Enqueued on the handle's stream, returns without waiting.  ``bodies=(first, count)`` selects the
         bodies themselves (``points_ptr`` must then be None, ``m`` is ignored)."""
-        _need_neighbor_lists("neighbor_lists_device()")
-        req = nb_neighbor_list_request()
-        req.struct_size = C.sizeof(nb_neighbor_list_request)
-        req.flags = NB_NBR_DEVICE
-        if bodies is not None:
-            req.flags |= NB_NBR_AT_BODIES
-            req.first_body, req.m = int(bodies[0]), int(bodies[1])
-        else:
-            req.m = int(m)
-        req.points = points_ptr or None
+        _need("nb_neighbor_lists", "neighbor_lists_device()")
+        req = _device_request(nb_neighbor_list_request, NB_NBR_DEVICE, NB_NBR_AT_BODIES, m, bodies, points_ptr)
         req.radii = radii_ptr or None
         req.radius = 0.0 if radius is None else float(radius)
         req.cap = int(cap)
@@ -1234,10 +1127,8 @@ class Simulation:
     def neighbor_lists_shape(self, m, cap):
         """{batch, chunks, j_per_chunk}: the launch shape nb_neighbor_lists gives an m-point request with rows of ``cap`` entries (the
         answers do not depend on it)."""
-        _need_neighbor_lists("neighbor_lists_shape()")
-        v = [C.c_uint32() for _ in range(3)]
-        self._check(self._L.nb_neighbor_lists_shape(self._h, int(m), int(cap), *[C.byref(x) for x in v]))
-        return dict(zip(("batch", "chunks", "j_per_chunk"), (x.value for x in v)))
+        _need("nb_neighbor_lists", "neighbor_lists_shape()")
+        return self._shape(self._L.nb_neighbor_lists_shape, ("batch", "chunks", "j_per_chunk"), int(m), int(cap))
 
     def list_force(self, lists, *, bodies=None, points=None, point_vel=None, count=None, accel=True, jerk=False, phi=False):
         """nb_list_force: acceleration, jerk and potential summed over the entries of each row of ``lists`` ((m, cap) uint32: the
@@ -1256,16 +1147,8 @@ class Simulation:
         ``list_ptr``: m * cap uint32, ``count_ptr``: m uint32, the outputs as list_force() returns them.  Read and written in place,
         enqueued on the handle's stream, returns without waiting.  ``bodies=(first, count)`` selects the bodies themselves
         (``points_ptr`` must then be None, ``m`` is ignored)."""
-        _need_list_force("list_force_device()")
-        req = nb_list_force_request()
-        req.struct_size = C.sizeof(nb_list_force_request)
-        req.flags = NB_LISTF_DEVICE
-        if bodies is not None:
-            req.flags |= NB_LISTF_AT_BODIES
-            req.first_body, req.m = int(bodies[0]), int(bodies[1])
-        else:
-            req.m = int(m)
-        req.points = points_ptr or None
+        _need("nb_list_force", "list_force_device()")
+        req = _device_request(nb_list_force_request, NB_LISTF_DEVICE, NB_LISTF_AT_BODIES, m, bodies, points_ptr)
         req.point_vel = point_vel_ptr or None
         req.list = list_ptr or None
         req.count = count_ptr or None
@@ -1278,17 +1161,15 @@ class Simulation:
     def list_force_shape(self, m, cap):
         """{batch, lanes_per_row}: the rows of every batch but the last that a host-pointer nb_list_force request of m rows at ``cap``
         entries is staged in, and the lanes that share one row (the answers depend on neither m nor the batch)."""
-        _need_list_force("list_force_shape()")
-        v = [C.c_uint32() for _ in range(2)]
-        self._check(self._L.nb_list_force_shape(self._h, int(m), int(cap), *[C.byref(x) for x in v]))
-        return dict(zip(("batch", "lanes_per_row"), (x.value for x in v)))
+        _need("nb_list_force", "list_force_shape()")
+        return self._shape(self._L.nb_list_force_shape, ("batch", "lanes_per_row"), int(m), int(cap))
 
     def irregular_force(self, radius, cap=128, *, jerk=None, phi=False):
         """The irregular force of an Ahmad-Cohen split at every body: nb_neighbor_lists with ``radius`` and rows of ``cap`` entries,
         then nb_list_force over those rows, both with device pointers on the handle's stream -- the rows never visit the host.
         ``jerk`` defaults to what the handle can give (Hermite handles: True).  Returns ``(accel (n, 4), jerk (n, 4) | None, phi (n,) |
         None, count (n,) uint32)``; where count exceeds cap the sums run over the cap members with the smallest indices."""
-        _need_list_force("irregular_force()")
+        _need("nb_list_force", "irregular_force()")
         import torch
         jerk = (self.integrator != "leapfrog") if jerk is None else bool(jerk)
         n, cap = self.n, int(cap)
@@ -1328,16 +1209,8 @@ class Simulation:
         """The device-pointer form (NB_SPLIT_DEVICE): device addresses on the handle's device (0 or None for what is not wanted), the
         outputs as split_force() returns them.  Read and written in place, enqueued on the handle's stream, returns without
         waiting.  ``bodies=(first, count)`` selects the bodies themselves (``points_ptr`` must then be None, ``m`` is ignored)."""
-        _need_split_force("split_force_device()")
-        req = nb_split_force_request()
-        req.struct_size = C.sizeof(nb_split_force_request)
-        req.flags = NB_SPLIT_DEVICE
-        if bodies is not None:
-            req.flags |= NB_SPLIT_AT_BODIES
-            req.first_body, req.m = int(bodies[0]), int(bodies[1])
-        else:
-            req.m = int(m)
-        req.points = points_ptr or None
+        _need("nb_split_force", "split_force_device()")
+        req = _device_request(nb_split_force_request, NB_SPLIT_DEVICE, NB_SPLIT_AT_BODIES, m, bodies, points_ptr)
         req.point_vel = point_vel_ptr or None
         req.radii = radii_ptr or None
         req.radius = 0.0 if radius is None else float(radius)
@@ -1350,10 +1223,8 @@ class Simulation:
     def split_force_shape(self, m):
         """{batch, chunks, j_per_chunk, rows_per_workgroup}: the launch shape nb_split_force gives an m-point request (on a Hermite
         handle: one with the jerk pair)."""
-        _need_split_force("split_force_shape()")
-        v = [C.c_uint32() for _ in range(4)]
-        self._check(self._L.nb_split_force_shape(self._h, int(m), *[C.byref(x) for x in v]))
-        return dict(zip(("batch", "chunks", "j_per_chunk", "rows_per_workgroup"), (x.value for x in v)))
+        _need("nb_split_force", "split_force_shape()")
+        return self._shape(self._L.nb_split_force_shape, ("batch", "chunks", "j_per_chunk", "rows_per_workgroup"), int(m))
 
     def knn(self, points=None, *, bodies=None, k=6, dist2=True):
         """nb_knn: the ``k`` nearest bodies (1 <= k <= 64) of each of ``points`` ((m, 3) or (m, 4); the fourth column is ignored) --
@@ -1369,16 +1240,8 @@ class Simulation:
         """The device-pointer form (NB_NBR_DEVICE): device addresses on the handle's device (0 or None for what is not wanted);
         ``index_ptr``: m * k uint32, ``dist2_ptr``: m * k elements of the handle's precision.  Enqueued on the handle's stream, returns
         without waiting.  ``bodies=(first, count)`` selects the bodies themselves (``points_ptr`` must then be None, ``m`` is ignored)."""
-        _need_knn("knn_device()")
-        req = nb_knn_request()
-        req.struct_size = C.sizeof(nb_knn_request)
-        req.flags = NB_NBR_DEVICE
-        if bodies is not None:
-            req.flags |= NB_NBR_AT_BODIES
-            req.first_body, req.m = int(bodies[0]), int(bodies[1])
-        else:
-            req.m = int(m)
-        req.points = points_ptr or None
+        _need("nb_knn", "knn_device()")
+        req = _device_request(nb_knn_request, NB_NBR_DEVICE, NB_NBR_AT_BODIES, m, bodies, points_ptr)
         req.k = int(k)
         req.index = index_ptr or None
         req.dist2 = dist2_ptr or None
@@ -1387,10 +1250,8 @@ class Simulation:
     def knn_shape(self, m, k):
         """{batch, chunks, j_per_chunk}: the launch shape nb_knn gives an m-point request for k neighbours (the answers do not depend
         on it)."""
-        _need_knn("knn_shape()")
-        v = [C.c_uint32() for _ in range(3)]
-        self._check(self._L.nb_knn_shape(self._h, int(m), int(k), *[C.byref(x) for x in v]))
-        return dict(zip(("batch", "chunks", "j_per_chunk"), (x.value for x in v)))
+        _need("nb_knn", "knn_shape()")
+        return self._shape(self._L.nb_knn_shape, ("batch", "chunks", "j_per_chunk"), int(m), int(k))
 
     def local_density(self, k=6):
         """The Casertano-Hut density at every body, (n,) float64: one knn(bodies=(0, n), k=k) call and density_from_knn() on its

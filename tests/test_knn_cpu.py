@@ -85,7 +85,7 @@ def test_a_library_without_the_symbol_is_a_clear_error(monkeypatch):
 
     monkeypatch.setattr(capi, "_lib", Old())
     with pytest.raises(capi.NBodyError) as e:
-        capi._need_knn("knn()")
+        capi._need("nb_knn", "knn()")
     assert e.value.code == 1 and "knn()" in str(e.value) and "no nb_knn" in str(e.value)
     with pytest.raises(capi.NBodyError):
         capi._knn_request(np.float32, np.zeros((1, 4)), None, 6, True)

@@ -87,7 +87,7 @@ def test_a_library_without_the_symbol_is_a_clear_error(monkeypatch):
 
     monkeypatch.setattr(capi, "_lib", Old())
     with pytest.raises(capi.NBodyError) as e:
-        capi._need_list_force("list_force()")
+        capi._need("nb_list_force", "list_force()")
     assert e.value.code == 1 and "list_force()" in str(e.value) and "no nb_list_force" in str(e.value)
     with pytest.raises(capi.NBodyError):
         capi._list_force_request(np.float32, np.zeros((1, 4), np.uint32), (0, 1), None, None, None, True, False, False)

@@ -85,7 +85,7 @@ def test_a_library_without_the_symbol_is_a_clear_error(monkeypatch):
 
     monkeypatch.setattr(capi, "_lib", Old())
     with pytest.raises(capi.NBodyError) as e:
-        capi._need_split_force("split_force()")
+        capi._need("nb_split_force", "split_force()")
     assert e.value.code == 1 and "split_force()" in str(e.value) and "no nb_split_force" in str(e.value)
 
 
@@ -103,6 +103,9 @@ def test_the_request_builder_checks_what_it_can_without_a_device():
         kw.update(bad)
         with pytest.raises(ValueError):
             capi._split_force_request(np.float32, kw["points"], kw["bodies"], kw["point_vel"], 1.0, kw["radii"], False)
+    with pytest.raises(ValueError) as e:                                # the message names the function that was called
+        capi._split_force_request(np.float32, np.zeros((3, 5)), None, None, 1.0, None, False)
+    assert "split_force()" in str(e.value)
 
 
 def test_the_two_sums_add_up_to_the_census_full_row_sums():
