@@ -65,7 +65,10 @@ extern "C" {
                              2.4 (round 15) likewise within 2.4: nb_split_force, nb_multi_split_force, nb_split_force_shape,
                                             nb_split_force_request, NB_SPLIT_*.  Detected by the presence of the symbol nb_split_force
                              2.4 (round 16) likewise within 2.4: nb_set_neighbor_scheme, nb_neighbor_scheme_stats, nb_download_neighbor_scheme,
-                                            nb_neighbor_scheme.  Detected by the presence of the symbol nb_set_neighbor_scheme */
+                                            nb_neighbor_scheme.  Detected by the presence of the symbol nb_set_neighbor_scheme
+                             2.4 (round 17) likewise within 2.4: nb_split_lists, nb_multi_split_lists, nb_split_lists_shape,
+                                            nb_split_lists_request, nb_neighbor_scheme_fused, NB_FLAG_AC_TWO_CALLS (an older library ignores
+                                            the bit: its scheme runs the two calls).  Detected by the presence of the symbol nb_split_lists */
 
 typedef struct nb_sim nb_sim; /* opaque */
 
@@ -128,6 +131,11 @@ typedef enum nb_precision { NB_F32 = 0, NB_F64 = 1 } nb_precision;
                                      runs the equal-mass kernels with UNIT mass product (form 2): the sums are kept unscaled and G*m
                                      multiplies each row once, where it is stored; a product by a power of two commutes with every
                                      rounding, so the results are bit-identical (nb_eqm_form) */
+
+#define NB_FLAG_AC_TWO_CALLS 4096u /* tuning/A-B: a list build of the Ahmad-Cohen neighbour scheme (nb_set_neighbor_scheme) always runs
+                                      nb_split_force and then nb_neighbor_lists.  By default it runs nb_split_lists -- the sums and the
+                                      rows from one pass over the pairs -- wherever that call's launch shape is nb_split_force's.
+                                      Bit-identical results (nb_neighbor_scheme_fused) */
 
 /* nb_array: selector for nb_device_ptr */
 typedef enum nb_array { NB_BODIES = 0, NB_VEL = 1, NB_ACCEL = 2, NB_JERK = 3 /* Hermite handles only */ } nb_array;
@@ -879,6 +887,71 @@ int nb_multi_split_force(nb_multi *m, const nb_split_force_request *req);
  * points one workgroup takes.  For tests and tools. */
 int nb_split_force_shape(nb_sim *s, uint32_t m, uint32_t *batch, uint32_t *chunks, uint32_t *j_per_chunk, uint32_t *rows_per_workgroup);
 
+/* ---- the two sums of nb_split_force and the rows of nb_neighbor_lists from one pass (added within ABI 2.4; no reference analogue) ----
+ * nb_split_force cuts every pair's term into the irregular or the regular sum by d2 < h2; nb_neighbor_lists derives the same d2,
+ * the same h2 and the same comparison twice more (a count pass and a fill pass) only to write down WHICH j were members.  This
+ * call does both in one pass over the M x N pairs: the comparison that selects the weights also writes the rows.  It is the start
+ * and the regular time of an Ahmad-Cohen scheme, and what a near/far decomposition wants: the two sums and the rows they were cut
+ * by, with no chance that the two disagree about a body on the sphere.
+ *   - Rows: `list` and `count` are BIT FOR BIT what nb_neighbor_lists returns for the same points, radii or radius, cap and
+ *     flags, whatever the launch shape: row k holds its members in ascending j; with more than cap members the cap smallest; the
+ *     tail [min(count, cap), cap) holds 0xffffffff (NB_NBR_NONE); all m * cap elements are written, in host and in device mode;
+ *     count is the TRUE number of members, never clipped.  With NB_SPLIT_AT_BODIES point k leaves ITSELF out of its row by index
+ *     (row first_body + k); another body at the same position is a member.
+ *   - Sums: the four sums are BIT FOR BIT what nb_split_force returns for the same request whenever nb_split_lists_shape reports
+ *     the (batch, chunks, j_per_chunk) that nb_split_force_shape reports for that m (a point's additions depend on the j-chunks
+ *     and the tiles, and on nothing else).  Otherwise they are nb_split_force's sums under another cut: the same membership, the
+ *     same terms, its error bounds.  Every rule of nb_split_force's section holds: membership, pair arithmetic, empty sides, the
+ *     summation, the handles, the positions read.  In the SUMS the own row and a body at the own position are handled as
+ *     nb_split_force handles them (an exact 0, no mask); the exclusion by index applies to the row only.
+ *   - Shape: nb_split_force's.  The batch is halved further (the chunks cut again by nb_split_force's rule at every candidate)
+ *     only while chunks x batch x cap x 4 bytes exceed 1 GiB: between the 256 MiB one batch of nb_neighbor_lists writes and what
+ *     nb_knn's working rows may take, and what N = 262,144 at cap 256 on a Hermite f32 handle needs to keep nb_split_force's shape
+ *     (4 chunks x 262,144 points x 256 entries x 4 bytes).  One workgroup's points are the floor of the halving; if very many
+ *     short chunks at a large cap still exceed the bound there, the chunks are made longer until they fit.
+ *   - State and determinism: the simulation state, the side copies, the captured graphs and the step counter are untouched:
+ *     stepping after a call is bit-identical to stepping without it.  No atomics: the same request on the same state gives the
+ *     same bits, and a scalar radius and a radii array filled with that value give the same bits.
+ *   - Errors: the union of the two calls' rules, each checked before any device call, nb_last_error naming the function and the
+ *     field.  NB_ERR_INVALID: NULL handle or request, wrong struct_size, m == 0, unknown flag bits (2u is one: no fp64 audit mode),
+ *     all four sums NULL (the message says to use nb_neighbor_lists), points / point_vel given with NB_SPLIT_AT_BODIES, points
+ *     missing without it, point_vel missing with a jerk at points or given without one, list NULL, cap outside 1 .. 4096,
+ *     reserved != 0, first_body + m > n, neither radii nor radius > 0, radius negative or NaN; on nb_multi a non-NULL jerk pointer.
+ *     NB_ERR_STATE: nothing uploaded, nb_set_params not called, a jerk on a leapfrog handle.
+ *   - Host pointers: points, point_vel, radii, the sums and count are staged whole (O(m)), `list` batch by batch, as
+ *     nb_neighbor_lists stages it; the call blocks until the outputs are written; no pointer is kept.  NB_SPLIT_DEVICE: every
+ *     pointer is device memory on the handle's device, read and written in place, enqueued on the handle's stream; the call
+ *     returns at once.
+ *   - Memory: nb_split_force's partial rows, and an engine-owned buffer, grown on demand and released by nb_destroy, of one
+ *     SEGMENT of cap entries per (j-chunk, point of a batch) with the chunk's true count -- a point's offset inside its row is not
+ *     known before all of its chunks are done; a second short pass gathers the segments into the rows in ascending chunk order,
+ *     pads them and writes the counts.  Bounded as above; nothing is proportional to m x N; the rows are not set beforehand. */
+typedef struct nb_split_lists_request {
+    uint32_t struct_size;   /* sizeof(nb_split_lists_request) */
+    uint32_t m;             /* number of points, >= 1 */
+    uint32_t flags;         /* NB_SPLIT_AT_BODIES | NB_SPLIT_DEVICE, nb_split_force's meaning */
+    uint32_t first_body;    /* NB_SPLIT_AT_BODIES only */
+    const void *points;     /* 4*m elements x, y, z, (ignored); NULL with NB_SPLIT_AT_BODIES */
+    const void *point_vel;  /* 4*m elements vx, vy, vz, (ignored); required iff a jerk is asked for at points, else NULL */
+    const void *radii;      /* optional: m elements of the handle's precision; an element may be 0 */
+    double radius;          /* used when radii == NULL; radii or radius > 0 is required */
+    void *accel_irr;        /* out, optional (at least one of the four): 4*m elements (ax, ay, az, 0) over the members */
+    void *accel_reg;        /* out, optional: 4*m elements over every other row */
+    void *jerk_irr;         /* out, optional: 4*m elements (jx, jy, jz, 0); Hermite handles only */
+    void *jerk_reg;         /* out, optional: likewise */
+    uint32_t cap;           /* entries per row, 1 <= cap <= 4096 */
+    uint32_t reserved;      /* must be 0 */
+    uint32_t *list;         /* out, required: m * cap indices */
+    uint32_t *count;        /* out, optional: m, the TRUE count (may exceed cap) */
+} nb_split_lists_request;   /* 104 bytes */
+int nb_split_lists(nb_sim *s, const nb_split_lists_request *req);
+/* The same on a multi-shard system: evaluated on shard 0 against the caller's UNPADDED n rows; the jerk pointers must be NULL. */
+int nb_multi_split_lists(nb_multi *m, const nb_split_lists_request *req);
+/* The shape of an m-point request at `cap` entries per row (no device call): the points of the first batch, its j-chunks, the
+ * bodies per chunk and the points one workgroup takes (on a Hermite handle: of a request with the jerk pair).  Equal to
+ * nb_split_force_shape's answer for the same m wherever the segments fit their bound.  For tests and tools. */
+int nb_split_lists_shape(nb_sim *s, uint32_t m, uint32_t cap, uint32_t *batch, uint32_t *chunks, uint32_t *j_per_chunk, uint32_t *rows_per_workgroup);
+
 /* ---- Ahmad-Cohen neighbour scheme with two shared step levels (added within ABI 2.4; no reference analogue) ----
  * A collisional system on a Hermite handle otherwise puts every body on the step its closest encounters need.  With the scheme
  * (Ahmad & Cohen 1973) a body's force is kept as two parts: the IRREGULAR part over the bodies inside its neighbour radius, which
@@ -895,7 +968,8 @@ int nb_split_force_shape(nb_sim *s, uint32_t m, uint32_t *batch, uint32_t *chunk
  *     (so that a handle whose dt changes continues exactly as a fresh handle given its (x, v) would), at the next nb_step,
  *     nb_download (accel), nb_download_jerk, nb_device_ptr(NB_ACCEL / NB_JERK) or nb_download_neighbor_scheme.  On (x, v) as they
  *     stand: (ai, ji, ar0, jr0) = the four outputs of nb_split_force at the bodies; L and count = nb_neighbor_lists at the bodies
- *     with the same radius or radii.  Both bit for bit what the public calls return.
+ *     with the same radius or radii.  Both bit for bit what the public calls return.  (Where nb_neighbor_scheme_fused answers 1 the
+ *     start and step 2 + 3 of the regular time are ONE nb_split_lists call: the same bits from one pass over the pairs.)
  *   - Substeps.  One regular step runs s = 0 .. N_sub - 1 with tau = s hs; all polynomial arithmetic is fp64 on the stored values,
  *     each stored value rounded once to the handle's precision, with the expressions of the shared step's predictor and corrector:
  *       1. a = ai + (ar0 + tau jr0), j = ji + jr0;
@@ -968,6 +1042,12 @@ int nb_neighbor_scheme_stats(nb_sim *s, struct nb_neighbor_scheme_stats *out, in
  * NB_ERR_STATE on a handle without the scheme. */
 int nb_download_neighbor_scheme(nb_sim *s, void *accel_irr, void *jerk_irr, void *accel_reg, void *jerk_reg,
                                 uint32_t *list /* n * cap */, uint32_t *count /* n */);
+
+/* Which route the next list build of the scheme takes (no device call): *fused = 1 when the start and the regular times call
+ * nb_split_lists once -- where its launch shape for (n, cap) is nb_split_force's, so that the four sums stay bit for bit what
+ * nb_split_force returns --, 0 when they call nb_split_force and then nb_neighbor_lists (elsewhere, and under
+ * NB_FLAG_AC_TWO_CALLS).  Both routes leave the same bits in every array.  0 with NB_OK on a handle without the scheme. */
+int nb_neighbor_scheme_fused(nb_sim *s, int *fused);
 
 #if defined(__GNUC__)
 #pragma GCC visibility pop

@@ -734,6 +734,12 @@ int nb_multi_split_force(nb_multi* m, const nb_split_force_request* req)
         return req->struct_size == sizeof(nb_split_force_request) && (req->jerk_irr || req->jerk_reg) ? "jerk_irr and jerk_reg must be NULL (the shards are leapfrog handles)" : nullptr; });
 }
 
+int nb_multi_split_lists(nb_multi* m, const nb_split_lists_request* req)
+{
+    return multi_query(m, req, "nb_multi_split_lists", nbi::split_lists, [&] {
+        return req->struct_size == sizeof(nb_split_lists_request) && (req->jerk_irr || req->jerk_reg) ? "jerk_irr and jerk_reg must be NULL (the shards are leapfrog handles)" : nullptr; });
+}
+
 int nb_multi_download(nb_multi* m, void* bodies, void* vel, void* accel)
 {
     if (!m) return NB_ERR_INVALID;

@@ -787,9 +787,21 @@ int block_step(nb_sim* s, uint32_t nsteps)
 
 // ---- the Ahmad-Cohen neighbour scheme (nb_set_neighbor_scheme; kernels/ac_scheme.hip.h) ----------
 // One list build at the bodies: nb_split_force's four outputs into (ai, ji, ar, jr) and nb_neighbor_lists' rows and counts into
-// ac_list / ac_count, both through the engine's own entry points with device pointers, on the handle's stream.
+// ac_list / ac_count, both through the engine's own entry points with device pointers, on the handle's stream -- or, where
+// nb_split_lists cuts the request as nb_split_force does (nbi::ac_fused), that one call: the same bits from one pass over the pairs.
 int ac_build(nb_sim* s, void* ai, void* ji, void* ar, void* jr, const char* who)
 {
+    if (nbi::ac_fused(s)) {
+        nb_split_lists_request q;
+        memset(&q, 0, sizeof q);
+        q.struct_size = sizeof q; q.m = s->n; q.flags = NB_SPLIT_AT_BODIES | NB_SPLIT_DEVICE;
+        q.radii = s->ac_radii; q.radius = s->ac_radii ? 0.0 : s->ac_radius;
+        q.accel_irr = ai; q.jerk_irr = ji; q.accel_reg = ar; q.jerk_reg = jr;
+        q.cap = s->ac_cap; q.list = s->ac_list; q.count = s->ac_count;
+        if (int rc = nbi::split_lists(s, &q, s->n, who)) return rc;
+        NB_HIP(s, hipMemsetAsync(s->ac_hdr, 0, sizeof(unsigned long long) * nb::kAcHdrWords, s->stream));
+        return NB_OK;
+    }
     nb_split_force_request sq;
     memset(&sq, 0, sizeof sq);
     sq.struct_size = sizeof sq; sq.m = s->n; sq.flags = NB_SPLIT_AT_BODIES | NB_SPLIT_DEVICE;
@@ -1085,6 +1097,7 @@ int nb_create(const nb_config* cfg_in, nb_sim** out)
     if (cfg.integrator == NB_INT_HERMITE4) {
         // plain unpadded arrays, no planner: (x, v) at one instant, the derived (a, j), the predicted state and the bounded partials
         s->hermite = true;
+        s->ac_two_calls = (cfg.flags & NB_FLAG_AC_TWO_CALLS) != 0;      // (the scheme exists on these handles only)
         fj_shape(s->n, s->f64, n_cu, &s->fj_chunks, &s->fj_per);
         s->jsplit = s->fj_chunks; s->j_per_split = s->fj_per;      // what nb_shape_info reports
         s->variant = std::string("hermite4_") + (s->f64 ? "f64" : "f32pk") + "_c" + std::to_string(s->fj_chunks) + "_j" + std::to_string(s->fj_per);
@@ -1228,7 +1241,7 @@ void nb_destroy(nb_sim* s)
     if (s->blk_hdr_host) (void)hipHostFree(s->blk_hdr_host);
     ac_release(s);
     if (s->diag) (void)hipFree(s->diag);
-    for (auto* b : {&s->q_in[0], &s->q_in[1], &s->q_in[2], &s->q_in[3], &s->q_out[0], &s->q_out[1], &s->q_out[2], &s->q_out[3], &s->q_part, &s->q_off, &s->q_work, &s->q_inf, &s->knn_stat})
+    for (auto* b : {&s->q_in[0], &s->q_in[1], &s->q_in[2], &s->q_in[3], &s->q_out[0], &s->q_out[1], &s->q_out[2], &s->q_out[3], &s->q_out[4], &s->q_out[5], &s->q_part, &s->q_off, &s->q_work, &s->q_inf, &s->q_seg, &s->q_segcnt, &s->knn_stat})
         if (b->p) (void)hipFree(b->p);
     if (s->zero_row) (void)hipFree(s->zero_row);
     if (s->own_stream && s->stream) (void)hipStreamDestroy(s->stream);
@@ -2644,6 +2657,146 @@ int nb_split_force_shape(nb_sim* s, uint32_t m, uint32_t* batch, uint32_t* chunk
     if (int rc = shape_begin(s, "nb_split_force_shape", m)) return rc;
     uint32_t b, c, per;
     split_shape(s, m, s->n, s->hermite ? 4u : 2u, &b, &c, &per);      // (a Hermite handle: the shape of a request with the jerk pair)
+    if (rows_per_workgroup) *rows_per_workgroup = split_rows(s);
+    return shape_put(b, c, per, batch, chunks, j_per_chunk);
+}
+
+/* ---- the two sums and the neighbour rows from one pass ---------------------------------------- */
+
+namespace {
+
+constexpr query_kind kQSplitLists = {"nb_split_lists_request", "NB_SPLIT_AT_BODIES", NB_SPLIT_AT_BODIES | NB_SPLIT_DEVICE, true};
+// Most bytes of segments (chunks x batch x cap x 4) one batch leaves: between kNblListBytes, what a batch of nb_neighbor_lists writes,
+// and what nb_knn's working rows may take; N = 262,144 at cap 256 on a Hermite f32 handle (4 chunks of 65,536 bodies for one batch
+// of 262,144 points) just keeps split_shape's shape under it.
+constexpr uint64_t kSplSegBytes = 1ull << 30;
+
+// split_shape's shape; the batch is halved further -- the chunks cut again by split_shape's rule at every candidate -- only while the
+// segments exceed their bound (one workgroup's points being the floor, as for every batch rule).
+void spl_shape(const nb_sim* s, uint32_t m, uint32_t cap, uint32_t rows, uint32_t planes, uint32_t* batch, uint32_t* chunks, uint32_t* per)
+{
+    const uint32_t prow = split_rows(s);
+    split_shape(s, m, rows, planes, batch, chunks, per);
+    while ((uint64_t)*chunks * *batch * cap * 4 > kSplSegBytes && *batch > prow)
+        split_shape(s, std::max(prow, (*batch / 2 + prow - 1) / prow * prow), rows, planes, batch, chunks, per);
+    // one workgroup's points against very many short chunks at a large cap: longer chunks are all that is left
+    const uint32_t room = (uint32_t)std::max<uint64_t>(1, kSplSegBytes / ((uint64_t)*batch * cap * 4));
+    if (*chunks > room) {
+        *per = ceil_div(ceil_div(s->n, room), (uint32_t)nb::kTile) * nb::kTile;
+        *chunks = std::max(1u, std::min(ceil_div(s->n, *per), ceil_div(rows, *per)));
+    }
+}
+
+// Whether nb_split_lists cuts EVERY batch of a request at all n bodies as nb_split_force cuts it (then its sums are that call's bits).
+bool spl_shape_is_splits(const nb_sim* s, uint32_t cap, uint32_t planes)
+{
+    for (uint32_t done = 0; done < s->n;) {
+        uint32_t b0, c0, p0, b1, c1, p1;
+        split_shape(s, s->n - done, s->n, planes, &b0, &c0, &p0);
+        spl_shape(s, s->n - done, cap, s->n, planes, &b1, &c1, &p1);
+        if (b0 != b1 || c0 != c1 || p0 != p1) return false;
+        done += b0;
+    }
+    return true;
+}
+
+// the lanes of nb_spl_rows that share a row: the power of two from 8 to 64 that covers cap (or 64)
+uint32_t spl_lanes(uint32_t cap)
+{
+    uint32_t l = 8;
+    while (l < 64 && l < cap) l *= 2;
+    return l;
+}
+
+}  // namespace
+
+extern "C++" int nbi::split_lists(nb_sim* s, const nb_split_lists_request* req, uint32_t rows, const char* who)
+{
+    if (int rc = query_begin(s, req, kQSplitLists, rows, who, [&]() -> const char* {
+            const bool at = (req->flags & NB_SPLIT_AT_BODIES) != 0, wj = req->jerk_irr || req->jerk_reg;
+            if (!req->accel_irr && !req->accel_reg && !wj) return "accel_irr, accel_reg, jerk_irr and jerk_reg are all NULL (use nb_neighbor_lists for the rows alone)";
+            if (at && req->point_vel) return "point_vel must be NULL with NB_SPLIT_AT_BODIES";
+            if (!at && wj && !req->point_vel) return "point_vel is NULL (the jerk at points needs their velocities)";
+            if (!at && !wj && req->point_vel) return "point_vel must be NULL when jerk_irr and jerk_reg are NULL";
+            if (!req->list) return "list is NULL";
+            if (bad_cap(req->cap)) return bad_cap(req->cap);
+            if (req->reserved != 0) return "reserved must be 0";
+            if (bad_radius(req->radius)) return bad_radius(req->radius);
+            return !req->radii && !(req->radius > 0.0) ? "radii is NULL and radius is not > 0" : nullptr; })) return rc;
+    const bool at = (req->flags & NB_SPLIT_AT_BODIES) != 0, dev = (req->flags & NB_SPLIT_DEVICE) != 0;
+    const bool wj = req->jerk_irr || req->jerk_reg;
+    if (wj && !s->hermite) return qfail(s, NB_ERR_STATE, who, "jerk_irr / jerk_reg need a Hermite handle (nb_config.integrator = NB_INT_HERMITE4)");
+    const size_t esz = s->esz, row4 = 4 * esz;
+    const uint32_t m = req->m;
+    const void* bodies = s->bodies[s->cur];
+    const void* vel = wj ? s->vel : nullptr;
+    // a host-pointer request: everything O(m) is staged whole as nb_split_force stages it, the rows batch by batch as nb_neighbor_lists stages them
+    q_array pts = query_points(s, req), rad = {req->radii, esz, false, &s->q_in[1], true};
+    q_array pvel = {!wj ? nullptr : at ? (const char*)s->vel + row4 * req->first_body : req->point_vel, row4, false, at ? nullptr : &s->q_in[2], true};
+    q_array out[4] = {{req->accel_irr, row4, true, &s->q_out[0], true}, {req->accel_reg, row4, true, &s->q_out[1], true},
+                      {req->jerk_irr, row4, true, &s->q_out[2], true}, {req->jerk_reg, row4, true, &s->q_out[3], true}};
+    q_array lst = {req->list, (size_t)4 * req->cap, true, &s->q_out[4], false}, cnt = {req->count, 4, true, &s->q_out[5], true};
+    if (int rc = stage_in(s, dev, {&pts, &pvel, &rad, &out[0], &out[1], &out[2], &out[3], &cnt}, true, 0, m, who)) return rc;
+
+    const uint32_t prow = split_rows(s);
+    const void* zero_row = s->zero_row;
+    uint32_t n = rows, planes = wj ? 4u : 2u, cap = req->cap, at_flag = at ? 1u : 0u, lanes = spl_lanes(cap);
+    double G = s->G, eps2d = s->eps2, rd = req->radius;
+    float eps2f = (float)s->eps2, rf = (float)req->radius;
+    for (uint32_t done = 0; done < m;) {
+        uint32_t mb, chunks, per;
+        spl_shape(s, m - done, cap, rows, planes, &mb, &chunks, &per);
+        if (int rc = field_reserve(s, s->q_part, row4 * planes * chunks * mb, who)) return rc;
+        if (int rc = field_reserve(s, s->q_seg, (size_t)4 * cap * chunks * mb, who)) return rc;
+        if (int rc = field_reserve(s, s->q_segcnt, (size_t)4 * chunks * mb, who)) return rc;
+        if (int rc = stage_in(s, dev, {&lst}, false, done, mb, who)) return rc;
+        const void* p = pts.at(done);
+        const void* pv = pvel.at(done);
+        const void* r = rad.at(done);
+        void* part = s->q_part.p;
+        void* seg = s->q_seg.p;
+        void* segcnt = s->q_segcnt.p;
+        void* l = lst.at(done);
+        void* oc = cnt.at(done);
+        void* o[4] = {out[0].at(done), out[1].at(done), out[2].at(done), out[3].at(done)};
+        uint32_t self0 = req->first_body + done;
+        dim3 grid(ceil_div(mb, prow), chunks), block(nb::kBlock);
+        void* rargs[] = {&part, &mb, &chunks, &planes, &G, &o[0], &o[1], &o[2], &o[3]};
+        void* gargs[] = {&seg, &segcnt, &mb, &chunks, &cap, &lanes, &l, &oc};
+        if (s->f64) {
+            void* args[] = {&bodies, &vel, &p, &pv, &r, &part, &n, &mb, &per, &eps2d, &rd, &seg, &segcnt, &cap, &at_flag, &self0};
+            const void* fn = wj ? (const void*)&nb::nb_spl64<double, true> : (const void*)&nb::nb_spl64<double, false>;
+            NB_HIP(s, hipLaunchKernel(fn, grid, block, args, 0, s->stream));
+            NB_HIP(s, hipLaunchKernel((const void*)&nb::nb_split_reduce<double, double>, dim3(ceil_div(mb, nb::kBlock)), block, rargs, 0, s->stream));
+        } else {
+            void* args[] = {&bodies, &vel, &p, &pv, &r, &part, &n, &mb, &per, &eps2f, &rf, &zero_row, &seg, &segcnt, &cap, &at_flag, &self0};
+            const void* fn = wj ? (const void*)&nb::nb_spl_pk<nb::kSplitNG, true> : (const void*)&nb::nb_spl_pk<nb::kSplitNG, false>;
+            NB_HIP(s, hipLaunchKernel(fn, grid, block, args, 0, s->stream));
+            NB_HIP(s, hipLaunchKernel((const void*)&nb::nb_split_reduce<float, float>, dim3(ceil_div(mb, nb::kBlock)), block, rargs, 0, s->stream));
+        }
+        NB_HIP(s, hipLaunchKernel((const void*)&nb::nb_spl_rows<>, dim3(ceil_div(mb, nb::kBlock / lanes)), block, gargs, 0, s->stream));
+        if (int rc = stage_out(s, dev, {&lst}, false, done, mb)) return rc;
+        done += mb;
+    }
+    return stage_out(s, dev, {&out[0], &out[1], &out[2], &out[3], &cnt}, true, 0, m);
+}
+
+extern "C++" bool nbi::ac_fused(const nb_sim* s) { return s->ac && !s->ac_two_calls && spl_shape_is_splits(s, s->ac_cap, 4u); }
+
+int nb_neighbor_scheme_fused(nb_sim* s, int* fused)
+{
+    if (!s || !fused) return qfail(s, NB_ERR_INVALID, "nb_neighbor_scheme_fused", !s ? "null handle" : "fused is NULL");
+    *fused = nbi::ac_fused(s) ? 1 : 0;
+    return NB_OK;
+}
+
+int nb_split_lists(nb_sim* s, const nb_split_lists_request* req) { return nbi::split_lists(s, req, s ? s->n : 0u, "nb_split_lists"); }
+
+int nb_split_lists_shape(nb_sim* s, uint32_t m, uint32_t cap, uint32_t* batch, uint32_t* chunks, uint32_t* j_per_chunk, uint32_t* rows_per_workgroup)
+{
+    if (int rc = shape_begin(s, "nb_split_lists_shape", m, bad_cap(cap))) return rc;
+    uint32_t b, c, per;
+    spl_shape(s, m, cap, s->n, s->hermite ? 4u : 2u, &b, &c, &per);      // (a Hermite handle: the shape of a request with the jerk pair)
     if (rows_per_workgroup) *rows_per_workgroup = split_rows(s);
     return shape_put(b, c, per, batch, chunks, j_per_chunk);
 }

@@ -149,15 +149,17 @@ struct nb_sim {
     nb_frame_slot frame[kFrameSlots];
     int frame_next = 0;              // slot the next request writes
     int frame_latest = -1;           // most recently requested slot
-    // The queries (nb_field_eval, nb_neighbors, nb_neighbor_lists, nb_knn, nb_list_force, nb_split_force): engine-owned buffers by
-    // role, grown on demand, released by nb_destroy.  The six share them: no two requests overlap on the stream, and within one
+    // The queries (nb_field_eval, nb_neighbors, nb_neighbor_lists, nb_knn, nb_list_force, nb_split_force, nb_split_lists): engine-owned
+    // buffers by role, grown on demand, released by nb_destroy.  They share them: no two requests overlap on the stream, and within one
     // request no two arrays take the same slot.  q_in / q_out stage a host-pointer request's inputs ([0] points, [1] radii or counts,
     // [2] point velocities, [3] list rows) and its outputs, whole (O(m)) or one batch at a time; q_part holds the partial rows per
     // (j-chunk, point of a batch) and q_off nb_neighbor_lists' uint32 offsets per (j-chunk, point of a batch): a bounded number of
     // rows whatever m and n are; q_work holds nb_knn's working rows, bounded by its memory rule; q_inf is one row at +inf, the LDS-DMA
-    // source of the f32 neighbour kernels for j past the range: written once, never used for anything else.
+    // source of the f32 neighbour kernels for j past the range: written once, never used for anything else.  q_out[4], [5] stage the rows
+    // and the counts of nb_split_lists (whose four sums take [0] .. [3]); q_seg holds its segments -- cap uint32 per (j-chunk, point of a
+    // batch), under its own bound -- and q_segcnt the chunks' true counts.
     int n_cu = 256;
-    struct field_buf { void* p = nullptr; size_t cap = 0; } q_in[4], q_out[4], q_part, q_off, q_work, q_inf;
+    struct field_buf { void* p = nullptr; size_t cap = 0; } q_in[4], q_out[6], q_part, q_off, q_work, q_inf, q_seg, q_segcnt;
     field_buf knn_stat;       // the calibration build's counters (NB_TUNING with NB_KNN_STATS set): never allocated otherwise
     // NB_INT_HERMITE4: bodies[0] / vel are the state at ONE instant, acc / jerk the derivatives derived from it.  None of the
     // leapfrog launch fields above is used: plain unpadded arrays, no planner, no graphs.
@@ -190,6 +192,7 @@ struct nb_sim {
     bool ac_over = false;            // a build at a regular time overflowed: nb_step fails with ac_msg until the scheme is set again
     std::string ac_msg;
     uint32_t ac_nsub = 8, ac_cap = 128;
+    bool ac_two_calls = false;       // NB_FLAG_AC_TWO_CALLS: a list build is nb_split_force + nb_neighbor_lists whatever the shapes are
     double ac_radius = 0.0;
     void* ac_radii = nullptr;        // device copy of the caller's radii (n elements), or null
     void* ac_ai = nullptr;           // the irregular derivatives, over the body's row of ac_list
@@ -221,6 +224,11 @@ int knn(nb_sim* s, const nb_knn_request* req, uint32_t rows, const char* who);
 int list_force(nb_sim* s, const nb_list_force_request* req, uint32_t rows, const char* who);
 // nb_split_force likewise (nb_multi_split_force: the caller's unpadded rows of shard 0)
 int split_force(nb_sim* s, const nb_split_force_request* req, uint32_t rows, const char* who);
+// nb_split_lists likewise (nb_multi_split_lists: the caller's unpadded rows of shard 0)
+int split_lists(nb_sim* s, const nb_split_lists_request* req, uint32_t rows, const char* who);
+// whether a list build of the neighbour scheme is ONE split_lists call (its shape is split_force's at every batch, and
+// NB_FLAG_AC_TWO_CALLS is not set)
+bool ac_fused(const nb_sim* s);
 const std::string& create_error();
 
 // nb_comm.hip: called by nb_step after the integrate kernel when a communicator is attached.

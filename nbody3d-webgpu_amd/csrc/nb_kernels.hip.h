@@ -67,5 +67,6 @@
 #include "kernels/list_force.hip.h"  // nb_lf32, nb_lf64 (nb_list_force: acceleration, jerk and potential over neighbour rows)
 #include "kernels/hermite.hip.h"     // nb_fj_pk, nb_fj64, nb_fj_reduce, nb_hermite_predict, nb_hermite_correct (NB_INT_HERMITE4)
 #include "kernels/split_force.hip.h" // nb_split_pk, nb_split64, nb_split_reduce (nb_split_force: regular and irregular force+jerk in one pass)
+#include "kernels/split_lists.hip.h" // nb_spl_pk, nb_spl64, nb_spl_rows (nb_split_lists: the two sums and the neighbour rows from one pass)
 #include "kernels/block.hip.h"       // nb_blk_start, nb_blk_sched, nb_blk_predict, nb_blk_fj_pk, nb_blk_fj64, nb_blk_correct (nb_set_block_steps)
 #include "kernels/ac_scheme.hip.h"   // nb_ac_sub32, nb_ac_sub64, nb_ac_predict0, nb_ac_regular, nb_ac_start (nb_set_neighbor_scheme: the Ahmad-Cohen neighbour scheme)

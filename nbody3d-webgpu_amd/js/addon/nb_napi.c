@@ -78,6 +78,9 @@ static int (*p_multi_split_force)(nb_multi *, const nb_split_force_request *);
 static int (*p_set_neighbor_scheme)(nb_sim *, const nb_neighbor_scheme *);          /* the Ahmad-Cohen neighbour scheme, likewise: optional symbols */
 static int (*p_neighbor_scheme_stats)(nb_sim *, struct nb_neighbor_scheme_stats *, int);
 static int (*p_download_neighbor_scheme)(nb_sim *, void *, void *, void *, void *, uint32_t *, uint32_t *);
+static int (*p_split_lists)(nb_sim *, const nb_split_lists_request *);              /* the two sums and the neighbour rows from one pass, likewise */
+static int (*p_multi_split_lists)(nb_multi *, const nb_split_lists_request *);
+static int (*p_neighbor_scheme_fused)(nb_sim *, int *);
 static int (*p_eqm_info)(nb_sim *, int *);                              /* the equal-mass kernels' report, also within ABI 2.4: optional symbol */
 static int (*p_eqm_form)(nb_sim *, int *);                              /* which equal-mass form, likewise */
 
@@ -177,6 +180,9 @@ static napi_value js_load(napi_env env, napi_callback_info info)
         *(void **)(&p_set_neighbor_scheme) = dlsym(h, "nb_set_neighbor_scheme");
         *(void **)(&p_neighbor_scheme_stats) = dlsym(h, "nb_neighbor_scheme_stats");
         *(void **)(&p_download_neighbor_scheme) = dlsym(h, "nb_download_neighbor_scheme");
+        *(void **)(&p_split_lists) = dlsym(h, "nb_split_lists");
+        *(void **)(&p_multi_split_lists) = dlsym(h, "nb_multi_split_lists");
+        *(void **)(&p_neighbor_scheme_fused) = dlsym(h, "nb_neighbor_scheme_fused");
         *(void **)(&p_eqm_info) = dlsym(h, "nb_eqm_info");
         *(void **)(&p_eqm_form) = dlsym(h, "nb_eqm_form");
         g_lib = h;
@@ -970,6 +976,80 @@ static napi_value js_split_force(napi_env env, napi_callback_info info)
     return undefined(env);
 }
 
+/* splitLists(handle, points|null, pointVel|null, firstBody, m, radii|null, radius, accelIrrOut|null, accelRegOut|null, jerkIrrOut|null,
+ * jerkRegOut|null, cap, listOut, countOut|null): nb_split_lists / nb_multi_split_lists.  As splitForce, and listOut (m * cap) / countOut
+ * (m): Uint32Array, written in place. */
+static napi_value js_split_lists(napi_env env, napi_callback_info info)
+{
+    size_t argc = 14; napi_value argv[14];
+    CHECK_NAPI(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    if (argc < 14) { napi_throw_type_error(env, NULL, "splitLists(handle, points|null, pointVel|null, firstBody, m, radii|null, radius, accelIrrOut|null, accelRegOut|null, jerkIrrOut|null, jerkRegOut|null, cap, listOut, countOut|null)"); return NULL; }
+    handle_t *h = get_handle(env, argv[0]); if (!h) return NULL;
+    if (!p_split_lists || !p_multi_split_lists) return throw_msg(env, NB_ERR_STATE, "the loaded library has no nb_split_lists", "nb_split_lists");
+    const napi_typedarray_type real = h->f64 ? napi_float64_array : napi_float32_array;
+    void *ptr[9] = {NULL, NULL, NULL, NULL, NULL, NULL, NULL, NULL, NULL}; size_t len[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+    static const int arg_of[9] = {1, 2, 5, 7, 8, 9, 10, 12, 13};
+    static const int is_u32[9] = {0, 0, 0, 0, 0, 0, 0, 1, 1};
+    static const char *const what[9] = {"points", "pointVel", "radii", "accelIrrOut", "accelRegOut", "jerkIrrOut", "jerkRegOut", "listOut", "countOut"};
+    for (int k = 0; k < 9; ++k) {
+        napi_valuetype vt; napi_typeof(env, argv[arg_of[k]], &vt);
+        if (vt == napi_null || vt == napi_undefined) continue;
+        bool is_ta = false; napi_is_typedarray(env, argv[arg_of[k]], &is_ta);
+        napi_typedarray_type tt; napi_value ab; size_t off;
+        const napi_typedarray_type want = is_u32[k] ? napi_uint32_array : real;
+        if (!is_ta || napi_get_typedarray_info(env, argv[arg_of[k]], &tt, &len[k], &ptr[k], &ab, &off) != napi_ok || tt != want) {
+            char buf[160]; snprintf(buf, sizeof buf, "splitLists: %s must be a %s or null", what[k], is_u32[k] ? "Uint32Array" : h->f64 ? "Float64Array" : "Float32Array");
+            napi_throw_type_error(env, NULL, buf); return NULL;
+        }
+    }
+    double first = 0, count = 0, radius = 0, cap = 0;
+    napi_get_value_double(env, argv[3], &first); napi_get_value_double(env, argv[4], &count); napi_get_value_double(env, argv[6], &radius);
+    napi_get_value_double(env, argv[11], &cap);
+    if (!(first >= 0 && first <= 4294967295.0) || !(count >= 0 && count <= 4294967295.0)) { napi_throw_range_error(env, NULL, "splitLists: firstBody / m out of range"); return NULL; }
+    if (!(cap >= 1 && cap <= 4096)) { napi_throw_range_error(env, NULL, "splitLists: cap must be in 1 .. 4096"); return NULL; }
+    nb_split_lists_request req;
+    memset(&req, 0, sizeof req);
+    req.struct_size = sizeof req;
+    req.m = (uint32_t)count;
+    req.cap = (uint32_t)cap;
+    const size_t m = req.m;
+    if ((ptr[0] && len[0] != 4 * m) || (ptr[1] && len[1] != 4 * m) || (ptr[2] && len[2] != m) || (ptr[3] && len[3] != 4 * m) ||
+        (ptr[4] && len[4] != 4 * m) || (ptr[5] && len[5] != 4 * m) || (ptr[6] && len[6] != 4 * m) || !ptr[7] || len[7] != m * (size_t)req.cap ||
+        (ptr[8] && len[8] != m)) {
+        napi_throw_range_error(env, NULL, "splitLists: points, pointVel and the sums must hold 4*m elements, radii and countOut m, listOut m * cap"); return NULL;
+    }
+    if (!ptr[0]) { req.flags = NB_SPLIT_AT_BODIES; req.first_body = (uint32_t)first; }
+    req.points = ptr[0]; req.point_vel = ptr[1]; req.radii = ptr[2]; req.radius = radius;
+    req.accel_irr = ptr[3]; req.accel_reg = ptr[4]; req.jerk_irr = ptr[5]; req.jerk_reg = ptr[6];
+    req.list = (uint32_t *)ptr[7]; req.count = (uint32_t *)ptr[8];
+    if (h->multi) {
+        int rcm = p_multi_split_lists(h->multi, &req);
+        if (rcm != NB_OK) return throw_msg(env, rcm, p_multi_last_error(h->multi), "nb_multi_split_lists");
+    } else {
+        int rc = p_split_lists(h->sim, &req);
+        if (rc != NB_OK) return throw_nb(env, rc, h->sim, "nb_split_lists");
+    }
+    return undefined(env);
+}
+
+/* neighborSchemeFused(handle) -> whether the next list build of the neighbour scheme is one nb_split_lists call (nb_neighbor_scheme_fused;
+ * false on a multi-device handle or an older library) */
+static napi_value js_neighbor_scheme_fused(napi_env env, napi_callback_info info)
+{
+    size_t argc = 1; napi_value argv[1];
+    CHECK_NAPI(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    if (argc < 1) { napi_throw_type_error(env, NULL, "neighborSchemeFused(handle)"); return NULL; }
+    handle_t *h = get_handle(env, argv[0]); if (!h) return NULL;
+    int fused = 0;
+    if (h->sim && p_neighbor_scheme_fused) {
+        int rc = p_neighbor_scheme_fused(h->sim, &fused);
+        if (rc != NB_OK) return throw_nb(env, rc, h->sim, "nb_neighbor_scheme_fused");
+    }
+    napi_value out;
+    CHECK_NAPI(env, napi_get_boolean(env, fused != 0, &out));
+    return out;
+}
+
 /* downloadJerk(handle, jerkOut): nb_download_jerk -- 4*n elements (jx, jy, jz, 0) of a Hermite handle, written in place. */
 static napi_value js_download_jerk(napi_env env, napi_callback_info info)
 {
@@ -1209,7 +1289,7 @@ static napi_value init_module(napi_env env, napi_value exports)
         {"fieldEval", js_field_eval}, {"downloadJerk", js_download_jerk}, {"uploadDerivs", js_upload_derivs},
         {"setBlockSteps", js_set_block_steps}, {"blockStats", js_block_stats}, {"downloadLevels", js_download_levels},
         {"uploadLevels", js_upload_levels}, {"neighbors", js_neighbors}, {"neighborLists", js_neighbor_lists},
-        {"knn", js_knn}, {"listForce", js_list_force}, {"splitForce", js_split_force},
+        {"knn", js_knn}, {"listForce", js_list_force}, {"splitForce", js_split_force}, {"splitLists", js_split_lists}, {"neighborSchemeFused", js_neighbor_scheme_fused},
         {"setNeighborScheme", js_set_neighbor_scheme}, {"neighborSchemeStats", js_neighbor_scheme_stats},
         {"downloadNeighborScheme", js_download_neighbor_scheme},
     };

@@ -505,6 +505,46 @@ class Simulation {
     return out;
   }
 
+  /** splitForce()'s sums AND neighborLists()' rows from ONE pass over the pairs, cut by one comparison (nb_split_lists; no reference
+   *  analogue).  The arguments of splitForce() and options.cap (entries per row, 1 .. 4096, default 64).  Returns splitForce()'s
+   *  object with two more members: list (Uint32Array, m * cap: a row's members in ascending order, padded with 0xffffffff, the cap
+   *  smallest where there are more) and count (Uint32Array, m: the true number of members) -- what neighborLists() returns; with
+   *  options.bodies a body leaves itself out of its row by index.  The simulation state is not touched. */
+  splitLists(points, options) {
+    this._need();
+    const o = options || {}, T = this.ArrayType;
+    const real = function (a, name) {
+      if (a === null || a === undefined) return null;
+      if (a instanceof T) return a;
+      if (typeof a.length === 'number') return T.from(a);
+      throw new TypeError(name + ': expected ' + T.name);
+    };
+    const pts = real(points, 'points'), pv = real(o.pointVel, 'pointVel'), radii = real(o.radii, 'radii');
+    let first = 0, m = 0;
+    if (pts) {
+      if (pts.length % 4 !== 0) throw new RangeError('points must hold 4*m elements (x, y, z, ignored)');
+      if (o.bodies) throw new RangeError('splitLists(): give either points or options.bodies, not both');
+      m = pts.length / 4;
+    } else if (o.bodies) { first = o.bodies[0] >>> 0; m = o.bodies[1] >>> 0; }
+    else throw new TypeError('splitLists(): points, or options.bodies = [first, count], required');
+    const cap = o.cap === undefined || o.cap === null ? 64 : +o.cap;
+    if (!(Number.isInteger(cap) && cap >= 1 && cap <= 4096)) throw new RangeError('splitLists(): options.cap must be an integer in 1 .. 4096');
+    const jerk = o.jerk === undefined || o.jerk === null ? this.integrator !== 'leapfrog' : !!o.jerk;
+    const radius = o.radius === undefined || o.radius === null ? 0 : +o.radius;
+    const out = { accelIrr: new T(4 * m), accelReg: new T(4 * m), jerkIrr: jerk ? new T(4 * m) : null, jerkReg: jerk ? new T(4 * m) : null,
+      list: new Uint32Array(m * cap), count: new Uint32Array(m), cap: cap };
+    addon.setParams(this._h, this.dt, this.G);   // the sums carry G
+    addon.splitLists(this._h, pts, pv, first, m, radii, radius, out.accelIrr, out.accelReg, out.jerkIrr, out.jerkReg, cap, out.list, out.count);
+    return out;
+  }
+
+  /** Whether the next list build of the neighbour scheme is ONE nb_split_lists call (nb_neighbor_scheme_fused): false with
+   *  flags: 4096 (NB_FLAG_AC_TWO_CALLS), where the launch shapes differ, and without the scheme.  Both routes leave the same bytes. */
+  neighborSchemeFused() {
+    this._need();
+    return addon.neighborSchemeFused(this._h);
+  }
+
   /** The Casertano-Hut local density at every body, a Float64Array of nBodies elements: one knn() call over all bodies, then per
    *  body the masses of its first k - 1 neighbours over the volume of the sphere that reaches the k-th (k >= 2, default 6); NaN
    *  where a body has fewer than k neighbours. */

@@ -30,6 +30,7 @@ NB_FLAG_WHOLE_SWEEPS = 256
 NB_FLAG_SINGLE_SWEEPS = 512
 NB_FLAG_NO_EQM = 1024
 NB_FLAG_NO_EQM_POW2 = 2048
+NB_FLAG_AC_TWO_CALLS = 4096
 NB_RCCL_ID_BYTES = 128
 NB_RCCL_OVERLAP = 1
 NB_MULTI_PEER, NB_MULTI_RCCL, NB_MULTI_PEER_OVERLAP = 0, 1, 2
@@ -119,6 +120,11 @@ class nb_split_force_request(C.Structure):  # include/nbody3d_hip.h (regular and
 
 NB_SPLIT_AT_BODIES, NB_SPLIT_DEVICE = 1, 4
 
+
+class nb_split_lists_request(C.Structure):  # include/nbody3d_hip.h (the two sums and the neighbour rows from one pass, added within ABI 2.4)
+    _fields_ = nb_split_force_request._fields_ + [("cap", C.c_uint32), ("reserved", C.c_uint32), ("list", C.c_void_p), ("count", C.c_void_p)]
+
+
 NB_BLOCK_FROZEN = 1
 
 
@@ -162,7 +168,8 @@ SYMBOLS = ["nb_abi_version", "nb_device_count", "nb_create", "nb_destroy", "nb_u
            "nb_knn", "nb_multi_knn", "nb_knn_shape",
            "nb_list_force", "nb_multi_list_force", "nb_list_force_shape",
            "nb_split_force", "nb_multi_split_force", "nb_split_force_shape",
-           "nb_set_neighbor_scheme", "nb_neighbor_scheme_stats", "nb_download_neighbor_scheme"]
+           "nb_set_neighbor_scheme", "nb_neighbor_scheme_stats", "nb_download_neighbor_scheme",
+           "nb_split_lists", "nb_multi_split_lists", "nb_split_lists_shape", "nb_neighbor_scheme_fused"]
 
 _lib = None
 
@@ -266,6 +273,11 @@ def load_library():
         L.nb_set_neighbor_scheme.argtypes = [vp, C.POINTER(nb_neighbor_scheme)]
         L.nb_neighbor_scheme_stats.argtypes = [vp, C.POINTER(nb_neighbor_scheme_stats), C.c_int]
         L.nb_download_neighbor_scheme.argtypes = [vp] * 7
+    if hasattr(L, "nb_split_lists"):        # the two sums and the neighbour rows from one pass, also within 2.4 and detected by the symbol
+        L.nb_split_lists.argtypes = [vp, C.POINTER(nb_split_lists_request)]
+        L.nb_multi_split_lists.argtypes = [vp, C.POINTER(nb_split_lists_request)]
+        L.nb_split_lists_shape.argtypes = [vp, C.c_uint32, C.c_uint32] + [C.POINTER(C.c_uint32)] * 4
+        L.nb_neighbor_scheme_fused.argtypes = [vp, C.POINTER(C.c_int)]
     if hasattr(L, "nb_eqm_info"):           # the equal-mass kernels' report, also within 2.4 and detected by the symbol
         L.nb_eqm_info.argtypes = [vp, C.POINTER(C.c_int)]
     if hasattr(L, "nb_eqm_form"):           # which of the equal-mass forms, likewise
@@ -482,6 +494,38 @@ def _split_force_request(dtype, points, bodies, point_vel, radius, radii, jerk):
     for name in SPLIT_OUTPUTS[:4 if jerk else 2]:
         out[name] = np.zeros((m, 4), dtype)
         setattr(req, name, _ptr(out[name]) if m else None)
+    return req, (pts, pv, rad), out
+
+
+def _split_lists_request(dtype, points, bodies, point_vel, radius, radii, jerk, cap):
+    """The nb_split_lists_request of split_lists(): (request, arrays kept alive, {output name: array}) -- split_force()'s four sums
+    plus ``list`` ((m, cap) uint32) and ``count`` ((m,) uint32)."""
+    _need("nb_split_lists", "split_lists()")
+    req = _new_request(nb_split_lists_request)
+    if points is None and bodies is None:
+        raise ValueError("split_lists(): give points or bodies=(first, count)")
+    pts, _ = _targets("split_lists()", req, dtype, points, bodies, NB_SPLIT_AT_BODIES)
+    m = req.m
+    pv = None
+    if point_vel is not None:
+        pv = _rows4(point_vel, dtype, "split_lists()", "point_vel")
+        if len(pv) != m:
+            raise ValueError("split_lists(): point_vel must hold one velocity per point")
+        req.point_vel = _ptr(pv) if m else None
+    rad = _radii("split_lists()", req, dtype, radii)
+    req.radius = 0.0 if radius is None else float(radius)
+    cap = int(cap)
+    if not 0 <= cap < 2 ** 32:
+        raise ValueError("split_lists(): cap out of range")
+    req.cap = cap
+    out = {}
+    for name in SPLIT_OUTPUTS[:4 if jerk else 2]:
+        out[name] = np.zeros((m, 4), dtype)
+        setattr(req, name, _ptr(out[name]) if m else None)
+    out["list"] = np.zeros((m, cap if 1 <= cap <= 4096 else 1), np.uint32)      # (an invalid cap is the engine's to refuse: nothing is written then)
+    out["count"] = np.zeros((m,), np.uint32)
+    req.list = _ptr(out["list"]) if m else None
+    req.count = _ptr(out["count"]) if m else None
     return req, (pts, pv, rad), out
 
 
@@ -876,6 +920,17 @@ class Simulation:
         self._check(self._L.nb_neighbor_scheme_stats(self._h, C.byref(st), 1 if reset else 0))
         return {k: int(getattr(st, k)) for k in ("enabled", "regular_steps", "substeps", "entries", "builds", "max_count", "overflowed")}
 
+    @property
+    def neighbor_scheme_fused(self):
+        """nb_neighbor_scheme_fused: whether the next list build of the neighbour scheme is ONE nb_split_lists call (True) or
+        nb_split_force followed by nb_neighbor_lists (False: NB_FLAG_AC_TWO_CALLS, a launch shape that differs, the scheme off, or
+        an older library).  Both routes leave the same bits."""
+        if not hasattr(self._L, "nb_neighbor_scheme_fused"):
+            return False
+        v = C.c_int()
+        self._check(self._L.nb_neighbor_scheme_fused(self._h, C.byref(v)))
+        return bool(v.value)
+
     def download_neighbor_scheme(self, cap):
         """nb_download_neighbor_scheme: {accel_irr, jerk_irr, accel_reg, jerk_reg ((N, 4)), list ((N, cap), uint32), count ((N,),
         uint32)} at the handle's instant; runs the scheme's start first if they are not current.  ``cap`` is the scheme's."""
@@ -1226,6 +1281,43 @@ class Simulation:
         _need("nb_split_force", "split_force_shape()")
         return self._shape(self._L.nb_split_force_shape, ("batch", "chunks", "j_per_chunk", "rows_per_workgroup"), int(m))
 
+    def split_lists(self, points=None, *, bodies=None, point_vel=None, radius=None, radii=None, jerk=None, cap=64):
+        """nb_split_lists: split_force()'s sums AND neighbor_lists()' rows from one pass over the pairs, cut by one comparison.
+        Returns split_force()'s dict with two more keys: ``list`` ((m, cap) uint32: the members in ascending order, padded with
+        NB_NBR_NONE, the cap smallest where there are more) and ``count`` ((m,) uint32: the true number of members) -- bit for bit
+        what neighbor_lists() returns; with ``bodies=(first, m)`` a body leaves itself out of its row by index (not out of its
+        sums, where it adds an exact 0).  The sums are split_force()'s bits wherever split_lists_shape() equals split_force_shape()."""
+        jerk = (self.integrator != "leapfrog") if jerk is None else bool(jerk)
+        req, keep, out = _split_lists_request(self.dtype, points, bodies, point_vel, radius, radii, jerk, cap)
+        self._check(self._L.nb_split_lists(self._h, C.byref(req)))
+        return out
+
+    def split_lists_device(self, m, list_ptr, cap, count_ptr=None, *, bodies=None, points_ptr=None, point_vel_ptr=None, radius=None,
+                           radii_ptr=None, accel_irr_ptr=None, accel_reg_ptr=None, jerk_irr_ptr=None, jerk_reg_ptr=None):
+        """The device-pointer form (NB_SPLIT_DEVICE): device addresses on the handle's device (0 or None for what is not wanted);
+        ``list_ptr``: m * cap uint32, ``count_ptr``: m uint32, the sums as split_force_device() takes them.  Read and written in
+        place, enqueued on the handle's stream, returns without waiting.  ``bodies=(first, count)`` selects the bodies themselves
+        (``points_ptr`` must then be None, ``m`` is ignored)."""
+        _need("nb_split_lists", "split_lists_device()")
+        req = _device_request(nb_split_lists_request, NB_SPLIT_DEVICE, NB_SPLIT_AT_BODIES, m, bodies, points_ptr)
+        req.point_vel = point_vel_ptr or None
+        req.radii = radii_ptr or None
+        req.radius = 0.0 if radius is None else float(radius)
+        req.accel_irr = accel_irr_ptr or None
+        req.accel_reg = accel_reg_ptr or None
+        req.jerk_irr = jerk_irr_ptr or None
+        req.jerk_reg = jerk_reg_ptr or None
+        req.cap = int(cap)
+        req.list = list_ptr or None
+        req.count = count_ptr or None
+        self._check(self._L.nb_split_lists(self._h, C.byref(req)))
+
+    def split_lists_shape(self, m, cap):
+        """{batch, chunks, j_per_chunk, rows_per_workgroup}: the launch shape nb_split_lists gives an m-point request with rows of
+        ``cap`` entries (on a Hermite handle: one with the jerk pair) -- split_force_shape()'s wherever the segments fit their bound."""
+        _need("nb_split_lists", "split_lists_shape()")
+        return self._shape(self._L.nb_split_lists_shape, ("batch", "chunks", "j_per_chunk", "rows_per_workgroup"), int(m), int(cap))
+
     def knn(self, points=None, *, bodies=None, k=6, dist2=True):
         """nb_knn: the ``k`` nearest bodies (1 <= k <= 64) of each of ``points`` ((m, 3) or (m, 4); the fourth column is ignored) --
         or, with ``bodies=(first, count)``, of each of those bodies, itself left out by index.  Returns ``(index (m, k) uint32,
@@ -1446,6 +1538,13 @@ class MultiSimulation:
         req, keep, a, j, f = _list_force_request(self.dtype, lists, bodies, points, point_vel, count, accel, jerk, phi)
         self._check(self._L.nb_multi_list_force(self._h, C.byref(req)))
         return a, j, f
+
+    def split_lists(self, points=None, *, bodies=None, point_vel=None, radius=None, radii=None, jerk=False, cap=64):
+        """nb_multi_split_lists: Simulation.split_lists() on the whole system (evaluated on shard 0 against the caller's unpadded
+        rows; ``jerk`` must stay False: the shards are leapfrog handles)."""
+        req, keep, out = _split_lists_request(self.dtype, points, bodies, point_vel, radius, radii, jerk, cap)
+        self._check(self._L.nb_multi_split_lists(self._h, C.byref(req)))
+        return out
 
     def split_force(self, points=None, *, bodies=None, point_vel=None, radius=None, radii=None, jerk=False):
         """nb_multi_split_force: Simulation.split_force() on the whole system (evaluated on shard 0 against the caller's unpadded
