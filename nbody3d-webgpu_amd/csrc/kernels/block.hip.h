@@ -255,6 +255,8 @@ __global__ __launch_bounds__(kBlock) void nb_blk_correct(const typename vec4<TP>
         if (want >= l) ln = want;
         else if ((t_next & (2u * s_i - 1u)) == 0u) ln = l - 1;
         lev[il] = (uint8_t)ln;
+        // a deeper level counts as held from here on: the last block step of a call has no schedule behind it that would see it
+        if (ln > l) atomicMax(hdr + kBlkFinest, ln);
     }
     due[il] = (t_next == (1u << L) ? 0u : t_next) + (1u << (L - ln));
 }

@@ -1,8 +1,11 @@
 """Block individual time steps (Simulation.set_block_steps) on the GPU, against the fp64 restatement in tests/block_ref.py: frozen
 levels with an exact schedule (every kernel path: active sets below, across and above the 512- and 1,024-row workgroups and the
-256-row tile, several j-chunks), pinned levels against a shared-step handle, dynamic levels on tiny systems where no decision
-sits near a level boundary, a 300-body sphere with a tight pair, an eccentric Kepler orbit, the bitwise invariants, the state
-changes that re-initialise the levels, and the errors."""
+256-row tile, several j-chunks), pinned levels against a shared-step handle, dynamic levels EXACTLY only on tiny systems (N = 6
+and 12: one wave of the scheduler, one workgroup of everything else), a 300-body sphere with a tight pair held to step counts
+within 2 % / 5 % and an energy bound, an eccentric Kepler orbit, the bitwise invariants (two handles against each other: a fault
+both share passes), the state changes that re-initialise the levels, and the errors.  Dynamic levels at sizes where the scheduler
+runs several waves and the active sets span many workgroups -- every level, every count, every decision in both precisions -- are
+held in test_block_decisions_gpu.py."""
 import ctypes as C
 
 import numpy as np
