@@ -1,5 +1,6 @@
 """GPU tests of the multi-GPU machinery on the one GPU a test box has, through the C ABI: nb_multi in RCCL mode and nb_rccl_attach with
-one rank (the partition / offset logic is covered by the virtual-shard tests here and the gloo tests in test_shard_gloo.py),
+one rank of the real RCCL (nb_rccl_attach with 2 to 4 ranks, its pointers, waits and counters: test_rccl_ranks_gpu.py, over a stand-in
+collective library; the partition logic is also covered by the virtual-shard tests here and the gloo tests in test_shard_gloo.py),
 bench.py's distributed path, virtual shards and the overlapped exchange with the planner's own split counts (BASELINE config 4's
 shard shapes).
 """
