@@ -68,7 +68,10 @@ extern "C" {
                                             nb_neighbor_scheme.  Detected by the presence of the symbol nb_set_neighbor_scheme
                              2.4 (round 17) likewise within 2.4: nb_split_lists, nb_multi_split_lists, nb_split_lists_shape,
                                             nb_split_lists_request, nb_neighbor_scheme_fused, NB_FLAG_AC_TWO_CALLS (an older library ignores
-                                            the bit: its scheme runs the two calls).  Detected by the presence of the symbol nb_split_lists */
+                                            the bit: its scheme runs the two calls).  Detected by the presence of the symbol nb_split_lists
+                             2.4 (round 18) likewise within 2.4: nb_set_neighbor_adapt, nb_neighbor_adapt_stats, nb_download_neighbor_radii,
+                                            nb_upload_neighbor_scheme, nb_neighbor_adapt, nb_neighbor_checkpoint.  Detected by the presence of
+                                            the symbol nb_set_neighbor_adapt */
 
 typedef struct nb_sim nb_sim; /* opaque */
 
@@ -957,8 +960,8 @@ int nb_split_lists_shape(nb_sim *s, uint32_t m, uint32_t cap, uint32_t *batch, u
  * (Ahmad & Cohen 1973) a body's force is kept as two parts: the IRREGULAR part over the bodies inside its neighbour radius, which
  * changes fast and is re-evaluated every hs = dt / N_sub, and the REGULAR part over every other row, which is evaluated once per dt
  * and extrapolated in between.  Only the list sums -- the entries of the lists, not N x N pairs -- run at the fine step.  Both step
- * levels are shared by all bodies, the radius is fixed (a scalar, or one per body), a list that does not fit its row is a reported
- * error.  Hermite handles only.
+ * levels are shared by all bodies, the radius is fixed (a scalar, or one per body; nb_set_neighbor_adapt below lets it follow a
+ * target count), a list that does not fit its row is a reported error.  Hermite handles only.
  *   - Quantities: per body x, v at one instant; the irregular derivatives (ai, ji) over the body's list; the regular derivatives
  *     (ar0, jr0) over every other row, valid at the last regular time t0; the body's row of the list L, of `cap` entries, with its
  *     true count.  Membership is nb_neighbors' rule letter for letter: d2 = fma(dz, dz, fma(dy, dy, dx * dx)) < h * h, strictly, in
@@ -1006,10 +1009,10 @@ int nb_split_lists_shape(nb_sim *s, uint32_t m, uint32_t cap, uint32_t *batch, u
  *     state at the regular time (nb_field_eval, nb_neighbors, nb_neighbor_lists, nb_knn, nb_list_force, nb_split_force,
  *     nb_diagnostics, frames).  nb_force_pass is unchanged.  nb_enable_timing / nb_step_times2 report one regular step per launch:
  *     force_ms is its span, integrate_ms = 0 (as for block handles).
- *   - NO bit-exact checkpoint: a restore through nb_upload (+ nb_upload_derivs) re-runs the start -- the uploaded totals are replaced
- *     by the start's components -- and continues within the scheme's accuracy, NOT bit-identically: the components a running handle
- *     carries (the irregular sums come from the list kernel's order of additions, the start's from nb_split_force's) are not part
- *     of any download that can be uploaded again.
+ *   - Checkpoint: a restore through nb_upload (+ nb_upload_derivs) alone re-runs the start -- the uploaded totals are replaced by
+ *     the start's components -- and continues within the scheme's accuracy, NOT bit-identically (the irregular sums a running handle
+ *     carries come from the list kernel's order of additions, the start's from nb_split_force's).  nb_upload_neighbor_scheme (below)
+ *     hands the running components, rows, counts and radii back and continues bit for bit.
  *   - Switching the scheme off (NULL) leaves a plain Hermite handle whose derivatives are re-evaluated at the next step.
  *   - Errors.  Leapfrog handle: NB_ERR_STATE.  Block steps and the scheme exclude each other: switching either on while the other is
  *     on is NB_ERR_STATE, the message naming both.  NULL handle, wrong struct_size, substeps not a power of two or > 1024,
@@ -1048,6 +1051,72 @@ int nb_download_neighbor_scheme(nb_sim *s, void *accel_irr, void *jerk_irr, void
  * nb_split_force returns --, 0 when they call nb_split_force and then nb_neighbor_lists (elsewhere, and under
  * NB_FLAG_AC_TWO_CALLS).  Both routes leave the same bits in every array.  0 with NB_OK on a handle without the scheme. */
 int nb_neighbor_scheme_fused(nb_sim *s, int *fused);
+
+/* ---- the neighbour scheme on a long run: radii that follow a target count, bit-exact restore (added within ABI 2.4) ----
+ * The scheme above cuts every build by the radii it was set with; a system whose density evolves sooner or later puts more than cap
+ * members into a row.  With nb_set_neighbor_adapt the engine keeps two per-body arrays in the handle's precision: `built`, the radii the
+ * current list was cut by, and `next`, the radii the next build will use.  Both are filled from the scheme's radii (or its scalar
+ * radius, rounded once) when adaptation is switched on; the scheme's own copy is never written.  nb_set_neighbor_scheme, with any
+ * argument, switches adaptation off; nb_set_neighbor_adapt, with any argument, makes the start run again (and zeroes the counters of
+ * nb_neighbor_adapt_stats).  A handle on which these calls are not used runs exactly the code it ran before them.
+ *   - A build, at the start and at a regular time, is the pass of the scheme (one nb_split_lists call, or nb_split_force and
+ *     nb_neighbor_lists), cut by `next`:
+ *       1. the pass; its header (rows with count > cap, largest count, sum of min(count, cap)) is read with the scheme's one host wait;
+ *       2. if rows have count > cap and fewer than max_rebuilds rebuilds of THIS build were made: those rows alone get
+ *          h <- rnd(h * cbrt((double)n_t / c)), c the row's count, in `next`; back to 1 on the same state (one more host wait);
+ *       3. if rows are still over after the last allowed rebuild, the scheme's overflow policy applies to the letter (at the start:
+ *          the call fails, the state and `next` are what they were; at a regular time: the state is completed and kept, nb_step
+ *          returns NB_ERR_STATE until nb_set_neighbor_scheme is called again);
+ *       4. every pass, repeated ones included, counts in nb_neighbor_scheme_stats.builds and adds to .entries.
+ *   - After the accepted pass built <- the radii used, and for every row, with c its accepted count, all in fp64:
+ *       1. f = cbrt((n_t + 0.5) / (c + 0.5)), clamped to [1.0 / g, g]            (g = grow_max);
+ *       2. h' = h * f;
+ *       3. h' is clamped to [radius_min, radius_max] where those are > 0;
+ *       4. next <- h' rounded once to the handle's precision.
+ *     A radius of exactly 0 stays 0: it skips 1-3.  With g = 1 and no clamp next = built, bit for bit.
+ *   - Order at a regular time: 1. the old-list sums (step 1 of the scheme's regular time); 2. the build with its rebuilds (steps 2-3);
+ *     3. ONE launch that makes the correction (steps 4-7) and applies the rule.  The correction moves x and v, so it runs after the
+ *     list is accepted.  aro = (ar' + ai') - aio does not depend on the new radii: any accepted list is consistent with the scheme.
+ *   - Checkpoint.  nb_download, nb_download_neighbor_scheme (components, rows, counts) and nb_download_neighbor_radii (`next`) are
+ *     the state of a running handle.  Restore, in this order: nb_upload, nb_set_params, nb_set_neighbor_scheme, nb_set_neighbor_adapt
+ *     if used, nb_upload_neighbor_scheme LAST.  All six arrays are required; radii is required with adaptation on and becomes `next`
+ *     and `built`, with adaptation off it must be NULL.  The call recomputes the totals (ai + ar0, ji + jr0 in fp64, rounded once:
+ *     the start's expression) and marks the scheme and the derivatives current for the G and dt in force; it counts no build.  The
+ *     next nb_step then equals, bit for bit, the next step of the handle the arrays came from.  Whatever stales the scheme
+ *     afterwards (a changed dt or G, nb_upload, ...) runs the start as ever.
+ *   - Errors, each before any device call, the message naming function and field.  NB_ERR_INVALID: a NULL handle or request, a wrong
+ *     struct_size, flags != 0, target == 0 or 2 target > cap, max_rebuilds > 16, grow_max < 1 (other than 0) or not finite, negative
+ *     or non-finite clamps, radius_min > radius_max when both are set; of an upload: a missing array, count[i] > cap, one of the first
+ *     count[i] entries of row i >= n or equal to i, a negative or non-finite radius, radii given with adaptation off or missing with
+ *     it on.  NB_ERR_STATE: a leapfrog handle, a handle without the scheme, an upload before nb_upload or nb_set_params. */
+typedef struct nb_neighbor_adapt {
+    uint32_t struct_size;   /* sizeof(nb_neighbor_adapt) */
+    uint32_t target;        /* n_t: 1 <= target, 2 * target <= cap of the scheme */
+    uint32_t max_rebuilds;  /* per build; 0 -> 4; at most 16 */
+    uint32_t flags;         /* none defined: must be 0 */
+    double   grow_max;      /* g >= 1: the largest factor per build, the smallest 1 / g; 0 -> cbrt(2.0) */
+    double   radius_min, radius_max; /* clamps of a non-zero radius; 0 -> none */
+} nb_neighbor_adapt;        /* 40 bytes */
+int nb_set_neighbor_adapt(nb_sim *s, const nb_neighbor_adapt *cfg /* NULL: fixed radii again */);
+
+struct nb_neighbor_adapt_stats {
+    uint32_t struct_size, enabled;
+    uint64_t rebuilds, rows_shrunk;   /* repeated passes, and the rows their shrinks touched, since set or last reset */
+    uint32_t last_rebuilds, reserved; /* of the LAST build */
+};                                    /* 32 bytes */
+int nb_neighbor_adapt_stats(nb_sim *s, struct nb_neighbor_adapt_stats *out, int reset);
+
+/* `built` and `next`, n elements of the handle's precision each (either may be NULL); runs the start first if the scheme is not
+ * current.  With adaptation off both hold the scheme's fixed radii.  Blocks. */
+int nb_download_neighbor_radii(nb_sim *s, void *built, void *next);
+
+typedef struct nb_neighbor_checkpoint {
+    uint32_t struct_size, reserved;                            /* sizeof(nb_neighbor_checkpoint), 0 */
+    const void *accel_irr, *jerk_irr, *accel_reg, *jerk_reg;   /* n rows of 4, the handle's precision: nb_download_neighbor_scheme's */
+    const uint32_t *list, *count;                              /* n * cap, n */
+    const void *radii;                                         /* n: `next`; NULL with adaptation off */
+} nb_neighbor_checkpoint;                                      /* 64 bytes */
+int nb_upload_neighbor_scheme(nb_sim *s, const nb_neighbor_checkpoint *ck);
 
 #if defined(__GNUC__)
 #pragma GCC visibility pop

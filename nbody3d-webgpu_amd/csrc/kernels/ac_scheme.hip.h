@@ -1,6 +1,7 @@
 // kernels/ac_scheme.hip.h -- the Ahmad-Cohen neighbour scheme of a Hermite handle with two shared step levels
 // (nb_set_neighbor_scheme): nb_ac_sub32 / nb_ac_sub64 (one launch per irregular substep), nb_ac_predict0, nb_ac_regular,
-// nb_ac_start.  No reference analogue.  Part of nb_kernels.hip.h (include that, not this file).
+// nb_ac_start; and, for radii that follow a target count and the checkpoint (nb_set_neighbor_adapt, nb_upload_neighbor_scheme; at
+// the end of the file): nb_ac_check, nb_ac_shrink, nb_ac_start_ad, nb_ac_regular_ad, nb_ac_restore.  No reference analogue.  Part of nb_kernels.hip.h (include that, not this file).
 //
 // A body's force is kept as two pairs of derivatives: (ai, ji) over the body's row of the neighbour list, re-evaluated every
 // hs = dt / N_sub, and (ar0, jr0) over every other row, evaluated at the regular times t0 only and extrapolated in between,
@@ -296,6 +297,126 @@ __global__ __launch_bounds__(kBlock) void nb_ac_regular(typename vec4<T>::type* 
     st4(jr0 + il, V4{JRP.x, JRP.y, JRP.z, (T)0});
     st4(acc + il, V4{(T)at[0], (T)at[1], (T)at[2], (T)0});
     st4(jerk + il, V4{(T)jt[0], (T)jt[1], (T)jt[2], (T)0});
+}
+
+// ---- radii that follow a target count (nb_set_neighbor_adapt) ----------------------------------------------------------------------
+// With adaptation on a build is cut by `next`; its header comes from nb_ac_check, so that the host can have the overflowed rows
+// shrunk (nb_ac_shrink) and the pass repeated BEFORE the correction moves x and v.  nb_ac_start_ad / nb_ac_regular_ad are the
+// parents without the header, followed by the rule on the accepted counts.  A handle on which adaptation is off launches none of these
+// (nb_ac_restore: nb_upload_neighbor_scheme, with adaptation on or off).
+struct AcRule { double nt, gmax, rmin, rmax; };      // the target count, the largest factor per build (the smallest: 1 / gmax), the clamps (0: none)
+
+// The rule, steps 1-6 of the header: all fp64, rounded once by the caller; a radius of exactly 0 stays 0.
+__device__ __forceinline__ double ac_rule(double h, uint32_t c, const AcRule& r)
+{
+    if (h == 0.0) return 0.0;
+    double f = cbrt((r.nt + 0.5) / ((double)c + 0.5));
+    f = fmin(fmax(f, 1.0 / r.gmax), r.gmax);
+    double hn = h * f;
+    if (r.rmin > 0.0) hn = fmax(hn, r.rmin);
+    if (r.rmax > 0.0) hn = fmin(hn, r.rmax);
+    return hn;
+}
+
+// The header of a build from the counts alone.  (A template as nb_spl_rows<>: the header is part of more than one translation unit.)
+template <int B = kBlock>
+__global__ __launch_bounds__(B) void nb_ac_check(const uint32_t* __restrict__ count, unsigned long long* __restrict__ hdr, uint32_t n, uint32_t cap)
+{
+    const uint32_t il = blockIdx.x * B + threadIdx.x;
+    const bool in = il < n;
+    const uint32_t ic = in ? il : n - 1;
+    ac_header(count[ic], in, cap, hdr);
+}
+
+// The rows of an overflowed build alone: h <- rnd(h cbrt(n_t / c)), c the row's count (> cap >= 2 n_t: at most cbrt(1/2) h).
+template <typename T>
+__global__ __launch_bounds__(kBlock) void nb_ac_shrink(T* __restrict__ next, const uint32_t* __restrict__ count, uint32_t n, uint32_t cap, double nt)
+{
+    const uint32_t il = blockIdx.x * kBlock + threadIdx.x;
+    if (il >= n) return;
+    const uint32_t c = count[il];
+    if (c > cap) next[il] = (T)((double)next[il] * cbrt(nt / (double)c));
+}
+
+// nb_ac_start's totals, then built <- the radii of the accepted pass and next <- the rule on its counts.
+template <typename T>
+__global__ __launch_bounds__(kBlock) void nb_ac_start_ad(const typename vec4<T>::type* __restrict__ ai,
+                                                        const typename vec4<T>::type* __restrict__ ji,
+                                                        const typename vec4<T>::type* __restrict__ ar0,
+                                                        const typename vec4<T>::type* __restrict__ jr0,
+                                                        typename vec4<T>::type* __restrict__ acc,
+                                                        typename vec4<T>::type* __restrict__ jerk, const uint32_t* __restrict__ count,
+                                                        T* __restrict__ built, T* __restrict__ next, uint32_t n, AcRule rule)
+{
+    using V4 = typename vec4<T>::type;
+    const uint32_t il = blockIdx.x * kBlock + threadIdx.x;
+    if (il >= n) return;
+    const auto AI = ld4(ai + il), JI = ld4(ji + il), AR = ld4(ar0 + il), JR = ld4(jr0 + il);
+    st4(acc + il, V4{(T)((double)AI.x + AR.x), (T)((double)AI.y + AR.y), (T)((double)AI.z + AR.z), (T)0});
+    st4(jerk + il, V4{(T)((double)JI.x + JR.x), (T)((double)JI.y + JR.y), (T)((double)JI.z + JR.z), (T)0});
+    const T h = next[il];
+    built[il] = h;
+    next[il] = (T)ac_rule((double)h, count[il], rule);
+}
+
+// nb_upload_neighbor_scheme: the totals of uploaded components (nb_ac_start's expression), nothing else.
+template <typename T>
+__global__ __launch_bounds__(kBlock) void nb_ac_restore(const typename vec4<T>::type* __restrict__ ai,
+                                                       const typename vec4<T>::type* __restrict__ ji,
+                                                       const typename vec4<T>::type* __restrict__ ar0,
+                                                       const typename vec4<T>::type* __restrict__ jr0,
+                                                       typename vec4<T>::type* __restrict__ acc,
+                                                       typename vec4<T>::type* __restrict__ jerk, uint32_t n)
+{
+    using V4 = typename vec4<T>::type;
+    const uint32_t il = blockIdx.x * kBlock + threadIdx.x;
+    if (il >= n) return;
+    const auto AI = ld4(ai + il), JI = ld4(ji + il), AR = ld4(ar0 + il), JR = ld4(jr0 + il);
+    st4(acc + il, V4{(T)((double)AI.x + AR.x), (T)((double)AI.y + AR.y), (T)((double)AI.z + AR.z), (T)0});
+    st4(jerk + il, V4{(T)((double)JI.x + JR.x), (T)((double)JI.y + JR.y), (T)((double)JI.z + JR.z), (T)0});
+}
+
+// nb_ac_regular's steps 4-7, expression for expression, on an ACCEPTED list (its header was read in front of this launch), then the
+// rule as in nb_ac_start_ad.
+template <typename T>
+__global__ __launch_bounds__(kBlock) void nb_ac_regular_ad(typename vec4<T>::type* __restrict__ x, typename vec4<T>::type* __restrict__ v,
+                                                          const typename vec4<T>::type* __restrict__ aip,
+                                                          const typename vec4<T>::type* __restrict__ jip,
+                                                          const typename vec4<T>::type* __restrict__ arp,
+                                                          const typename vec4<T>::type* __restrict__ jrp,
+                                                          const typename vec4<T>::type* __restrict__ aio,
+                                                          const typename vec4<T>::type* __restrict__ jio,
+                                                          typename vec4<T>::type* __restrict__ ar0, typename vec4<T>::type* __restrict__ jr0,
+                                                          typename vec4<T>::type* __restrict__ acc, typename vec4<T>::type* __restrict__ jerk,
+                                                          const uint32_t* __restrict__ count, T* __restrict__ built, T* __restrict__ next,
+                                                          uint32_t n, double dt, AcRule rule)
+{
+    using V4 = typename vec4<T>::type;
+    const uint32_t il = blockIdx.x * kBlock + threadIdx.x;
+    if (il >= n) return;
+    const auto X = ld4(x + il), V = ld4(v + il), AIP = ld4(aip + il), JIP = ld4(jip + il), ARP = ld4(arp + il), JRP = ld4(jrp + il);
+    const auto AIO = ld4(aio + il), JIO = ld4(jio + il), AR = ld4(ar0 + il), JR = ld4(jr0 + il);
+    const double c1 = dt * 0.5, c2 = dt * dt * (1.0 / 12.0), c3 = dt * dt * (1.0 / 6.0), c4 = dt * dt * dt * (1.0 / 24.0);
+    double xn[3], vn[3], at[3], jt[3];
+    auto one = [&](int c, double X0, double V0, double aip_, double jip_, double arp_, double jrp_, double aio_, double jio_, double ar, double jr) {
+        at[c] = arp_ + aip_;
+        jt[c] = jrp_ + jip_;
+        const double da = (at[c] - aio_) - ar, jro = jt[c] - jio_;
+        vn[c] = V0 + (c1 * da - c2 * (5.0 * jr + jro));
+        xn[c] = X0 + (c3 * da - c4 * (3.0 * jr + jro));
+    };
+    one(0, X.x, V.x, AIP.x, JIP.x, ARP.x, JRP.x, AIO.x, JIO.x, AR.x, JR.x);
+    one(1, X.y, V.y, AIP.y, JIP.y, ARP.y, JRP.y, AIO.y, JIO.y, AR.y, JR.y);
+    one(2, X.z, V.z, AIP.z, JIP.z, ARP.z, JRP.z, AIO.z, JIO.z, AR.z, JR.z);
+    st4(x + il, V4{(T)xn[0], (T)xn[1], (T)xn[2], X.w});
+    st4(v + il, V4{(T)vn[0], (T)vn[1], (T)vn[2], V.w});
+    st4(ar0 + il, V4{ARP.x, ARP.y, ARP.z, (T)0});
+    st4(jr0 + il, V4{JRP.x, JRP.y, JRP.z, (T)0});
+    st4(acc + il, V4{(T)at[0], (T)at[1], (T)at[2], (T)0});
+    st4(jerk + il, V4{(T)jt[0], (T)jt[1], (T)jt[2], (T)0});
+    const T h = next[il];
+    built[il] = h;
+    next[il] = (T)ac_rule((double)h, count[il], rule);
 }
 
 }  // namespace nb

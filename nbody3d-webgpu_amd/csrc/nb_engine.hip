@@ -569,7 +569,17 @@ int get_events(nb_sim* s, nb_events* out)
     return 0;
 }
 
-// Releases what nb_set_neighbor_scheme allocated, switches the scheme off and zeroes its counters.
+// Releases what nb_set_neighbor_adapt allocated, switches adaptation off and zeroes its counters.
+void ad_release(nb_sim* s)
+{
+    for (void** p : {&s->ad_built, &s->ad_next, &s->ad_keep})
+        if (*p) { (void)hipFree(*p); *p = nullptr; }
+    s->ad = false;
+    s->ad_rebuilds = s->ad_rows_shrunk = 0;
+    s->ad_last_rebuilds = 0;
+}
+
+// Releases what nb_set_neighbor_scheme allocated, switches the scheme (and with it adaptation) off and zeroes its counters.
 void ac_release(nb_sim* s)
 {
     for (void** p : {&s->ac_ai, &s->ac_ji, &s->ac_ar, &s->ac_jr, &s->ac_px, &s->ac_pv, &s->ac_radii, (void**)&s->ac_list, (void**)&s->ac_count, (void**)&s->ac_hdr})
@@ -579,6 +589,7 @@ void ac_release(nb_sim* s)
     s->ac_msg.clear();
     s->ac_regular = s->ac_substeps = s->ac_entries = s->ac_builds = 0;
     s->ac_max_count = s->ac_overflowed = 0;
+    ad_release(s);
 }
 
 void free_frames(nb_sim* s)
@@ -791,11 +802,12 @@ int block_step(nb_sim* s, uint32_t nsteps)
 // nb_split_lists cuts the request as nb_split_force does (nbi::ac_fused), that one call: the same bits from one pass over the pairs.
 int ac_build(nb_sim* s, void* ai, void* ji, void* ar, void* jr, const char* who)
 {
+    const void* radii = s->ad ? s->ad_next : s->ac_radii;      // (with adaptation on the scheme's own copy is only the first `next`)
     if (nbi::ac_fused(s)) {
         nb_split_lists_request q;
         memset(&q, 0, sizeof q);
         q.struct_size = sizeof q; q.m = s->n; q.flags = NB_SPLIT_AT_BODIES | NB_SPLIT_DEVICE;
-        q.radii = s->ac_radii; q.radius = s->ac_radii ? 0.0 : s->ac_radius;
+        q.radii = radii; q.radius = radii ? 0.0 : s->ac_radius;
         q.accel_irr = ai; q.jerk_irr = ji; q.accel_reg = ar; q.jerk_reg = jr;
         q.cap = s->ac_cap; q.list = s->ac_list; q.count = s->ac_count;
         if (int rc = nbi::split_lists(s, &q, s->n, who)) return rc;
@@ -805,13 +817,13 @@ int ac_build(nb_sim* s, void* ai, void* ji, void* ar, void* jr, const char* who)
     nb_split_force_request sq;
     memset(&sq, 0, sizeof sq);
     sq.struct_size = sizeof sq; sq.m = s->n; sq.flags = NB_SPLIT_AT_BODIES | NB_SPLIT_DEVICE;
-    sq.radii = s->ac_radii; sq.radius = s->ac_radii ? 0.0 : s->ac_radius;
+    sq.radii = radii; sq.radius = radii ? 0.0 : s->ac_radius;
     sq.accel_irr = ai; sq.jerk_irr = ji; sq.accel_reg = ar; sq.jerk_reg = jr;
     if (int rc = nbi::split_force(s, &sq, s->n, who)) return rc;
     nb_neighbor_list_request lq;
     memset(&lq, 0, sizeof lq);
     lq.struct_size = sizeof lq; lq.m = s->n; lq.flags = NB_NBR_AT_BODIES | NB_NBR_DEVICE;
-    lq.radii = s->ac_radii; lq.radius = s->ac_radii ? 0.0 : s->ac_radius;
+    lq.radii = radii; lq.radius = radii ? 0.0 : s->ac_radius;
     lq.cap = s->ac_cap; lq.list = s->ac_list; lq.count = s->ac_count;
     if (int rc = nbi::neighbor_lists(s, &lq, s->n, who)) return rc;
     NB_HIP(s, hipMemsetAsync(s->ac_hdr, 0, sizeof(unsigned long long) * nb::kAcHdrWords, s->stream));
@@ -834,6 +846,54 @@ int ac_read_header(nb_sim* s, bool* over, std::string* msg)
     return NB_OK;
 }
 
+nb::AcRule ad_rule(const nb_sim* s) { return nb::AcRule{(double)s->ad_target, s->ad_gmax, s->ad_rmin, s->ad_rmax}; }
+
+// A build with adaptation on (nb_set_neighbor_adapt): the pass cut by `next`, its header from the counts alone (ac_read_header's
+// wait), and, while rows are over cap and rebuilds are left, the shrink of those rows and the pass again on the same state -- one
+// more wait each.  keep: the first shrink saves `next` (a start that fails puts it back).  *over: rows are over after the last pass.
+int ad_build(nb_sim* s, void* ai, void* ji, void* ar, void* jr, const char* who, bool keep, bool* over, std::string* msg)
+{
+    uint32_t n = s->n, cap = s->ac_cap, rebuilds = 0;
+    double nt = (double)s->ad_target;
+    const dim3 grid(ceil_div(n, nb::kBlock)), block(nb::kBlock);
+    for (;;) {
+        if (int rc = ac_build(s, ai, ji, ar, jr, who)) return rc;
+        void* cargs[] = {&s->ac_count, &s->ac_hdr, &n, &cap};
+        NB_HIP(s, hipLaunchKernel((const void*)&nb::nb_ac_check<>, grid, block, cargs, 0, s->stream));
+        if (int rc = ac_read_header(s, over, msg)) return rc;
+        if (!*over || rebuilds == s->ad_max_rebuilds) break;
+        if (keep && rebuilds == 0) NB_HIP(s, hipMemcpyAsync(s->ad_keep, s->ad_next, s->esz * n, hipMemcpyDeviceToDevice, s->stream));
+        void* sargs[] = {&s->ad_next, &s->ac_count, &n, &cap, &nt};
+        const void* fn = s->f64 ? (const void*)&nb::nb_ac_shrink<double> : (const void*)&nb::nb_ac_shrink<float>;
+        NB_HIP(s, hipLaunchKernel(fn, grid, block, sargs, 0, s->stream));
+        ++rebuilds;
+        s->ad_rows_shrunk += s->ac_overflowed;
+    }
+    s->ad_rebuilds += rebuilds;
+    s->ad_last_rebuilds = rebuilds;
+    return NB_OK;
+}
+
+// The start with adaptation on: the build with its rebuilds, then the totals and the rule in one launch.
+int ad_start(nb_sim* s, const char* who)
+{
+    bool over = false;
+    std::string msg;
+    if (int rc = ad_build(s, s->ac_ai, s->ac_ji, s->ac_ar, s->ac_jr, who, true, &over, &msg)) return rc;
+    uint32_t n = s->n;
+    if (over) {      // as without adaptation: the state is untouched, and so is `next`: every later call starts again
+        if (s->ad_last_rebuilds) NB_HIP(s, hipMemcpyAsync(s->ad_next, s->ad_keep, s->esz * n, hipMemcpyDeviceToDevice, s->stream));
+        return fail(s, NB_ERR_STATE, std::string(who) + ": " + msg);
+    }
+    nb::AcRule rule = ad_rule(s);
+    void* args[] = {&s->ac_ai, &s->ac_ji, &s->ac_ar, &s->ac_jr, &s->acc, &s->jerk, &s->ac_count, &s->ad_built, &s->ad_next, &n, &rule};
+    const void* fn = s->f64 ? (const void*)&nb::nb_ac_start_ad<double> : (const void*)&nb::nb_ac_start_ad<float>;
+    NB_HIP(s, hipLaunchKernel(fn, dim3(ceil_div(n, nb::kBlock)), dim3(nb::kBlock), args, 0, s->stream));
+    s->ac_ok = true; s->ac_over = false;
+    s->derivs_ok = true; s->derivs_any_G = false; s->derivs_G = s->G;
+    return NB_OK;
+}
+
 // The start: makes the scheme's arrays current for (bodies, vel) and the G in force (a no-op while they are).
 int ensure_scheme(nb_sim* s, const char* who)
 {
@@ -841,6 +901,7 @@ int ensure_scheme(nb_sim* s, const char* who)
     if (s->ac_ok && s->derivs_ok && s->derivs_any_G) { s->derivs_any_G = false; s->derivs_G = s->G; }      // (never set while the scheme is on)
     if (s->ac_ok && s->derivs_ok && s->derivs_G == s->G) return NB_OK;
     s->ac_ok = false; s->derivs_ok = false;
+    if (s->ad) return ad_start(s, who);
     if (int rc = ac_build(s, s->ac_ai, s->ac_ji, s->ac_ar, s->ac_jr, who)) return rc;
     uint32_t n = s->n, cap = s->ac_cap;
     void* args[] = {&s->ac_ai, &s->ac_ji, &s->ac_ar, &s->ac_jr, &s->acc, &s->jerk, &s->ac_count, &s->ac_hdr, &n, &cap};
@@ -897,6 +958,22 @@ int ac_step(nb_sim* s, uint32_t nsteps)
         fq.struct_size = sizeof fq; fq.m = n; fq.flags = NB_LISTF_AT_BODIES | NB_LISTF_DEVICE;
         fq.list = s->ac_list; fq.count = s->ac_count; fq.cap = cap; fq.accel = s->hx; fq.jerk = s->hv;
         if (int rc = nbi::list_force(s, &fq, n, "nb_step")) return rc;
+        if (s->ad) {      // the list is accepted (the waits are ad_build's) in front of the correction, which moves x and v; then ONE launch
+            bool over = false;
+            if (int rc = ad_build(s, s->ac_ai, s->ac_ji, s->ac_px, s->ac_pv, "nb_step", false, &over, &s->ac_msg)) return rc;
+            nb::AcRule rule = ad_rule(s);
+            void* args[] = {&x, &v, &s->ac_ai, &s->ac_ji, &s->ac_px, &s->ac_pv, &s->hx, &s->hv, &s->ac_ar, &s->ac_jr, &s->acc, &s->jerk, &s->ac_count, &s->ad_built, &s->ad_next, &n, &dt, &rule};
+            const void* fn = s->f64 ? (const void*)&nb::nb_ac_regular_ad<double> : (const void*)&nb::nb_ac_regular_ad<float>;
+            NB_HIP(s, hipLaunchKernel(fn, rows_grid, block, args, 0, s->stream));
+            if (rec) { NB_HIP(s, hipEventRecord(ev.e[1], s->stream)); ev.blk = true; s->pending.push_back(ev); }
+            ++s->ac_regular; s->ac_substeps += nsub;
+            ++s->steps_done;
+            if (over) {      // rows are still over after the last allowed rebuild: the fixed-radii policy, to the letter
+                s->ac_over = true;
+                return fail(s, NB_ERR_STATE, "nb_step: " + s->ac_msg);
+            }
+            continue;
+        }
         if (int rc = ac_build(s, s->ac_ai, s->ac_ji, s->ac_px, s->ac_pv, "nb_step")) return rc;
         {
             void* args[] = {&x, &v, &s->ac_ai, &s->ac_ji, &s->ac_px, &s->ac_pv, &s->hx, &s->hv, &s->ac_ar, &s->ac_jr, &s->acc, &s->jerk, &s->ac_count, &s->ac_hdr, &n, &cap, &dt};
@@ -1648,6 +1725,160 @@ int nb_download_neighbor_scheme(nb_sim* s, void* accel_irr, void* jerk_irr, void
     if (jerk_reg) NB_HIP(s, hipMemcpy(jerk_reg, s->ac_jr, rows, hipMemcpyDeviceToHost));
     if (list) NB_HIP(s, hipMemcpy(list, s->ac_list, sizeof(uint32_t) * (size_t)s->n * s->ac_cap, hipMemcpyDeviceToHost));
     if (count) NB_HIP(s, hipMemcpy(count, s->ac_count, sizeof(uint32_t) * s->n, hipMemcpyDeviceToHost));
+    return NB_OK;
+}
+
+namespace {
+
+// n elements of the handle's precision, every one `h` rounded once
+void ad_fill(const nb_sim* s, double h, std::vector<char>* to)
+{
+    std::vector<char>& out = *to;
+    out.resize(s->esz * (size_t)s->n);
+    for (uint32_t i = 0; i < s->n; ++i) {
+        if (s->f64) ((double*)out.data())[i] = h; else ((float*)out.data())[i] = (float)h;
+    }
+}
+
+// what every call on the scheme's radii or checkpoint asks of the handle; nullptr: fine
+const char* ad_bad_handle(const nb_sim* s)
+{
+    if (!s->hermite) return "needs a Hermite handle (nb_config.integrator = NB_INT_HERMITE4)";
+    return s->ac ? nullptr : "the neighbour scheme is not switched on (nb_set_neighbor_scheme)";
+}
+
+}  // namespace
+
+int nb_set_neighbor_adapt(nb_sim* s, const nb_neighbor_adapt* cfg)
+{
+    const std::string F = "nb_set_neighbor_adapt: ";
+    if (cfg) {      // the fields that need no handle first: the message names the field whatever else is wrong
+        if (cfg->struct_size != sizeof(nb_neighbor_adapt)) return fail(s, NB_ERR_INVALID, F + "struct_size must be sizeof(nb_neighbor_adapt)");
+        if (cfg->flags != 0) return fail(s, NB_ERR_INVALID, F + "flags must be 0");
+        if (cfg->target == 0) return fail(s, NB_ERR_INVALID, F + "target must be >= 1");
+        if (cfg->max_rebuilds > 16) return fail(s, NB_ERR_INVALID, F + "max_rebuilds is at most 16 (0: the default 4)");
+        if (!(cfg->grow_max == 0.0 || cfg->grow_max >= 1.0) || std::isinf(cfg->grow_max)) return fail(s, NB_ERR_INVALID, F + "grow_max must be finite and >= 1 (0: the default cbrt(2))");
+        if (!(cfg->radius_min >= 0.0) || std::isinf(cfg->radius_min)) return fail(s, NB_ERR_INVALID, F + "radius_min must be finite and >= 0 (0: none)");
+        if (!(cfg->radius_max >= 0.0) || std::isinf(cfg->radius_max)) return fail(s, NB_ERR_INVALID, F + "radius_max must be finite and >= 0 (0: none)");
+        if (cfg->radius_min > 0.0 && cfg->radius_max > 0.0 && cfg->radius_min > cfg->radius_max) return fail(s, NB_ERR_INVALID, F + "radius_min must not exceed radius_max");
+    }
+    if (!s) return fail(nullptr, NB_ERR_INVALID, F + "null handle");
+    if (const char* bad = ad_bad_handle(s)) return fail(s, NB_ERR_STATE, F + bad);
+    if (cfg && 2ull * cfg->target > s->ac_cap) return fail(s, NB_ERR_INVALID, F + "target must be at most cap / 2 of the scheme (cap " + std::to_string(s->ac_cap) + ")");
+    NB_HIP(s, hipSetDevice(s->device));
+    NB_HIP(s, hipStreamSynchronize(s->stream));
+    ad_release(s);
+    s->ac_ok = false;      // the start runs again, with or without adaptation
+    if (!cfg) return NB_OK;
+    const size_t bytes = s->esz * (size_t)s->n;
+    hipError_t e = hipSuccess;
+    for (void** p : {&s->ad_built, &s->ad_next, &s->ad_keep})
+        if (e == hipSuccess) e = hipMalloc(p, bytes);
+    if (e == hipSuccess) {      // both from the scheme's radii, or from its radius; the scheme's own copy is never written
+        if (s->ac_radii) {
+            e = hipMemcpy(s->ad_built, s->ac_radii, bytes, hipMemcpyDeviceToDevice);
+            if (e == hipSuccess) e = hipMemcpy(s->ad_next, s->ac_radii, bytes, hipMemcpyDeviceToDevice);
+        } else {
+            std::vector<char> h;
+            ad_fill(s, s->ac_radius, &h);
+            e = hipMemcpy(s->ad_built, h.data(), bytes, hipMemcpyHostToDevice);
+            if (e == hipSuccess) e = hipMemcpy(s->ad_next, h.data(), bytes, hipMemcpyHostToDevice);
+        }
+    }
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        ad_release(s);
+        return fail(s, e == hipErrorOutOfMemory ? NB_ERR_NOMEM : NB_ERR_HIP, F + "cannot allocate the radii: " + hipGetErrorString(e));
+    }
+    s->ad = true;
+    s->ad_target = cfg->target;
+    s->ad_max_rebuilds = cfg->max_rebuilds ? cfg->max_rebuilds : 4u;
+    s->ad_gmax = cfg->grow_max > 0.0 ? cfg->grow_max : std::cbrt(2.0);
+    s->ad_rmin = cfg->radius_min; s->ad_rmax = cfg->radius_max;
+    return NB_OK;
+}
+
+int nb_neighbor_adapt_stats(nb_sim* s, struct nb_neighbor_adapt_stats* out, int reset)
+{
+    if (!s) return fail(nullptr, NB_ERR_INVALID, "nb_neighbor_adapt_stats: null handle");
+    if (!out || out->struct_size != sizeof(struct nb_neighbor_adapt_stats)) return fail(s, NB_ERR_INVALID, "nb_neighbor_adapt_stats: set out->struct_size to sizeof(nb_neighbor_adapt_stats)");
+    if (!s->hermite) return fail(s, NB_ERR_STATE, "nb_neighbor_adapt_stats: needs a Hermite handle (nb_config.integrator = NB_INT_HERMITE4)");
+    std::memset(out, 0, sizeof(*out));
+    out->struct_size = sizeof(*out);
+    if (!s->ad) return NB_OK;
+    out->enabled = 1u;
+    out->rebuilds = s->ad_rebuilds; out->rows_shrunk = s->ad_rows_shrunk; out->last_rebuilds = s->ad_last_rebuilds;
+    if (reset) s->ad_rebuilds = s->ad_rows_shrunk = 0;
+    return NB_OK;
+}
+
+int nb_download_neighbor_radii(nb_sim* s, void* built, void* next)
+{
+    const std::string F = "nb_download_neighbor_radii: ";
+    if (!s) return fail(nullptr, NB_ERR_INVALID, F + "null handle");
+    if (const char* bad = ad_bad_handle(s)) return fail(s, NB_ERR_STATE, F + bad);
+    if (!s->uploaded) return fail(s, NB_ERR_STATE, F + "nothing uploaded yet");
+    NB_HIP(s, hipSetDevice(s->device));
+    if (int rc = ensure_scheme(s, "nb_download_neighbor_radii")) return rc;
+    NB_HIP(s, hipStreamSynchronize(s->stream));
+    const size_t bytes = s->esz * (size_t)s->n;
+    if (s->ad || s->ac_radii) {
+        if (built) NB_HIP(s, hipMemcpy(built, s->ad ? s->ad_built : s->ac_radii, bytes, hipMemcpyDeviceToHost));
+        if (next) NB_HIP(s, hipMemcpy(next, s->ad ? s->ad_next : s->ac_radii, bytes, hipMemcpyDeviceToHost));
+        return NB_OK;
+    }
+    std::vector<char> h;      // fixed radii: both arrays hold them
+    ad_fill(s, s->ac_radius, &h);
+    if (built) memcpy(built, h.data(), bytes);
+    if (next) memcpy(next, h.data(), bytes);
+    return NB_OK;
+}
+
+int nb_upload_neighbor_scheme(nb_sim* s, const nb_neighbor_checkpoint* ck)
+{
+    const std::string F = "nb_upload_neighbor_scheme: ";
+    if (ck && ck->struct_size != sizeof(nb_neighbor_checkpoint)) return fail(s, NB_ERR_INVALID, F + "struct_size must be sizeof(nb_neighbor_checkpoint)");
+    if (ck && ck->reserved != 0) return fail(s, NB_ERR_INVALID, F + "reserved must be 0");
+    if (ck && !(ck->accel_irr && ck->jerk_irr && ck->accel_reg && ck->jerk_reg && ck->list && ck->count))
+        return fail(s, NB_ERR_INVALID, F + "accel_irr, jerk_irr, accel_reg, jerk_reg, list and count are all required");
+    if (!s || !ck) return fail(s, NB_ERR_INVALID, F + (!s ? "null handle" : "the checkpoint is NULL"));
+    if (const char* bad = ad_bad_handle(s)) return fail(s, NB_ERR_STATE, F + bad);
+    if (!s->uploaded) return fail(s, NB_ERR_STATE, F + "nb_upload has not been called");
+    if (!s->params_set) return fail(s, NB_ERR_STATE, F + "nb_set_params has not been called (G, dt)");
+    if (s->ad && !ck->radii) return fail(s, NB_ERR_INVALID, F + "radii is required while adaptation is on (nb_set_neighbor_adapt)");
+    if (!s->ad && ck->radii) return fail(s, NB_ERR_INVALID, F + "radii must be NULL while adaptation is off: the radii are the scheme's (nb_set_neighbor_scheme)");
+    const uint32_t n = s->n, cap = s->ac_cap;
+    for (uint32_t i = 0; i < n; ++i) {
+        const uint32_t c = ck->count[i];
+        if (c > cap) return fail(s, NB_ERR_INVALID, F + "count[" + std::to_string(i) + "] = " + std::to_string(c) + " exceeds the scheme's cap " + std::to_string(cap));
+        for (uint32_t e = 0; e < c; ++e) {
+            const uint32_t j = ck->list[(size_t)i * cap + e];
+            if (j >= n || j == i) return fail(s, NB_ERR_INVALID, F + "list[" + std::to_string(i) + "][" + std::to_string(e) + "] = " + std::to_string(j) + (j == i ? " is the row's own body" : " is not a body"));
+        }
+        if (ck->radii) {
+            const double h = s->f64 ? ((const double*)ck->radii)[i] : (double)((const float*)ck->radii)[i];
+            if (!(h >= 0.0) || std::isinf(h)) return fail(s, NB_ERR_INVALID, F + "radii[" + std::to_string(i) + "] must be finite and >= 0");
+        }
+    }
+    NB_HIP(s, hipSetDevice(s->device));
+    NB_HIP(s, hipStreamSynchronize(s->stream));
+    const size_t rows = 4 * s->esz * n;
+    NB_HIP(s, hipMemcpy(s->ac_ai, ck->accel_irr, rows, hipMemcpyHostToDevice));
+    NB_HIP(s, hipMemcpy(s->ac_ji, ck->jerk_irr, rows, hipMemcpyHostToDevice));
+    NB_HIP(s, hipMemcpy(s->ac_ar, ck->accel_reg, rows, hipMemcpyHostToDevice));
+    NB_HIP(s, hipMemcpy(s->ac_jr, ck->jerk_reg, rows, hipMemcpyHostToDevice));
+    NB_HIP(s, hipMemcpy(s->ac_list, ck->list, sizeof(uint32_t) * (size_t)n * cap, hipMemcpyHostToDevice));
+    NB_HIP(s, hipMemcpy(s->ac_count, ck->count, sizeof(uint32_t) * n, hipMemcpyHostToDevice));
+    if (ck->radii) {
+        NB_HIP(s, hipMemcpy(s->ad_next, ck->radii, s->esz * n, hipMemcpyHostToDevice));
+        NB_HIP(s, hipMemcpy(s->ad_built, ck->radii, s->esz * n, hipMemcpyHostToDevice));
+    }
+    uint32_t nn = n;
+    void* args[] = {&s->ac_ai, &s->ac_ji, &s->ac_ar, &s->ac_jr, &s->acc, &s->jerk, &nn};
+    const void* fn = s->f64 ? (const void*)&nb::nb_ac_restore<double> : (const void*)&nb::nb_ac_restore<float>;
+    NB_HIP(s, hipLaunchKernel(fn, dim3(ceil_div(n, nb::kBlock)), dim3(nb::kBlock), args, 0, s->stream));
+    s->ac_ok = true;      // current for the G and dt in force; it counts no build
+    s->derivs_ok = true; s->derivs_any_G = false; s->derivs_G = s->G;
     return NB_OK;
 }
 

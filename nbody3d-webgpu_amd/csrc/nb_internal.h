@@ -207,6 +207,15 @@ struct nb_sim {
     unsigned long long* ac_hdr_host = nullptr;   // pinned host copy the step loop reads after its wait
     uint64_t ac_regular = 0, ac_substeps = 0, ac_entries = 0, ac_builds = 0;
     uint32_t ac_max_count = 0, ac_overflowed = 0;      // of the last build
+    // nb_set_neighbor_adapt: radii that follow a target count.  Off: none of this is read and a build is cut by ac_radii / ac_radius.
+    bool ad = false;
+    uint32_t ad_target = 0, ad_max_rebuilds = 4;
+    double ad_gmax = 0.0, ad_rmin = 0.0, ad_rmax = 0.0;
+    void* ad_built = nullptr;        // n radii of the handle's precision: what the current list was cut by
+    void* ad_next = nullptr;         // what the next build will use
+    void* ad_keep = nullptr;         // `next` as a start found it (put back when the start fails)
+    uint64_t ad_rebuilds = 0, ad_rows_shrunk = 0;
+    uint32_t ad_last_rebuilds = 0;
 };
 
 namespace nbi {

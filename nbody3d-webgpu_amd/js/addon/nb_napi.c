@@ -78,6 +78,10 @@ static int (*p_multi_split_force)(nb_multi *, const nb_split_force_request *);
 static int (*p_set_neighbor_scheme)(nb_sim *, const nb_neighbor_scheme *);          /* the Ahmad-Cohen neighbour scheme, likewise: optional symbols */
 static int (*p_neighbor_scheme_stats)(nb_sim *, struct nb_neighbor_scheme_stats *, int);
 static int (*p_download_neighbor_scheme)(nb_sim *, void *, void *, void *, void *, uint32_t *, uint32_t *);
+static int (*p_set_neighbor_adapt)(nb_sim *, const nb_neighbor_adapt *);            /* its radii that follow a target count and its checkpoint, likewise */
+static int (*p_neighbor_adapt_stats)(nb_sim *, struct nb_neighbor_adapt_stats *, int);
+static int (*p_download_neighbor_radii)(nb_sim *, void *, void *);
+static int (*p_upload_neighbor_scheme)(nb_sim *, const nb_neighbor_checkpoint *);
 static int (*p_split_lists)(nb_sim *, const nb_split_lists_request *);              /* the two sums and the neighbour rows from one pass, likewise */
 static int (*p_multi_split_lists)(nb_multi *, const nb_split_lists_request *);
 static int (*p_neighbor_scheme_fused)(nb_sim *, int *);
@@ -180,6 +184,10 @@ static napi_value js_load(napi_env env, napi_callback_info info)
         *(void **)(&p_set_neighbor_scheme) = dlsym(h, "nb_set_neighbor_scheme");
         *(void **)(&p_neighbor_scheme_stats) = dlsym(h, "nb_neighbor_scheme_stats");
         *(void **)(&p_download_neighbor_scheme) = dlsym(h, "nb_download_neighbor_scheme");
+        *(void **)(&p_set_neighbor_adapt) = dlsym(h, "nb_set_neighbor_adapt");
+        *(void **)(&p_neighbor_adapt_stats) = dlsym(h, "nb_neighbor_adapt_stats");
+        *(void **)(&p_download_neighbor_radii) = dlsym(h, "nb_download_neighbor_radii");
+        *(void **)(&p_upload_neighbor_scheme) = dlsym(h, "nb_upload_neighbor_scheme");
         *(void **)(&p_split_lists) = dlsym(h, "nb_split_lists");
         *(void **)(&p_multi_split_lists) = dlsym(h, "nb_multi_split_lists");
         *(void **)(&p_neighbor_scheme_fused) = dlsym(h, "nb_neighbor_scheme_fused");
@@ -1278,6 +1286,97 @@ static napi_value js_download_neighbor_scheme(napi_env env, napi_callback_info i
     return undefined(env);
 }
 
+/* setNeighborAdapt(handle, null) | setNeighborAdapt(handle, target, growMax, maxRebuilds, radiusMin, radiusMax): nb_set_neighbor_adapt
+ * (growMax 0 / maxRebuilds 0: the defaults cbrt(2) / 4; radiusMin / radiusMax 0: none) */
+static napi_value js_set_neighbor_adapt(napi_env env, napi_callback_info info)
+{
+    size_t argc = 6; napi_value argv[6];
+    CHECK_NAPI(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    if (argc < 2) { napi_throw_type_error(env, NULL, "setNeighborAdapt(handle, null | target, growMax, maxRebuilds, radiusMin, radiusMax)"); return NULL; }
+    handle_t *h = scheme_handle(env, argv[0], *(void **)&p_set_neighbor_adapt, "nb_set_neighbor_adapt"); if (!h) return NULL;
+    napi_valuetype t; napi_typeof(env, argv[1], &t);
+    int rc;
+    if (argc < 6 && (t == napi_null || t == napi_undefined)) rc = p_set_neighbor_adapt(h->sim, NULL);
+    else {
+        if (argc < 6) { napi_throw_type_error(env, NULL, "setNeighborAdapt(handle, target, growMax, maxRebuilds, radiusMin, radiusMax)"); return NULL; }
+        nb_neighbor_adapt cfg;
+        memset(&cfg, 0, sizeof cfg);
+        cfg.struct_size = sizeof cfg;
+        uint32_t u = 0;
+        CHECK_NAPI(env, napi_get_value_uint32(env, argv[1], &u)); cfg.target = u;
+        CHECK_NAPI(env, napi_get_value_double(env, argv[2], &cfg.grow_max));
+        CHECK_NAPI(env, napi_get_value_uint32(env, argv[3], &u)); cfg.max_rebuilds = u;
+        CHECK_NAPI(env, napi_get_value_double(env, argv[4], &cfg.radius_min));
+        CHECK_NAPI(env, napi_get_value_double(env, argv[5], &cfg.radius_max));
+        rc = p_set_neighbor_adapt(h->sim, &cfg);
+    }
+    if (rc != NB_OK) return throw_nb(env, rc, h->sim, "nb_set_neighbor_adapt");
+    return undefined(env);
+}
+
+/* neighborAdaptStats(handle, reset) -> {enabled, rebuilds, rowsShrunk, lastRebuilds} (counts as doubles) */
+static napi_value js_neighbor_adapt_stats(napi_env env, napi_callback_info info)
+{
+    size_t argc = 2; napi_value argv[2];
+    CHECK_NAPI(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    if (argc < 1) { napi_throw_type_error(env, NULL, "neighborAdaptStats(handle, reset)"); return NULL; }
+    handle_t *h = scheme_handle(env, argv[0], *(void **)&p_neighbor_adapt_stats, "nb_neighbor_adapt_stats"); if (!h) return NULL;
+    bool reset = false;
+    if (argc > 1) napi_get_value_bool(env, argv[1], &reset);
+    struct nb_neighbor_adapt_stats st;
+    memset(&st, 0, sizeof st);
+    st.struct_size = sizeof st;
+    int rc = p_neighbor_adapt_stats(h->sim, &st, reset ? 1 : 0);
+    if (rc != NB_OK) return throw_nb(env, rc, h->sim, "nb_neighbor_adapt_stats");
+    napi_value o, v;
+    CHECK_NAPI(env, napi_create_object(env, &o));
+    napi_get_boolean(env, st.enabled != 0, &v); napi_set_named_property(env, o, "enabled", v);
+    napi_create_double(env, (double)st.rebuilds, &v); napi_set_named_property(env, o, "rebuilds", v);
+    napi_create_double(env, (double)st.rows_shrunk, &v); napi_set_named_property(env, o, "rowsShrunk", v);
+    napi_create_uint32(env, st.last_rebuilds, &v); napi_set_named_property(env, o, "lastRebuilds", v);
+    return o;
+}
+
+/* downloadNeighborRadii(handle, built, next): nb_download_neighbor_radii, written in place; either may be null.  n elements of the
+ * simulation's precision each */
+static napi_value js_download_neighbor_radii(napi_env env, napi_callback_info info)
+{
+    size_t argc = 3; napi_value argv[3];
+    CHECK_NAPI(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    if (argc < 3) { napi_throw_type_error(env, NULL, "downloadNeighborRadii(handle, built, next)"); return NULL; }
+    handle_t *h = scheme_handle(env, argv[0], *(void **)&p_download_neighbor_radii, "nb_download_neighbor_radii"); if (!h) return NULL;
+    void *r[2];
+    for (int k = 0; k < 2; ++k)
+        if (!get_typed(env, argv[1 + k], h->f64 ? napi_float64_array : napi_float32_array, h->n, 1, &r[k], "built / next must be null or typed arrays of n elements of the simulation's precision")) return NULL;
+    int rc = p_download_neighbor_radii(h->sim, r[0], r[1]);
+    if (rc != NB_OK) return throw_nb(env, rc, h->sim, "nb_download_neighbor_radii");
+    return undefined(env);
+}
+
+/* uploadNeighborScheme(handle, accelIrr, jerkIrr, accelReg, jerkReg, list, count, radii | null): nb_upload_neighbor_scheme, the last call
+ * of a restore.  The shapes of downloadNeighborScheme; radii: n elements (`next`), null with adaptation off */
+static napi_value js_upload_neighbor_scheme(napi_env env, napi_callback_info info)
+{
+    size_t argc = 8; napi_value argv[8];
+    CHECK_NAPI(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    if (argc < 8) { napi_throw_type_error(env, NULL, "uploadNeighborScheme(handle, accelIrr, jerkIrr, accelReg, jerkReg, list, count, radii)"); return NULL; }
+    handle_t *h = scheme_handle(env, argv[0], *(void **)&p_upload_neighbor_scheme, "nb_upload_neighbor_scheme"); if (!h) return NULL;
+    void *row[4], *list, *count, *radii;
+    for (int k = 0; k < 4; ++k)
+        if (!get_array(env, argv[1 + k], h, 1, &row[k], "accelIrr / jerkIrr / accelReg / jerkReg must be typed arrays of 4*n elements")) return NULL;
+    if (!get_typed(env, argv[5], napi_uint32_array, (size_t)h->n * h->ac_cap, 1, &list, "list must be a Uint32Array of n * cap elements")) return NULL;
+    if (!get_typed(env, argv[6], napi_uint32_array, h->n, 1, &count, "count must be a Uint32Array of n elements")) return NULL;
+    if (!get_typed(env, argv[7], h->f64 ? napi_float64_array : napi_float32_array, h->n, 1, &radii, "radii must be null or a typed array of n elements of the simulation's precision")) return NULL;
+    nb_neighbor_checkpoint ck;
+    memset(&ck, 0, sizeof ck);
+    ck.struct_size = sizeof ck;
+    ck.accel_irr = row[0]; ck.jerk_irr = row[1]; ck.accel_reg = row[2]; ck.jerk_reg = row[3];
+    ck.list = (const uint32_t *)list; ck.count = (const uint32_t *)count; ck.radii = radii;
+    int rc = p_upload_neighbor_scheme(h->sim, &ck);      /* (a missing array is the library's NB_ERR_INVALID) */
+    if (rc != NB_OK) return throw_nb(env, rc, h->sim, "nb_upload_neighbor_scheme");
+    return undefined(env);
+}
+
 static napi_value init_module(napi_env env, napi_value exports)
 {
     static const struct { const char *name; napi_callback fn; } fns[] = {
@@ -1292,6 +1391,8 @@ static napi_value init_module(napi_env env, napi_value exports)
         {"knn", js_knn}, {"listForce", js_list_force}, {"splitForce", js_split_force}, {"splitLists", js_split_lists}, {"neighborSchemeFused", js_neighbor_scheme_fused},
         {"setNeighborScheme", js_set_neighbor_scheme}, {"neighborSchemeStats", js_neighbor_scheme_stats},
         {"downloadNeighborScheme", js_download_neighbor_scheme},
+        {"setNeighborAdapt", js_set_neighbor_adapt}, {"neighborAdaptStats", js_neighbor_adapt_stats},
+        {"downloadNeighborRadii", js_download_neighbor_radii}, {"uploadNeighborScheme", js_upload_neighbor_scheme},
     };
     for (size_t i = 0; i < sizeof fns / sizeof fns[0]; ++i) {
         napi_value f;

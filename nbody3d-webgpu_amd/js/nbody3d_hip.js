@@ -258,6 +258,42 @@ class Simulation {
     return out;
   }
 
+  /** Radii that follow a target count (nb_set_neighbor_adapt; needs setNeighborScheme first): after every list build each radius moves
+   *  towards the one that would hold `target` members, by at most growMax per build (default cbrt(2)); a build with rows over cap
+   *  shrinks those rows and runs again, up to maxRebuilds times (default 4).  {target, growMax, maxRebuilds, radiusMin, radiusMax};
+   *  2 * target <= cap.  setNeighborAdapt(null) goes back to the scheme's fixed radii. */
+  setNeighborAdapt(options) {
+    this._need();
+    if (options === null || options === undefined) { addon.setNeighborAdapt(this._h, null); return this; }
+    addon.setNeighborAdapt(this._h, (options.target || 0) >>> 0, +(options.growMax || 0), (options.maxRebuilds || 0) >>> 0,
+      +(options.radiusMin || 0), +(options.radiusMax || 0));
+    return this;
+  }
+
+  /** {enabled, rebuilds, rowsShrunk, lastRebuilds} (nb_neighbor_adapt_stats); lastRebuilds belongs to the last build. */
+  neighborAdaptStats(reset) { this._need(); return addon.neighborAdaptStats(this._h, !!reset); }
+
+  /** {built, next} (nb_download_neighbor_radii; N each): the radii the current list was cut by and those the next build will use;
+   *  with adaptation off both are the scheme's fixed radii. */
+  downloadNeighborRadii() {
+    this._need();
+    const T = this.ArrayType, out = { built: new T(this.nBodies), next: new T(this.nBodies) };
+    addon.setParams(this._h, this.dt, this.G);
+    addon.downloadNeighborRadii(this._h, out.built, out.next);
+    return out;
+  }
+
+  /** The last call of a restore that continues bit for bit (nb_upload_neighbor_scheme): restore({bodies, vel}), setNeighborScheme(...),
+   *  setNeighborAdapt(...) if used, then uploadNeighborScheme(downloadNeighborScheme()'s object, downloadNeighborRadii().next | null). */
+  uploadNeighborScheme(scheme, radii) {
+    this._need();
+    const T = this.ArrayType, as = (a, A) => (a === null || a === undefined ? null : (a instanceof A ? a : A.from(a)));
+    addon.setParams(this._h, this.dt, this.G);
+    addon.uploadNeighborScheme(this._h, as(scheme.accelIrr, T), as(scheme.jerkIrr, T), as(scheme.accelReg, T), as(scheme.jerkReg, T),
+      as(scheme.list, Uint32Array), as(scheme.count, Uint32Array), as(radii, T));
+    return this;
+  }
+
   /** util.js:230-244: write the three arrays into the EXISTING buffers (N must match).  A 'hermite4' simulation ignores accel on its
    *  own (a derived array); with BOTH state.accel and state.jerk it takes them as its derivatives (nb_upload_derivs). */
   restore(state) {

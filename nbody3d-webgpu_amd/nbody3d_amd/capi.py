@@ -148,6 +148,21 @@ class nb_neighbor_scheme_stats(C.Structure):
                 ("entries", C.c_uint64), ("builds", C.c_uint64), ("max_count", C.c_uint32), ("overflowed", C.c_uint32)]
 
 
+class nb_neighbor_adapt(C.Structure):       # include/nbody3d_hip.h (the scheme's radii follow a target count)
+    _fields_ = [("struct_size", C.c_uint32), ("target", C.c_uint32), ("max_rebuilds", C.c_uint32), ("flags", C.c_uint32),
+                ("grow_max", C.c_double), ("radius_min", C.c_double), ("radius_max", C.c_double)]
+
+
+class nb_neighbor_adapt_stats(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("enabled", C.c_uint32), ("rebuilds", C.c_uint64), ("rows_shrunk", C.c_uint64),
+                ("last_rebuilds", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class nb_neighbor_checkpoint(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_uint32), ("accel_irr", C.c_void_p), ("jerk_irr", C.c_void_p),
+                ("accel_reg", C.c_void_p), ("jerk_reg", C.c_void_p), ("list", C.c_void_p), ("count", C.c_void_p), ("radii", C.c_void_p)]
+
+
 EXCHANGE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p)
 EXCHANGE_WAIT_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p)
 
@@ -169,7 +184,8 @@ SYMBOLS = ["nb_abi_version", "nb_device_count", "nb_create", "nb_destroy", "nb_u
            "nb_list_force", "nb_multi_list_force", "nb_list_force_shape",
            "nb_split_force", "nb_multi_split_force", "nb_split_force_shape",
            "nb_set_neighbor_scheme", "nb_neighbor_scheme_stats", "nb_download_neighbor_scheme",
-           "nb_split_lists", "nb_multi_split_lists", "nb_split_lists_shape", "nb_neighbor_scheme_fused"]
+           "nb_split_lists", "nb_multi_split_lists", "nb_split_lists_shape", "nb_neighbor_scheme_fused",
+           "nb_set_neighbor_adapt", "nb_neighbor_adapt_stats", "nb_download_neighbor_radii", "nb_upload_neighbor_scheme"]
 
 _lib = None
 
@@ -278,6 +294,11 @@ def load_library():
         L.nb_multi_split_lists.argtypes = [vp, C.POINTER(nb_split_lists_request)]
         L.nb_split_lists_shape.argtypes = [vp, C.c_uint32, C.c_uint32] + [C.POINTER(C.c_uint32)] * 4
         L.nb_neighbor_scheme_fused.argtypes = [vp, C.POINTER(C.c_int)]
+    if hasattr(L, "nb_set_neighbor_adapt"):     # radii that follow a target count and the scheme's checkpoint, also within 2.4
+        L.nb_set_neighbor_adapt.argtypes = [vp, C.POINTER(nb_neighbor_adapt)]
+        L.nb_neighbor_adapt_stats.argtypes = [vp, C.POINTER(nb_neighbor_adapt_stats), C.c_int]
+        L.nb_download_neighbor_radii.argtypes = [vp, vp, vp]
+        L.nb_upload_neighbor_scheme.argtypes = [vp, C.POINTER(nb_neighbor_checkpoint)]
     if hasattr(L, "nb_eqm_info"):           # the equal-mass kernels' report, also within 2.4 and detected by the symbol
         L.nb_eqm_info.argtypes = [vp, C.POINTER(C.c_int)]
     if hasattr(L, "nb_eqm_form"):           # which of the equal-mass forms, likewise
@@ -940,6 +961,102 @@ class Simulation:
         out["count"] = np.zeros(self.n, np.uint32)
         self._check(self._L.nb_download_neighbor_scheme(self._h, *[_ptr(out[k]) for k in ("accel_irr", "jerk_irr", "accel_reg", "jerk_reg", "list", "count")]))
         return out
+
+    # -- the scheme on a long run: radii that follow a target count, bit-exact restore --
+    def _need_adapt(self, what):
+        if not hasattr(self._L, "nb_set_neighbor_adapt"):
+            raise NBodyError(1, "%s: the loaded library has no nb_set_neighbor_adapt" % what)
+
+    def set_neighbor_adapt(self, *args, **kw):
+        """set_neighbor_adapt(target, grow_max=None, max_rebuilds=None, radius_min=None, radius_max=None): nb_set_neighbor_adapt --
+        after every list build each radius moves towards the one that would hold ``target`` members (by at most grow_max per
+        build, None: cbrt(2)), and a build with rows over cap shrinks those rows and runs again, up to max_rebuilds times (None: 4).
+        radius_min / radius_max clamp a non-zero radius.  Needs set_neighbor_scheme first; 2 * target <= its cap.
+        set_neighbor_adapt(None) goes back to the scheme's fixed radii."""
+        self._need_adapt("set_neighbor_adapt()")
+        if args == (None,) and not kw:
+            self._check(self._L.nb_set_neighbor_adapt(self._h, None))
+            return self
+
+        def bind(target, grow_max=None, max_rebuilds=None, radius_min=None, radius_max=None):
+            return target, grow_max, max_rebuilds, radius_min, radius_max
+        target, grow_max, max_rebuilds, radius_min, radius_max = bind(*args, **kw)
+        cfg = nb_neighbor_adapt()
+        cfg.struct_size = C.sizeof(nb_neighbor_adapt)
+        cfg.target = int(target)
+        cfg.max_rebuilds = 0 if max_rebuilds is None else int(max_rebuilds)
+        cfg.flags = 0
+        cfg.grow_max = 0.0 if grow_max is None else float(grow_max)
+        cfg.radius_min = 0.0 if radius_min is None else float(radius_min)
+        cfg.radius_max = 0.0 if radius_max is None else float(radius_max)
+        self._check(self._L.nb_set_neighbor_adapt(self._h, C.byref(cfg)))
+        return self
+
+    def neighbor_adapt_stats(self, reset=False):
+        """nb_neighbor_adapt_stats: {enabled, rebuilds, rows_shrunk, last_rebuilds}; last_rebuilds belongs to the last build."""
+        self._need_adapt("neighbor_adapt_stats()")
+        st = nb_neighbor_adapt_stats()
+        st.struct_size = C.sizeof(nb_neighbor_adapt_stats)
+        self._check(self._L.nb_neighbor_adapt_stats(self._h, C.byref(st), 1 if reset else 0))
+        return {k: int(getattr(st, k)) for k in ("enabled", "rebuilds", "rows_shrunk", "last_rebuilds")}
+
+    def download_neighbor_radii(self):
+        """nb_download_neighbor_radii: (built, next), each (N,): the radii the current list was cut by and those the next build
+        will use (with adaptation off both are the scheme's fixed radii); runs the scheme's start first if it is not current."""
+        self._need_adapt("download_neighbor_radii()")
+        built, nxt = np.zeros(self.n, self.dtype), np.zeros(self.n, self.dtype)
+        self._check(self._L.nb_download_neighbor_radii(self._h, _ptr(built), _ptr(nxt)))
+        return built, nxt
+
+    def upload_neighbor_scheme(self, accel_irr=None, jerk_irr=None, accel_reg=None, jerk_reg=None, list=None, count=None, radii=None):
+        """nb_upload_neighbor_scheme: the last call of a restore -- the arrays of download_neighbor_scheme() and, with adaptation on,
+        ``radii`` = the `next` of download_neighbor_radii().  The next step continues bit for bit."""
+        self._need_adapt("upload_neighbor_scheme()")
+        ck = nb_neighbor_checkpoint()
+        ck.struct_size = C.sizeof(nb_neighbor_checkpoint)
+        keep = []
+        for name, a in (("accel_irr", accel_irr), ("jerk_irr", jerk_irr), ("accel_reg", accel_reg), ("jerk_reg", jerk_reg)):
+            if a is not None:
+                keep.append(self._arr(a, name))
+                setattr(ck, name, _ptr(keep[-1]))
+        if count is not None:
+            keep.append(np.ascontiguousarray(count, np.uint32))
+            if keep[-1].shape != (self.n,):
+                raise ValueError("count must have shape (%d,)" % self.n)
+            ck.count = _ptr(keep[-1])
+        if list is not None:
+            keep.append(np.ascontiguousarray(list, np.uint32))
+            if keep[-1].ndim != 2 or keep[-1].shape[0] != self.n:
+                raise ValueError("list must have shape (%d, cap)" % self.n)
+            ck.list = _ptr(keep[-1])
+        if radii is not None:
+            keep.append(np.ascontiguousarray(radii, self.dtype))
+            if keep[-1].shape != (self.n,):
+                raise ValueError("radii must have shape (%d,)" % self.n)
+            ck.radii = _ptr(keep[-1])
+        self._check(self._L.nb_upload_neighbor_scheme(self._h, C.byref(ck)))
+        return self
+
+    def neighbor_scheme_checkpoint(self, cap):
+        """Everything a restore of a handle with the neighbour scheme needs, as host arrays: {bodies, vel, dt, G, scheme (the arrays
+        of download_neighbor_scheme(cap)), radii (`next`), adaptive}.  The scheme's and the adaptation's settings are the caller's."""
+        b, v, _ = self.read(accel=False)
+        ck = {"bodies": b, "vel": v, "dt": self.dt, "G": self.G, "scheme": self.download_neighbor_scheme(cap),
+              "adaptive": bool(self.neighbor_adapt_stats()["enabled"])}
+        ck["radii"] = self.download_neighbor_radii()[1]
+        return ck
+
+    def restore_neighbor_scheme(self, ck, scheme=None, adapt=None):
+        """The calls of a restore in their order: init, set_params, set_neighbor_scheme(**scheme) and set_neighbor_adapt(**adapt)
+        where given (a handle that already has them set keeps them otherwise), upload_neighbor_scheme last."""
+        self.init(ck["bodies"], ck["vel"])
+        self.set_params(ck["dt"], ck["G"])
+        if scheme is not None:
+            self.set_neighbor_scheme(**scheme)
+        if adapt is not None:
+            self.set_neighbor_adapt(**adapt)
+        self.upload_neighbor_scheme(radii=ck["radii"] if self.neighbor_adapt_stats()["enabled"] else None, **ck["scheme"])
+        return self
 
     # -- multi-GPU / measurement / diagnostics ------------------------------
     def device_ptr(self, which):
