@@ -71,7 +71,10 @@ extern "C" {
                                             the bit: its scheme runs the two calls).  Detected by the presence of the symbol nb_split_lists
                              2.4 (round 18) likewise within 2.4: nb_set_neighbor_adapt, nb_neighbor_adapt_stats, nb_download_neighbor_radii,
                                             nb_upload_neighbor_scheme, nb_neighbor_adapt, nb_neighbor_checkpoint.  Detected by the presence of
-                                            the symbol nb_set_neighbor_adapt */
+                                            the symbol nb_set_neighbor_adapt
+                             2.4 (round 19) likewise within 2.4: nb_set_neighbor_levels, nb_neighbor_level_stats, nb_download_neighbor_levels,
+                                            nb_upload_neighbor_levels, nb_neighbor_levels, NB_NLEV_FROZEN.  Detected by the presence of the
+                                            symbol nb_set_neighbor_levels */
 
 typedef struct nb_sim nb_sim; /* opaque */
 
@@ -1117,6 +1120,78 @@ typedef struct nb_neighbor_checkpoint {
     const void *radii;                                         /* n: `next`; NULL with adaptation off */
 } nb_neighbor_checkpoint;                                      /* 64 bytes */
 int nb_upload_neighbor_scheme(nb_sim *s, const nb_neighbor_checkpoint *ck);
+
+/* ---- the neighbour scheme with block individual IRREGULAR steps per body (added within ABI 2.4) ----
+ * The scheme above re-evaluates every body's list force at the same fine step dt / N_sub: one tight pair sets N_sub for all n bodies.
+ * With nb_set_neighbor_levels every body steps its irregular force at a power-of-two fraction of dt of its own, chosen by the step
+ * criterion of the block-step section on the body's TOTAL force.  The regular step, the builds, adaptation, the overflow policy and
+ * the regular-time correction stay exactly as they are; only the N_sub shared substeps between two regular times are replaced.
+ *   - L = log2(substeps) of the scheme, tick = dt / (double)substeps, T(k) = (double)k * tick.  Body i holds a level l_i in
+ *     [min_level, L] and steps by s_i = 2^(L - l_i) ticks.
+ *   - Inside one regular step t_i = 0 for all bodies; then, until t_next == 2^L:
+ *       1. t_next = min_i (t_i + s_i); the active set is A = { i : t_i + s_i == t_next };
+ *       2. EVERY body is predicted to T(t_next) from its own stored (x, v, ai, ji, ar0, jr0) at t_i: a = ai + (ar0 + T(t_i) jr0),
+ *          j = ji + jr0, h = (double)(t_next - t_i) * tick, with the predictor expressions of the shared substep, fp64, rounded once
+ *          to the handle's precision; always from the stored state, never from an earlier prediction;
+ *       3. for i in A: (ai1, ji1) = nb_list_force's sums over i's row at the predicted state (the point (xp_i, vp_i), the entries
+ *          gathered from (xp, vp)); every rule of step 3 of the shared substep applies;
+ *       4. for i in A: h = (double)s_i * tick, tau0 = T(t_i), tau1 = tau0 + h; a0 = ai + (ar0 + tau0 jr0), j0 = ji + jr0,
+ *          a1 = ai1 + (ar0 + tau1 jr0), j1 = ji1 + jr0; the Hermite corrector over h with the shared substep's expressions;
+ *          (x, v, ai, ji)_i <- (x1, v1, ai1, ji1), each rounded once;
+ *       5. unless NB_NLEV_FROZEN is set, steps 5-6 of the block-step section run with the fp64 totals (a0, j0, a1, j1) of 4 and h:
+ *          tau as defined there in fp64, want = level_for(tau) over [min_level, L] (level_for against dt: the smallest l with
+ *          dt / 2^l <= tau); want >= l_i is taken; want < l_i coarsens by ONE level, and only if t_next is a multiple of 2 s_i; a
+ *          wish finer than L takes L and counts as `clamped`.  The regular part is linear in time and adds nothing to a2 and a3:
+ *          a body whose row is empty (min(count, cap) == 0) has tau = infinity and wants min_level;
+ *       6. t_i = t_next.
+ *     At tick 2^L all bodies stand at the regular time.  Levels persist across regular steps.
+ *   - Start of the levels.  Runs when the levels are not current: after the scheme's start has run for any reason, after
+ *     nb_upload_neighbor_scheme, and after nb_set_neighbor_levels; at the next nb_step or nb_download_neighbor_levels.
+ *     l_i = level_for((eta / 2) |a| / |j|) on a = ai + ar0, j = ji + jr0, summed in fp64 from the stored components; |j| = 0 gives
+ *     min_level.  With NB_NLEV_FROZEN every body takes min_level.
+ *   - min_level is the accuracy floor: the error of a run is set by the bodies at the coarsest level in use, whatever eta is.  With
+ *     min_level = 0 a quiet body's irregular force is stepped with dt itself.
+ *   - nb_step(k) equals k x nb_step(1) bit for bit, two handles give the same bits, and every bit is independent of the order in
+ *     which the active bodies of a tick are processed.  With every level frozen at L the scheme is the shared scheme at N_sub = 2^L
+ *     (bit for bit where dt is a power of two), frozen at 0 it is the shared scheme at N_sub = 1.
+ *   - No host wait per tick: the host enqueues one launch for every tick 1 .. 2^L, which leaves at once where no body is due at the
+ *     tick or at the one behind it.  The host waits of a regular step stay what they are.  nb_neighbor_scheme_stats.substeps keeps
+ *     counting 2^L per step.  The counters of nb_neighbor_level_stats are kept per body on the device and summed when asked for.
+ *   - Switching on and off.  nb_set_neighbor_scheme, with any argument, switches levels off, as it switches adaptation off.
+ *     nb_set_neighbor_levels leaves the scheme's components and adaptation alone: it makes only the levels stale and zeroes its own
+ *     counters.  Levels work with nb_set_neighbor_adapt on or off.  Block steps stay excluded from scheme handles.
+ *   - Checkpoint: nb_download_neighbor_levels next to the arrays of the scheme's checkpoint; restore in the scheme's order, then
+ *     nb_set_neighbor_levels in front of and nb_upload_neighbor_levels behind nb_upload_neighbor_scheme.  The restored handle
+ *     continues bit for bit.
+ *   - Errors, each before any device call, the message naming the function and the field.  NB_ERR_STATE: a leapfrog handle, no
+ *     scheme set, levels not set (download, upload), an upload before the scheme is current.  NB_ERR_INVALID: a NULL handle, a wrong
+ *     struct_size, unknown flag bits, reserved != 0, min_level > log2(substeps), eta < 0 or not finite, an uploaded level outside
+ *     [min_level, L]. */
+#define NB_NLEV_FROZEN 1u  /* levels never change: min_level everywhere, or what nb_upload_neighbor_levels gave */
+typedef struct nb_neighbor_levels {
+    uint32_t struct_size;  /* sizeof(nb_neighbor_levels) */
+    uint32_t min_level;    /* 0 .. log2(substeps) of the scheme */
+    uint32_t flags;        /* NB_NLEV_FROZEN */
+    uint32_t reserved;     /* must be 0 */
+    double   eta;          /* the accuracy parameter of the step criterion; 0 -> 0.02 */
+} nb_neighbor_levels;      /* 24 bytes */
+int nb_set_neighbor_levels(nb_sim *s, const nb_neighbor_levels *cfg /* NULL: the shared substeps again */);
+
+struct nb_neighbor_level_stats {
+    uint32_t struct_size, enabled;
+    uint64_t regular_steps, ticks;    /* ticks = 2^L per regular step */
+    uint64_t block_steps;             /* ticks with a due body */
+    uint64_t body_steps;              /* correctors */
+    uint64_t entries;                 /* sum of min(count, cap) over the body-steps */
+    uint64_t clamped;                 /* decisions that wished a level finer than L (the start included) */
+    uint32_t finest_level, reserved;  /* the finest level any body held since set or last reset */
+};                                    /* 64 bytes */
+/* The counters since the levels were set or last reset (set out->struct_size).  Blocks.  A handle without levels: enabled = 0, zeros. */
+int nb_neighbor_level_stats(nb_sim *s, struct nb_neighbor_level_stats *out, int reset);
+/* n levels at the handle's instant; runs the starts (the scheme's, then the levels') first where they are not current.  Blocks. */
+int nb_download_neighbor_levels(nb_sim *s, uint8_t *levels /* n */);
+/* After nb_upload_neighbor_scheme (or any call that left the scheme current): the levels are these, the start rule does not run. */
+int nb_upload_neighbor_levels(nb_sim *s, const uint8_t *levels /* n */);
 
 #if defined(__GNUC__)
 #pragma GCC visibility pop

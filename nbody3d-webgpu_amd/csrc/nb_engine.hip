@@ -579,9 +579,20 @@ void ad_release(nb_sim* s)
     s->ad_last_rebuilds = 0;
 }
 
-// Releases what nb_set_neighbor_scheme allocated, switches the scheme (and with it adaptation) off and zeroes its counters.
+// Releases what nb_set_neighbor_levels allocated, switches the levels off and zeroes their counters.
+void lv_release(nb_sim* s)
+{
+    for (void** p : {(void**)&s->lv_lev, (void**)&s->lv_due, (void**)&s->lv_words, (void**)&s->lv_cnt, (void**)&s->lv_rec})
+        if (*p) { (void)hipFree(*p); *p = nullptr; }
+    s->lv = s->lv_frozen = false;
+    s->lv_state = 0;
+    s->lv_regular = s->lv_ticks = 0;
+}
+
+// Releases what nb_set_neighbor_scheme allocated, switches the scheme (and with it adaptation and the levels) off and zeroes its counters.
 void ac_release(nb_sim* s)
 {
+    lv_release(s);
     for (void** p : {&s->ac_ai, &s->ac_ji, &s->ac_ar, &s->ac_jr, &s->ac_px, &s->ac_pv, &s->ac_radii, (void**)&s->ac_list, (void**)&s->ac_count, (void**)&s->ac_hdr})
         if (*p) { (void)hipFree(*p); *p = nullptr; }
     if (s->ac_hdr_host) { (void)hipHostFree(s->ac_hdr_host); s->ac_hdr_host = nullptr; }
@@ -901,6 +912,7 @@ int ensure_scheme(nb_sim* s, const char* who)
     if (s->ac_ok && s->derivs_ok && s->derivs_any_G) { s->derivs_any_G = false; s->derivs_G = s->G; }      // (never set while the scheme is on)
     if (s->ac_ok && s->derivs_ok && s->derivs_G == s->G) return NB_OK;
     s->ac_ok = false; s->derivs_ok = false;
+    s->lv_state = 0;      // the levels start again with the scheme (read only while nb_set_neighbor_levels is on)
     if (s->ad) return ad_start(s, who);
     if (int rc = ac_build(s, s->ac_ai, s->ac_ji, s->ac_ar, s->ac_jr, who)) return rc;
     uint32_t n = s->n, cap = s->ac_cap;
@@ -916,6 +928,61 @@ int ensure_scheme(nb_sim* s, const char* who)
     return NB_OK;
 }
 
+nb::LvCfg lv_cfg(const nb_sim* s)
+{
+    uint32_t L = 0;
+    while ((1u << L) < s->ac_nsub) ++L;
+    return nb::LvCfg{L, s->lv_lmin, s->lv_frozen ? 1u : 0u, s->ac_nsub, s->lv_eta, s->dt, s->dt / (double)s->ac_nsub};
+}
+
+// The start of the levels (nb_set_neighbor_levels): runs where they are not current, behind the scheme's own start.  No host wait.
+int ensure_levels(nb_sim* s)
+{
+    if (s->lv_state == 2) return NB_OK;
+    uint32_t n = s->n;
+    int mode = s->lv_state == 1 ? 2 : s->lv_frozen ? 1 : 0;
+    nb::LvCfg c = lv_cfg(s);
+    void* args[] = {&s->ac_ai, &s->ac_ji, &s->ac_ar, &s->ac_jr, &s->lv_lev, &s->lv_rec, &n, &mode, &c};
+    const void* fn = s->f64 ? (const void*)&nb::nb_ac_lv_start<double> : (const void*)&nb::nb_ac_lv_start<float>;
+    NB_HIP(s, hipLaunchKernel(fn, dim3(ceil_div(n, nb::kBlock)), dim3(nb::kBlock), args, 0, s->stream));
+    s->lv_state = 2;
+    return NB_OK;
+}
+
+// The irregular part of one regular step with levels on: the clock and the first prediction, then ONE launch for EVERY tick -- the
+// corrector of the due bodies and the prediction of all bodies to the next tick -- which leaves at once where no body is due at
+// the tick or the one behind it.  The host never learns which ticks those are: no wait.
+int lv_ticks(nb_sim* s)
+{
+    uint32_t n = s->n, cap = s->ac_cap;
+    const uint32_t nsub = s->ac_nsub;
+    double G = s->G, eps2d = s->eps2;
+    float eps2f = (float)s->eps2;
+    void *x = s->bodies[0], *v = s->vel;
+    void* P[2][2] = {{s->hx, s->hv}, {s->ac_px, s->ac_pv}};      // launch k reads P[k & 1] and writes P[(k + 1) & 1]
+    nb::LvCfg c = lv_cfg(s);
+    const dim3 rows_grid(ceil_div(n, nb::kBlock)), sub_grid(ceil_div(n, nb::lf_rows(s->f64))), block(nb::kBlock);
+    NB_HIP(s, hipMemsetAsync(s->lv_words, 0, sizeof(uint32_t) * nb::lv_words(nsub), s->stream));
+    {
+        void* args[] = {&x, &v, &s->ac_ai, &s->ac_ji, &s->ac_ar, &s->ac_jr, &P[1][0], &P[1][1], &s->lv_lev, &s->lv_due, &s->lv_words, &n, &c};
+        const void* fn = s->f64 ? (const void*)&nb::nb_ac_lv_begin<double> : (const void*)&nb::nb_ac_lv_begin<float>;
+        NB_HIP(s, hipLaunchKernel(fn, rows_grid, block, args, 0, s->stream));
+    }
+    for (uint32_t k = 1; k <= nsub; ++k) {
+        void **pr = P[k & 1], **pw = P[(k + 1) & 1];
+        void *wx = k < nsub ? pw[0] : nullptr, *wv = k < nsub ? pw[1] : nullptr;
+        if (s->f64) {
+            void* args[] = {&pr[0], &pr[1], &s->ac_list, &s->ac_count, &s->lv_words, &s->lv_cnt, &s->lv_rec, &n, &cap, &eps2d, &G, &x, &v, &s->ac_ai, &s->ac_ji, &s->ac_ar, &s->ac_jr, &s->lv_lev, &s->lv_due, &k, &c, &wx, &wv};
+            NB_HIP(s, hipLaunchKernel((const void*)&nb::nb_ac_lv_sub64<nb::kLfLanes64>, sub_grid, block, args, 0, s->stream));
+        } else {
+            void* args[] = {&pr[0], &pr[1], &s->ac_list, &s->ac_count, &s->lv_words, &s->lv_cnt, &s->lv_rec, &n, &cap, &eps2f, &G, &x, &v, &s->ac_ai, &s->ac_ji, &s->ac_ar, &s->ac_jr, &s->lv_lev, &s->lv_due, &k, &c, &wx, &wv};
+            NB_HIP(s, hipLaunchKernel((const void*)&nb::nb_ac_lv_sub32<nb::kLfLanes32>, sub_grid, block, args, 0, s->stream));
+        }
+    }
+    ++s->lv_regular; s->lv_ticks += nsub;
+    return NB_OK;
+}
+
 // nb_step of a handle with the neighbour scheme: nsteps regular steps of dt.  Per regular step: the first prediction, N_sub substep
 // launches, the sums over the old list, the split pass and the list build at the arrived state, the regular correction, and ONE
 // host wait for the header of the build.  Timed steps record e[0] .. e[1] around the regular step (as block steps).
@@ -923,6 +990,7 @@ int ac_step(nb_sim* s, uint32_t nsteps)
 {
     if (s->ac_over) return fail(s, NB_ERR_STATE, "nb_step: " + s->ac_msg);
     if (int rc = ensure_scheme(s, "nb_step")) return rc;
+    if (s->lv) { if (int rc = ensure_levels(s)) return rc; }
     uint32_t n = s->n, cap = s->ac_cap;
     const uint32_t nsub = s->ac_nsub;
     double dt = s->dt, hs = s->dt / (double)nsub, G = s->G, eps2d = s->eps2;
@@ -934,12 +1002,14 @@ int ac_step(nb_sim* s, uint32_t nsteps)
         nb_events ev;
         const bool rec = s->timing && get_events(s, &ev) == 0;
         if (rec) NB_HIP(s, hipEventRecord(ev.e[0], s->stream));
-        {
+        if (s->lv) {      // nb_set_neighbor_levels: every body on its own irregular step, one launch per tick in place of the shared substeps
+            if (int rc = lv_ticks(s)) return rc;
+        } else {
             void* args[] = {&x, &v, &s->ac_ai, &s->ac_ji, &s->ac_ar, &s->ac_jr, &P[0][0], &P[0][1], &n, &hs};
             const void* fn = s->f64 ? (const void*)&nb::nb_ac_predict0<double> : (const void*)&nb::nb_ac_predict0<float>;
             NB_HIP(s, hipLaunchKernel(fn, rows_grid, block, args, 0, s->stream));
         }
-        for (uint32_t q = 0; q < nsub; ++q) {
+        for (uint32_t q = 0; q < (s->lv ? 0u : nsub); ++q) {      // the shared substeps (none with levels on)
             double tau0 = (double)q * hs, tau1 = tau0 + hs;
             void **pr = P[q & 1], **pw = P[(q + 1) & 1];
             void *wx = q + 1 < nsub ? pw[0] : nullptr, *wv = q + 1 < nsub ? pw[1] : nullptr;
@@ -1879,6 +1949,111 @@ int nb_upload_neighbor_scheme(nb_sim* s, const nb_neighbor_checkpoint* ck)
     NB_HIP(s, hipLaunchKernel(fn, dim3(ceil_div(n, nb::kBlock)), dim3(nb::kBlock), args, 0, s->stream));
     s->ac_ok = true;      // current for the G and dt in force; it counts no build
     s->derivs_ok = true; s->derivs_any_G = false; s->derivs_G = s->G;
+    s->lv_state = 0;      // the levels follow (nb_upload_neighbor_levels), or start by their rule on these components
+    return NB_OK;
+}
+
+int nb_set_neighbor_levels(nb_sim* s, const nb_neighbor_levels* cfg)
+{
+    const std::string F = "nb_set_neighbor_levels: ";
+    if (cfg) {      // the fields that need no handle first
+        if (cfg->struct_size != sizeof(nb_neighbor_levels)) return fail(s, NB_ERR_INVALID, F + "struct_size must be sizeof(nb_neighbor_levels)");
+        if (cfg->flags & ~NB_NLEV_FROZEN) return fail(s, NB_ERR_INVALID, F + "flags has unknown bits (NB_NLEV_FROZEN is the only one)");
+        if (cfg->reserved != 0) return fail(s, NB_ERR_INVALID, F + "reserved must be 0");
+        if (!(cfg->eta >= 0.0) || std::isinf(cfg->eta)) return fail(s, NB_ERR_INVALID, F + "eta must be finite and >= 0 (0: the default 0.02)");
+    }
+    if (!s) return fail(nullptr, NB_ERR_INVALID, F + "null handle");
+    if (const char* bad = ad_bad_handle(s)) return fail(s, NB_ERR_STATE, F + bad);
+    uint32_t L = 0;
+    while ((1u << L) < s->ac_nsub) ++L;
+    if (cfg && cfg->min_level > L) return fail(s, NB_ERR_INVALID, F + "min_level must not exceed log2(substeps) of the scheme (" + std::to_string(L) + ")");
+    NB_HIP(s, hipSetDevice(s->device));
+    NB_HIP(s, hipStreamSynchronize(s->stream));
+    lv_release(s);
+    if (!cfg) return NB_OK;
+    hipError_t e = hipMalloc((void**)&s->lv_lev, s->n);
+    if (e == hipSuccess) e = hipMalloc((void**)&s->lv_due, sizeof(uint32_t) * s->n);
+    if (e == hipSuccess) e = hipMalloc((void**)&s->lv_words, sizeof(uint32_t) * nb::lv_words(s->ac_nsub));
+    if (e == hipSuccess) e = hipMalloc((void**)&s->lv_cnt, sizeof(unsigned long long) * nb::kLvCntWords);
+    if (e == hipSuccess) e = hipMemset(s->lv_cnt, 0, sizeof(unsigned long long) * nb::kLvCntWords);
+    if (e == hipSuccess) e = hipMalloc((void**)&s->lv_rec, sizeof(unsigned long long) * nb::kLvRecWords * (size_t)s->n);
+    if (e == hipSuccess) e = hipMemset(s->lv_rec, 0, sizeof(unsigned long long) * nb::kLvRecWords * (size_t)s->n);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        lv_release(s);
+        return fail(s, e == hipErrorOutOfMemory ? NB_ERR_NOMEM : NB_ERR_HIP, F + "cannot allocate the levels: " + hipGetErrorString(e));
+    }
+    s->lv = true;
+    s->lv_lmin = cfg->min_level; s->lv_frozen = (cfg->flags & NB_NLEV_FROZEN) != 0;
+    s->lv_eta = cfg->eta > 0.0 ? cfg->eta : 0.02;
+    s->lv_state = 0;
+    return NB_OK;
+}
+
+int nb_neighbor_level_stats(nb_sim* s, struct nb_neighbor_level_stats* out, int reset)
+{
+    const std::string F = "nb_neighbor_level_stats: ";
+    if (!s) return fail(nullptr, NB_ERR_INVALID, F + "null handle");
+    if (!out || out->struct_size != sizeof(struct nb_neighbor_level_stats)) return fail(s, NB_ERR_INVALID, F + "set out->struct_size to sizeof(nb_neighbor_level_stats)");
+    if (!s->hermite) return fail(s, NB_ERR_STATE, F + "needs a Hermite handle (nb_config.integrator = NB_INT_HERMITE4)");
+    std::memset(out, 0, sizeof(*out));
+    out->struct_size = sizeof(*out);
+    if (!s->lv) return NB_OK;
+    out->enabled = 1u;
+    NB_HIP(s, hipSetDevice(s->device));
+    unsigned long long w[nb::kLvCntWords];
+    std::vector<unsigned long long> rec((size_t)nb::kLvRecWords * s->n);      // the per-body records, summed here
+    NB_HIP(s, hipStreamSynchronize(s->stream));
+    NB_HIP(s, hipMemcpy(w, s->lv_cnt, sizeof w, hipMemcpyDeviceToHost));
+    NB_HIP(s, hipMemcpy(rec.data(), s->lv_rec, sizeof(unsigned long long) * rec.size(), hipMemcpyDeviceToHost));
+    out->regular_steps = s->lv_regular; out->ticks = s->lv_ticks;
+    out->block_steps = w[nb::kLvBlockSteps];
+    for (uint32_t i = 0; i < s->n; ++i) {
+        const unsigned long long* r = rec.data() + (size_t)nb::kLvRecWords * i;
+        out->body_steps += r[nb::kLvBodySteps]; out->entries += r[nb::kLvEntries]; out->clamped += r[nb::kLvClamped];
+        if (r[nb::kLvFinest] > out->finest_level) out->finest_level = (uint32_t)r[nb::kLvFinest];
+    }
+    if (reset) {
+        s->lv_regular = s->lv_ticks = 0;
+        NB_HIP(s, hipMemsetAsync(s->lv_cnt, 0, sizeof w, s->stream));
+        NB_HIP(s, hipMemsetAsync(s->lv_rec, 0, sizeof(unsigned long long) * rec.size(), s->stream));
+    }
+    return NB_OK;
+}
+
+int nb_download_neighbor_levels(nb_sim* s, uint8_t* levels)
+{
+    const std::string F = "nb_download_neighbor_levels: ";
+    if (!s) return fail(nullptr, NB_ERR_INVALID, F + "null handle");
+    if (!levels) return fail(s, NB_ERR_INVALID, F + "levels is NULL");
+    if (const char* bad = ad_bad_handle(s)) return fail(s, NB_ERR_STATE, F + bad);
+    if (!s->lv) return fail(s, NB_ERR_STATE, F + "the levels are not switched on (nb_set_neighbor_levels)");
+    if (!s->uploaded) return fail(s, NB_ERR_STATE, F + "nothing uploaded yet");
+    NB_HIP(s, hipSetDevice(s->device));
+    if (int rc = ensure_scheme(s, "nb_download_neighbor_levels")) return rc;
+    if (int rc = ensure_levels(s)) return rc;
+    NB_HIP(s, hipStreamSynchronize(s->stream));
+    NB_HIP(s, hipMemcpy(levels, s->lv_lev, s->n, hipMemcpyDeviceToHost));
+    return NB_OK;
+}
+
+int nb_upload_neighbor_levels(nb_sim* s, const uint8_t* levels)
+{
+    const std::string F = "nb_upload_neighbor_levels: ";
+    if (!s) return fail(nullptr, NB_ERR_INVALID, F + "null handle");
+    if (!levels) return fail(s, NB_ERR_INVALID, F + "levels is NULL");
+    if (const char* bad = ad_bad_handle(s)) return fail(s, NB_ERR_STATE, F + bad);
+    if (!s->lv) return fail(s, NB_ERR_STATE, F + "the levels are not switched on (nb_set_neighbor_levels)");
+    if (!(s->uploaded && s->params_set && s->ac_ok && s->derivs_ok && s->derivs_G == s->G))
+        return fail(s, NB_ERR_STATE, F + "the scheme is not current: call it after nb_upload_neighbor_scheme (or after a call that ran the scheme's start)");
+    const nb::LvCfg c = lv_cfg(s);
+    for (uint32_t i = 0; i < s->n; ++i)
+        if (levels[i] < c.lmin || levels[i] > c.L)
+            return fail(s, NB_ERR_INVALID, F + "levels[" + std::to_string(i) + "] = " + std::to_string(levels[i]) + " is outside [min_level, log2(substeps)]");
+    NB_HIP(s, hipSetDevice(s->device));
+    NB_HIP(s, hipStreamSynchronize(s->stream));
+    NB_HIP(s, hipMemcpy(s->lv_lev, levels, s->n, hipMemcpyHostToDevice));
+    s->lv_state = 1;      // current: the start rule does not run (the next step counts them into finest_level)
     return NB_OK;
 }
 

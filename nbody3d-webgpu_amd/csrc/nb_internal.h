@@ -216,6 +216,17 @@ struct nb_sim {
     void* ad_keep = nullptr;         // `next` as a start found it (put back when the start fails)
     uint64_t ad_rebuilds = 0, ad_rows_shrunk = 0;
     uint32_t ad_last_rebuilds = 0;
+    // nb_set_neighbor_levels: block individual irregular steps inside the scheme (kernels/ac_levels.hip.h).  Off: none of this is read.
+    bool lv = false, lv_frozen = false;
+    uint32_t lv_lmin = 0;
+    double lv_eta = 0.02;
+    int lv_state = 0;                // 0: stale (the start rule runs); 1: lv_lev came from nb_upload_neighbor_levels; 2: current
+    uint8_t* lv_lev = nullptr;       // device: level per body
+    uint32_t* lv_due = nullptr;      // device: tick of the body's next corrector inside the regular step
+    uint32_t* lv_words = nullptr;    // device: nb::lv_words(ac_nsub) words, zeroed in front of every regular step
+    unsigned long long* lv_cnt = nullptr;      // device: nb::kLvCntWords counters
+    unsigned long long* lv_rec = nullptr;      // device: n records of nb::kLvRecWords counters, each written by its body's own lane
+    uint64_t lv_regular = 0, lv_ticks = 0;
 };
 
 namespace nbi {

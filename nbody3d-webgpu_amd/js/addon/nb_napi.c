@@ -82,6 +82,10 @@ static int (*p_set_neighbor_adapt)(nb_sim *, const nb_neighbor_adapt *);        
 static int (*p_neighbor_adapt_stats)(nb_sim *, struct nb_neighbor_adapt_stats *, int);
 static int (*p_download_neighbor_radii)(nb_sim *, void *, void *);
 static int (*p_upload_neighbor_scheme)(nb_sim *, const nb_neighbor_checkpoint *);
+static int (*p_set_neighbor_levels)(nb_sim *, const nb_neighbor_levels *);         /* block individual irregular steps inside the scheme, likewise */
+static int (*p_neighbor_level_stats)(nb_sim *, struct nb_neighbor_level_stats *, int);
+static int (*p_download_neighbor_levels)(nb_sim *, uint8_t *);
+static int (*p_upload_neighbor_levels)(nb_sim *, const uint8_t *);
 static int (*p_split_lists)(nb_sim *, const nb_split_lists_request *);              /* the two sums and the neighbour rows from one pass, likewise */
 static int (*p_multi_split_lists)(nb_multi *, const nb_split_lists_request *);
 static int (*p_neighbor_scheme_fused)(nb_sim *, int *);
@@ -188,6 +192,10 @@ static napi_value js_load(napi_env env, napi_callback_info info)
         *(void **)(&p_neighbor_adapt_stats) = dlsym(h, "nb_neighbor_adapt_stats");
         *(void **)(&p_download_neighbor_radii) = dlsym(h, "nb_download_neighbor_radii");
         *(void **)(&p_upload_neighbor_scheme) = dlsym(h, "nb_upload_neighbor_scheme");
+        *(void **)(&p_set_neighbor_levels) = dlsym(h, "nb_set_neighbor_levels");
+        *(void **)(&p_neighbor_level_stats) = dlsym(h, "nb_neighbor_level_stats");
+        *(void **)(&p_download_neighbor_levels) = dlsym(h, "nb_download_neighbor_levels");
+        *(void **)(&p_upload_neighbor_levels) = dlsym(h, "nb_upload_neighbor_levels");
         *(void **)(&p_split_lists) = dlsym(h, "nb_split_lists");
         *(void **)(&p_multi_split_lists) = dlsym(h, "nb_multi_split_lists");
         *(void **)(&p_neighbor_scheme_fused) = dlsym(h, "nb_neighbor_scheme_fused");
@@ -1377,6 +1385,77 @@ static napi_value js_upload_neighbor_scheme(napi_env env, napi_callback_info inf
     return undefined(env);
 }
 
+/* setNeighborLevels(handle, null) | setNeighborLevels(handle, minLevel, eta, frozen): nb_set_neighbor_levels (eta 0: the default 0.02) */
+static napi_value js_set_neighbor_levels(napi_env env, napi_callback_info info)
+{
+    size_t argc = 4; napi_value argv[4];
+    CHECK_NAPI(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    if (argc < 2) { napi_throw_type_error(env, NULL, "setNeighborLevels(handle, null | minLevel, eta, frozen)"); return NULL; }
+    handle_t *h = scheme_handle(env, argv[0], *(void **)&p_set_neighbor_levels, "nb_set_neighbor_levels"); if (!h) return NULL;
+    napi_valuetype t; napi_typeof(env, argv[1], &t);
+    int rc;
+    if (argc < 4 && (t == napi_null || t == napi_undefined)) rc = p_set_neighbor_levels(h->sim, NULL);
+    else {
+        if (argc < 4) { napi_throw_type_error(env, NULL, "setNeighborLevels(handle, minLevel, eta, frozen)"); return NULL; }
+        nb_neighbor_levels cfg;
+        memset(&cfg, 0, sizeof cfg);
+        cfg.struct_size = sizeof cfg;
+        uint32_t u = 0;
+        bool frozen = false;
+        CHECK_NAPI(env, napi_get_value_uint32(env, argv[1], &u)); cfg.min_level = u;
+        CHECK_NAPI(env, napi_get_value_double(env, argv[2], &cfg.eta));
+        CHECK_NAPI(env, napi_get_value_bool(env, argv[3], &frozen));
+        cfg.flags = frozen ? NB_NLEV_FROZEN : 0u;
+        rc = p_set_neighbor_levels(h->sim, &cfg);
+    }
+    if (rc != NB_OK) return throw_nb(env, rc, h->sim, "nb_set_neighbor_levels");
+    return undefined(env);
+}
+
+/* neighborLevelStats(handle, reset) -> {enabled, regularSteps, ticks, blockSteps, bodySteps, entries, clamped, finestLevel} (counts as doubles) */
+static napi_value js_neighbor_level_stats(napi_env env, napi_callback_info info)
+{
+    size_t argc = 2; napi_value argv[2];
+    CHECK_NAPI(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    if (argc < 1) { napi_throw_type_error(env, NULL, "neighborLevelStats(handle, reset)"); return NULL; }
+    handle_t *h = scheme_handle(env, argv[0], *(void **)&p_neighbor_level_stats, "nb_neighbor_level_stats"); if (!h) return NULL;
+    bool reset = false;
+    if (argc > 1) napi_get_value_bool(env, argv[1], &reset);
+    struct nb_neighbor_level_stats st;
+    memset(&st, 0, sizeof st);
+    st.struct_size = sizeof st;
+    int rc = p_neighbor_level_stats(h->sim, &st, reset ? 1 : 0);
+    if (rc != NB_OK) return throw_nb(env, rc, h->sim, "nb_neighbor_level_stats");
+    napi_value o, v;
+    CHECK_NAPI(env, napi_create_object(env, &o));
+    napi_get_boolean(env, st.enabled != 0, &v); napi_set_named_property(env, o, "enabled", v);
+    napi_create_double(env, (double)st.regular_steps, &v); napi_set_named_property(env, o, "regularSteps", v);
+    napi_create_double(env, (double)st.ticks, &v); napi_set_named_property(env, o, "ticks", v);
+    napi_create_double(env, (double)st.block_steps, &v); napi_set_named_property(env, o, "blockSteps", v);
+    napi_create_double(env, (double)st.body_steps, &v); napi_set_named_property(env, o, "bodySteps", v);
+    napi_create_double(env, (double)st.entries, &v); napi_set_named_property(env, o, "entries", v);
+    napi_create_double(env, (double)st.clamped, &v); napi_set_named_property(env, o, "clamped", v);
+    napi_create_uint32(env, st.finest_level, &v); napi_set_named_property(env, o, "finestLevel", v);
+    return o;
+}
+
+/* downloadNeighborLevels(handle, levels) / uploadNeighborLevels(handle, levels): a Uint8Array of n elements, written in place / read */
+static napi_value js_neighbor_levels_io(napi_env env, napi_callback_info info, int up)
+{
+    size_t argc = 2; napi_value argv[2];
+    CHECK_NAPI(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    const char *what = up ? "nb_upload_neighbor_levels" : "nb_download_neighbor_levels";
+    if (argc < 2) { napi_throw_type_error(env, NULL, up ? "uploadNeighborLevels(handle, levels)" : "downloadNeighborLevels(handle, levels)"); return NULL; }
+    handle_t *h = scheme_handle(env, argv[0], up ? *(void **)&p_upload_neighbor_levels : *(void **)&p_download_neighbor_levels, what); if (!h) return NULL;
+    void *lev;
+    if (!get_typed(env, argv[1], napi_uint8_array, h->n, 0, &lev, "levels must be a Uint8Array of n elements")) return NULL;
+    int rc = up ? p_upload_neighbor_levels(h->sim, (const uint8_t *)lev) : p_download_neighbor_levels(h->sim, (uint8_t *)lev);
+    if (rc != NB_OK) return throw_nb(env, rc, h->sim, what);
+    return undefined(env);
+}
+static napi_value js_download_neighbor_levels(napi_env env, napi_callback_info info) { return js_neighbor_levels_io(env, info, 0); }
+static napi_value js_upload_neighbor_levels(napi_env env, napi_callback_info info) { return js_neighbor_levels_io(env, info, 1); }
+
 static napi_value init_module(napi_env env, napi_value exports)
 {
     static const struct { const char *name; napi_callback fn; } fns[] = {
@@ -1393,6 +1472,8 @@ static napi_value init_module(napi_env env, napi_value exports)
         {"downloadNeighborScheme", js_download_neighbor_scheme},
         {"setNeighborAdapt", js_set_neighbor_adapt}, {"neighborAdaptStats", js_neighbor_adapt_stats},
         {"downloadNeighborRadii", js_download_neighbor_radii}, {"uploadNeighborScheme", js_upload_neighbor_scheme},
+        {"setNeighborLevels", js_set_neighbor_levels}, {"neighborLevelStats", js_neighbor_level_stats},
+        {"downloadNeighborLevels", js_download_neighbor_levels}, {"uploadNeighborLevels", js_upload_neighbor_levels},
     };
     for (size_t i = 0; i < sizeof fns / sizeof fns[0]; ++i) {
         napi_value f;

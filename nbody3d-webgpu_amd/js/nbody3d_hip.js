@@ -294,6 +294,37 @@ class Simulation {
     return this;
   }
 
+  /** Block individual irregular steps inside the neighbour scheme (nb_set_neighbor_levels; needs setNeighborScheme first): every body
+   *  re-evaluates its list force at dt / 2^l of its own, l in [minLevel, log2(substeps)], chosen by the step criterion (eta, default
+   *  0.02).  {minLevel, eta, frozen}; minLevel is the accuracy floor of a run; frozen keeps every body at minLevel, or at what
+   *  uploadNeighborLevels gave.  setNeighborLevels(null): the shared substeps again (and so does every setNeighborScheme). */
+  setNeighborLevels(options) {
+    this._need();
+    if (options === null || options === undefined) { addon.setNeighborLevels(this._h, null); return this; }
+    addon.setNeighborLevels(this._h, (options.minLevel || 0) >>> 0, +(options.eta || 0), !!options.frozen);
+    return this;
+  }
+
+  /** {enabled, regularSteps, ticks, blockSteps, bodySteps, entries, clamped, finestLevel} (nb_neighbor_level_stats). */
+  neighborLevelStats(reset) { this._need(); return addon.neighborLevelStats(this._h, !!reset); }
+
+  /** Uint8Array(N): the levels at the simulation's instant (nb_download_neighbor_levels; runs the starts first where they are due). */
+  downloadNeighborLevels() {
+    this._need();
+    const out = new Uint8Array(this.nBodies);
+    addon.setParams(this._h, this.dt, this.G);
+    addon.downloadNeighborLevels(this._h, out);
+    return out;
+  }
+
+  /** After uploadNeighborScheme: the levels are these and the start rule does not run (nb_upload_neighbor_levels). */
+  uploadNeighborLevels(levels) {
+    this._need();
+    addon.setParams(this._h, this.dt, this.G);
+    addon.uploadNeighborLevels(this._h, levels instanceof Uint8Array ? levels : Uint8Array.from(levels));
+    return this;
+  }
+
   /** util.js:230-244: write the three arrays into the EXISTING buffers (N must match).  A 'hermite4' simulation ignores accel on its
    *  own (a derived array); with BOTH state.accel and state.jerk it takes them as its derivatives (nb_upload_derivs). */
   restore(state) {

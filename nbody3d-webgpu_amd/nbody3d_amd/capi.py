@@ -163,6 +163,19 @@ class nb_neighbor_checkpoint(C.Structure):
                 ("accel_reg", C.c_void_p), ("jerk_reg", C.c_void_p), ("list", C.c_void_p), ("count", C.c_void_p), ("radii", C.c_void_p)]
 
 
+class nb_neighbor_levels(C.Structure):      # include/nbody3d_hip.h (block individual irregular steps inside the scheme)
+    _fields_ = [("struct_size", C.c_uint32), ("min_level", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint32),
+                ("eta", C.c_double)]
+
+
+class nb_neighbor_level_stats(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("enabled", C.c_uint32), ("regular_steps", C.c_uint64), ("ticks", C.c_uint64),
+                ("block_steps", C.c_uint64), ("body_steps", C.c_uint64), ("entries", C.c_uint64), ("clamped", C.c_uint64),
+                ("finest_level", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+NLEV_FROZEN = 1
+
 EXCHANGE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p)
 EXCHANGE_WAIT_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p)
 
@@ -185,7 +198,8 @@ SYMBOLS = ["nb_abi_version", "nb_device_count", "nb_create", "nb_destroy", "nb_u
            "nb_split_force", "nb_multi_split_force", "nb_split_force_shape",
            "nb_set_neighbor_scheme", "nb_neighbor_scheme_stats", "nb_download_neighbor_scheme",
            "nb_split_lists", "nb_multi_split_lists", "nb_split_lists_shape", "nb_neighbor_scheme_fused",
-           "nb_set_neighbor_adapt", "nb_neighbor_adapt_stats", "nb_download_neighbor_radii", "nb_upload_neighbor_scheme"]
+           "nb_set_neighbor_adapt", "nb_neighbor_adapt_stats", "nb_download_neighbor_radii", "nb_upload_neighbor_scheme",
+           "nb_set_neighbor_levels", "nb_neighbor_level_stats", "nb_download_neighbor_levels", "nb_upload_neighbor_levels"]
 
 _lib = None
 
@@ -299,6 +313,11 @@ def load_library():
         L.nb_neighbor_adapt_stats.argtypes = [vp, C.POINTER(nb_neighbor_adapt_stats), C.c_int]
         L.nb_download_neighbor_radii.argtypes = [vp, vp, vp]
         L.nb_upload_neighbor_scheme.argtypes = [vp, C.POINTER(nb_neighbor_checkpoint)]
+    if hasattr(L, "nb_set_neighbor_levels"):    # block individual irregular steps inside the scheme, also within 2.4
+        L.nb_set_neighbor_levels.argtypes = [vp, C.POINTER(nb_neighbor_levels)]
+        L.nb_neighbor_level_stats.argtypes = [vp, C.POINTER(nb_neighbor_level_stats), C.c_int]
+        L.nb_download_neighbor_levels.argtypes = [vp, vp]
+        L.nb_upload_neighbor_levels.argtypes = [vp, vp]
     if hasattr(L, "nb_eqm_info"):           # the equal-mass kernels' report, also within 2.4 and detected by the symbol
         L.nb_eqm_info.argtypes = [vp, C.POINTER(C.c_int)]
     if hasattr(L, "nb_eqm_form"):           # which of the equal-mass forms, likewise
@@ -1044,18 +1063,78 @@ class Simulation:
         ck = {"bodies": b, "vel": v, "dt": self.dt, "G": self.G, "scheme": self.download_neighbor_scheme(cap),
               "adaptive": bool(self.neighbor_adapt_stats()["enabled"])}
         ck["radii"] = self.download_neighbor_radii()[1]
+        if hasattr(self._L, "nb_set_neighbor_levels") and self.neighbor_level_stats()["enabled"]:
+            ck["levels"] = self.download_neighbor_levels()
         return ck
 
-    def restore_neighbor_scheme(self, ck, scheme=None, adapt=None):
-        """The calls of a restore in their order: init, set_params, set_neighbor_scheme(**scheme) and set_neighbor_adapt(**adapt)
-        where given (a handle that already has them set keeps them otherwise), upload_neighbor_scheme last."""
+    def restore_neighbor_scheme(self, ck, scheme=None, adapt=None, levels=None):
+        """The calls of a restore in their order: init, set_params, set_neighbor_scheme(**scheme), set_neighbor_adapt(**adapt) and
+        set_neighbor_levels(**levels) where given (a handle that already has them set keeps them otherwise), upload_neighbor_scheme
+        and, where the checkpoint holds levels and the handle has them switched on, upload_neighbor_levels last."""
         self.init(ck["bodies"], ck["vel"])
         self.set_params(ck["dt"], ck["G"])
         if scheme is not None:
             self.set_neighbor_scheme(**scheme)
         if adapt is not None:
             self.set_neighbor_adapt(**adapt)
+        if levels is not None:
+            self.set_neighbor_levels(**levels)
         self.upload_neighbor_scheme(radii=ck["radii"] if self.neighbor_adapt_stats()["enabled"] else None, **ck["scheme"])
+        if ck.get("levels") is not None and self.neighbor_level_stats()["enabled"]:
+            self.upload_neighbor_levels(ck["levels"])
+        return self
+
+    # -- block individual irregular steps inside the scheme --
+    def _need_levels(self, what):
+        if not hasattr(self._L, "nb_set_neighbor_levels"):
+            raise NBodyError(1, "%s: the loaded library has no nb_set_neighbor_levels" % what)
+
+    def set_neighbor_levels(self, *args, **kw):
+        """set_neighbor_levels(min_level=0, eta=None, frozen=False): nb_set_neighbor_levels -- inside the neighbour scheme every
+        body re-evaluates its list force at a step of its own, dt / 2^l with l in [min_level, log2(substeps)], chosen by the step
+        criterion (eta None: 0.02); frozen keeps every body at min_level, or at what upload_neighbor_levels gave.  min_level is
+        the accuracy floor of a run.  Needs set_neighbor_scheme first.  set_neighbor_levels(None): the shared substeps again."""
+        self._need_levels("set_neighbor_levels()")
+        if args == (None,) and not kw:
+            self._check(self._L.nb_set_neighbor_levels(self._h, None))
+            return self
+
+        def bind(min_level=0, eta=None, frozen=False, flags=None, reserved=0):
+            return min_level, eta, frozen, flags, reserved
+        min_level, eta, frozen, flags, reserved = bind(*args, **kw)
+        cfg = nb_neighbor_levels()
+        cfg.struct_size = C.sizeof(nb_neighbor_levels)
+        cfg.min_level = int(min_level)
+        cfg.flags = (NLEV_FROZEN if frozen else 0) if flags is None else int(flags)
+        cfg.reserved = int(reserved)
+        cfg.eta = 0.0 if eta is None else float(eta)
+        self._check(self._L.nb_set_neighbor_levels(self._h, C.byref(cfg)))
+        return self
+
+    def neighbor_level_stats(self, reset=False):
+        """nb_neighbor_level_stats: {enabled, regular_steps, ticks, block_steps (ticks with a due body), body_steps, entries (the sum
+        of min(count, cap) over the body-steps), clamped, finest_level}.  Blocks."""
+        self._need_levels("neighbor_level_stats()")
+        st = nb_neighbor_level_stats()
+        st.struct_size = C.sizeof(nb_neighbor_level_stats)
+        self._check(self._L.nb_neighbor_level_stats(self._h, C.byref(st), 1 if reset else 0))
+        return {k: int(getattr(st, k)) for k in ("enabled", "regular_steps", "ticks", "block_steps", "body_steps", "entries", "clamped", "finest_level")}
+
+    def download_neighbor_levels(self):
+        """nb_download_neighbor_levels: (N,) uint8; runs the scheme's start and the levels' start first where they are not current."""
+        self._need_levels("download_neighbor_levels()")
+        lev = np.zeros(self.n, np.uint8)
+        self._check(self._L.nb_download_neighbor_levels(self._h, _ptr(lev)))
+        return lev
+
+    def upload_neighbor_levels(self, levels):
+        """nb_upload_neighbor_levels: after upload_neighbor_scheme (or any call that left the scheme current) -- the levels are
+        these and the start rule does not run."""
+        self._need_levels("upload_neighbor_levels()")
+        lev = np.ascontiguousarray(levels, np.uint8)
+        if lev.shape != (self.n,):
+            raise ValueError("levels must have shape (%d,)" % self.n)
+        self._check(self._L.nb_upload_neighbor_levels(self._h, _ptr(lev)))
         return self
 
     # -- multi-GPU / measurement / diagnostics ------------------------------
