@@ -74,7 +74,9 @@ extern "C" {
                                             the symbol nb_set_neighbor_adapt
                              2.4 (round 19) likewise within 2.4: nb_set_neighbor_levels, nb_neighbor_level_stats, nb_download_neighbor_levels,
                                             nb_upload_neighbor_levels, nb_neighbor_levels, NB_NLEV_FROZEN.  Detected by the presence of the
-                                            symbol nb_set_neighbor_levels */
+                                            symbol nb_set_neighbor_levels
+                             2.4 (round 20) likewise within 2.4: nb_set_hermite_order, nb_hermite_order, nb_download_snap, nb_upload_derivs6.
+                                            Detected by the presence of the symbol nb_set_hermite_order */
 
 typedef struct nb_sim nb_sim; /* opaque */
 
@@ -1192,6 +1194,57 @@ int nb_neighbor_level_stats(nb_sim *s, struct nb_neighbor_level_stats *out, int 
 int nb_download_neighbor_levels(nb_sim *s, uint8_t *levels /* n */);
 /* After nb_upload_neighbor_scheme (or any call that left the scheme current): the levels are these, the start rule does not run. */
 int nb_upload_neighbor_levels(nb_sim *s, const uint8_t *levels /* n */);
+
+/* ---- the 6th-order scheme on a Hermite handle: force, jerk and snap (no reference analogue) ---------------
+ * nb_set_hermite_order(s, 6) turns a Hermite handle into the 6th-order predictor-corrector of Nitadori & Makino (2008) with one
+ * shared step dt: a higher order at a larger step.  A handle that never calls it runs the 4th-order scheme exactly as before.
+ *   - Per pair, with dr = x_j - x_i, dv = v_j - v_i, da = a_j - a_i and rho^2 = |dr|^2 + eps2:
+ *         alpha = (dr.dv) / rho^2            beta = (dv.dv + dr.da) / rho^2 + alpha^2
+ *         A = m_j dr / rho^3
+ *         J = m_j dv / rho^3 - 3 alpha A                      ( = s3 t,  t = dv - 3 alpha dr,  s3 = m_j / rho^3 )
+ *         S = m_j da / rho^3 - 6 alpha J - 3 beta A           ( = s3 (da - 6 alpha t - 3 beta dr) )
+ *     Each of the nine components is ONE sum s3 (...); no self mask (for j = i all nine terms are exactly 0); G multiplies each row
+ *     once in fp64; the chunks of the j-range are added in ascending order in fp64; on f32 handles a chunk is summed in binary32 in
+ *     two levels with at most 1,024 terms per register, as the force+jerk pass.
+ *   - State: (x, v) at one instant plus the derived a, j, s (snap, d2a/dt2) and c (crackle, d3a/dt3), all in the handle's precision.
+ *   - One step, h = dt, the polynomials in fp64 (Horner, fused), each stored value rounded once:
+ *         xp = x + h v + h^2/2 a + h^3/6 j + h^4/24 s + h^5/120 c
+ *         vp = v + h a + h^2/2 j + h^3/6 s + h^4/24 c
+ *         ap = a + h j + h^2/2 s + h^3/6 c
+ *         (a1, j1, s1) = FJS(xp, vp, ap)                    -- the only O(N^2) pass of the step
+ *         v1 = v + h/2 (a + a1) - h^2/10 (j1 - j) + h^3/120 (s + s1)
+ *         x1 = x + h/2 (v + v1) - h^2/10 (a1 - a) + h^3/120 (j + j1)
+ *         P = a1 - a - h j - h^2/2 s;   Q = h (j1 - j - h s);   R = h^2 (s1 - s)
+ *         c1 = (60 P - 36 Q + 9 R) / h^3                    -- p'''(t1) of the quintic through (a, j, s) at both ends
+ *         state <- (x1, v1, a1, j1, s1, c1)
+ *     The a1, j1, s1 of the corrector and of c1 are the values as stored; v1 enters x1 before it is rounded.  The mass lane and vel.w
+ *     are carried; the .w of a, j, s and c is 0.
+ *   - Start.  Runs when the snap is not current: after nb_set_hermite_order(6) and after anything that makes the derivatives of a
+ *     Hermite handle stale (see above; a changed G among them).  (a, j) come from the force+jerk pass on (x, v) -- the bits an order-4
+ *     handle holds --, s from the force+jerk+snap pass on (x, v, a) (its a and j are discarded), c = 0.  With c = 0 the first step
+ *     has a local error of O(h^6), the order of the scheme's global error: no iteration.  dt may change between steps.
+ *   - nb_set_hermite_order(s, 4) frees s and c; (a, j) stay current.
+ *   - Unchanged on an order-6 handle: nb_download (accel), nb_download_jerk, nb_device_ptr(NB_ACCEL / NB_JERK), every query,
+ *     nb_diagnostics, frames (they read bodies and vel), dt <= 0 is a no-op, nb_step(k) equals k x nb_step(1) bit for bit, two handles
+ *     give the same bits, plain launches, ext_stream.
+ *   - Changed: nb_force_pass first makes the derived arrays current (the start, where it is due: the pass streams the accelerations), then
+ *     runs the force+jerk+snap pass and its reduce into scratch: bodies and vel are untouched, and so are current derivatives; nb_step_times2:
+ *     force_ms = that kernel and its reduce, integrate_ms = predictor + corrector; nb_variant_name starts with "hermite6_";
+ *     nb_shape_info reports the chunks of the force+jerk+snap pass.
+ *   - Checkpoint: nb_download (accel), nb_download_jerk, nb_download_snap; restore with nb_upload, nb_set_params,
+ *     nb_set_hermite_order(6), nb_upload_derivs6: the next step equals the source handle's bit for bit.
+ *   - Errors, each before any device call, the message naming the function and the field.  NB_ERR_INVALID: a NULL handle, an order
+ *     other than 4 or 6, a NULL array of nb_upload_derivs6.  NB_ERR_STATE: a leapfrog handle (all four calls); order 6 while block
+ *     steps or the neighbour scheme are switched on; nb_set_block_steps or nb_set_neighbor_scheme with a non-NULL argument on an
+ *     order-6 handle; nb_upload_derivs on an order-6 handle (see nb_upload_derivs6); nb_download_snap or nb_upload_derivs6 on an
+ *     order-4 handle.
+ *   - Not built: block steps, the neighbour scheme and the 8th order on order-6 handles. */
+int nb_set_hermite_order(nb_sim *s, uint32_t order /* 4 or 6 */);
+int nb_hermite_order(nb_sim *s, uint32_t *order);
+/* 4*n elements each of the handle's precision, either pointer may be NULL; runs the start first if needed.  Blocks. */
+int nb_download_snap(nb_sim *s, void *snap, void *crackle);
+/* All four arrays are required, 4*n elements each; after nb_upload.  Marks the derivatives current. */
+int nb_upload_derivs6(nb_sim *s, const void *accel, const void *jerk, const void *snap, const void *crackle);
 
 #if defined(__GNUC__)
 #pragma GCC visibility pop

@@ -624,14 +624,18 @@ constexpr uint32_t kFjMaxChunk = 1u << 20;     // most bodies of one j-chunk (bo
 
 // The j-chunks of a handle's force+jerk pass: enough workgroups for kFjWavesPerSimd per SIMD, in chunks of whole 256-row tiles and
 // at least kFjMinChunk bodies; the partial sums (2 x chunks x n rows) stay below ~ 2 x (workgroups wanted x rows per workgroup + n) rows.
-void fj_shape(uint32_t n, bool f64, int n_cu, uint32_t* chunks, uint32_t* per)
+void chunk_shape(uint32_t n, uint32_t rows, int n_cu, uint32_t* chunks, uint32_t* per)      // rows: i-bodies of one workgroup
 {
-    const uint32_t rows = f64 ? nb::kFjRows64 : nb::kFjRows;
     const uint32_t want = kFjWavesPerSimd * (uint32_t)n_cu;
     uint32_t c = std::min(ceil_div(want, ceil_div(n, rows)), n / kFjMinChunk);
     c = std::max(std::max(c, 1u), ceil_div(n, kFjMaxChunk));
     *per = ceil_div(ceil_div(n, c), (uint32_t)nb::kTile) * nb::kTile;
     *chunks = ceil_div(n, *per);
+}
+
+void fj_shape(uint32_t n, bool f64, int n_cu, uint32_t* chunks, uint32_t* per)
+{
+    chunk_shape(n, f64 ? nb::kFjRows64 : nb::kFjRows, n_cu, chunks, per);
 }
 
 // One force+jerk pass on the state (pos, vel): the O(N^2) kernel into fj_part, then the fp64 reduce into (acc_out, jerk_out).
@@ -667,6 +671,7 @@ int ensure_derivs(nb_sim* s, const char* who)
     if (!s->params_set) return fail(s, NB_ERR_STATE, std::string(who) + ": nb_set_params has not been called (G)");
     if (s->derivs_ok && s->derivs_any_G) { s->derivs_any_G = false; s->derivs_G = s->G; }
     if (s->derivs_ok && s->derivs_G == s->G) return NB_OK;
+    s->snap_ok = false;      // an order-6 handle's snap and crackle belong to the (a, j) replaced here, whoever asked for them: its start runs again
     launch_fj(s, s->bodies[0], s->vel, s->acc, s->jerk);
     NB_HIP(s, hipGetLastError());
     s->derivs_ok = true; s->derivs_any_G = false; s->derivs_G = s->G;
@@ -704,6 +709,101 @@ int hermite_step(nb_sim* s, uint32_t nsteps)
         ++s->steps_done;
     }
     return NB_OK;
+}
+
+// ---- the 6th-order scheme (nb_set_hermite_order; kernels/hermite6.hip.h) -------------------------
+// The j-chunks of the force+jerk+snap pass: fj_shape's rule with the pass's own rows per workgroup.
+void h6_shape(uint32_t n, bool f64, int n_cu, uint32_t* chunks, uint32_t* per)
+{
+    chunk_shape(n, f64 ? nb::kH6Rows64 : nb::kH6Rows, n_cu, chunks, per);
+}
+
+// One force+jerk+snap pass on the state (pos, vel, acc): the O(N^2) kernel into h6_part, then the fp64 reduce into (acc_out,
+// jerk_out, snap_out); acc_out and jerk_out null together: the snap alone.  Errors are picked up by the caller's hipGetLastError.
+void launch_h6(nb_sim* s, const void* pos, const void* vel, const void* acc, void* acc_out, void* jerk_out, void* snap_out)
+{
+    uint32_t n = s->n, chunks = s->h6_chunks, per = s->h6_per;
+    const size_t plane = (size_t)4 * s->esz * chunks * n;
+    void* pa = s->h6_part;
+    void* pj = (char*)s->h6_part + plane;
+    void* ps = (char*)s->h6_part + 2 * plane;
+    double G = s->G;
+    void* rargs[] = {&pa, &pj, &ps, &n, &chunks, &G, &acc_out, &jerk_out, &snap_out};
+    if (s->f64) {
+        double e2 = s->eps2;
+        void* args[] = {&pos, &vel, &acc, &pa, &pj, &ps, &n, &per, &e2};
+        (void)hipLaunchKernel((const void*)&nb::nb_h6_fjs64<double>, dim3(ceil_div(n, nb::kH6Rows64), chunks), dim3(nb::kBlock), args, 0, s->stream);
+        (void)hipLaunchKernel((const void*)&nb::nb_h6_reduce<double>, dim3(ceil_div(n, nb::kBlock)), dim3(nb::kBlock), rargs, 0, s->stream);
+    } else {
+        float e2 = (float)s->eps2;
+        const void* zr = s->zero_row;
+        void* args[] = {&pos, &vel, &acc, &pa, &pj, &ps, &n, &per, &e2, &zr};
+        (void)hipLaunchKernel((const void*)&nb::nb_h6_fjs_pk<nb::kH6NG>, dim3(ceil_div(n, nb::kH6Rows), chunks), dim3(nb::kBlock), args, 0, s->stream);
+        (void)hipLaunchKernel((const void*)&nb::nb_h6_reduce<float>, dim3(ceil_div(n, nb::kBlock)), dim3(nb::kBlock), rargs, 0, s->stream);
+    }
+}
+
+// The start of an order-6 handle (a no-op while everything is current): (a, j) from the force+jerk pass on (x, v) -- the bits an
+// order-4 handle holds --, the snap from the new pass on (x, v, a), crackle = 0.
+int ensure_derivs6(nb_sim* s, const char* who)
+{
+    if (!s->params_set) return fail(s, NB_ERR_STATE, std::string(who) + ": nb_set_params has not been called (G)");
+    const bool current = s->snap_ok && s->derivs_ok && (s->derivs_any_G || s->derivs_G == s->G);
+    if (int rc = ensure_derivs(s, who)) return rc;
+    if (current) return NB_OK;
+    launch_h6(s, s->bodies[0], s->vel, s->acc, nullptr, nullptr, s->snap);
+    NB_HIP(s, hipMemsetAsync(s->crackle, 0, 4 * s->esz * s->n, s->stream));
+    NB_HIP(s, hipGetLastError());
+    s->snap_ok = true;
+    return NB_OK;
+}
+
+template <typename T>
+void launch_h6_oc(nb_sim* s, bool correct)
+{
+    using V4 = typename nb::vec4<T>::type;
+    V4 *x = (V4*)s->bodies[0], *v = (V4*)s->vel, *a = (V4*)s->acc, *j = (V4*)s->jerk, *sn = (V4*)s->snap, *c = (V4*)s->crackle;
+    V4 *hx = (V4*)s->hx, *hv = (V4*)s->hv, *ha = (V4*)s->ha;
+    uint32_t n = s->n;
+    double h = s->dt;
+    void* args[] = {&x, &v, &a, &j, &sn, &c, &hx, &hv, &ha, &n, &h};      // predict: -> (xp, vp, ap); correct: <- with (a1, j1, s1)
+    const void* fn = correct ? (const void*)&nb::nb_h6_correct<T> : (const void*)&nb::nb_h6_predict<T>;
+    (void)hipLaunchKernel(fn, dim3(ceil_div(n, nb::kBlock)), dim3(nb::kBlock), args, 0, s->stream);
+}
+
+// nb_step of an order-6 handle: plain launches, nsteps x (predict, force+jerk+snap at the predicted state, correct).
+// Timed steps record the events of hermite_step.
+int hermite6_step(nb_sim* s, uint32_t nsteps)
+{
+    if (int rc = ensure_derivs6(s, "nb_step")) return rc;
+    for (uint32_t k = 0; k < nsteps; ++k) {
+        nb_events ev;
+        const bool rec = s->timing && get_events(s, &ev) == 0;
+        if (rec) NB_HIP(s, hipEventRecord(ev.e[6], s->stream));
+        if (s->f64) launch_h6_oc<double>(s, false); else launch_h6_oc<float>(s, false);
+        if (rec) NB_HIP(s, hipEventRecord(ev.e[0], s->stream));
+        launch_h6(s, s->hx, s->hv, s->ha, s->hx, s->hv, s->ha);      // (a1, j1, s1) over the predicted state: the reduce runs after every read of it
+        if (rec) NB_HIP(s, hipEventRecord(ev.e[1], s->stream));
+        if (s->f64) launch_h6_oc<double>(s, true); else launch_h6_oc<float>(s, true);
+        if (rec) { NB_HIP(s, hipEventRecord(ev.e[2], s->stream)); s->pending.push_back(ev); }
+        NB_HIP(s, hipGetLastError());
+        ++s->steps_done;
+    }
+    return NB_OK;
+}
+
+void h6_release(nb_sim* s)
+{
+    for (void** p : {&s->snap, &s->crackle, &s->ha, &s->h6_part}) { if (*p) (void)hipFree(*p); *p = nullptr; }
+    s->h6 = false; s->snap_ok = false;
+}
+
+// what nb_variant_name and nb_shape_info report: the pass a step of the handle runs
+void hermite_names(nb_sim* s)
+{
+    const uint32_t c = s->h6 ? s->h6_chunks : s->fj_chunks, per = s->h6 ? s->h6_per : s->fj_per;
+    s->jsplit = c; s->j_per_split = per;
+    s->variant = std::string(s->h6 ? "hermite6_" : "hermite4_") + (s->f64 ? "f64" : "f32pk") + "_c" + std::to_string(c) + "_j" + std::to_string(per);
 }
 
 // ---- block individual time steps (nb_set_block_steps; kernels/block.hip.h) ----------------------
@@ -1387,6 +1487,7 @@ void nb_destroy(nb_sim* s)
     for (void* p : {s->jerk, s->hx, s->hv, s->fj_part, (void*)s->blk_lev, (void*)s->blk_due, (void*)s->blk_act, (void*)s->blk_hdr}) if (p) (void)hipFree(p);
     if (s->blk_hdr_host) (void)hipHostFree(s->blk_hdr_host);
     ac_release(s);
+    h6_release(s);
     if (s->diag) (void)hipFree(s->diag);
     for (auto* b : {&s->q_in[0], &s->q_in[1], &s->q_in[2], &s->q_in[3], &s->q_out[0], &s->q_out[1], &s->q_out[2], &s->q_out[3], &s->q_out[4], &s->q_out[5], &s->q_part, &s->q_off, &s->q_work, &s->q_inf, &s->q_seg, &s->q_segcnt, &s->knn_stat})
         if (b->p) (void)hipFree(b->p);
@@ -1461,7 +1562,7 @@ int nb_step(nb_sim* s, uint32_t nsteps)
     if (!s->params_set) return fail(s, NB_ERR_STATE, "nb_step: nb_set_params has not been called");
     if (!(s->dt > 0.0)) return NB_OK;   // `if (dt > 0)` gate, nbody3d.js:474
     NB_HIP(s, hipSetDevice(s->device));
-    if (s->hermite) return s->ac ? ac_step(s, nsteps) : s->blk ? block_step(s, nsteps) : hermite_step(s, nsteps);
+    if (s->hermite) return s->ac ? ac_step(s, nsteps) : s->blk ? block_step(s, nsteps) : s->h6 ? hermite6_step(s, nsteps) : hermite_step(s, nsteps);
     const bool exchange = s->xfn || s->rccl;
     ensure_pairs(s);      // the j-packed step's position copy, if something outside the step rewrote the positions or G
     if (gm_active(s) && !s->gm_ok) { if (int rc = finish_gather(s)) return rc; }
@@ -1621,6 +1722,7 @@ int nb_upload_derivs(nb_sim* s, const void* accel, const void* jerk)
     if (!s) return fail(nullptr, NB_ERR_INVALID, "nb_upload_derivs: null handle");
     if (!accel || !jerk) return fail(s, NB_ERR_INVALID, "nb_upload_derivs: accel and jerk are required");
     if (!s->hermite) return fail(s, NB_ERR_STATE, "nb_upload_derivs: needs a Hermite handle (nb_config.integrator = NB_INT_HERMITE4)");
+    if (s->h6) return fail(s, NB_ERR_STATE, "nb_upload_derivs: the handle's order is 6 (nb_set_hermite_order): its checkpoint is four arrays, see nb_upload_derivs6");
     if (!s->uploaded) return fail(s, NB_ERR_STATE, "nb_upload_derivs: nb_upload has not been called");
     NB_HIP(s, hipSetDevice(s->device));
     NB_HIP(s, hipStreamSynchronize(s->stream));
@@ -1633,11 +1735,87 @@ int nb_upload_derivs(nb_sim* s, const void* accel, const void* jerk)
     return NB_OK;
 }
 
+int nb_set_hermite_order(nb_sim* s, uint32_t order)
+{
+    if (!s) return fail(nullptr, NB_ERR_INVALID, "nb_set_hermite_order: null handle");
+    if (order != 4 && order != 6) return fail(s, NB_ERR_INVALID, "nb_set_hermite_order: order must be 4 or 6");
+    if (!s->hermite) return fail(s, NB_ERR_STATE, "nb_set_hermite_order: needs a Hermite handle (nb_config.integrator = NB_INT_HERMITE4)");
+    if (order == 6 && s->blk) return fail(s, NB_ERR_STATE, "nb_set_hermite_order: order = 6 while block steps are switched on (nb_set_block_steps): they exclude each other");
+    if (order == 6 && s->ac) return fail(s, NB_ERR_STATE, "nb_set_hermite_order: order = 6 while the neighbour scheme is switched on (nb_set_neighbor_scheme): they exclude each other");
+    if ((order == 6) == s->h6) return NB_OK;
+    NB_HIP(s, hipSetDevice(s->device));
+    NB_HIP(s, hipStreamSynchronize(s->stream));
+    if (order == 4) {          // snap and crackle go, (a, j) stay current
+        h6_release(s);
+        hermite_names(s);
+        return NB_OK;
+    }
+    h6_shape(s->n, s->f64, s->n_cu, &s->h6_chunks, &s->h6_per);
+    const size_t rows = 4 * s->esz * s->n;
+    hipError_t e = hipSuccess;
+    for (void** p : {&s->snap, &s->crackle, &s->ha})
+        if (e == hipSuccess) e = hipMalloc(p, rows);
+    if (e == hipSuccess) e = hipMalloc(&s->h6_part, (size_t)3 * rows * s->h6_chunks);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        h6_release(s);
+        return fail(s, NB_ERR_HIP, std::string("nb_set_hermite_order: ") + hipGetErrorString(e));
+    }
+    s->h6 = true; s->snap_ok = false;
+    hermite_names(s);
+    return NB_OK;
+}
+
+int nb_hermite_order(nb_sim* s, uint32_t* order)
+{
+    if (!s) return fail(nullptr, NB_ERR_INVALID, "nb_hermite_order: null handle");
+    if (!order) return fail(s, NB_ERR_INVALID, "nb_hermite_order: order is NULL");
+    if (!s->hermite) return fail(s, NB_ERR_STATE, "nb_hermite_order: needs a Hermite handle (nb_config.integrator = NB_INT_HERMITE4)");
+    *order = s->h6 ? 6u : 4u;
+    return NB_OK;
+}
+
+int nb_download_snap(nb_sim* s, void* snap, void* crackle)
+{
+    if (!s) return fail(nullptr, NB_ERR_INVALID, "nb_download_snap: null handle");
+    if (!s->hermite) return fail(s, NB_ERR_STATE, "nb_download_snap: needs a Hermite handle (nb_config.integrator = NB_INT_HERMITE4)");
+    if (!s->h6) return fail(s, NB_ERR_STATE, "nb_download_snap: the handle's order is 4: snap and crackle exist at order 6 (nb_set_hermite_order)");
+    if (!s->uploaded) return fail(s, NB_ERR_STATE, "nb_download_snap: nothing uploaded yet");
+    NB_HIP(s, hipSetDevice(s->device));
+    if (int rc = ensure_derivs6(s, "nb_download_snap")) return rc;
+    NB_HIP(s, hipStreamSynchronize(s->stream));
+    if (snap) NB_HIP(s, hipMemcpy(snap, s->snap, 4 * s->esz * s->n, hipMemcpyDeviceToHost));
+    if (crackle) NB_HIP(s, hipMemcpy(crackle, s->crackle, 4 * s->esz * s->n, hipMemcpyDeviceToHost));
+    return NB_OK;
+}
+
+int nb_upload_derivs6(nb_sim* s, const void* accel, const void* jerk, const void* snap, const void* crackle)
+{
+    if (!s) return fail(nullptr, NB_ERR_INVALID, "nb_upload_derivs6: null handle");
+    if (!accel || !jerk || !snap || !crackle) return fail(s, NB_ERR_INVALID, "nb_upload_derivs6: accel, jerk, snap and crackle are required");
+    if (!s->hermite) return fail(s, NB_ERR_STATE, "nb_upload_derivs6: needs a Hermite handle (nb_config.integrator = NB_INT_HERMITE4)");
+    if (!s->h6) return fail(s, NB_ERR_STATE, "nb_upload_derivs6: the handle's order is 4 (nb_set_hermite_order): see nb_upload_derivs");
+    if (!s->uploaded) return fail(s, NB_ERR_STATE, "nb_upload_derivs6: nb_upload has not been called");
+    NB_HIP(s, hipSetDevice(s->device));
+    NB_HIP(s, hipStreamSynchronize(s->stream));
+    const size_t rows = 4 * s->esz * s->n;
+    NB_HIP(s, hipMemcpy(s->acc, accel, rows, hipMemcpyHostToDevice));
+    NB_HIP(s, hipMemcpy(s->jerk, jerk, rows, hipMemcpyHostToDevice));
+    NB_HIP(s, hipMemcpy(s->snap, snap, rows, hipMemcpyHostToDevice));
+    NB_HIP(s, hipMemcpy(s->crackle, crackle, rows, hipMemcpyHostToDevice));
+    s->derivs_ok = true;
+    s->derivs_any_G = !s->params_set;
+    s->derivs_G = s->G;
+    s->snap_ok = true;
+    return NB_OK;
+}
+
 int nb_set_block_steps(nb_sim* s, const nb_block_steps* cfg)
 {
     if (!s) return fail(nullptr, NB_ERR_INVALID, "nb_set_block_steps: null handle");
     if (!s->hermite) return fail(s, NB_ERR_STATE, "nb_set_block_steps: needs a Hermite handle (nb_config.integrator = NB_INT_HERMITE4)");
     if (!cfg) { s->blk = false; s->levels = 0; return NB_OK; }
+    if (s->h6) return fail(s, NB_ERR_STATE, "nb_set_block_steps: the handle's order is 6 (nb_set_hermite_order): block steps and the 6th-order scheme exclude each other");
     if (s->ac) return fail(s, NB_ERR_STATE, "nb_set_block_steps: the neighbour scheme is switched on (nb_set_neighbor_scheme): block steps and the neighbour scheme exclude each other");
     if (cfg->struct_size != sizeof(nb_block_steps)) return fail(s, NB_ERR_INVALID, "nb_set_block_steps: struct_size must be sizeof(nb_block_steps)");
     const uint32_t L = cfg->max_level ? cfg->max_level : 20u;
@@ -1726,6 +1904,7 @@ int nb_set_neighbor_scheme(nb_sim* s, const nb_neighbor_scheme* cfg)
         ac_release(s);
         return NB_OK;
     }
+    if (s->h6) return fail(s, NB_ERR_STATE, "nb_set_neighbor_scheme: the handle's order is 6 (nb_set_hermite_order): the neighbour scheme and the 6th-order scheme exclude each other");
     if (cfg->struct_size != sizeof(nb_neighbor_scheme)) return fail(s, NB_ERR_INVALID, "nb_set_neighbor_scheme: struct_size must be sizeof(nb_neighbor_scheme)");
     const uint32_t nsub = cfg->substeps ? cfg->substeps : 8u, cap = cfg->cap ? cfg->cap : 128u;
     if (nsub > 1024 || (nsub & (nsub - 1))) return fail(s, NB_ERR_INVALID, "nb_set_neighbor_scheme: substeps must be a power of two in 1 .. 1024 (0: the default 8)");
@@ -2218,7 +2397,9 @@ int nb_force_pass(nb_sim* s, uint32_t reps, double* avg_ms)
     if (int rc = ensure_gm(s)) return rc;
     if (int rc = ensure_eqm(s)) return rc;
     if (s->hermite && !s->params_set) return fail(s, NB_ERR_STATE, "nb_force_pass: nb_set_params has not been called (G)");
+    if (s->h6) { if (int rc = ensure_derivs6(s, "nb_force_pass")) return rc; }      // the pass streams the accelerations: they are made current, the state is untouched
     auto once = [&]() -> int {
+        if (s->h6) { launch_h6(s, s->bodies[0], s->vel, s->acc, s->hx, s->hv, s->ha); return NB_OK; }      // into the step's scratch
         if (s->hermite) { launch_fj(s, s->bodies[0], s->vel, s->hx, s->hv); return NB_OK; }      // into the step's scratch: state and derivatives untouched
         if (s->sym_rank) return s->f64 ? nbi::sym_rank_phase_a_t<double>(s, nullptr, false) : nbi::sym_rank_phase_a_t<float>(s, nullptr, false);
         if (s->f64) launch_force<double>(s); else launch_force<float>(s);

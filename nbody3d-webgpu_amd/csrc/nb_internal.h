@@ -172,6 +172,16 @@ struct nb_sim {
     bool derivs_ok = false;        // acc / jerk belong to (bodies, vel) and derivs_G
     bool derivs_any_G = false;     // nb_upload_derivs before the first nb_set_params: the derivatives belong to whatever G comes
     double derivs_G = 0.0;
+    // nb_set_hermite_order(6): the 6th-order scheme on force, jerk and snap (kernels/hermite6.hip.h).  Allocated by the call,
+    // released by order 4 or nb_destroy.  Off: none of this is read.
+    bool h6 = false;
+    void* snap = nullptr;          // d2a/dt2 of the state
+    void* crackle = nullptr;       // d3a/dt3: 0 after a start, the corrector's c1 afterwards
+    void* ha = nullptr;            // the predicted accelerations (ap), then s1 (hx / hv hold xp / vp, then a1 / j1)
+    void* h6_part = nullptr;       // 3 x h6_chunks x n rows of partial sums: accelerations, jerks, snaps
+    uint32_t h6_chunks = 1, h6_per = 0;   // the force+jerk+snap pass's j-chunks and bodies per chunk
+    bool snap_ok = false;          // snap / crackle belong to the current acc / jerk (which derivs_ok and derivs_G speak for); cleared by
+                                   // ensure_derivs whenever it re-evaluates acc / jerk, set by the start and by nb_upload_derivs6
     // nb_set_block_steps: block individual time steps (kernels/block.hip.h).  Allocated when first switched on.
     bool blk = false, blk_frozen = false;
     uint32_t blk_L = 20, blk_lmin = 0;

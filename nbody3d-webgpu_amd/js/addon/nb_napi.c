@@ -61,6 +61,10 @@ static int (*p_field_eval)(nb_sim *, const nb_field_request *);
 static int (*p_multi_field_eval)(nb_multi *, const nb_field_request *);
 static int (*p_download_jerk)(nb_sim *, void *);                        /* the Hermite additions within ABI 2.4: optional symbols */
 static int (*p_upload_derivs)(nb_sim *, const void *, const void *);
+static int (*p_set_hermite_order)(nb_sim *, uint32_t);                  /* the 6th-order scheme, also within ABI 2.4: optional symbols */
+static int (*p_hermite_order)(nb_sim *, uint32_t *);
+static int (*p_download_snap)(nb_sim *, void *, void *);
+static int (*p_upload_derivs6)(nb_sim *, const void *, const void *, const void *, const void *);
 static int (*p_set_block_steps)(nb_sim *, const nb_block_steps *);      /* block time steps, also within ABI 2.4: optional symbols */
 static int (*p_block_stats)(nb_sim *, struct nb_block_stats *, int);
 static int (*p_download_levels)(nb_sim *, uint8_t *);
@@ -171,6 +175,10 @@ static napi_value js_load(napi_env env, napi_callback_info info)
         /* present from the library that has NB_INT_HERMITE4; an older 2.4 library still loads */
         *(void **)(&p_download_jerk) = dlsym(h, "nb_download_jerk");
         *(void **)(&p_upload_derivs) = dlsym(h, "nb_upload_derivs");
+        *(void **)(&p_set_hermite_order) = dlsym(h, "nb_set_hermite_order");
+        *(void **)(&p_hermite_order) = dlsym(h, "nb_hermite_order");
+        *(void **)(&p_download_snap) = dlsym(h, "nb_download_snap");
+        *(void **)(&p_upload_derivs6) = dlsym(h, "nb_upload_derivs6");
         *(void **)(&p_set_block_steps) = dlsym(h, "nb_set_block_steps");
         *(void **)(&p_block_stats) = dlsym(h, "nb_block_stats");
         *(void **)(&p_download_levels) = dlsym(h, "nb_download_levels");
@@ -1097,6 +1105,75 @@ static napi_value js_upload_derivs(napi_env env, napi_callback_info info)
     return undefined(env);
 }
 
+/* the single-device handle of an order-6 call, or NULL with an exception pending */
+static handle_t *order_handle(napi_env env, napi_value v, const void *sym, const char *where)
+{
+    handle_t *h = get_handle(env, v); if (!h) return NULL;
+    if (h->multi || !sym) { throw_msg(env, NB_ERR_STATE, "needs a single-device Hermite handle and a library with nb_set_hermite_order", where); return NULL; }
+    return h;
+}
+
+/* setHermiteOrder(handle, order): nb_set_hermite_order -- 4 or 6. */
+static napi_value js_set_hermite_order(napi_env env, napi_callback_info info)
+{
+    size_t argc = 2; napi_value argv[2];
+    CHECK_NAPI(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    if (argc < 2) { napi_throw_type_error(env, NULL, "setHermiteOrder(handle, order)"); return NULL; }
+    handle_t *h = order_handle(env, argv[0], (const void *)p_set_hermite_order, "nb_set_hermite_order"); if (!h) return NULL;
+    uint32_t order = 0;
+    CHECK_NAPI(env, napi_get_value_uint32(env, argv[1], &order));
+    int rc = p_set_hermite_order(h->sim, order);
+    if (rc != NB_OK) return throw_nb(env, rc, h->sim, "nb_set_hermite_order");
+    return undefined(env);
+}
+
+/* hermiteOrder(handle) -> 4 or 6: nb_hermite_order. */
+static napi_value js_hermite_order(napi_env env, napi_callback_info info)
+{
+    size_t argc = 1; napi_value argv[1];
+    CHECK_NAPI(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    if (argc < 1) { napi_throw_type_error(env, NULL, "hermiteOrder(handle)"); return NULL; }
+    handle_t *h = order_handle(env, argv[0], (const void *)p_hermite_order, "nb_hermite_order"); if (!h) return NULL;
+    uint32_t order = 0;
+    int rc = p_hermite_order(h->sim, &order);
+    if (rc != NB_OK) return throw_nb(env, rc, h->sim, "nb_hermite_order");
+    napi_value out;
+    CHECK_NAPI(env, napi_create_uint32(env, order, &out));
+    return out;
+}
+
+/* downloadSnap(handle, snapOut, crackleOut): nb_download_snap -- 4*n elements each, written in place; either may be null. */
+static napi_value js_download_snap(napi_env env, napi_callback_info info)
+{
+    size_t argc = 3; napi_value argv[3];
+    CHECK_NAPI(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    if (argc < 3) { napi_throw_type_error(env, NULL, "downloadSnap(handle, snapOut, crackleOut)"); return NULL; }
+    handle_t *h = order_handle(env, argv[0], (const void *)p_download_snap, "nb_download_snap"); if (!h) return NULL;
+    void *s, *c;
+    if (!get_array(env, argv[1], h, 1, &s, "snapOut must be null or a typed array of 4*n elements")) return NULL;
+    if (!get_array(env, argv[2], h, 1, &c, "crackleOut must be null or a typed array of 4*n elements")) return NULL;
+    int rc = p_download_snap(h->sim, s, c);
+    if (rc != NB_OK) return throw_nb(env, rc, h->sim, "nb_download_snap");
+    return undefined(env);
+}
+
+/* uploadDerivs6(handle, accel, jerk, snap, crackle): nb_upload_derivs6 -- the checkpoint restore of an order-6 handle, after upload(). */
+static napi_value js_upload_derivs6(napi_env env, napi_callback_info info)
+{
+    size_t argc = 5; napi_value argv[5];
+    CHECK_NAPI(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    if (argc < 5) { napi_throw_type_error(env, NULL, "uploadDerivs6(handle, accel, jerk, snap, crackle)"); return NULL; }
+    handle_t *h = order_handle(env, argv[0], (const void *)p_upload_derivs6, "nb_upload_derivs6"); if (!h) return NULL;
+    void *p[4];
+    static const char *const what[4] = {"accel must be a typed array of 4*n elements", "jerk must be a typed array of 4*n elements",
+                                        "snap must be a typed array of 4*n elements", "crackle must be a typed array of 4*n elements"};
+    for (int k = 0; k < 4; ++k)
+        if (!get_array(env, argv[1 + k], h, 0, &p[k], what[k])) return NULL;
+    int rc = p_upload_derivs6(h->sim, p[0], p[1], p[2], p[3]);
+    if (rc != NB_OK) return throw_nb(env, rc, h->sim, "nb_upload_derivs6");
+    return undefined(env);
+}
+
 /* the single-device handle of a block-step call, or NULL with an exception pending */
 static handle_t *block_handle(napi_env env, napi_value v, const void *sym, const char *where)
 {
@@ -1465,6 +1542,7 @@ static napi_value init_module(napi_env env, napi_value exports)
         {"variant", js_variant}, {"eqm", js_eqm}, {"eqmForm", js_eqm_form}, {"diagnostics", js_diagnostics}, {"stepTimes", js_step_times},
         {"collectiveInfo", js_collective_info}, {"requestFrame", js_request_frame}, {"frame", js_frame}, {"planQuery", js_plan_query},
         {"fieldEval", js_field_eval}, {"downloadJerk", js_download_jerk}, {"uploadDerivs", js_upload_derivs},
+        {"setHermiteOrder", js_set_hermite_order}, {"hermiteOrder", js_hermite_order}, {"downloadSnap", js_download_snap}, {"uploadDerivs6", js_upload_derivs6},
         {"setBlockSteps", js_set_block_steps}, {"blockStats", js_block_stats}, {"downloadLevels", js_download_levels},
         {"uploadLevels", js_upload_levels}, {"neighbors", js_neighbors}, {"neighborLists", js_neighbor_lists},
         {"knn", js_knn}, {"listForce", js_list_force}, {"splitForce", js_split_force}, {"splitLists", js_split_lists}, {"neighborSchemeFused", js_neighbor_scheme_fused},

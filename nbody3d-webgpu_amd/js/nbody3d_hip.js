@@ -17,6 +17,8 @@
  *   G / dt / pause()       nbody3d.js:6-7, util.js:36-64 (dt and G are mutable
  *                          between frames; pause saves dt and sets it to 0)
  *   readJerk()             (no reference analogue) the jerk of a {integrator: 'hermite4'} simulation
+ *   setHermiteOrder(6 | 4), hermiteOrder(), readSnap(), uploadDerivs6(accel, jerk, snap, crackle)
+ *                          (no reference analogue) the 6th-order scheme of a 'hermite4' simulation on force, jerk and snap
  *   setBlockSteps() / blockStats() / readLevels() / uploadLevels()
  *                          (no reference analogue) block individual time steps of a 'hermite4' simulation
  *   requestFrame()/frame() nbody3d.js:408-415,482-487 what the render pass reads each frame
@@ -190,6 +192,37 @@ class Simulation {
     const j = new this.ArrayType(4 * this.nBodies);
     addon.downloadJerk(this._h, j);
     return j;
+  }
+
+  /** The order of a 'hermite4' simulation (nb_set_hermite_order; no reference analogue): 6 switches to the 6th-order
+   *  predictor-corrector on force, jerk and snap, 4 back (snap and crackle are freed, accel and jerk stay current). */
+  setHermiteOrder(order) {
+    this._need();
+    addon.setHermiteOrder(this._h, order >>> 0);
+    return this;
+  }
+
+  /** 4 or 6 (nb_hermite_order). */
+  hermiteOrder() {
+    this._need();
+    return addon.hermiteOrder(this._h);
+  }
+
+  /** {snap, crackle} (4 elements per body, .w = 0) of an order-6 simulation at the state as it stands (nb_download_snap).  With
+   *  read() and readJerk() this is the whole checkpoint uploadDerivs6() continues bit-identically from. */
+  readSnap() {
+    this._need();
+    addon.setParams(this._h, this.dt, this.G);
+    const snap = new this.ArrayType(4 * this.nBodies), crackle = new this.ArrayType(4 * this.nBodies);
+    addon.downloadSnap(this._h, snap, crackle);
+    return { snap: snap, crackle: crackle };
+  }
+
+  /** After restore({bodies, vel}) and setHermiteOrder(6): hands a checkpoint's four derivative arrays back (nb_upload_derivs6). */
+  uploadDerivs6(accel, jerk, snap, crackle) {
+    this._need();
+    addon.uploadDerivs6(this._h, this._coerce(accel, 'accel'), this._coerce(jerk, 'jerk'), this._coerce(snap, 'snap'), this._coerce(crackle, 'crackle'));
+    return this;
   }
 
   /** Block individual time steps of a 'hermite4' simulation (nb_set_block_steps; no reference analogue): every body steps by

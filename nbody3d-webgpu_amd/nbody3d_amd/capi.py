@@ -199,7 +199,8 @@ SYMBOLS = ["nb_abi_version", "nb_device_count", "nb_create", "nb_destroy", "nb_u
            "nb_set_neighbor_scheme", "nb_neighbor_scheme_stats", "nb_download_neighbor_scheme",
            "nb_split_lists", "nb_multi_split_lists", "nb_split_lists_shape", "nb_neighbor_scheme_fused",
            "nb_set_neighbor_adapt", "nb_neighbor_adapt_stats", "nb_download_neighbor_radii", "nb_upload_neighbor_scheme",
-           "nb_set_neighbor_levels", "nb_neighbor_level_stats", "nb_download_neighbor_levels", "nb_upload_neighbor_levels"]
+           "nb_set_neighbor_levels", "nb_neighbor_level_stats", "nb_download_neighbor_levels", "nb_upload_neighbor_levels",
+           "nb_set_hermite_order", "nb_hermite_order", "nb_download_snap", "nb_upload_derivs6"]
 
 _lib = None
 
@@ -318,6 +319,11 @@ def load_library():
         L.nb_neighbor_level_stats.argtypes = [vp, C.POINTER(nb_neighbor_level_stats), C.c_int]
         L.nb_download_neighbor_levels.argtypes = [vp, vp]
         L.nb_upload_neighbor_levels.argtypes = [vp, vp]
+    if hasattr(L, "nb_set_hermite_order"):      # the 6th-order scheme on force, jerk and snap, also within 2.4 and detected by the symbol
+        L.nb_set_hermite_order.argtypes = [vp, C.c_uint32]
+        L.nb_hermite_order.argtypes = [vp, C.POINTER(C.c_uint32)]
+        L.nb_download_snap.argtypes = [vp, vp, vp]
+        L.nb_upload_derivs6.argtypes = [vp, vp, vp, vp, vp]
     if hasattr(L, "nb_eqm_info"):           # the equal-mass kernels' report, also within 2.4 and detected by the symbol
         L.nb_eqm_info.argtypes = [vp, C.POINTER(C.c_int)]
     if hasattr(L, "nb_eqm_form"):           # which of the equal-mass forms, likewise
@@ -747,8 +753,10 @@ class Simulation:
         L = load_library()
         self._L = L
         self.n = int(n)
-        if integrator not in INTEGRATORS:
-            raise ValueError("integrator must be one of %s, got %r" % (sorted(INTEGRATORS), integrator))
+        if integrator not in INTEGRATORS and integrator != "hermite6":
+            raise ValueError("integrator must be one of %s, got %r" % (sorted(INTEGRATORS) + ["hermite6"], integrator))
+        if integrator == "hermite6" and not hasattr(L, "nb_set_hermite_order"):
+            raise NBodyError(1, "integrator='hermite6': the loaded library has no nb_set_hermite_order")
         if integrator != "leapfrog" and not hasattr(L, "nb_download_jerk"):
             raise NBodyError(1, "integrator=%r: the loaded library has no Hermite integrator (nb_download_jerk is missing)" % (integrator,))
         self.integrator = integrator
@@ -773,7 +781,7 @@ class Simulation:
         cfg.jsplit = jsplit
         cfg.flags |= int(flags)
         cfg.layer_budget_mib = int(layer_budget_mib)
-        cfg.integrator = INTEGRATORS[integrator]
+        cfg.integrator = INTEGRATORS["hermite4" if integrator == "hermite6" else integrator]      # "hermite6": hermite4 + set_hermite_order(6)
         h = C.c_void_p()
         rc = L.nb_create(C.byref(cfg), C.byref(h))
         if rc != 0:
@@ -782,6 +790,12 @@ class Simulation:
         self._hook = None
         self.dt = 0.0
         self.G = 0.0
+        if integrator == "hermite6":
+            try:
+                self.set_hermite_order(6)
+            except Exception:
+                self.close()
+                raise
 
     # -- lifecycle ---------------------------------------------------------
     def close(self):
@@ -864,6 +878,41 @@ class Simulation:
             raise NBodyError(1, "upload_derivs(): the loaded library has no nb_upload_derivs")
         a, j = self._arr(accel, "accel"), self._arr(jerk, "jerk")
         self._check(self._L.nb_upload_derivs(self._h, _ptr(a), _ptr(j)))
+        return self
+
+    # -- the 6th-order scheme of a Hermite handle (force, jerk and snap) --------
+    def _need_order(self, what):
+        if not hasattr(self._L, "nb_set_hermite_order"):
+            raise NBodyError(1, "%s: the loaded library has no nb_set_hermite_order" % what)
+
+    def set_hermite_order(self, order):
+        """nb_set_hermite_order: 6 switches the handle to the 6th-order predictor-corrector on force, jerk and snap (the snap is
+        evaluated when next needed), 4 back to the 4th-order one (snap and crackle are freed, accel and jerk stay current)."""
+        self._need_order("set_hermite_order()")
+        self._check(self._L.nb_set_hermite_order(self._h, int(order)))
+        return self
+
+    def hermite_order(self):
+        """nb_hermite_order: 4 or 6."""
+        self._need_order("hermite_order()")
+        o = C.c_uint32()
+        self._check(self._L.nb_hermite_order(self._h, C.byref(o)))
+        return int(o.value)
+
+    def read_snap(self):
+        """nb_download_snap: (snap, crackle) of the state as it stands, shape (N,4) each.  With read() and read_jerk() this is the
+        whole checkpoint of an order-6 handle."""
+        self._need_order("read_snap()")
+        s, c = np.zeros((self.n, 4), self.dtype), np.zeros((self.n, 4), self.dtype)
+        self._check(self._L.nb_download_snap(self._h, _ptr(s), _ptr(c)))
+        return s, c
+
+    def upload_derivs6(self, accel, jerk, snap, crackle):
+        """nb_upload_derivs6: after init() / restore() and set_hermite_order(6), hands a checkpoint's (accel, jerk, snap, crackle)
+        back, so that the next step continues bit-identically."""
+        self._need_order("upload_derivs6()")
+        a, j, s, c = self._arr(accel, "accel"), self._arr(jerk, "jerk"), self._arr(snap, "snap"), self._arr(crackle, "crackle")
+        self._check(self._L.nb_upload_derivs6(self._h, _ptr(a), _ptr(j), _ptr(s), _ptr(c)))
         return self
 
     # -- block individual time steps of a Hermite handle -----------------------
