@@ -76,7 +76,9 @@ extern "C" {
                                             nb_upload_neighbor_levels, nb_neighbor_levels, NB_NLEV_FROZEN.  Detected by the presence of the
                                             symbol nb_set_neighbor_levels
                              2.4 (round 20) likewise within 2.4: nb_set_hermite_order, nb_hermite_order, nb_download_snap, nb_upload_derivs6.
-                                            Detected by the presence of the symbol nb_set_hermite_order */
+                                            Detected by the presence of the symbol nb_set_hermite_order
+                             2.4 (round 21) likewise within 2.4: nb_set_block_steps6.  Detected by the presence of the symbol
+                                            nb_set_block_steps6 */
 
 typedef struct nb_sim nb_sim; /* opaque */
 
@@ -1238,13 +1240,56 @@ int nb_upload_neighbor_levels(nb_sim *s, const uint8_t *levels /* n */);
  *     steps or the neighbour scheme are switched on; nb_set_block_steps or nb_set_neighbor_scheme with a non-NULL argument on an
  *     order-6 handle; nb_upload_derivs on an order-6 handle (see nb_upload_derivs6); nb_download_snap or nb_upload_derivs6 on an
  *     order-4 handle.
- *   - Not built: block steps, the neighbour scheme and the 8th order on order-6 handles. */
+ *   - Block steps on an order-6 handle: nb_set_block_steps6 below.  Not built: the neighbour scheme and the 8th order on order-6
+ *     handles. */
 int nb_set_hermite_order(nb_sim *s, uint32_t order /* 4 or 6 */);
 int nb_hermite_order(nb_sim *s, uint32_t *order);
 /* 4*n elements each of the handle's precision, either pointer may be NULL; runs the start first if needed.  Blocks. */
 int nb_download_snap(nb_sim *s, void *snap, void *crackle);
 /* All four arrays are required, 4*n elements each; after nb_upload.  Marks the derivatives current. */
 int nb_upload_derivs6(nb_sim *s, const void *accel, const void *jerk, const void *snap, const void *crackle);
+
+/* ---- block individual time steps on an order-6 handle (no reference analogue) -----------------------------
+ * nb_set_block_steps6 gives every body of an order-6 Hermite handle a step of its own (Nitadori & Makino 2008, the production setup
+ * of phi-GPU): the higher order divides the number of block steps a hierarchy needs.  The scheme is that of "block individual time
+ * steps" above with steps 2 - 5 replaced; ticks, levels, level_for, the active set, the coarsen-by-one-when-aligned rule,
+ * `clamped`, `finest_level` and the last block step of an outer step restarting the clock are unchanged.  nb_set_block_steps and
+ * nb_set_hermite_order keep their behaviour: nb_set_block_steps(non-NULL) on an order-6 handle and nb_set_hermite_order(6) on an
+ * order-4 handle with block steps stay NB_ERR_STATE.
+ *   - Start (levels not current): the order-6 start makes (a, j, s) current with c = 0, then l_i = level_for((eta / 2) |a_i| / |j_i|);
+ *     |j_i| = 0 gives min_level (the order-4 rule).
+ *       2. EVERY body is predicted from its own stored (x, v, a, j, s, c) at t_i over (t_next - t_i) ticks with xp, vp, ap of the
+ *          shared order-6 step (fp64, Horner, fused, each rounded once) -- always from the stored state;
+ *       3. (a1, j1, s1) of i in A against all n predicted rows (xp, vp, ap); all nine self terms are exactly 0;
+ *       4. the corrector and c1 = (60 P - 36 Q + 9 R) / h^3 of the shared order-6 step over h = s_i ticks:
+ *          (x, v, a, j, s, c)_i <- (x1, v1, a1, j1, s1, c1);
+ *       5. (NB_F64, not frozen) from the same P, Q, R, in fp64 on the values as stored:
+ *            a4 = (360 P - 192 Q + 36 R) / h^4            -- the quintic's fourth derivative at the end of the step
+ *            a5 = (720 P - 360 Q + 60 R) / h^5
+ *            tau = cbrt(sqrt(eta^3 (|a1| |s1| + |j1|^2) / (|c1| |a5| + |a4|^2))), inf when the denominator is 0.
+ *          This is Nitadori & Makino's dt = eta_NM (A1 / A4)^(1/3) with eta_NM = sqrt(eta): eta keeps Aarseth's scale, its default
+ *          0.02 corresponds to eta_NM ~ 0.14.  Step 6 is unchanged.
+ *   - Configuration: the nb_block_steps struct, with the defaults and argument checks of nb_set_block_steps.  NULL switches back to
+ *     the shared order-6 step; nb_set_block_steps(s, NULL) does the same.
+ *   - Precision.  With binary32 storage a4 and a5 are rounding noise (on a 300-body system with a tight pair every body went to the
+ *     deepest level and nearly every decision was clamped): an NB_F32 handle without NB_BLOCK_FROZEN is NB_ERR_STATE.  With
+ *     NB_BLOCK_FROZEN it works: the levels are fixed, or uploaded by a host that brings its own criterion.
+ *   - While it is on: nb_block_stats, nb_download_levels, nb_upload_levels, nb_download, nb_download_jerk, nb_download_snap, the
+ *     queries and nb_diagnostics keep their meaning; nb_upload_derivs6 works and marks the derivatives current; nb_step(k) advances
+ *     by k x dt, equals k x nb_step(1) bit for bit, and two handles give the same bits; dt <= 0 is a no-op; nb_variant_name keeps its
+ *     "hermite6_" prefix; timing reports one outer step per launch (as for order 4); nb_force_pass keeps its order-6 meaning.
+ *     nb_set_hermite_order(4) and nb_set_neighbor_scheme(non-NULL) are NB_ERR_STATE.
+ *   - Checkpoint: (bodies, vel, accel, jerk, snap, crackle, levels); restore with nb_upload, nb_set_params,
+ *     nb_set_hermite_order(6), nb_upload_derivs6, nb_set_block_steps6, nb_upload_levels: the restored handle continues bit for bit.
+ *     nb_set_block_steps6 leaves the state and all six derived arrays as they are; only the levels go stale.
+ *   - Staleness: the order-4 rules.  Everything that stales the derivatives, a change of dt or G and the setter itself stale the
+ *     levels; stale levels are made by the start rule at the next nb_step or nb_download_levels.
+ *   - Errors: a NULL handle is NB_ERR_INVALID; an order-4 or leapfrog handle is NB_ERR_STATE with a message that names
+ *     nb_set_hermite_order; the argument checks are those of nb_set_block_steps, the message naming nb_set_block_steps6 and the field.
+ *   - The start rule is order 4's and the first step runs with c = 0: on systems with hard pairs the first outer step makes most of a
+ *     run's energy error (profiles/r21/block6.md).  A host that cares downloads the start levels, adds two and uploads them.
+ *   - Not built: a start rule of its own; the neighbour scheme on order-6 handles; block steps without the host wait per block step. */
+int nb_set_block_steps6(nb_sim *s, const nb_block_steps *cfg /* NULL: back to the shared order-6 step */);
 
 #if defined(__GNUC__)
 #pragma GCC visibility pop

@@ -40,13 +40,15 @@ constexpr uint32_t kH6Flush = 4;                    // tiles between two flushes
 //   Registers: 9 packed i-values and 2 x 9 packed sums per group, ~14 packed values live per chain, four chains issued
 // stage-major.  Two waves per SIMD (256 VGPRs each).  Built: two groups per lane take 240 VGPRs and no scratch, one group 174;
 // two groups halve the LDS reads per pair and keep nb_fj_pk's launch shape (profiles/r20/hermite6.md).
-template <int NG>
-__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(NB_H6_WAVES, NB_H6_WAVES)))
-void nb_h6_fjs_pk(const float4* __restrict__ pos, const float4* __restrict__ vel, const float4* __restrict__ acc,
-                  float4* __restrict__ pa, float4* __restrict__ pj, float4* __restrict__ ps, uint32_t n, uint32_t j_per_chunk,
-                  float eps2, const float4* __restrict__ zero_row)
+//   The body is shared with nb_blk6_fjs_pk (kernels/block6.hip.h), as fj_pk_body is with nb_blk_fj_pk: with GATHER the ni i-rows are
+// act[0 .. ni) and the partial rows are compact (row k of chunk c belongs to act[k]); without it ni == n and row k is body k.
+// Everything between the prologue's loads and the epilogue's stores is the same code.
+template <int NG, bool GATHER>
+__device__ __forceinline__ void h6_fjs_pk_body(const float4* __restrict__ pos, const float4* __restrict__ vel,
+                                               const float4* __restrict__ acc, const uint32_t* __restrict__ act, uint32_t ni,
+                                               float4* __restrict__ pa, float4* __restrict__ pj, float4* __restrict__ ps,
+                                               uint32_t n, uint32_t j_per_chunk, float eps2, const float4* __restrict__ zero_row)
 {
-    static_assert(kBlock * 2 * NG == kH6Rows, "the engine sizes the grid by kH6Rows");
     constexpr int TILE = kTile;
     constexpr int U = 8;                  // tile rows per unrolled chunk
     constexpr int JB = 4 / NG;            // j-bodies per stage: JB * NG = 4 independent chains
@@ -62,7 +64,8 @@ void nb_h6_fjs_pk(const float4* __restrict__ pos, const float4* __restrict__ vel
 #pragma unroll
     for (int g = 0; g < NG; ++g) {
         const uint32_t il0 = i0 + (2 * g) * kBlock + tid, il1 = il0 + kBlock;
-        const uint32_t c0 = il0 < n ? il0 : n - 1, c1 = il1 < n ? il1 : n - 1;        // clamped, branch-free (never stored)
+        uint32_t c0 = il0 < ni ? il0 : ni - 1, c1 = il1 < ni ? il1 : ni - 1;        // clamped, branch-free (never stored)
+        if constexpr (GATHER) { c0 = act[c0]; c1 = act[c1]; }
         const float4 b0 = ld4(pos + c0), b1 = ld4(pos + c1), v0 = ld4(vel + c0), v1 = ld4(vel + c1);
         const float4 a0 = ld4(acc + c0), a1 = ld4(acc + c1);
         xi[g] = nb_f2{b0.x, b1.x}; yi[g] = nb_f2{b0.y, b1.y}; zi[g] = nb_f2{b0.z, b1.z};
@@ -254,18 +257,18 @@ void nb_h6_fjs_pk(const float4* __restrict__ pos, const float4* __restrict__ vel
     }
     flush();
 
-    float4* oa = pa + (size_t)blockIdx.y * n;
-    float4* oj = pj + (size_t)blockIdx.y * n;
-    float4* os = ps + (size_t)blockIdx.y * n;
+    float4* oa = pa + (size_t)blockIdx.y * ni;
+    float4* oj = pj + (size_t)blockIdx.y * ni;
+    float4* os = ps + (size_t)blockIdx.y * ni;
 #pragma unroll
     for (int g = 0; g < NG; ++g) {
         const uint32_t il0 = i0 + (2 * g) * kBlock + tid, il1 = il0 + kBlock;
-        if (il0 < n) {
+        if (il0 < ni) {
             oa[il0] = float4{SM[g][0].x, SM[g][1].x, SM[g][2].x, 0.0f};
             oj[il0] = float4{SM[g][3].x, SM[g][4].x, SM[g][5].x, 0.0f};
             os[il0] = float4{SM[g][6].x, SM[g][7].x, SM[g][8].x, 0.0f};
         }
-        if (il1 < n) {
+        if (il1 < ni) {
             oa[il1] = float4{SM[g][0].y, SM[g][1].y, SM[g][2].y, 0.0f};
             oj[il1] = float4{SM[g][3].y, SM[g][4].y, SM[g][5].y, 0.0f};
             os[il1] = float4{SM[g][6].y, SM[g][7].y, SM[g][8].y, 0.0f};
@@ -273,14 +276,25 @@ void nb_h6_fjs_pk(const float4* __restrict__ pos, const float4* __restrict__ vel
     }
 }
 
+template <int NG>
+__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(NB_H6_WAVES, NB_H6_WAVES)))
+void nb_h6_fjs_pk(const float4* __restrict__ pos, const float4* __restrict__ vel, const float4* __restrict__ acc,
+                  float4* __restrict__ pa, float4* __restrict__ pj, float4* __restrict__ ps, uint32_t n, uint32_t j_per_chunk,
+                  float eps2, const float4* __restrict__ zero_row)
+{
+    static_assert(kBlock * 2 * NG == kH6Rows, "the engine sizes the grid by kH6Rows");
+    h6_fjs_pk_body<NG, false>(pos, vel, acc, nullptr, n, pa, pj, ps, n, j_per_chunk, eps2, zero_row);
+}
+
 // fp64 handles.  One body per lane, the three j-tiles staged through registers; v_rsq_f64 seed + one correction as in nb_fj64;
 // every difference, product and sum is fp64.  (T = double: a template so that every translation unit may include it.)
-template <typename T>
-__global__ __launch_bounds__(kBlock) void nb_h6_fjs64(const typename vec4<T>::type* __restrict__ pos,
-                                                     const typename vec4<T>::type* __restrict__ vel,
-                                                     const typename vec4<T>::type* __restrict__ acc, double4* __restrict__ pa,
-                                                     double4* __restrict__ pj, double4* __restrict__ ps, uint32_t n,
-                                                     uint32_t j_per_chunk, double eps2)
+// h6_fjs64_body<T, GATHER>: shared with nb_blk6_fjs64, as h6_fjs_pk_body above.
+template <typename T, bool GATHER>
+__device__ __forceinline__ void h6_fjs64_body(const typename vec4<T>::type* __restrict__ pos,
+                                              const typename vec4<T>::type* __restrict__ vel,
+                                              const typename vec4<T>::type* __restrict__ acc, const uint32_t* __restrict__ act,
+                                              uint32_t ni, double4* __restrict__ pa, double4* __restrict__ pj,
+                                              double4* __restrict__ ps, uint32_t n, uint32_t j_per_chunk, double eps2)
 {
     static_assert(std::is_same<T, double>::value, "the fp64 pass of fp64 handles");
     __shared__ double4 tp[kTile];
@@ -290,7 +304,8 @@ __global__ __launch_bounds__(kBlock) void nb_h6_fjs64(const typename vec4<T>::ty
     const uint32_t il = blockIdx.x * kH6Rows64 + tid;
     const uint32_t j0 = blockIdx.y * j_per_chunk;
     const uint32_t j1 = j0 + j_per_chunk < n ? j0 + j_per_chunk : n;
-    const uint32_t ic = il < n ? il : n - 1;
+    uint32_t ic = il < ni ? il : ni - 1;
+    if constexpr (GATHER) ic = act[ic];
     const double4 bi = ld4(pos + ic), wi = ld4(vel + ic), ci = ld4(acc + ic);
     double ax = 0.0, ay = 0.0, az = 0.0, jx = 0.0, jy = 0.0, jz = 0.0, sx = 0.0, sy = 0.0, sz = 0.0;
     for (uint32_t jt = j0; jt < j1; jt += kTile) {
@@ -333,11 +348,21 @@ __global__ __launch_bounds__(kBlock) void nb_h6_fjs64(const typename vec4<T>::ty
             ax = nb_fma(s3, dx, ax); ay = nb_fma(s3, dy, ay); az = nb_fma(s3, dz, az);
         }
     }
-    if (il < n) {
-        pa[(size_t)blockIdx.y * n + il] = double4{ax, ay, az, 0.0};
-        pj[(size_t)blockIdx.y * n + il] = double4{jx, jy, jz, 0.0};
-        ps[(size_t)blockIdx.y * n + il] = double4{sx, sy, sz, 0.0};
+    if (il < ni) {
+        pa[(size_t)blockIdx.y * ni + il] = double4{ax, ay, az, 0.0};
+        pj[(size_t)blockIdx.y * ni + il] = double4{jx, jy, jz, 0.0};
+        ps[(size_t)blockIdx.y * ni + il] = double4{sx, sy, sz, 0.0};
     }
+}
+
+template <typename T>
+__global__ __launch_bounds__(kBlock) void nb_h6_fjs64(const typename vec4<T>::type* __restrict__ pos,
+                                                     const typename vec4<T>::type* __restrict__ vel,
+                                                     const typename vec4<T>::type* __restrict__ acc, double4* __restrict__ pa,
+                                                     double4* __restrict__ pj, double4* __restrict__ ps, uint32_t n,
+                                                     uint32_t j_per_chunk, double eps2)
+{
+    h6_fjs64_body<T, false>(pos, vel, acc, nullptr, n, pa, pj, ps, n, j_per_chunk, eps2);
 }
 
 // Adds a body's chunk rows in ascending chunk order in fp64, multiplies by G once and writes the derivative rows (ax, ay, az, 0),

@@ -811,7 +811,7 @@ void hermite_names(nb_sim* s)
 // are kept), and the clock of the outer step at 0.
 int ensure_levels(nb_sim* s, const char* who)
 {
-    if (int rc = ensure_derivs(s, who)) return rc;      // also: a changed G re-evaluates them
+    if (int rc = s->h6 ? ensure_derivs6(s, who) : ensure_derivs(s, who)) return rc;      // also: a changed G re-evaluates them (order 6: its start, c = 0)
     if (s->levels == 2) return NB_OK;
     void *a = s->acc, *j = s->jerk;
     uint32_t n = s->n, lmin = s->blk_lmin, L = s->blk_L;
@@ -892,6 +892,88 @@ int block_step(nb_sim* s, uint32_t nsteps)
             launch_blk_fj(s, na, &chunks, &pa, &pj);
             void* cargs[] = {&pa, &pj, &s->blk_act, &na, &chunks, &G, &x, &v, &a, &j, &s->blk_due, &s->blk_lev, &s->blk_hdr, &t_next, &Lk, &lmin, &frozen, &eta, &dt};
             const void* cf = s->f64 ? (const void*)&nb::nb_blk_correct<double, double> : (const void*)&nb::nb_blk_correct<float, float>;
+            (void)hipLaunchKernel(cf, dim3(ceil_div(na, nb::kBlock)), dim3(nb::kBlock), cargs, 0, s->stream);
+            ++s->blk_steps; s->blk_body_steps += na;
+            if (t_next == end) break;
+            schedule_and_predict();
+            NB_HIP(s, hipGetLastError());
+        }
+        if (rec) { NB_HIP(s, hipEventRecord(ev.e[1], s->stream)); ev.blk = true; s->pending.push_back(ev); }
+        if (k + 1 < nsteps && !s->timing) { schedule_and_predict(); ahead = true; }      // (timed steps launch it inside their own span)
+        NB_HIP(s, hipGetLastError());
+        ++s->blk_outer;
+        ++s->steps_done;
+    }
+    return NB_OK;
+}
+
+// ---- block steps on order-6 handles (nb_set_block_steps6; kernels/block6.hip.h) ------------------
+// The force+jerk+snap launch of one block step: launch_blk_fj's rule with the order-6 pass's rows per workgroup, bounded by the
+// partial rows the handle owns (h6_chunks x n each for accelerations, jerks and snaps).  A function of (n, na) alone.
+void launch_blk6_fjs(nb_sim* s, uint32_t na, uint32_t* chunks_out, void** pa_out, void** pj_out, void** ps_out)
+{
+    const uint32_t n = s->n, want = kFjWavesPerSimd * (uint32_t)s->n_cu, tiles = ceil_div(n, (uint32_t)nb::kTile);
+    uint32_t rows = s->f64 ? nb::kH6Rows64 : nb::kBlock * 4;      // f32: NG = 2
+    if (!s->f64 && (na <= rows / 2 || (uint64_t)ceil_div(na, rows) * tiles < want)) rows /= 2;      // NG = 1
+    const uint32_t iblocks = ceil_div(na, rows);
+    const uint32_t cap = (uint32_t)std::min<uint64_t>((uint64_t)s->h6_chunks * n / na, tiles);
+    uint32_t c = std::min(ceil_div(want, iblocks), cap);
+    c = std::max(std::max(c, 1u), ceil_div(n, kFjMaxChunk));
+    uint32_t per = ceil_div(ceil_div(n, c), (uint32_t)nb::kTile) * nb::kTile;
+    uint32_t chunks = ceil_div(n, per);
+    const size_t plane = (size_t)4 * s->esz * chunks * na;
+    void* pa = s->h6_part;
+    void* pj = (char*)s->h6_part + plane;
+    void* ps = (char*)s->h6_part + 2 * plane;
+    const void *pos = s->hx, *vel = s->hv, *acc = s->ha;
+    uint32_t nn = n;
+    if (s->f64) {
+        double e2 = s->eps2;
+        void* args[] = {&pos, &vel, &acc, &s->blk_act, &na, &pa, &pj, &ps, &nn, &per, &e2};
+        (void)hipLaunchKernel((const void*)&nb::nb_blk6_fjs64<double>, dim3(iblocks, chunks), dim3(nb::kBlock), args, 0, s->stream);
+    } else {
+        float e2 = (float)s->eps2;
+        const void* zr = s->zero_row;
+        void* args[] = {&pos, &vel, &acc, &s->blk_act, &na, &pa, &pj, &ps, &nn, &per, &e2, &zr};
+        const void* fn = rows == nb::kBlock * 4 ? (const void*)&nb::nb_blk6_fjs_pk<2> : (const void*)&nb::nb_blk6_fjs_pk<1>;
+        (void)hipLaunchKernel(fn, dim3(iblocks, chunks), dim3(nb::kBlock), args, 0, s->stream);
+    }
+    *chunks_out = chunks; *pa_out = pa; *pj_out = pj; *ps_out = ps;
+}
+
+// nb_step of an order-6 handle with block steps: block_step's loop on the order-6 state.
+int block6_step(nb_sim* s, uint32_t nsteps)
+{
+    if (int rc = ensure_levels(s, "nb_step")) return rc;
+    const uint32_t L = s->blk_L, end = 1u << L;
+    uint32_t n = s->n, lmin = s->blk_lmin, Lk = L;
+    int frozen = s->blk_frozen ? 1 : 0;
+    double eta = s->blk_eta, dt = s->dt, G = s->G, tick = std::ldexp(s->dt, -(int)L);
+    void *x = s->bodies[0], *v = s->vel, *a = s->acc, *j = s->jerk, *sn = s->snap, *c = s->crackle, *hx = s->hx, *hv = s->hv, *ha = s->ha;
+    auto schedule_and_predict = [&]() {
+        void* sargs[] = {&s->blk_due, &s->blk_lev, &n, &s->blk_act, &s->blk_hdr, &s->blk_hdr_pub};
+        (void)hipLaunchKernel((const void*)&nb::nb_blk_sched<nb::kBlkSched>, dim3(1), dim3(nb::kBlkSched), sargs, 0, s->stream);
+        void* pargs[] = {&x, &v, &a, &j, &sn, &c, &s->blk_due, &s->blk_lev, &hx, &hv, &ha, &n, &s->blk_hdr, &Lk, &tick};
+        const void* pf = s->f64 ? (const void*)&nb::nb_blk6_predict<double> : (const void*)&nb::nb_blk6_predict<float>;
+        (void)hipLaunchKernel(pf, dim3(ceil_div(n, nb::kBlock)), dim3(nb::kBlock), pargs, 0, s->stream);
+    };
+    bool ahead = false;      // the first schedule + predict of this outer step went out behind the previous one's last corrector
+    for (uint32_t k = 0; k < nsteps; ++k) {
+        nb_events ev;
+        const bool rec = s->timing && get_events(s, &ev) == 0;
+        if (rec) NB_HIP(s, hipEventRecord(ev.e[0], s->stream));
+        if (!ahead) schedule_and_predict();
+        ahead = false;
+        for (;;) {
+            NB_HIP(s, hipStreamSynchronize(s->stream));
+            uint32_t na = s->blk_hdr_host[nb::kBlkCount], t_next = s->blk_hdr_host[nb::kBlkNext];
+            if (na == 0 || na > n || t_next == 0 || t_next > end)
+                return fail(s, NB_ERR_HIP, "nb_step: block schedule out of range (active " + std::to_string(na) + ", tick " + std::to_string(t_next) + ")");
+            uint32_t chunks = 1;
+            void *pa = nullptr, *pj = nullptr, *ps = nullptr;
+            launch_blk6_fjs(s, na, &chunks, &pa, &pj, &ps);
+            void* cargs[] = {&pa, &pj, &ps, &s->blk_act, &na, &chunks, &G, &x, &v, &a, &j, &sn, &c, &s->blk_due, &s->blk_lev, &s->blk_hdr, &t_next, &Lk, &lmin, &frozen, &eta, &dt};
+            const void* cf = s->f64 ? (const void*)&nb::nb_blk6_correct<double, double> : (const void*)&nb::nb_blk6_correct<float, float>;
             (void)hipLaunchKernel(cf, dim3(ceil_div(na, nb::kBlock)), dim3(nb::kBlock), cargs, 0, s->stream);
             ++s->blk_steps; s->blk_body_steps += na;
             if (t_next == end) break;
@@ -1562,7 +1644,7 @@ int nb_step(nb_sim* s, uint32_t nsteps)
     if (!s->params_set) return fail(s, NB_ERR_STATE, "nb_step: nb_set_params has not been called");
     if (!(s->dt > 0.0)) return NB_OK;   // `if (dt > 0)` gate, nbody3d.js:474
     NB_HIP(s, hipSetDevice(s->device));
-    if (s->hermite) return s->ac ? ac_step(s, nsteps) : s->blk ? block_step(s, nsteps) : s->h6 ? hermite6_step(s, nsteps) : hermite_step(s, nsteps);
+    if (s->hermite) return s->ac ? ac_step(s, nsteps) : s->blk ? (s->h6 ? block6_step(s, nsteps) : block_step(s, nsteps)) : s->h6 ? hermite6_step(s, nsteps) : hermite_step(s, nsteps);
     const bool exchange = s->xfn || s->rccl;
     ensure_pairs(s);      // the j-packed step's position copy, if something outside the step rewrote the positions or G
     if (gm_active(s) && !s->gm_ok) { if (int rc = finish_gather(s)) return rc; }
@@ -1740,7 +1822,8 @@ int nb_set_hermite_order(nb_sim* s, uint32_t order)
     if (!s) return fail(nullptr, NB_ERR_INVALID, "nb_set_hermite_order: null handle");
     if (order != 4 && order != 6) return fail(s, NB_ERR_INVALID, "nb_set_hermite_order: order must be 4 or 6");
     if (!s->hermite) return fail(s, NB_ERR_STATE, "nb_set_hermite_order: needs a Hermite handle (nb_config.integrator = NB_INT_HERMITE4)");
-    if (order == 6 && s->blk) return fail(s, NB_ERR_STATE, "nb_set_hermite_order: order = 6 while block steps are switched on (nb_set_block_steps): they exclude each other");
+    if (order == 6 && s->blk && !s->h6) return fail(s, NB_ERR_STATE, "nb_set_hermite_order: order = 6 while block steps are switched on (nb_set_block_steps): they exclude each other");
+    if (order == 4 && s->blk && s->h6) return fail(s, NB_ERR_STATE, "nb_set_hermite_order: order = 4 while block steps of order 6 are switched on (nb_set_block_steps6): switch them off first");
     if (order == 6 && s->ac) return fail(s, NB_ERR_STATE, "nb_set_hermite_order: order = 6 while the neighbour scheme is switched on (nb_set_neighbor_scheme): they exclude each other");
     if ((order == 6) == s->h6) return NB_OK;
     NB_HIP(s, hipSetDevice(s->device));
@@ -1810,21 +1893,18 @@ int nb_upload_derivs6(nb_sim* s, const void* accel, const void* jerk, const void
     return NB_OK;
 }
 
-int nb_set_block_steps(nb_sim* s, const nb_block_steps* cfg)
+// What nb_set_block_steps and nb_set_block_steps6 share: the checks of the configuration, the arrays (allocated when first switched
+// on, each on its own: a failed call may be repeated) and the switch.  The levels go stale, nothing else.
+static int blk_configure(nb_sim* s, const nb_block_steps* cfg, const char* who)
 {
-    if (!s) return fail(nullptr, NB_ERR_INVALID, "nb_set_block_steps: null handle");
-    if (!s->hermite) return fail(s, NB_ERR_STATE, "nb_set_block_steps: needs a Hermite handle (nb_config.integrator = NB_INT_HERMITE4)");
-    if (!cfg) { s->blk = false; s->levels = 0; return NB_OK; }
-    if (s->h6) return fail(s, NB_ERR_STATE, "nb_set_block_steps: the handle's order is 6 (nb_set_hermite_order): block steps and the 6th-order scheme exclude each other");
-    if (s->ac) return fail(s, NB_ERR_STATE, "nb_set_block_steps: the neighbour scheme is switched on (nb_set_neighbor_scheme): block steps and the neighbour scheme exclude each other");
-    if (cfg->struct_size != sizeof(nb_block_steps)) return fail(s, NB_ERR_INVALID, "nb_set_block_steps: struct_size must be sizeof(nb_block_steps)");
+    const std::string w(who);
+    if (cfg->struct_size != sizeof(nb_block_steps)) return fail(s, NB_ERR_INVALID, w + ": struct_size must be sizeof(nb_block_steps)");
     const uint32_t L = cfg->max_level ? cfg->max_level : 20u;
-    if (cfg->max_level > 30) return fail(s, NB_ERR_INVALID, "nb_set_block_steps: max_level is at most 30");
-    if (cfg->min_level > L) return fail(s, NB_ERR_INVALID, "nb_set_block_steps: min_level must not exceed max_level");
-    if (cfg->flags & ~NB_BLOCK_FROZEN) return fail(s, NB_ERR_INVALID, "nb_set_block_steps: unknown flags");
-    if (!(cfg->eta >= 0.0)) return fail(s, NB_ERR_INVALID, "nb_set_block_steps: eta must be > 0 (0: the default 0.02)");
+    if (cfg->max_level > 30) return fail(s, NB_ERR_INVALID, w + ": max_level is at most 30");
+    if (cfg->min_level > L) return fail(s, NB_ERR_INVALID, w + ": min_level must not exceed max_level");
+    if (cfg->flags & ~NB_BLOCK_FROZEN) return fail(s, NB_ERR_INVALID, w + ": unknown flags");
+    if (!(cfg->eta >= 0.0)) return fail(s, NB_ERR_INVALID, w + ": eta must be > 0 (0: the default 0.02)");
     NB_HIP(s, hipSetDevice(s->device));
-    // allocated when first switched on (each on its own: a failed call may be repeated)
     if (!s->blk_lev) NB_HIP(s, hipMalloc((void**)&s->blk_lev, s->n));
     if (!s->blk_due) NB_HIP(s, hipMalloc((void**)&s->blk_due, sizeof(uint32_t) * s->n));
     if (!s->blk_act) NB_HIP(s, hipMalloc((void**)&s->blk_act, sizeof(uint32_t) * s->n));
@@ -1839,6 +1919,27 @@ int nb_set_block_steps(nb_sim* s, const nb_block_steps* cfg)
     s->blk_eta = cfg->eta > 0.0 ? cfg->eta : 0.02;
     s->levels = 0;
     return NB_OK;
+}
+
+int nb_set_block_steps(nb_sim* s, const nb_block_steps* cfg)
+{
+    if (!s) return fail(nullptr, NB_ERR_INVALID, "nb_set_block_steps: null handle");
+    if (!s->hermite) return fail(s, NB_ERR_STATE, "nb_set_block_steps: needs a Hermite handle (nb_config.integrator = NB_INT_HERMITE4)");
+    if (!cfg) { s->blk = false; s->levels = 0; return NB_OK; }
+    if (s->h6) return fail(s, NB_ERR_STATE, "nb_set_block_steps: the handle's order is 6 (nb_set_hermite_order): block steps and the 6th-order scheme exclude each other here, see nb_set_block_steps6");
+    if (s->ac) return fail(s, NB_ERR_STATE, "nb_set_block_steps: the neighbour scheme is switched on (nb_set_neighbor_scheme): block steps and the neighbour scheme exclude each other");
+    return blk_configure(s, cfg, "nb_set_block_steps");
+}
+
+int nb_set_block_steps6(nb_sim* s, const nb_block_steps* cfg)
+{
+    if (!s) return fail(nullptr, NB_ERR_INVALID, "nb_set_block_steps6: null handle");
+    if (!s->hermite) return fail(s, NB_ERR_STATE, "nb_set_block_steps6: needs a Hermite handle (nb_config.integrator = NB_INT_HERMITE4) of order 6 (nb_set_hermite_order)");
+    if (!cfg) { s->blk = false; s->levels = 0; return NB_OK; }
+    if (!s->h6) return fail(s, NB_ERR_STATE, "nb_set_block_steps6: the handle's order is 4 (nb_set_hermite_order): see nb_set_block_steps");
+    if (cfg->struct_size == sizeof(nb_block_steps) && !s->f64 && !(cfg->flags & NB_BLOCK_FROZEN))
+        return fail(s, NB_ERR_STATE, "nb_set_block_steps6: precision NB_F32 without flags = NB_BLOCK_FROZEN: the criterion's a4 and a5 cannot be formed from binary32 derivatives (rounding noise); dynamic levels of order 6 need an NB_F64 handle");
+    return blk_configure(s, cfg, "nb_set_block_steps6");
 }
 
 int nb_block_stats(nb_sim* s, struct nb_block_stats* out, int reset)

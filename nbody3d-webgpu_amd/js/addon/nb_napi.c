@@ -65,6 +65,7 @@ static int (*p_set_hermite_order)(nb_sim *, uint32_t);                  /* the 6
 static int (*p_hermite_order)(nb_sim *, uint32_t *);
 static int (*p_download_snap)(nb_sim *, void *, void *);
 static int (*p_upload_derivs6)(nb_sim *, const void *, const void *, const void *, const void *);
+static int (*p_set_block_steps6)(nb_sim *, const nb_block_steps *);     /* block steps on order-6 handles (round 21): optional */
 static int (*p_set_block_steps)(nb_sim *, const nb_block_steps *);      /* block time steps, also within ABI 2.4: optional symbols */
 static int (*p_block_stats)(nb_sim *, struct nb_block_stats *, int);
 static int (*p_download_levels)(nb_sim *, uint8_t *);
@@ -180,6 +181,7 @@ static napi_value js_load(napi_env env, napi_callback_info info)
         *(void **)(&p_download_snap) = dlsym(h, "nb_download_snap");
         *(void **)(&p_upload_derivs6) = dlsym(h, "nb_upload_derivs6");
         *(void **)(&p_set_block_steps) = dlsym(h, "nb_set_block_steps");
+        *(void **)(&p_set_block_steps6) = dlsym(h, "nb_set_block_steps6");
         *(void **)(&p_block_stats) = dlsym(h, "nb_block_stats");
         *(void **)(&p_download_levels) = dlsym(h, "nb_download_levels");
         *(void **)(&p_upload_levels) = dlsym(h, "nb_upload_levels");
@@ -1183,15 +1185,15 @@ static handle_t *block_handle(napi_env env, napi_value v, const void *sym, const
 }
 
 /* setBlockSteps(handle, null) | setBlockSteps(handle, eta, maxLevel, minLevel, frozen): nb_set_block_steps (eta 0 / maxLevel 0: the defaults) */
-static napi_value js_set_block_steps(napi_env env, napi_callback_info info)
+static napi_value set_block_steps_with(napi_env env, napi_callback_info info, int (*fn)(nb_sim *, const nb_block_steps *), const char *where)
 {
     size_t argc = 5; napi_value argv[5];
     CHECK_NAPI(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
     if (argc < 2) { napi_throw_type_error(env, NULL, "setBlockSteps(handle, null | eta, maxLevel, minLevel, frozen)"); return NULL; }
-    handle_t *h = block_handle(env, argv[0], *(void **)&p_set_block_steps, "nb_set_block_steps"); if (!h) return NULL;
+    handle_t *h = block_handle(env, argv[0], *(void **)&fn, where); if (!h) return NULL;
     napi_valuetype t; napi_typeof(env, argv[1], &t);
     int rc;
-    if (t == napi_null || t == napi_undefined) rc = p_set_block_steps(h->sim, NULL);
+    if (t == napi_null || t == napi_undefined) rc = fn(h->sim, NULL);
     else {
         if (argc < 5) { napi_throw_type_error(env, NULL, "setBlockSteps(handle, eta, maxLevel, minLevel, frozen)"); return NULL; }
         nb_block_steps cfg;
@@ -1203,10 +1205,21 @@ static napi_value js_set_block_steps(napi_env env, napi_callback_info info)
         CHECK_NAPI(env, napi_get_value_uint32(env, argv[3], &u)); cfg.min_level = u;
         CHECK_NAPI(env, napi_get_value_bool(env, argv[4], &frozen));
         cfg.flags = frozen ? NB_BLOCK_FROZEN : 0u;
-        rc = p_set_block_steps(h->sim, &cfg);
+        rc = fn(h->sim, &cfg);
     }
-    if (rc != NB_OK) return throw_nb(env, rc, h->sim, "nb_set_block_steps");
+    if (rc != NB_OK) return throw_nb(env, rc, h->sim, where);
     return undefined(env);
+}
+
+static napi_value js_set_block_steps(napi_env env, napi_callback_info info)
+{
+    return set_block_steps_with(env, info, p_set_block_steps, "nb_set_block_steps");
+}
+
+/* setBlockSteps6(handle, null) | setBlockSteps6(handle, eta, maxLevel, minLevel, frozen): nb_set_block_steps6, on an order-6 handle */
+static napi_value js_set_block_steps6(napi_env env, napi_callback_info info)
+{
+    return set_block_steps_with(env, info, p_set_block_steps6, "nb_set_block_steps6");
 }
 
 /* blockStats(handle, reset) -> {enabled, outerSteps, blockSteps, bodySteps, clamped, finestLevel} (counts as doubles) */
@@ -1543,7 +1556,7 @@ static napi_value init_module(napi_env env, napi_value exports)
         {"collectiveInfo", js_collective_info}, {"requestFrame", js_request_frame}, {"frame", js_frame}, {"planQuery", js_plan_query},
         {"fieldEval", js_field_eval}, {"downloadJerk", js_download_jerk}, {"uploadDerivs", js_upload_derivs},
         {"setHermiteOrder", js_set_hermite_order}, {"hermiteOrder", js_hermite_order}, {"downloadSnap", js_download_snap}, {"uploadDerivs6", js_upload_derivs6},
-        {"setBlockSteps", js_set_block_steps}, {"blockStats", js_block_stats}, {"downloadLevels", js_download_levels},
+        {"setBlockSteps", js_set_block_steps}, {"setBlockSteps6", js_set_block_steps6}, {"blockStats", js_block_stats}, {"downloadLevels", js_download_levels},
         {"uploadLevels", js_upload_levels}, {"neighbors", js_neighbors}, {"neighborLists", js_neighbor_lists},
         {"knn", js_knn}, {"listForce", js_list_force}, {"splitForce", js_split_force}, {"splitLists", js_split_lists}, {"neighborSchemeFused", js_neighbor_scheme_fused},
         {"setNeighborScheme", js_set_neighbor_scheme}, {"neighborSchemeStats", js_neighbor_scheme_stats},

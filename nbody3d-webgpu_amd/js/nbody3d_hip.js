@@ -19,7 +19,7 @@
  *   readJerk()             (no reference analogue) the jerk of a {integrator: 'hermite4'} simulation
  *   setHermiteOrder(6 | 4), hermiteOrder(), readSnap(), uploadDerivs6(accel, jerk, snap, crackle)
  *                          (no reference analogue) the 6th-order scheme of a 'hermite4' simulation on force, jerk and snap
- *   setBlockSteps() / blockStats() / readLevels() / uploadLevels()
+ *   setBlockSteps() / setBlockSteps6() / blockStats() / readLevels() / uploadLevels()
  *                          (no reference analogue) block individual time steps of a 'hermite4' simulation
  *   requestFrame()/frame() nbody3d.js:408-415,482-487 what the render pass reads each frame
  *                          (bodies + speed), delivered asynchronously to a host-side viewer
@@ -233,6 +233,17 @@ class Simulation {
     this._need();
     if (options === null || options === undefined) { addon.setBlockSteps(this._h, null); return this; }
     addon.setBlockSteps(this._h, options.eta || 0, (options.maxLevel || 0) >>> 0, (options.minLevel || 0) >>> 0, !!options.frozen);
+    return this;
+  }
+
+  /** Block individual time steps of an order-6 simulation (nb_set_block_steps6; after setHermiteOrder(6)): setBlockSteps' options.
+   *  Dynamic levels need precision 'f64'; an 'f32' simulation takes {frozen: true} (levels fixed or uploaded).  blockStats(),
+   *  readLevels() and uploadLevels() work as with setBlockSteps().  setBlockSteps6(null) switches back to the shared order-6 step.
+   *  Checkpoint restore: restore({bodies, vel}), setHermiteOrder(6), uploadDerivs6(...), setBlockSteps6(...), uploadLevels(levels). */
+  setBlockSteps6(options) {
+    this._need();
+    if (options === null || options === undefined) { addon.setBlockSteps6(this._h, null); return this; }
+    addon.setBlockSteps6(this._h, options.eta || 0, (options.maxLevel || 0) >>> 0, (options.minLevel || 0) >>> 0, !!options.frozen);
     return this;
   }
 

@@ -6,8 +6,8 @@ binding used by the tests and ``bench.py``, initial-condition generators, and
 the one-process-per-GPU shard driver that runs the position all-gather through
 ``torch.distributed`` (RCCL on GPUs, gloo in the CPU tests).
 
-Hermite handles (``Simulation(..., integrator="hermite4")``) also carry block time steps (``set_block_steps``) and the
-Ahmad-Cohen neighbour scheme (``set_neighbor_scheme``, ``neighbor_scheme_stats``, ``download_neighbor_scheme``).
+Hermite handles (``Simulation(..., integrator="hermite4")``) also carry block time steps (``set_block_steps``; on order-6 handles
+``set_block_steps6``) and the Ahmad-Cohen neighbour scheme (``set_neighbor_scheme``, ``neighbor_scheme_stats``, ``download_neighbor_scheme``).
 
 There is NO CPU compute path in here: every force/integrate call goes through
 the HIP library and fails loudly when it (or a GPU) is missing.

@@ -200,7 +200,8 @@ SYMBOLS = ["nb_abi_version", "nb_device_count", "nb_create", "nb_destroy", "nb_u
            "nb_split_lists", "nb_multi_split_lists", "nb_split_lists_shape", "nb_neighbor_scheme_fused",
            "nb_set_neighbor_adapt", "nb_neighbor_adapt_stats", "nb_download_neighbor_radii", "nb_upload_neighbor_scheme",
            "nb_set_neighbor_levels", "nb_neighbor_level_stats", "nb_download_neighbor_levels", "nb_upload_neighbor_levels",
-           "nb_set_hermite_order", "nb_hermite_order", "nb_download_snap", "nb_upload_derivs6"]
+           "nb_set_hermite_order", "nb_hermite_order", "nb_download_snap", "nb_upload_derivs6",
+           "nb_set_block_steps6"]
 
 _lib = None
 
@@ -324,6 +325,8 @@ def load_library():
         L.nb_hermite_order.argtypes = [vp, C.POINTER(C.c_uint32)]
         L.nb_download_snap.argtypes = [vp, vp, vp]
         L.nb_upload_derivs6.argtypes = [vp, vp, vp, vp, vp]
+    if hasattr(L, "nb_set_block_steps6"):       # block steps on order-6 handles, likewise
+        L.nb_set_block_steps6.argtypes = [vp, C.POINTER(nb_block_steps)]
     if hasattr(L, "nb_eqm_info"):           # the equal-mass kernels' report, also within 2.4 and detected by the symbol
         L.nb_eqm_info.argtypes = [vp, C.POINTER(C.c_int)]
     if hasattr(L, "nb_eqm_form"):           # which of the equal-mass forms, likewise
@@ -926,8 +929,11 @@ class Simulation:
         the library's defaults, eta 0.02 and max_level 20); frozen=True keeps the levels as initialised or uploaded.  step() /
         simulate() still advance by whole dt.  set_block_steps(None) switches back to one shared step."""
         self._need_block("set_block_steps()")
+        return self._set_block(self._L.nb_set_block_steps, args, kw)
+
+    def _set_block(self, fn, args, kw):
         if args == (None,) and not kw:
-            self._check(self._L.nb_set_block_steps(self._h, None))
+            self._check(fn(self._h, None))
             return self
 
         def bind(eta=None, max_level=None, min_level=0, frozen=False):
@@ -939,8 +945,17 @@ class Simulation:
         cfg.min_level = int(min_level)
         cfg.flags = NB_BLOCK_FROZEN if frozen else 0
         cfg.eta = 0.0 if eta is None else float(eta)
-        self._check(self._L.nb_set_block_steps(self._h, C.byref(cfg)))
+        self._check(fn(self._h, C.byref(cfg)))
         return self
+
+    def set_block_steps6(self, *args, **kw):
+        """set_block_steps6(eta=None, max_level=None, min_level=0, frozen=False): nb_set_block_steps6 -- block steps on an order-6
+        handle (after set_hermite_order(6)): every body steps by dt / 2^level, chosen from its own (a, j, s, c, a4, a5) with the
+        accuracy parameter eta.  Dynamic levels need an f64 handle; an f32 handle takes frozen=True.  block_stats(), read_levels()
+        and upload_levels() work as with set_block_steps().  set_block_steps6(None) switches back to the shared order-6 step."""
+        if not hasattr(self._L, "nb_set_block_steps6"):
+            raise NBodyError(1, "set_block_steps6(): the loaded library has no nb_set_block_steps6")
+        return self._set_block(self._L.nb_set_block_steps6, args, kw)
 
     def block_stats(self, reset=False):
         """nb_block_stats: {enabled, outer_steps, block_steps, body_steps, clamped, finest_level} since the last reset."""

@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""Measures block individual time steps (Simulation.set_block_steps) on one GPU and prints ONE JSON line.
+"""Measures block individual time steps (Simulation.set_block_steps; with --order 6 Simulation.set_block_steps6 on order-6 handles,
+every counterpart below then an order-6 handle too) on one GPU and prints ONE JSON line.
 
   (a) full     one outer step with every body pinned at level 0 (ONE block step with |A| = N: nb_blk_sched, the host's wait,
                nb_blk_predict, nb_blk_fj_pk / nb_blk_fj64 over the full gathered set, nb_blk_correct) against nb_force_pass of a plain
@@ -9,7 +10,8 @@
                centre, on the circular orbit of their masses): wall time of one time unit with block steps (eta 0.02, outer step
                --outer-dt), |dE/E0| from nb_diagnostics, body_steps, block_steps and the level histogram; then shared-step Hermite at
                dt = 2^-k, k rising from --shared-from until its |dE/E0| is no worse (at most --shared-to: past that the run is recorded as
-               not reached), with each run's wall time.  --pair-half / --eps2 make the pairs hard (e.g. 0.001 and 1e-8: a period of ~0.1
+               not reached), with each run's wall time (--shared-to below --shared-from: no shared runs).  --eta sets the block steps' accuracy
+               parameter, --start-deeper K uploads the start rule's levels K deeper before the run.  --pair-half / --eps2 make the pairs hard (e.g. 0.001 and 1e-8: a period of ~0.1
                time units at N = 16,384 instead of ~4.5), the case the step hierarchy is for
   (c) small    microseconds per block step with |A| = 64 at N = --full-n: frozen levels, 64 bodies at level 6 and the rest at level 0
                (64 block steps per outer step, 63 of them with |A| = 64) minus the same outer step with every body at level 0, over 63
@@ -28,8 +30,18 @@ sys.path.insert(0, os.path.join(ROOT, "nbody3d-webgpu_amd"))
 from nbody3d_amd import Simulation, capi, ic  # noqa: E402
 
 
+ORDER = 4      # --order: 6 makes every handle an order-6 one (set_hermite_order(6)) and switches block steps on with set_block_steps6
+
+
 def hermite(n, prec, eps2=None):
-    return Simulation(n, precision=prec, integrator="hermite4", eps2=eps2)
+    sim = Simulation(n, precision=prec, integrator="hermite4", eps2=eps2)
+    if ORDER == 6:
+        sim.set_hermite_order(6)
+    return sim
+
+
+def block_steps(sim, **kw):
+    return sim.set_block_steps6(**kw) if ORDER == 6 else sim.set_block_steps(**kw)
 
 
 def with_tight_pairs(n, seed=1, frac=0.01, half=0.02):
@@ -69,7 +81,7 @@ def part_a(args, out):
             for s in (blk, plain):
                 s.init(b, v)
                 s.set_params(1e-3, 1.0)
-            blk.set_block_steps(max_level=0, frozen=True)
+            block_steps(blk, max_level=0, frozen=True)
             est = plain.force_pass(2)
             reps = max(4, int(np.ceil(args.min_seconds * 1e3 / est)))
             got = {"force_pass_ms": [], "shared_step_ms": [], "block_step_ms": []}
@@ -91,14 +103,17 @@ def part_b(args, out):
     for n in args.sizes:
         b, v = with_tight_pairs(n, half=args.pair_half)
         outer = int(round(1.0 / args.outer_dt))
-        r = {"n": n, "pairs": int(0.01 * n) // 2, "precision": args.precision, "outer_dt": args.outer_dt, "eta": 0.02,
-             "pair_half": args.pair_half, "eps2": args.eps2}
+        r = {"n": n, "pairs": int(0.01 * n) // 2, "precision": args.precision, "outer_dt": args.outer_dt, "eta": args.eta, "order": ORDER,
+             "start_deeper": args.start_deeper, "pair_half": args.pair_half, "eps2": args.eps2}
         with hermite(n, args.precision, args.eps2) as sim:
             sim.init(b, v)
             sim.set_params(args.outer_dt, 1.0)
-            sim.set_block_steps(eta=0.02, max_level=args.max_level)
+            block_steps(sim, eta=args.eta, max_level=args.max_level)
             e0 = energy(sim)
             lev0 = sim.read_levels()
+            if args.start_deeper:      # the start rule's levels made deeper through nb_upload_levels: every body's first step shorter
+                lev0 = np.minimum(lev0 + args.start_deeper, args.max_level).astype(np.uint8)
+                sim.upload_levels(lev0)
             sim.block_stats(reset=True)
             t = wall(sim, outer)
             r["block"] = {"wall_s": t, "dE": abs((energy(sim) - e0) / e0), "stats": sim.block_stats(),
@@ -119,7 +134,8 @@ def part_b(args, out):
                 break
         else:
             r["shared_match"] = None      # not reached by 2^-shared_to: the speedup over the LAST run is a lower bound
-            r["speedup_at_least"] = r["shared"][-1]["wall_s"] / r["block"]["wall_s"]
+            if r["shared"]:
+                r["speedup_at_least"] = r["shared"][-1]["wall_s"] / r["block"]["wall_s"]
         out["end2end"].append(r)
 
 
@@ -134,7 +150,7 @@ def part_c(args, out):
             sim.init(b, v)
             sim.set_params(1e-3, 1.0)
             for name, levels in (("all_level0", np.zeros(n, np.uint8)), ("64_at_level6", lev)):
-                sim.set_block_steps(max_level=L, frozen=True)
+                block_steps(sim, max_level=L, frozen=True)
                 sim.upload_levels(levels)
                 wall(sim, 4)
                 sim.block_stats(reset=True)
@@ -157,6 +173,9 @@ def main():
     ap.add_argument("--precision", default="f32", choices=["f32", "f64"])
     ap.add_argument("--pair-half", type=float, default=0.02, help="(b): half the separation of a pair (the issue's workload: 0.02)")
     ap.add_argument("--eps2", type=float, default=None, help="(b): softening (default: the engine's 1e-4)")
+    ap.add_argument("--order", type=int, default=4, choices=[4, 6], help="the Hermite order of every handle (6: set_hermite_order(6) + set_block_steps6)")
+    ap.add_argument("--eta", type=float, default=0.02, help="(b): the accuracy parameter of the block steps")
+    ap.add_argument("--start-deeper", type=int, default=0, help="(b): upload the start rule's levels this many levels deeper before the run")
     ap.add_argument("--outer-dt", type=float, default=2.0 ** -4)
     ap.add_argument("--max-level", type=int, default=16)
     ap.add_argument("--shared-from", type=int, default=6)
@@ -165,9 +184,11 @@ def main():
     ap.add_argument("--min-seconds", type=float, default=0.3)
     ap.add_argument("--rounds", type=int, default=3)
     args = ap.parse_args()
+    global ORDER
+    ORDER = args.order
     if capi.device_count() < 1:
         sys.exit("block_bench: no GPU")
-    out = {"tool": "block_bench", "full": {}, "end2end": [], "small": {}}
+    out = {"tool": "block_bench", "order": ORDER, "full": {}, "end2end": [], "small": {}}
     if "a" in args.only:
         part_a(args, out)
     if "b" in args.only:
