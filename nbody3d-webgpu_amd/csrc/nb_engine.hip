@@ -633,38 +633,115 @@ void chunk_shape(uint32_t n, uint32_t rows, int n_cu, uint32_t* chunks, uint32_t
     *chunks = ceil_div(n, *per);
 }
 
-void fj_shape(uint32_t n, bool f64, int n_cu, uint32_t* chunks, uint32_t* per)
+// What the host needs to know about an order, as data: the order-4 scheme works on (a, j), the order-6 one on (a, j, s).  Everything
+// below that serves both orders reads the order here and nowhere else.  Arrays of two are indexed by the handle's f64.
+struct hermite_order {
+    const char* name;                 // the head of nb_variant_name
+    uint32_t planes;                  // derivative planes of a pass, and predicted arrays: (a, j) | (a, j, s) and (xp, vp) | (xp, vp, ap)
+    uint32_t states;                  // arrays the predictor and the corrector take: (x, v, a, j) | (x, v, a, j, s, c)
+    uint32_t rows[2];                 // i-bodies of one workgroup of the full pass
+    uint32_t gather_rows[2];          // ... and of the gathered pass; f32: the NG = 2 kernel's, the NG = 1 kernel takes half of them
+    const void *pass[2], *reduce[2];
+    const void *gather[2], *gather_ng1;      // gather[0]: the f32 kernel with NG = 2
+    const void *predict[2], *correct[2], *blk_predict[2], *blk_correct[2];
+    void* nb_sim::*part;              // the partial sums the order's passes write (planes x chunks x n rows) ...
+    uint32_t nb_sim::*chunks, nb_sim::*per;      // ... and the j-chunks of its full pass
+};
+
+#define NB_BOTH(K) {(const void*)&nb::K<float>, (const void*)&nb::K<double>}
+const hermite_order kOrder4 = {
+    "hermite4_", 2, 4, {nb::kFjRows, nb::kFjRows64}, {nb::kFjRows, nb::kFjRows64},
+    {(const void*)&nb::nb_fj_pk<nb::kFjNG>, (const void*)&nb::nb_fj64<double>},
+    {(const void*)&nb::nb_fj_reduce<float, float>, (const void*)&nb::nb_fj_reduce<double, double>},
+    {(const void*)&nb::nb_blk_fj_pk<2>, (const void*)&nb::nb_blk_fj64<double>}, (const void*)&nb::nb_blk_fj_pk<1>,
+    NB_BOTH(nb_hermite_predict), NB_BOTH(nb_hermite_correct), NB_BOTH(nb_blk_predict),
+    {(const void*)&nb::nb_blk_correct<float, float>, (const void*)&nb::nb_blk_correct<double, double>},
+    &nb_sim::fj_part, &nb_sim::fj_chunks, &nb_sim::fj_per};
+const hermite_order kOrder6 = {
+    "hermite6_", 3, 6, {nb::kH6Rows, nb::kH6Rows64}, {nb::kBlock * 4, nb::kH6Rows64},      // (the gathered kernels are NG = 2 and 1 whatever NB_H6_NG the full pass is built with)
+    {(const void*)&nb::nb_h6_fjs_pk<nb::kH6NG>, (const void*)&nb::nb_h6_fjs64<double>},
+    NB_BOTH(nb_h6_reduce),
+    {(const void*)&nb::nb_blk6_fjs_pk<2>, (const void*)&nb::nb_blk6_fjs64<double>}, (const void*)&nb::nb_blk6_fjs_pk<1>,
+    NB_BOTH(nb_h6_predict), NB_BOTH(nb_h6_correct), NB_BOTH(nb_blk6_predict),
+    {(const void*)&nb::nb_blk6_correct<float, float>, (const void*)&nb::nb_blk6_correct<double, double>},
+    &nb_sim::h6_part, &nb_sim::h6_chunks, &nb_sim::h6_per};
+#undef NB_BOTH
+
+const hermite_order& order_of(const nb_sim* s) { return s->h6 ? kOrder6 : kOrder4; }
+
+// Sets the j-chunks of the order's full pass on the handle: chunk_shape with the pass's own rows per workgroup.
+void set_chunks(nb_sim* s, const hermite_order& o) { chunk_shape(s->n, o.rows[s->f64], s->n_cu, &(s->*o.chunks), &(s->*o.per)); }
+
+// The arrays of a handle in the order the kernels take them; an order reads its first `states` and `planes` of them.
+struct hermite_arrays {
+    void *state[6], *pred[3];
+    explicit hermite_arrays(nb_sim* s) : state{s->bodies[0], s->vel, s->acc, s->jerk, s->snap, s->crackle}, pred{s->hx, s->hv, s->ha} {}
+};
+
+// The arguments of one launch, collected in the kernel's order: scalars one by one, the arrays of an order by their count.
+struct kernel_args {
+    void* v[24];
+    uint32_t k = 0;
+    kernel_args& operator()(void* p) { v[k++] = p; return *this; }
+    kernel_args& operator()(void** arr, uint32_t count) { for (uint32_t i = 0; i < count; ++i) v[k++] = &arr[i]; return *this; }
+};
+
+// The launch shape of a gathered pass: `na` gathered i-rows against all n predicted rows.  Rows per workgroup and j-chunks are
+// chosen so that a small active set still fills the machine (f32: half the rows, the NG = 1 kernel; chunks down to one 256-row tile),
+// bounded by the partial rows the handle owns (owned_chunks x n per plane) and by kFjMaxChunk.  A function of its arguments alone:
+// the summation order is fixed by (n, na).
+struct pass_shape { uint32_t rows, chunks, per; };
+pass_shape gathered_shape(uint32_t n, uint32_t na, uint32_t rows, bool f64, uint32_t owned_chunks, int n_cu)
 {
-    chunk_shape(n, f64 ? nb::kFjRows64 : nb::kFjRows, n_cu, chunks, per);
+    const uint32_t want = kFjWavesPerSimd * (uint32_t)n_cu, tiles = ceil_div(n, (uint32_t)nb::kTile);
+    if (!f64 && (na <= rows / 2 || (uint64_t)ceil_div(na, rows) * tiles < want)) rows /= 2;      // NG = 1
+    const uint32_t cap = (uint32_t)std::min<uint64_t>((uint64_t)owned_chunks * n / na, tiles);
+    uint32_t c = std::min(ceil_div(want, ceil_div(na, rows)), cap);
+    c = std::max(std::max(c, 1u), ceil_div(n, kFjMaxChunk));
+    const uint32_t per = ceil_div(ceil_div(n, c), (uint32_t)nb::kTile) * nb::kTile;
+    return {rows, ceil_div(n, per), per};
 }
 
-// One force+jerk pass on the state (pos, vel): the O(N^2) kernel into fj_part, then the fp64 reduce into (acc_out, jerk_out).
+// What a gathered pass hands to the corrector: its j-chunks and where each plane of partial sums starts.
+struct pass_parts { uint32_t chunks; void* plane[3]; };
+
+// One O(N^2) pass of order `o` on the state in[0 .. o.planes) = (pos, vel[, acc]) into the order's partial sums.
+//   na == 0  the full pass with the handle's stored j-chunks, then the fp64 reduce into out[0 .. o.planes) (order 6: out[0] and
+//            out[1] null together: the snap alone);
+//   na > 0   the gathered pass of one block step over the rows blk_act[0 .. na), in gathered_shape's shape; no reduce: the block
+//            corrector sums the planes handed back in *got.
 // Errors are picked up by the caller's hipGetLastError.
-void launch_fj(nb_sim* s, const void* pos, const void* vel, void* acc_out, void* jerk_out)
+void launch_pass(nb_sim* s, const hermite_order& o, void** in, void** out, uint32_t na = 0, pass_parts* got = nullptr)
 {
-    uint32_t n = s->n, chunks = s->fj_chunks, per = s->fj_per;
-    void* pa = s->fj_part;
-    void* pj = (char*)s->fj_part + (size_t)4 * (s->f64 ? 8 : 4) * chunks * n;
-    double G = s->G;
-    void* rargs[] = {&pa, &pj, &n, &chunks, &G, &acc_out, &jerk_out};
-    if (s->f64) {
-        double e2 = s->eps2;
-        void* args[] = {&pos, &vel, &pa, &pj, &n, &per, &e2};
-        (void)hipLaunchKernel((const void*)&nb::nb_fj64<double>, dim3(ceil_div(n, nb::kFjRows64), chunks), dim3(nb::kBlock), args, 0, s->stream);
-        (void)hipLaunchKernel((const void*)&nb::nb_fj_reduce<double, double>, dim3(ceil_div(n, nb::kBlock)), dim3(nb::kBlock), rargs, 0, s->stream);
-    } else {
-        float e2 = (float)s->eps2;
-        const void* zr = s->zero_row;
-        void* args[] = {&pos, &vel, &pa, &pj, &n, &per, &e2, &zr};
-        (void)hipLaunchKernel((const void*)&nb::nb_fj_pk<nb::kFjNG>, dim3(ceil_div(n, nb::kFjRows), chunks), dim3(nb::kBlock), args, 0, s->stream);
-        (void)hipLaunchKernel((const void*)&nb::nb_fj_reduce<float, float>, dim3(ceil_div(n, nb::kBlock)), dim3(nb::kBlock), rargs, 0, s->stream);
+    uint32_t n = s->n, irows = n;
+    pass_shape sh = {o.rows[s->f64], s->*o.chunks, s->*o.per};
+    const void* fn = o.pass[s->f64];
+    if (na) {
+        irows = na;
+        sh = gathered_shape(n, na, o.gather_rows[s->f64], s->f64, s->*o.chunks, s->n_cu);
+        fn = sh.rows == o.gather_rows[s->f64] ? o.gather[s->f64] : o.gather_ng1;
     }
+    pass_parts part = {sh.chunks, {}};
+    for (uint32_t p = 0; p < o.planes; ++p) part.plane[p] = (char*)(s->*o.part) + p * ((size_t)4 * s->esz * sh.chunks * irows);
+    double e2 = s->eps2, G = s->G;
+    float e2f = (float)s->eps2;
+    const void* zr = s->zero_row;
+    kernel_args a;
+    a(in, o.planes);
+    if (na) a(&s->blk_act)(&na);
+    a(part.plane, o.planes)(&n)(&sh.per);
+    if (s->f64) a(&e2); else a(&e2f)(&zr);
+    (void)hipLaunchKernel(fn, dim3(ceil_div(irows, sh.rows), sh.chunks), dim3(nb::kBlock), a.v, 0, s->stream);
+    if (na) { *got = part; return; }
+    kernel_args r;
+    r(part.plane, o.planes)(&n)(&part.chunks)(&G)(out, o.planes);
+    (void)hipLaunchKernel(o.reduce[s->f64], dim3(ceil_div(n, nb::kBlock)), dim3(nb::kBlock), r.v, 0, s->stream);
 }
 
 int ensure_scheme(nb_sim* s, const char* who);
 
-// Makes acc / jerk the derivatives of (bodies, vel) for the G in force (a no-op while they are current).  With the neighbour scheme
-// on they are the scheme's totals and come from its start.
+// Makes acc / jerk the derivatives of (bodies, vel) for the G in force (a no-op while they are current): the order-4 force+jerk
+// pass, on handles of either order.  With the neighbour scheme on they are the scheme's totals and come from its start.
 int ensure_derivs(nb_sim* s, const char* who)
 {
     if (s->ac) return ensure_scheme(s, who);
@@ -672,119 +749,55 @@ int ensure_derivs(nb_sim* s, const char* who)
     if (s->derivs_ok && s->derivs_any_G) { s->derivs_any_G = false; s->derivs_G = s->G; }
     if (s->derivs_ok && s->derivs_G == s->G) return NB_OK;
     s->snap_ok = false;      // an order-6 handle's snap and crackle belong to the (a, j) replaced here, whoever asked for them: its start runs again
-    launch_fj(s, s->bodies[0], s->vel, s->acc, s->jerk);
+    void *in[] = {s->bodies[0], s->vel}, *out[] = {s->acc, s->jerk};
+    launch_pass(s, kOrder4, in, out);
     NB_HIP(s, hipGetLastError());
     s->derivs_ok = true; s->derivs_any_G = false; s->derivs_G = s->G;
     return NB_OK;
 }
 
-template <typename T>
-void launch_hermite_oc(nb_sim* s, bool correct)
+// The start of a step of the handle's order (a no-op while everything is current): ensure_derivs, and at order 6 the snap from the
+// force+jerk+snap pass on (x, v, a) and crackle = 0 -- so an order-6 handle starts from the (a, j) bits an order-4 handle holds.
+int ensure_start(nb_sim* s, const char* who)
 {
-    using V4 = typename nb::vec4<T>::type;
-    V4 *x = (V4*)s->bodies[0], *v = (V4*)s->vel, *a = (V4*)s->acc, *j = (V4*)s->jerk, *hx = (V4*)s->hx, *hv = (V4*)s->hv;
-    uint32_t n = s->n;
-    double h = s->dt;
-    void* args[] = {&x, &v, &a, &j, &hx, &hv, &n, &h};      // predict: (x, v, a, j) -> (xp, vp); correct: (x, v, a, j) <- with (a1, j1)
-    const void* fn = correct ? (const void*)&nb::nb_hermite_correct<T> : (const void*)&nb::nb_hermite_predict<T>;
-    (void)hipLaunchKernel(fn, dim3(ceil_div(n, nb::kBlock)), dim3(nb::kBlock), args, 0, s->stream);
-}
-
-// nb_step of a Hermite handle: plain launches, nsteps x (predict, force+jerk at the predicted state, correct).
-// Timed steps record e[6] predict e[0] force+jerk, reduce e[1] correct e[2] (collect_times).
-int hermite_step(nb_sim* s, uint32_t nsteps)
-{
-    if (int rc = ensure_derivs(s, "nb_step")) return rc;
-    for (uint32_t k = 0; k < nsteps; ++k) {
-        nb_events ev;
-        const bool rec = s->timing && get_events(s, &ev) == 0;
-        if (rec) NB_HIP(s, hipEventRecord(ev.e[6], s->stream));
-        if (s->f64) launch_hermite_oc<double>(s, false); else launch_hermite_oc<float>(s, false);
-        if (rec) NB_HIP(s, hipEventRecord(ev.e[0], s->stream));
-        launch_fj(s, s->hx, s->hv, s->hx, s->hv);         // (a1, j1) over the predicted state: the reduce runs after every read of it
-        if (rec) NB_HIP(s, hipEventRecord(ev.e[1], s->stream));
-        if (s->f64) launch_hermite_oc<double>(s, true); else launch_hermite_oc<float>(s, true);
-        if (rec) { NB_HIP(s, hipEventRecord(ev.e[2], s->stream)); s->pending.push_back(ev); }
-        NB_HIP(s, hipGetLastError());
-        ++s->steps_done;
-    }
-    return NB_OK;
-}
-
-// ---- the 6th-order scheme (nb_set_hermite_order; kernels/hermite6.hip.h) -------------------------
-// The j-chunks of the force+jerk+snap pass: fj_shape's rule with the pass's own rows per workgroup.
-void h6_shape(uint32_t n, bool f64, int n_cu, uint32_t* chunks, uint32_t* per)
-{
-    chunk_shape(n, f64 ? nb::kH6Rows64 : nb::kH6Rows, n_cu, chunks, per);
-}
-
-// One force+jerk+snap pass on the state (pos, vel, acc): the O(N^2) kernel into h6_part, then the fp64 reduce into (acc_out,
-// jerk_out, snap_out); acc_out and jerk_out null together: the snap alone.  Errors are picked up by the caller's hipGetLastError.
-void launch_h6(nb_sim* s, const void* pos, const void* vel, const void* acc, void* acc_out, void* jerk_out, void* snap_out)
-{
-    uint32_t n = s->n, chunks = s->h6_chunks, per = s->h6_per;
-    const size_t plane = (size_t)4 * s->esz * chunks * n;
-    void* pa = s->h6_part;
-    void* pj = (char*)s->h6_part + plane;
-    void* ps = (char*)s->h6_part + 2 * plane;
-    double G = s->G;
-    void* rargs[] = {&pa, &pj, &ps, &n, &chunks, &G, &acc_out, &jerk_out, &snap_out};
-    if (s->f64) {
-        double e2 = s->eps2;
-        void* args[] = {&pos, &vel, &acc, &pa, &pj, &ps, &n, &per, &e2};
-        (void)hipLaunchKernel((const void*)&nb::nb_h6_fjs64<double>, dim3(ceil_div(n, nb::kH6Rows64), chunks), dim3(nb::kBlock), args, 0, s->stream);
-        (void)hipLaunchKernel((const void*)&nb::nb_h6_reduce<double>, dim3(ceil_div(n, nb::kBlock)), dim3(nb::kBlock), rargs, 0, s->stream);
-    } else {
-        float e2 = (float)s->eps2;
-        const void* zr = s->zero_row;
-        void* args[] = {&pos, &vel, &acc, &pa, &pj, &ps, &n, &per, &e2, &zr};
-        (void)hipLaunchKernel((const void*)&nb::nb_h6_fjs_pk<nb::kH6NG>, dim3(ceil_div(n, nb::kH6Rows), chunks), dim3(nb::kBlock), args, 0, s->stream);
-        (void)hipLaunchKernel((const void*)&nb::nb_h6_reduce<float>, dim3(ceil_div(n, nb::kBlock)), dim3(nb::kBlock), rargs, 0, s->stream);
-    }
-}
-
-// The start of an order-6 handle (a no-op while everything is current): (a, j) from the force+jerk pass on (x, v) -- the bits an
-// order-4 handle holds --, the snap from the new pass on (x, v, a), crackle = 0.
-int ensure_derivs6(nb_sim* s, const char* who)
-{
-    if (!s->params_set) return fail(s, NB_ERR_STATE, std::string(who) + ": nb_set_params has not been called (G)");
-    const bool current = s->snap_ok && s->derivs_ok && (s->derivs_any_G || s->derivs_G == s->G);
+    const bool snap_current = s->snap_ok && s->derivs_ok && (s->derivs_any_G || s->derivs_G == s->G);
     if (int rc = ensure_derivs(s, who)) return rc;
-    if (current) return NB_OK;
-    launch_h6(s, s->bodies[0], s->vel, s->acc, nullptr, nullptr, s->snap);
+    if (!s->h6 || snap_current) return NB_OK;
+    void *in[] = {s->bodies[0], s->vel, s->acc}, *out[] = {nullptr, nullptr, s->snap};
+    launch_pass(s, kOrder6, in, out);
     NB_HIP(s, hipMemsetAsync(s->crackle, 0, 4 * s->esz * s->n, s->stream));
     NB_HIP(s, hipGetLastError());
     s->snap_ok = true;
     return NB_OK;
 }
 
-template <typename T>
-void launch_h6_oc(nb_sim* s, bool correct)
+// The predictor, state -> predicted arrays, or the corrector, state <- with the derivatives the pass left in the predicted arrays.
+void launch_oc(nb_sim* s, const hermite_order& o, bool correct)
 {
-    using V4 = typename nb::vec4<T>::type;
-    V4 *x = (V4*)s->bodies[0], *v = (V4*)s->vel, *a = (V4*)s->acc, *j = (V4*)s->jerk, *sn = (V4*)s->snap, *c = (V4*)s->crackle;
-    V4 *hx = (V4*)s->hx, *hv = (V4*)s->hv, *ha = (V4*)s->ha;
+    hermite_arrays h(s);
     uint32_t n = s->n;
-    double h = s->dt;
-    void* args[] = {&x, &v, &a, &j, &sn, &c, &hx, &hv, &ha, &n, &h};      // predict: -> (xp, vp, ap); correct: <- with (a1, j1, s1)
-    const void* fn = correct ? (const void*)&nb::nb_h6_correct<T> : (const void*)&nb::nb_h6_predict<T>;
-    (void)hipLaunchKernel(fn, dim3(ceil_div(n, nb::kBlock)), dim3(nb::kBlock), args, 0, s->stream);
+    double dt = s->dt;
+    kernel_args a;
+    a(h.state, o.states)(h.pred, o.planes)(&n)(&dt);
+    (void)hipLaunchKernel((correct ? o.correct : o.predict)[s->f64], dim3(ceil_div(n, nb::kBlock)), dim3(nb::kBlock), a.v, 0, s->stream);
 }
 
-// nb_step of an order-6 handle: plain launches, nsteps x (predict, force+jerk+snap at the predicted state, correct).
-// Timed steps record the events of hermite_step.
-int hermite6_step(nb_sim* s, uint32_t nsteps)
+// nb_step of a Hermite handle: plain launches, nsteps x (predict, the order's pass at the predicted state, correct).
+// Timed steps record e[6] predict e[0] pass, reduce e[1] correct e[2] (collect_times).
+int hermite_step(nb_sim* s, uint32_t nsteps)
 {
-    if (int rc = ensure_derivs6(s, "nb_step")) return rc;
+    if (int rc = ensure_start(s, "nb_step")) return rc;
+    const hermite_order& o = order_of(s);
+    hermite_arrays h(s);
     for (uint32_t k = 0; k < nsteps; ++k) {
         nb_events ev;
         const bool rec = s->timing && get_events(s, &ev) == 0;
         if (rec) NB_HIP(s, hipEventRecord(ev.e[6], s->stream));
-        if (s->f64) launch_h6_oc<double>(s, false); else launch_h6_oc<float>(s, false);
+        launch_oc(s, o, false);
         if (rec) NB_HIP(s, hipEventRecord(ev.e[0], s->stream));
-        launch_h6(s, s->hx, s->hv, s->ha, s->hx, s->hv, s->ha);      // (a1, j1, s1) over the predicted state: the reduce runs after every read of it
+        launch_pass(s, o, h.pred, h.pred);      // (a1, j1[, s1]) over the predicted state: the reduce runs after every read of it
         if (rec) NB_HIP(s, hipEventRecord(ev.e[1], s->stream));
-        if (s->f64) launch_h6_oc<double>(s, true); else launch_h6_oc<float>(s, true);
+        launch_oc(s, o, true);
         if (rec) { NB_HIP(s, hipEventRecord(ev.e[2], s->stream)); s->pending.push_back(ev); }
         NB_HIP(s, hipGetLastError());
         ++s->steps_done;
@@ -801,17 +814,18 @@ void h6_release(nb_sim* s)
 // what nb_variant_name and nb_shape_info report: the pass a step of the handle runs
 void hermite_names(nb_sim* s)
 {
-    const uint32_t c = s->h6 ? s->h6_chunks : s->fj_chunks, per = s->h6 ? s->h6_per : s->fj_per;
+    const hermite_order& o = order_of(s);
+    const uint32_t c = s->*o.chunks, per = s->*o.per;
     s->jsplit = c; s->j_per_split = per;
-    s->variant = std::string(s->h6 ? "hermite6_" : "hermite4_") + (s->f64 ? "f64" : "f32pk") + "_c" + std::to_string(c) + "_j" + std::to_string(per);
+    s->variant = std::string(o.name) + (s->f64 ? "f64" : "f32pk") + "_c" + std::to_string(c) + "_j" + std::to_string(per);
 }
 
-// ---- block individual time steps (nb_set_block_steps; kernels/block.hip.h) ----------------------
+// ---- block individual time steps (nb_set_block_steps, nb_set_block_steps6; kernels/block.hip.h, kernels/block6.hip.h) ----------
 // Makes the levels current: the start rule on current derivatives (or every body at min_level on a frozen handle; uploaded levels
 // are kept), and the clock of the outer step at 0.
 int ensure_levels(nb_sim* s, const char* who)
 {
-    if (int rc = s->h6 ? ensure_derivs6(s, who) : ensure_derivs(s, who)) return rc;      // also: a changed G re-evaluates them (order 6: its start, c = 0)
+    if (int rc = ensure_start(s, who)) return rc;      // also: a changed G re-evaluates them (order 6: its start, c = 0)
     if (s->levels == 2) return NB_OK;
     void *a = s->acc, *j = s->jerk;
     uint32_t n = s->n, lmin = s->blk_lmin, L = s->blk_L;
@@ -825,55 +839,24 @@ int ensure_levels(nb_sim* s, const char* who)
     return NB_OK;
 }
 
-// The force+jerk launch of one block step: `na` gathered i-rows against all n predicted rows.  Rows per workgroup and j-chunks are
-// chosen so that a small active set still fills the machine (chunks down to one 256-row tile), bounded by the partial rows the
-// handle owns (fj_chunks x n each for accelerations and jerks).  A function of (n, na) alone: the summation order is fixed.
-void launch_blk_fj(nb_sim* s, uint32_t na, uint32_t* chunks_out, void** pa_out, void** pj_out)
-{
-    const uint32_t n = s->n, want = kFjWavesPerSimd * (uint32_t)s->n_cu, tiles = ceil_div(n, (uint32_t)nb::kTile);
-    uint32_t rows = s->f64 ? nb::kFjRows64 : nb::kFjRows;
-    if (!s->f64 && (na <= rows / 2 || (uint64_t)ceil_div(na, rows) * tiles < want)) rows /= 2;      // NG = 1
-    const uint32_t iblocks = ceil_div(na, rows);
-    const uint32_t cap = (uint32_t)std::min<uint64_t>((uint64_t)s->fj_chunks * n / na, tiles);
-    uint32_t c = std::min(ceil_div(want, iblocks), cap);
-    c = std::max(std::max(c, 1u), ceil_div(n, kFjMaxChunk));
-    uint32_t per = ceil_div(ceil_div(n, c), (uint32_t)nb::kTile) * nb::kTile;
-    uint32_t chunks = ceil_div(n, per);
-    void* pa = s->fj_part;
-    void* pj = (char*)s->fj_part + (size_t)4 * s->esz * chunks * na;
-    const void *pos = s->hx, *vel = s->hv;
-    uint32_t nn = n;
-    if (s->f64) {
-        double e2 = s->eps2;
-        void* args[] = {&pos, &vel, &s->blk_act, &na, &pa, &pj, &nn, &per, &e2};
-        (void)hipLaunchKernel((const void*)&nb::nb_blk_fj64<double>, dim3(iblocks, chunks), dim3(nb::kBlock), args, 0, s->stream);
-    } else {
-        float e2 = (float)s->eps2;
-        const void* zr = s->zero_row;
-        void* args[] = {&pos, &vel, &s->blk_act, &na, &pa, &pj, &nn, &per, &e2, &zr};
-        const void* fn = rows == nb::kFjRows ? (const void*)&nb::nb_blk_fj_pk<2> : (const void*)&nb::nb_blk_fj_pk<1>;
-        (void)hipLaunchKernel(fn, dim3(iblocks, chunks), dim3(nb::kBlock), args, 0, s->stream);
-    }
-    *chunks_out = chunks; *pa_out = pa; *pj_out = pj;
-}
-
-// nb_step of a block-step handle: nsteps outer steps of dt.  Per block step: schedule and predict-all (launched right behind the
-// previous corrector), ONE host wait for the header (the active count sizes the next launch), force+jerk of the active bodies,
-// reduce + correct + new levels.
+// nb_step of a block-step handle of either order: nsteps outer steps of dt.  Per block step: schedule and predict-all (launched
+// right behind the previous corrector), ONE host wait for the header (the active count sizes the next launch), the order's gathered
+// pass over the active bodies, reduce + correct + new levels.
 int block_step(nb_sim* s, uint32_t nsteps)
 {
     if (int rc = ensure_levels(s, "nb_step")) return rc;
+    const hermite_order& o = order_of(s);
+    hermite_arrays h(s);
     const uint32_t L = s->blk_L, end = 1u << L;
     uint32_t n = s->n, lmin = s->blk_lmin, Lk = L;
     int frozen = s->blk_frozen ? 1 : 0;
     double eta = s->blk_eta, dt = s->dt, G = s->G, tick = std::ldexp(s->dt, -(int)L);
-    void *x = s->bodies[0], *v = s->vel, *a = s->acc, *j = s->jerk, *hx = s->hx, *hv = s->hv;
     auto schedule_and_predict = [&]() {
         void* sargs[] = {&s->blk_due, &s->blk_lev, &n, &s->blk_act, &s->blk_hdr, &s->blk_hdr_pub};
         (void)hipLaunchKernel((const void*)&nb::nb_blk_sched<nb::kBlkSched>, dim3(1), dim3(nb::kBlkSched), sargs, 0, s->stream);
-        void* pargs[] = {&x, &v, &a, &j, &s->blk_due, &s->blk_lev, &hx, &hv, &n, &s->blk_hdr, &Lk, &tick};
-        const void* pf = s->f64 ? (const void*)&nb::nb_blk_predict<double> : (const void*)&nb::nb_blk_predict<float>;
-        (void)hipLaunchKernel(pf, dim3(ceil_div(n, nb::kBlock)), dim3(nb::kBlock), pargs, 0, s->stream);
+        kernel_args p;
+        p(h.state, o.states)(&s->blk_due)(&s->blk_lev)(h.pred, o.planes)(&n)(&s->blk_hdr)(&Lk)(&tick);
+        (void)hipLaunchKernel(o.blk_predict[s->f64], dim3(ceil_div(n, nb::kBlock)), dim3(nb::kBlock), p.v, 0, s->stream);
     };
     bool ahead = false;      // the first schedule + predict of this outer step went out behind the previous one's last corrector
     for (uint32_t k = 0; k < nsteps; ++k) {
@@ -883,98 +866,15 @@ int block_step(nb_sim* s, uint32_t nsteps)
         if (!ahead) schedule_and_predict();
         ahead = false;
         for (;;) {
-            NB_HIP(s, hipStreamSynchronize(s->stream));
+            NB_HIP(s, hipStreamSynchronize(s->stream));      // the one host wait of a block step
             uint32_t na = s->blk_hdr_host[nb::kBlkCount], t_next = s->blk_hdr_host[nb::kBlkNext];
             if (na == 0 || na > n || t_next == 0 || t_next > end)
                 return fail(s, NB_ERR_HIP, "nb_step: block schedule out of range (active " + std::to_string(na) + ", tick " + std::to_string(t_next) + ")");
-            uint32_t chunks = 1;
-            void *pa = nullptr, *pj = nullptr;
-            launch_blk_fj(s, na, &chunks, &pa, &pj);
-            void* cargs[] = {&pa, &pj, &s->blk_act, &na, &chunks, &G, &x, &v, &a, &j, &s->blk_due, &s->blk_lev, &s->blk_hdr, &t_next, &Lk, &lmin, &frozen, &eta, &dt};
-            const void* cf = s->f64 ? (const void*)&nb::nb_blk_correct<double, double> : (const void*)&nb::nb_blk_correct<float, float>;
-            (void)hipLaunchKernel(cf, dim3(ceil_div(na, nb::kBlock)), dim3(nb::kBlock), cargs, 0, s->stream);
-            ++s->blk_steps; s->blk_body_steps += na;
-            if (t_next == end) break;
-            schedule_and_predict();
-            NB_HIP(s, hipGetLastError());
-        }
-        if (rec) { NB_HIP(s, hipEventRecord(ev.e[1], s->stream)); ev.blk = true; s->pending.push_back(ev); }
-        if (k + 1 < nsteps && !s->timing) { schedule_and_predict(); ahead = true; }      // (timed steps launch it inside their own span)
-        NB_HIP(s, hipGetLastError());
-        ++s->blk_outer;
-        ++s->steps_done;
-    }
-    return NB_OK;
-}
-
-// ---- block steps on order-6 handles (nb_set_block_steps6; kernels/block6.hip.h) ------------------
-// The force+jerk+snap launch of one block step: launch_blk_fj's rule with the order-6 pass's rows per workgroup, bounded by the
-// partial rows the handle owns (h6_chunks x n each for accelerations, jerks and snaps).  A function of (n, na) alone.
-void launch_blk6_fjs(nb_sim* s, uint32_t na, uint32_t* chunks_out, void** pa_out, void** pj_out, void** ps_out)
-{
-    const uint32_t n = s->n, want = kFjWavesPerSimd * (uint32_t)s->n_cu, tiles = ceil_div(n, (uint32_t)nb::kTile);
-    uint32_t rows = s->f64 ? nb::kH6Rows64 : nb::kBlock * 4;      // f32: NG = 2
-    if (!s->f64 && (na <= rows / 2 || (uint64_t)ceil_div(na, rows) * tiles < want)) rows /= 2;      // NG = 1
-    const uint32_t iblocks = ceil_div(na, rows);
-    const uint32_t cap = (uint32_t)std::min<uint64_t>((uint64_t)s->h6_chunks * n / na, tiles);
-    uint32_t c = std::min(ceil_div(want, iblocks), cap);
-    c = std::max(std::max(c, 1u), ceil_div(n, kFjMaxChunk));
-    uint32_t per = ceil_div(ceil_div(n, c), (uint32_t)nb::kTile) * nb::kTile;
-    uint32_t chunks = ceil_div(n, per);
-    const size_t plane = (size_t)4 * s->esz * chunks * na;
-    void* pa = s->h6_part;
-    void* pj = (char*)s->h6_part + plane;
-    void* ps = (char*)s->h6_part + 2 * plane;
-    const void *pos = s->hx, *vel = s->hv, *acc = s->ha;
-    uint32_t nn = n;
-    if (s->f64) {
-        double e2 = s->eps2;
-        void* args[] = {&pos, &vel, &acc, &s->blk_act, &na, &pa, &pj, &ps, &nn, &per, &e2};
-        (void)hipLaunchKernel((const void*)&nb::nb_blk6_fjs64<double>, dim3(iblocks, chunks), dim3(nb::kBlock), args, 0, s->stream);
-    } else {
-        float e2 = (float)s->eps2;
-        const void* zr = s->zero_row;
-        void* args[] = {&pos, &vel, &acc, &s->blk_act, &na, &pa, &pj, &ps, &nn, &per, &e2, &zr};
-        const void* fn = rows == nb::kBlock * 4 ? (const void*)&nb::nb_blk6_fjs_pk<2> : (const void*)&nb::nb_blk6_fjs_pk<1>;
-        (void)hipLaunchKernel(fn, dim3(iblocks, chunks), dim3(nb::kBlock), args, 0, s->stream);
-    }
-    *chunks_out = chunks; *pa_out = pa; *pj_out = pj; *ps_out = ps;
-}
-
-// nb_step of an order-6 handle with block steps: block_step's loop on the order-6 state.
-int block6_step(nb_sim* s, uint32_t nsteps)
-{
-    if (int rc = ensure_levels(s, "nb_step")) return rc;
-    const uint32_t L = s->blk_L, end = 1u << L;
-    uint32_t n = s->n, lmin = s->blk_lmin, Lk = L;
-    int frozen = s->blk_frozen ? 1 : 0;
-    double eta = s->blk_eta, dt = s->dt, G = s->G, tick = std::ldexp(s->dt, -(int)L);
-    void *x = s->bodies[0], *v = s->vel, *a = s->acc, *j = s->jerk, *sn = s->snap, *c = s->crackle, *hx = s->hx, *hv = s->hv, *ha = s->ha;
-    auto schedule_and_predict = [&]() {
-        void* sargs[] = {&s->blk_due, &s->blk_lev, &n, &s->blk_act, &s->blk_hdr, &s->blk_hdr_pub};
-        (void)hipLaunchKernel((const void*)&nb::nb_blk_sched<nb::kBlkSched>, dim3(1), dim3(nb::kBlkSched), sargs, 0, s->stream);
-        void* pargs[] = {&x, &v, &a, &j, &sn, &c, &s->blk_due, &s->blk_lev, &hx, &hv, &ha, &n, &s->blk_hdr, &Lk, &tick};
-        const void* pf = s->f64 ? (const void*)&nb::nb_blk6_predict<double> : (const void*)&nb::nb_blk6_predict<float>;
-        (void)hipLaunchKernel(pf, dim3(ceil_div(n, nb::kBlock)), dim3(nb::kBlock), pargs, 0, s->stream);
-    };
-    bool ahead = false;      // the first schedule + predict of this outer step went out behind the previous one's last corrector
-    for (uint32_t k = 0; k < nsteps; ++k) {
-        nb_events ev;
-        const bool rec = s->timing && get_events(s, &ev) == 0;
-        if (rec) NB_HIP(s, hipEventRecord(ev.e[0], s->stream));
-        if (!ahead) schedule_and_predict();
-        ahead = false;
-        for (;;) {
-            NB_HIP(s, hipStreamSynchronize(s->stream));
-            uint32_t na = s->blk_hdr_host[nb::kBlkCount], t_next = s->blk_hdr_host[nb::kBlkNext];
-            if (na == 0 || na > n || t_next == 0 || t_next > end)
-                return fail(s, NB_ERR_HIP, "nb_step: block schedule out of range (active " + std::to_string(na) + ", tick " + std::to_string(t_next) + ")");
-            uint32_t chunks = 1;
-            void *pa = nullptr, *pj = nullptr, *ps = nullptr;
-            launch_blk6_fjs(s, na, &chunks, &pa, &pj, &ps);
-            void* cargs[] = {&pa, &pj, &ps, &s->blk_act, &na, &chunks, &G, &x, &v, &a, &j, &sn, &c, &s->blk_due, &s->blk_lev, &s->blk_hdr, &t_next, &Lk, &lmin, &frozen, &eta, &dt};
-            const void* cf = s->f64 ? (const void*)&nb::nb_blk6_correct<double, double> : (const void*)&nb::nb_blk6_correct<float, float>;
-            (void)hipLaunchKernel(cf, dim3(ceil_div(na, nb::kBlock)), dim3(nb::kBlock), cargs, 0, s->stream);
+            pass_parts part;
+            launch_pass(s, o, h.pred, nullptr, na, &part);
+            kernel_args c;
+            c(part.plane, o.planes)(&s->blk_act)(&na)(&part.chunks)(&G)(h.state, o.states)(&s->blk_due)(&s->blk_lev)(&s->blk_hdr)(&t_next)(&Lk)(&lmin)(&frozen)(&eta)(&dt);
+            (void)hipLaunchKernel(o.blk_correct[s->f64], dim3(ceil_div(na, nb::kBlock)), dim3(nb::kBlock), c.v, 0, s->stream);
             ++s->blk_steps; s->blk_body_steps += na;
             if (t_next == end) break;
             schedule_and_predict();
@@ -1427,9 +1327,8 @@ int nb_create(const nb_config* cfg_in, nb_sim** out)
         // plain unpadded arrays, no planner: (x, v) at one instant, the derived (a, j), the predicted state and the bounded partials
         s->hermite = true;
         s->ac_two_calls = (cfg.flags & NB_FLAG_AC_TWO_CALLS) != 0;      // (the scheme exists on these handles only)
-        fj_shape(s->n, s->f64, n_cu, &s->fj_chunks, &s->fj_per);
-        s->jsplit = s->fj_chunks; s->j_per_split = s->fj_per;      // what nb_shape_info reports
-        s->variant = std::string("hermite4_") + (s->f64 ? "f64" : "f32pk") + "_c" + std::to_string(s->fj_chunks) + "_j" + std::to_string(s->fj_per);
+        set_chunks(s, kOrder4);
+        hermite_names(s);
         const size_t hrow = 4 * s->esz;
         NB_HIPC(hipMalloc(&s->bodies[0], hrow * s->n));
         s->own_bodies = true;
@@ -1644,7 +1543,7 @@ int nb_step(nb_sim* s, uint32_t nsteps)
     if (!s->params_set) return fail(s, NB_ERR_STATE, "nb_step: nb_set_params has not been called");
     if (!(s->dt > 0.0)) return NB_OK;   // `if (dt > 0)` gate, nbody3d.js:474
     NB_HIP(s, hipSetDevice(s->device));
-    if (s->hermite) return s->ac ? ac_step(s, nsteps) : s->blk ? (s->h6 ? block6_step(s, nsteps) : block_step(s, nsteps)) : s->h6 ? hermite6_step(s, nsteps) : hermite_step(s, nsteps);
+    if (s->hermite) return s->ac ? ac_step(s, nsteps) : s->blk ? block_step(s, nsteps) : hermite_step(s, nsteps);
     const bool exchange = s->xfn || s->rccl;
     ensure_pairs(s);      // the j-packed step's position copy, if something outside the step rewrote the positions or G
     if (gm_active(s) && !s->gm_ok) { if (int rc = finish_gather(s)) return rc; }
@@ -1833,7 +1732,7 @@ int nb_set_hermite_order(nb_sim* s, uint32_t order)
         hermite_names(s);
         return NB_OK;
     }
-    h6_shape(s->n, s->f64, s->n_cu, &s->h6_chunks, &s->h6_per);
+    set_chunks(s, kOrder6);
     const size_t rows = 4 * s->esz * s->n;
     hipError_t e = hipSuccess;
     for (void** p : {&s->snap, &s->crackle, &s->ha})
@@ -1865,7 +1764,7 @@ int nb_download_snap(nb_sim* s, void* snap, void* crackle)
     if (!s->h6) return fail(s, NB_ERR_STATE, "nb_download_snap: the handle's order is 4: snap and crackle exist at order 6 (nb_set_hermite_order)");
     if (!s->uploaded) return fail(s, NB_ERR_STATE, "nb_download_snap: nothing uploaded yet");
     NB_HIP(s, hipSetDevice(s->device));
-    if (int rc = ensure_derivs6(s, "nb_download_snap")) return rc;
+    if (int rc = ensure_start(s, "nb_download_snap")) return rc;
     NB_HIP(s, hipStreamSynchronize(s->stream));
     if (snap) NB_HIP(s, hipMemcpy(snap, s->snap, 4 * s->esz * s->n, hipMemcpyDeviceToHost));
     if (crackle) NB_HIP(s, hipMemcpy(crackle, s->crackle, 4 * s->esz * s->n, hipMemcpyDeviceToHost));
@@ -2498,10 +2397,9 @@ int nb_force_pass(nb_sim* s, uint32_t reps, double* avg_ms)
     if (int rc = ensure_gm(s)) return rc;
     if (int rc = ensure_eqm(s)) return rc;
     if (s->hermite && !s->params_set) return fail(s, NB_ERR_STATE, "nb_force_pass: nb_set_params has not been called (G)");
-    if (s->h6) { if (int rc = ensure_derivs6(s, "nb_force_pass")) return rc; }      // the pass streams the accelerations: they are made current, the state is untouched
+    if (s->h6) { if (int rc = ensure_start(s, "nb_force_pass")) return rc; }      // the pass streams the accelerations: they are made current, the state is untouched
     auto once = [&]() -> int {
-        if (s->h6) { launch_h6(s, s->bodies[0], s->vel, s->acc, s->hx, s->hv, s->ha); return NB_OK; }      // into the step's scratch
-        if (s->hermite) { launch_fj(s, s->bodies[0], s->vel, s->hx, s->hv); return NB_OK; }      // into the step's scratch: state and derivatives untouched
+        if (s->hermite) { hermite_arrays h(s); launch_pass(s, order_of(s), h.state, h.pred); return NB_OK; }      // the order's pass into the step's scratch: state and derivatives untouched
         if (s->sym_rank) return s->f64 ? nbi::sym_rank_phase_a_t<double>(s, nullptr, false) : nbi::sym_rank_phase_a_t<float>(s, nullptr, false);
         if (s->f64) launch_force<double>(s); else launch_force<float>(s);
         return NB_OK;
