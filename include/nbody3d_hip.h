@@ -78,7 +78,9 @@ extern "C" {
                              2.4 (round 20) likewise within 2.4: nb_set_hermite_order, nb_hermite_order, nb_download_snap, nb_upload_derivs6.
                                             Detected by the presence of the symbol nb_set_hermite_order
                              2.4 (round 21) likewise within 2.4: nb_set_block_steps6.  Detected by the presence of the symbol
-                                            nb_set_block_steps6 */
+                                            nb_set_block_steps6
+                             2.4 (round 22) likewise within 2.4: nb_set_start6, nb_start6, NB_START6_*.  Detected by the presence of the
+                                            symbol nb_set_start6 */
 
 typedef struct nb_sim nb_sim; /* opaque */
 
@@ -1286,10 +1288,40 @@ int nb_upload_derivs6(nb_sim *s, const void *accel, const void *jerk, const void
  *     levels; stale levels are made by the start rule at the next nb_step or nb_download_levels.
  *   - Errors: a NULL handle is NB_ERR_INVALID; an order-4 or leapfrog handle is NB_ERR_STATE with a message that names
  *     nb_set_hermite_order; the argument checks are those of nb_set_block_steps, the message naming nb_set_block_steps6 and the field.
- *   - The start rule is order 4's and the first step runs with c = 0: on systems with hard pairs the first outer step makes most of a
- *     run's energy error (profiles/r21/block6.md).  A host that cares downloads the start levels, adds two and uploads them.
- *   - Not built: a start rule of its own; the neighbour scheme on order-6 handles; block steps without the host wait per block step. */
+ *   - By default the start rule is order 4's and the first step runs with c = 0: on systems with hard pairs the first outer step
+ *     makes most of a run's energy error (profiles/r21/block6.md).  nb_set_start6(s, NB_START6_CRACKLE) below is the start of its own.
+ *   - Not built: the neighbour scheme on order-6 handles; block steps without the host wait per block step. */
 int nb_set_block_steps6(nb_sim *s, const nb_block_steps *cfg /* NULL: back to the shared order-6 step */);
+
+/* ---- the start of an order-6 handle: exact crackle, two-rule levels (no reference analogue) ----------------
+ * nb_set_start6 chooses how the engine makes the starts of an order-6 handle ITSELF: after nb_upload, after a changed G, wherever the
+ * start of "the 6th-order scheme" above runs.  A handle that never calls it starts as before (NB_START6_ZERO), bit for bit.
+ *   - NB_START6_CRACKLE: a, j and s are made as before (the same bits); c is the direct sum of the pair crackles on (x, v, a, j).
+ *     Per pair, with dj = j_j - j_i and y^2 = 1 / rho^2 next to the dr, dv, da, s3, alpha, beta, t of the snap:
+ *         alpha = (dr.dv) y^2
+ *         beta  = (dv.dv + dr.da) y^2 + alpha^2
+ *         gamma = (3 dv.da + dr.dj) y^2 + alpha (3 beta - 4 alpha^2)
+ *         t = dv - 3 alpha dr
+ *         q = da - 6 alpha t - 3 beta dr
+ *         w = dj - 9 alpha q - 9 beta t - 3 gamma dr
+ *         c_i = G sum_j m_j y^3 w
+ *     Each of the three components is ONE sum s3 (...); no self mask (for j = i the term is exactly 0); a row past the range adds
+ *     nothing; G multiplies each row once in fp64; chunks and the two-level binary32 sums of f32 handles are the snap pass's.
+ *   - The two-rule start of nb_set_block_steps6 (dynamic levels, NB_F64 handles) at NB_START6_CRACKLE, in fp64 on the values as stored:
+ *         l_i = max(level_for((eta / 2) |a| / |j|), level_for(sqrt(eta (|a| |s| + |j|^2) / (|j| |c| + |s|^2))))
+ *     A rule whose denominator is 0 votes min_level.  A body counts once in `clamped` if either rule found no level.  Frozen handles
+ *     and uploaded levels are untouched by the mode.
+ *   - A start that arrived through nb_upload_derivs6 is kept as uploaded.  The setter drops a start the engine made itself that no step
+ *     has consumed yet (nb_download_snap, the setter, nb_download_snap shows the new c), and levels the engine chose itself that no block
+ *     step has consumed; uploaded levels stay.  On a handle that has stepped the setter changes nothing about the running state: the run
+ *     continues bit for bit as a twin without the call; the mode governs the next start.
+ *   - nb_set_hermite_order(s, 4) returns the mode to NB_START6_ZERO.  f32 and f64 handles both take it.
+ *   - Errors: a NULL handle and an unknown mode are NB_ERR_INVALID; a leapfrog handle or an order-4 handle is NB_ERR_STATE.
+ *   - Not built: an iterated start; a start rule for order-4 handles; dynamic order-6 levels on f32 handles. */
+#define NB_START6_ZERO    0u   /* today's start: snap from the pass, c = 0, block levels from (eta / 2)|a|/|j| */
+#define NB_START6_CRACKLE 1u   /* c = the direct sum above; dynamic block levels from the two-rule start */
+int nb_set_start6(nb_sim *s, uint32_t mode);
+int nb_start6(nb_sim *s, uint32_t *mode);
 
 #if defined(__GNUC__)
 #pragma GCC visibility pop

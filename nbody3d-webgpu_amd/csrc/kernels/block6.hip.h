@@ -2,7 +2,8 @@
 // production setup of phi-GPU).  No reference analogue.  Part of nb_kernels.hip.h (include that, not this file).
 //
 // The scheme of kernels/block.hip.h -- ticks, levels, due_i, the active list, the header, nb_blk_sched and nb_blk_start are that
-// file's, unchanged -- with the order-6 state (x, v, a, j, s, c) per body.  One block step, with the launches the host makes of it:
+// file's, unchanged; nb_blk6_start is the two-rule start of nb_set_start6 -- with the order-6 state (x, v, a, j, s, c) per body.
+// One block step, with the launches the host makes of it:
 //   nb_blk_sched        as for order 4
 //   nb_blk6_predict     every body from its own state over (t_next - t_i) ticks into xp, vp, ap (nb_h6_predict's polynomials)
 //   (the host reads the header: |A| sizes the next launches)
@@ -14,6 +15,38 @@
 #pragma once
 
 namespace nb {
+
+// nb_blk_start with the two-rule start of nb_set_start6(NB_START6_CRACKLE), on the stored (a, j, s, c) in fp64.  Mode 0:
+//   l_i = max(level_for((eta / 2) |a| / |j|), level_for(sqrt(eta (|a| |s| + |j|^2) / (|j| |c| + |s|^2))))
+// a rule whose denominator is 0 votes lmin; a body counts ONCE as clamped when either rule found no level.  Modes 1 (frozen) and 2
+// (uploaded levels) are nb_blk_start's.  Every mode starts the outer step's clock: due_i = s_i.
+template <typename T>
+__global__ __launch_bounds__(kBlock) void nb_blk6_start(const typename vec4<T>::type* __restrict__ a,
+                                                       const typename vec4<T>::type* __restrict__ j,
+                                                       const typename vec4<T>::type* __restrict__ s,
+                                                       const typename vec4<T>::type* __restrict__ c, uint8_t* __restrict__ lev,
+                                                       uint32_t* __restrict__ due, uint32_t* __restrict__ hdr, uint32_t n, int mode,
+                                                       double eta, double dt, uint32_t lmin, uint32_t L)
+{
+    const uint32_t il = blockIdx.x * kBlock + threadIdx.x;
+    if (il >= n) return;
+    uint32_t l = lmin;
+    if (mode == 2) l = lev[il];
+    else if (mode == 0) {
+        const auto A = ld4(a + il), J = ld4(j + il), S = ld4(s + il), C = ld4(c + il);
+        auto nrm = [](double p, double q, double r) { return __builtin_sqrt(p * p + q * q + r * r); };
+        const double aa = nrm(A.x, A.y, A.z), jj = nrm(J.x, J.y, J.z), ss = nrm(S.x, S.y, S.z), cc = nrm(C.x, C.y, C.z);
+        uint32_t clamped = 0, l1 = lmin, l2 = lmin;
+        if (jj > 0.0) l1 = lv_level_for(0.5 * eta * aa / jj, dt, lmin, L, &clamped);
+        const double den = jj * cc + ss * ss;
+        if (den > 0.0) l2 = lv_level_for(__builtin_sqrt(eta * (aa * ss + jj * jj) / den), dt, lmin, L, &clamped);
+        l = l1 > l2 ? l1 : l2;
+        if (clamped) atomicAdd(hdr + kBlkClamped, 1u);
+    }
+    lev[il] = (uint8_t)l;
+    due[il] = 1u << (L - l);
+    atomicMax(hdr + kBlkFinest, l);
+}
 
 // nb_h6_predict with a step of the body's own: h_i = (t_next - t_i) ticks, t_i = due_i - s_i.  Always from the stored state, never
 // from an earlier prediction.  t_next is read from the device header: the launch follows nb_blk_sched without the host in between.

@@ -638,6 +638,7 @@ void chunk_shape(uint32_t n, uint32_t rows, int n_cu, uint32_t* chunks, uint32_t
 struct hermite_order {
     const char* name;                 // the head of nb_variant_name
     uint32_t planes;                  // derivative planes of a pass, and predicted arrays: (a, j) | (a, j, s) and (xp, vp) | (xp, vp, ap)
+    uint32_t inputs;                  // arrays a pass reads: (x, v) | (x, v, a); the crackle pass of a start: (x, v, a, j) into one plane
     uint32_t states;                  // arrays the predictor and the corrector take: (x, v, a, j) | (x, v, a, j, s, c)
     uint32_t rows[2];                 // i-bodies of one workgroup of the full pass
     uint32_t gather_rows[2];          // ... and of the gathered pass; f32: the NG = 2 kernel's, the NG = 1 kernel takes half of them
@@ -650,7 +651,7 @@ struct hermite_order {
 
 #define NB_BOTH(K) {(const void*)&nb::K<float>, (const void*)&nb::K<double>}
 const hermite_order kOrder4 = {
-    "hermite4_", 2, 4, {nb::kFjRows, nb::kFjRows64}, {nb::kFjRows, nb::kFjRows64},
+    "hermite4_", 2, 2, 4, {nb::kFjRows, nb::kFjRows64}, {nb::kFjRows, nb::kFjRows64},
     {(const void*)&nb::nb_fj_pk<nb::kFjNG>, (const void*)&nb::nb_fj64<double>},
     {(const void*)&nb::nb_fj_reduce<float, float>, (const void*)&nb::nb_fj_reduce<double, double>},
     {(const void*)&nb::nb_blk_fj_pk<2>, (const void*)&nb::nb_blk_fj64<double>}, (const void*)&nb::nb_blk_fj_pk<1>,
@@ -658,12 +659,19 @@ const hermite_order kOrder4 = {
     {(const void*)&nb::nb_blk_correct<float, float>, (const void*)&nb::nb_blk_correct<double, double>},
     &nb_sim::fj_part, &nb_sim::fj_chunks, &nb_sim::fj_per};
 const hermite_order kOrder6 = {
-    "hermite6_", 3, 6, {nb::kH6Rows, nb::kH6Rows64}, {nb::kBlock * 4, nb::kH6Rows64},      // (the gathered kernels are NG = 2 and 1 whatever NB_H6_NG the full pass is built with)
+    "hermite6_", 3, 3, 6, {nb::kH6Rows, nb::kH6Rows64}, {nb::kBlock * 4, nb::kH6Rows64},      // (the gathered kernels are NG = 2 and 1 whatever NB_H6_NG the full pass is built with)
     {(const void*)&nb::nb_h6_fjs_pk<nb::kH6NG>, (const void*)&nb::nb_h6_fjs64<double>},
     NB_BOTH(nb_h6_reduce),
     {(const void*)&nb::nb_blk6_fjs_pk<2>, (const void*)&nb::nb_blk6_fjs64<double>}, (const void*)&nb::nb_blk6_fjs_pk<1>,
     NB_BOTH(nb_h6_predict), NB_BOTH(nb_h6_correct), NB_BOTH(nb_blk6_predict),
     {(const void*)&nb::nb_blk6_correct<float, float>, (const void*)&nb::nb_blk6_correct<double, double>},
+    &nb_sim::h6_part, &nb_sim::h6_chunks, &nb_sim::h6_per};
+// The crackle pass of an order-6 start (nb_set_start6): a full pass only, in the order-6 pass's j-chunks and partial rows.
+const hermite_order kStart6 = {
+    "hermite6_", 1, 4, 6, {nb::kH6CrkRows, nb::kH6Rows64}, {0, 0},
+    {(const void*)&nb::nb_h6_crk_pk<nb::kH6CrkNG>, (const void*)&nb::nb_h6_crk64<double>},
+    NB_BOTH(nb_h6_reduce1),
+    {nullptr, nullptr}, nullptr, {nullptr, nullptr}, {nullptr, nullptr}, {nullptr, nullptr}, {nullptr, nullptr},
     &nb_sim::h6_part, &nb_sim::h6_chunks, &nb_sim::h6_per};
 #undef NB_BOTH
 
@@ -705,7 +713,7 @@ pass_shape gathered_shape(uint32_t n, uint32_t na, uint32_t rows, bool f64, uint
 // What a gathered pass hands to the corrector: its j-chunks and where each plane of partial sums starts.
 struct pass_parts { uint32_t chunks; void* plane[3]; };
 
-// One O(N^2) pass of order `o` on the state in[0 .. o.planes) = (pos, vel[, acc]) into the order's partial sums.
+// One O(N^2) pass of order `o` on the state in[0 .. o.inputs) = (pos, vel[, acc[, jerk]]) into the order's partial sums.
 //   na == 0  the full pass with the handle's stored j-chunks, then the fp64 reduce into out[0 .. o.planes) (order 6: out[0] and
 //            out[1] null together: the snap alone);
 //   na > 0   the gathered pass of one block step over the rows blk_act[0 .. na), in gathered_shape's shape; no reduce: the block
@@ -727,7 +735,7 @@ void launch_pass(nb_sim* s, const hermite_order& o, void** in, void** out, uint3
     float e2f = (float)s->eps2;
     const void* zr = s->zero_row;
     kernel_args a;
-    a(in, o.planes);
+    a(in, o.inputs);
     if (na) a(&s->blk_act)(&na);
     a(part.plane, o.planes)(&n)(&sh.per);
     if (s->f64) a(&e2); else a(&e2f)(&zr);
@@ -758,6 +766,7 @@ int ensure_derivs(nb_sim* s, const char* who)
 
 // The start of a step of the handle's order (a no-op while everything is current): ensure_derivs, and at order 6 the snap from the
 // force+jerk+snap pass on (x, v, a) and crackle = 0 -- so an order-6 handle starts from the (a, j) bits an order-4 handle holds.
+// With nb_set_start6(NB_START6_CRACKLE) the crackle is the direct sum on (x, v, a, j) instead; a, j and s are the same bits.
 int ensure_start(nb_sim* s, const char* who)
 {
     const bool snap_current = s->snap_ok && s->derivs_ok && (s->derivs_any_G || s->derivs_G == s->G);
@@ -765,9 +774,14 @@ int ensure_start(nb_sim* s, const char* who)
     if (!s->h6 || snap_current) return NB_OK;
     void *in[] = {s->bodies[0], s->vel, s->acc}, *out[] = {nullptr, nullptr, s->snap};
     launch_pass(s, kOrder6, in, out);
-    NB_HIP(s, hipMemsetAsync(s->crackle, 0, 4 * s->esz * s->n, s->stream));
+    if (s->start6 == NB_START6_CRACKLE) {
+        void *in4[] = {s->bodies[0], s->vel, s->acc, s->jerk}, *out1[] = {s->crackle};
+        launch_pass(s, kStart6, in4, out1);
+    } else {
+        NB_HIP(s, hipMemsetAsync(s->crackle, 0, 4 * s->esz * s->n, s->stream));
+    }
     NB_HIP(s, hipGetLastError());
-    s->snap_ok = true;
+    s->snap_ok = true; s->start_own = true;
     return NB_OK;
 }
 
@@ -801,6 +815,7 @@ int hermite_step(nb_sim* s, uint32_t nsteps)
         if (rec) { NB_HIP(s, hipEventRecord(ev.e[2], s->stream)); s->pending.push_back(ev); }
         NB_HIP(s, hipGetLastError());
         ++s->steps_done;
+        s->start_own = false;      // consumed: the state is a running one (nb_set_start6 leaves it alone)
     }
     return NB_OK;
 }
@@ -808,7 +823,7 @@ int hermite_step(nb_sim* s, uint32_t nsteps)
 void h6_release(nb_sim* s)
 {
     for (void** p : {&s->snap, &s->crackle, &s->ha, &s->h6_part}) { if (*p) (void)hipFree(*p); *p = nullptr; }
-    s->h6 = false; s->snap_ok = false;
+    s->h6 = false; s->snap_ok = false; s->start_own = false; s->start6 = NB_START6_ZERO;
 }
 
 // what nb_variant_name and nb_shape_info report: the pass a step of the handle runs
@@ -825,15 +840,20 @@ void hermite_names(nb_sim* s)
 // are kept), and the clock of the outer step at 0.
 int ensure_levels(nb_sim* s, const char* who)
 {
-    if (int rc = ensure_start(s, who)) return rc;      // also: a changed G re-evaluates them (order 6: its start, c = 0)
+    if (int rc = ensure_start(s, who)) return rc;      // also: a changed G re-evaluates them (order 6: its start, c = 0 or the direct sum)
     if (s->levels == 2) return NB_OK;
+    s->levels_own = s->levels == 0;
     void *a = s->acc, *j = s->jerk;
     uint32_t n = s->n, lmin = s->blk_lmin, L = s->blk_L;
     int mode = s->levels == 1 ? 2 : s->blk_frozen ? 1 : 0;
     double eta = s->blk_eta, dt = s->dt;
     void* args[] = {&a, &j, &s->blk_lev, &s->blk_due, &s->blk_hdr, &n, &mode, &eta, &dt, &lmin, &L};
     const void* fn = s->f64 ? (const void*)&nb::nb_blk_start<double> : (const void*)&nb::nb_blk_start<float>;
-    (void)hipLaunchKernel(fn, dim3(ceil_div(n, nb::kBlock)), dim3(nb::kBlock), args, 0, s->stream);
+    if (s->h6 && mode == 0 && s->start6 == NB_START6_CRACKLE) {      // the two-rule start on (a, j, s, c); dynamic levels of order 6 are f64 handles
+        void* args6[] = {&a, &j, &s->snap, &s->crackle, &s->blk_lev, &s->blk_due, &s->blk_hdr, &n, &mode, &eta, &dt, &lmin, &L};
+        (void)hipLaunchKernel((const void*)&nb::nb_blk6_start<double>, dim3(ceil_div(n, nb::kBlock)), dim3(nb::kBlock), args6, 0, s->stream);
+    } else
+        (void)hipLaunchKernel(fn, dim3(ceil_div(n, nb::kBlock)), dim3(nb::kBlock), args, 0, s->stream);
     NB_HIP(s, hipGetLastError());
     s->levels = 2;
     return NB_OK;
@@ -885,6 +905,7 @@ int block_step(nb_sim* s, uint32_t nsteps)
         NB_HIP(s, hipGetLastError());
         ++s->blk_outer;
         ++s->steps_done;
+        s->start_own = s->levels_own = false;      // consumed: state and levels are running ones (nb_set_start6 leaves them alone)
     }
     return NB_OK;
 }
@@ -1788,7 +1809,32 @@ int nb_upload_derivs6(nb_sim* s, const void* accel, const void* jerk, const void
     s->derivs_ok = true;
     s->derivs_any_G = !s->params_set;
     s->derivs_G = s->G;
-    s->snap_ok = true;
+    s->snap_ok = true; s->start_own = false;
+    return NB_OK;
+}
+
+int nb_set_start6(nb_sim* s, uint32_t mode)
+{
+    if (!s) return fail(nullptr, NB_ERR_INVALID, "nb_set_start6: null handle");
+    if (mode != NB_START6_ZERO && mode != NB_START6_CRACKLE) return fail(s, NB_ERR_INVALID, "nb_set_start6: mode must be NB_START6_ZERO or NB_START6_CRACKLE");
+    if (!s->hermite) return fail(s, NB_ERR_STATE, "nb_set_start6: needs a Hermite handle (nb_config.integrator = NB_INT_HERMITE4) of order 6 (nb_set_hermite_order)");
+    if (!s->h6) return fail(s, NB_ERR_STATE, "nb_set_start6: the handle's order is 4 (nb_set_hermite_order): the start of an order-4 handle has no modes");
+    if (mode == s->start6) return NB_OK;
+    s->start6 = mode;
+    // a start and levels the engine made itself and no step has consumed are made again in the new mode; an uploaded start, uploaded
+    // levels and a running state stay as they are
+    if (s->snap_ok && s->start_own) s->snap_ok = false;
+    if (s->levels == 2 && s->levels_own) s->levels = 0;
+    return NB_OK;
+}
+
+int nb_start6(nb_sim* s, uint32_t* mode)
+{
+    if (!s) return fail(nullptr, NB_ERR_INVALID, "nb_start6: null handle");
+    if (!mode) return fail(s, NB_ERR_INVALID, "nb_start6: mode is NULL");
+    if (!s->hermite) return fail(s, NB_ERR_STATE, "nb_start6: needs a Hermite handle (nb_config.integrator = NB_INT_HERMITE4) of order 6 (nb_set_hermite_order)");
+    if (!s->h6) return fail(s, NB_ERR_STATE, "nb_start6: the handle's order is 4 (nb_set_hermite_order): the start of an order-4 handle has no modes");
+    *mode = s->start6;
     return NB_OK;
 }
 

@@ -182,6 +182,8 @@ struct nb_sim {
     uint32_t h6_chunks = 1, h6_per = 0;   // the force+jerk+snap pass's j-chunks and bodies per chunk
     bool snap_ok = false;          // snap / crackle belong to the current acc / jerk (which derivs_ok and derivs_G speak for); cleared by
                                    // ensure_derivs whenever it re-evaluates acc / jerk, set by the start and by nb_upload_derivs6
+    uint32_t start6 = 0;           // nb_set_start6: NB_START6_ZERO | NB_START6_CRACKLE, what the engine's own starts (and start levels) are made by
+    bool start_own = false;        // snap / crackle came from the engine's start and no step has consumed them (nb_set_start6 may drop them)
     // nb_set_block_steps: block individual time steps (kernels/block.hip.h).  Allocated when first switched on.
     bool blk = false, blk_frozen = false;
     uint32_t blk_L = 20, blk_lmin = 0;
@@ -194,6 +196,7 @@ struct nb_sim {
     uint32_t* blk_hdr_pub = nullptr;    // the device's address of blk_hdr_host: nb_blk_sched stores into it
     int levels = 0;                  // 0: stale; 1: blk_lev came from nb_upload_levels, the outer step's clock (blk_due) is not started yet;
                                      // 2: blk_lev / blk_due belong to the state, dt, G and the configuration
+    bool levels_own = false;         // levels == 2 by the engine's own start rule, no block step since (nb_set_start6 may drop them)
     uint64_t blk_outer = 0, blk_steps = 0, blk_body_steps = 0;
     // nb_set_neighbor_scheme: the Ahmad-Cohen neighbour scheme with two shared step levels (kernels/ac_scheme.hip.h).  Allocated
     // by the call, released by NULL or nb_destroy.  While it is on, acc / jerk hold the totals ai + ar0, ji + jr0.

@@ -71,5 +71,5 @@
 #include "kernels/block.hip.h"       // nb_blk_start, nb_blk_sched, nb_blk_predict, nb_blk_fj_pk, nb_blk_fj64, nb_blk_correct (nb_set_block_steps)
 #include "kernels/ac_scheme.hip.h"   // nb_ac_sub32, nb_ac_sub64, nb_ac_predict0, nb_ac_regular, nb_ac_start (nb_set_neighbor_scheme: the Ahmad-Cohen neighbour scheme)
 #include "kernels/ac_levels.hip.h"   // nb_ac_lv_start, nb_ac_lv_begin, nb_ac_lv_sub32, nb_ac_lv_sub64 (nb_set_neighbor_levels: block individual irregular steps)
-#include "kernels/hermite6.hip.h"    // nb_h6_fjs_pk, nb_h6_fjs64, nb_h6_reduce, nb_h6_predict, nb_h6_correct (nb_set_hermite_order(6): force, jerk and snap)
-#include "kernels/block6.hip.h"      // nb_blk6_predict, nb_blk6_fjs_pk, nb_blk6_fjs64, nb_blk6_correct (nb_set_block_steps6: block steps on order-6 handles)
+#include "kernels/hermite6.hip.h"    // nb_h6_fjs_pk, nb_h6_fjs64, nb_h6_reduce, nb_h6_predict, nb_h6_correct (nb_set_hermite_order(6): force, jerk and snap); nb_h6_crk_pk, nb_h6_crk64, nb_h6_reduce1 (nb_set_start6: the crackle of a start)
+#include "kernels/block6.hip.h"      // nb_blk6_start, nb_blk6_predict, nb_blk6_fjs_pk, nb_blk6_fjs64, nb_blk6_correct (nb_set_block_steps6: block steps on order-6 handles)

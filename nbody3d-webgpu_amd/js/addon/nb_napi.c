@@ -66,6 +66,8 @@ static int (*p_hermite_order)(nb_sim *, uint32_t *);
 static int (*p_download_snap)(nb_sim *, void *, void *);
 static int (*p_upload_derivs6)(nb_sim *, const void *, const void *, const void *, const void *);
 static int (*p_set_block_steps6)(nb_sim *, const nb_block_steps *);     /* block steps on order-6 handles (round 21): optional */
+static int (*p_set_start6)(nb_sim *, uint32_t);                         /* the start mode of order-6 handles (round 22): optional */
+static int (*p_start6)(nb_sim *, uint32_t *);
 static int (*p_set_block_steps)(nb_sim *, const nb_block_steps *);      /* block time steps, also within ABI 2.4: optional symbols */
 static int (*p_block_stats)(nb_sim *, struct nb_block_stats *, int);
 static int (*p_download_levels)(nb_sim *, uint8_t *);
@@ -182,6 +184,8 @@ static napi_value js_load(napi_env env, napi_callback_info info)
         *(void **)(&p_upload_derivs6) = dlsym(h, "nb_upload_derivs6");
         *(void **)(&p_set_block_steps) = dlsym(h, "nb_set_block_steps");
         *(void **)(&p_set_block_steps6) = dlsym(h, "nb_set_block_steps6");
+        *(void **)(&p_set_start6) = dlsym(h, "nb_set_start6");
+        *(void **)(&p_start6) = dlsym(h, "nb_start6");
         *(void **)(&p_block_stats) = dlsym(h, "nb_block_stats");
         *(void **)(&p_download_levels) = dlsym(h, "nb_download_levels");
         *(void **)(&p_upload_levels) = dlsym(h, "nb_upload_levels");
@@ -1144,6 +1148,35 @@ static napi_value js_hermite_order(napi_env env, napi_callback_info info)
     return out;
 }
 
+/* setStart6(handle, mode): nb_set_start6 -- NB_START6_ZERO (0) or NB_START6_CRACKLE (1). */
+static napi_value js_set_start6(napi_env env, napi_callback_info info)
+{
+    size_t argc = 2; napi_value argv[2];
+    CHECK_NAPI(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    if (argc < 2) { napi_throw_type_error(env, NULL, "setStart6(handle, mode)"); return NULL; }
+    handle_t *h = order_handle(env, argv[0], (const void *)p_set_start6, "nb_set_start6"); if (!h) return NULL;
+    uint32_t mode = 0;
+    CHECK_NAPI(env, napi_get_value_uint32(env, argv[1], &mode));
+    int rc = p_set_start6(h->sim, mode);
+    if (rc != NB_OK) return throw_nb(env, rc, h->sim, "nb_set_start6");
+    return undefined(env);
+}
+
+/* start6(handle) -> 0 or 1: nb_start6. */
+static napi_value js_start6(napi_env env, napi_callback_info info)
+{
+    size_t argc = 1; napi_value argv[1];
+    CHECK_NAPI(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    if (argc < 1) { napi_throw_type_error(env, NULL, "start6(handle)"); return NULL; }
+    handle_t *h = order_handle(env, argv[0], (const void *)p_start6, "nb_start6"); if (!h) return NULL;
+    uint32_t mode = 0;
+    int rc = p_start6(h->sim, &mode);
+    if (rc != NB_OK) return throw_nb(env, rc, h->sim, "nb_start6");
+    napi_value out;
+    CHECK_NAPI(env, napi_create_uint32(env, mode, &out));
+    return out;
+}
+
 /* downloadSnap(handle, snapOut, crackleOut): nb_download_snap -- 4*n elements each, written in place; either may be null. */
 static napi_value js_download_snap(napi_env env, napi_callback_info info)
 {
@@ -1556,6 +1589,7 @@ static napi_value init_module(napi_env env, napi_value exports)
         {"collectiveInfo", js_collective_info}, {"requestFrame", js_request_frame}, {"frame", js_frame}, {"planQuery", js_plan_query},
         {"fieldEval", js_field_eval}, {"downloadJerk", js_download_jerk}, {"uploadDerivs", js_upload_derivs},
         {"setHermiteOrder", js_set_hermite_order}, {"hermiteOrder", js_hermite_order}, {"downloadSnap", js_download_snap}, {"uploadDerivs6", js_upload_derivs6},
+        {"setStart6", js_set_start6}, {"start6", js_start6},
         {"setBlockSteps", js_set_block_steps}, {"setBlockSteps6", js_set_block_steps6}, {"blockStats", js_block_stats}, {"downloadLevels", js_download_levels},
         {"uploadLevels", js_upload_levels}, {"neighbors", js_neighbors}, {"neighborLists", js_neighbor_lists},
         {"knn", js_knn}, {"listForce", js_list_force}, {"splitForce", js_split_force}, {"splitLists", js_split_lists}, {"neighborSchemeFused", js_neighbor_scheme_fused},

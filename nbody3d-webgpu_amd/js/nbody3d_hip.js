@@ -225,6 +225,22 @@ class Simulation {
     return this;
   }
 
+  /** How the engine makes the starts of an order-6 simulation itself (nb_set_start6; no reference analogue): 0 -- snap from the
+   *  pass, crackle 0, block levels from (eta / 2)|a|/|j|; 1 -- the crackle is the direct sum on (x, v, a, j) and dynamic block
+   *  levels come from the two-rule start.  A start or levels the engine made that no step has consumed are made again; uploaded
+   *  ones and a running state are kept. */
+  setStart6(mode) {
+    this._need();
+    addon.setStart6(this._h, mode >>> 0);
+    return this;
+  }
+
+  /** 0 or 1 (nb_start6). */
+  get start6() {
+    this._need();
+    return addon.start6(this._h);
+  }
+
   /** Block individual time steps of a 'hermite4' simulation (nb_set_block_steps; no reference analogue): every body steps by
    *  dt / 2^level, minLevel <= level <= maxLevel, chosen from its own derivatives with the accuracy parameter eta; step() and
    *  simulate() still advance by whole dt.  {eta, maxLevel, minLevel, frozen}: missing eta / maxLevel take the library's defaults

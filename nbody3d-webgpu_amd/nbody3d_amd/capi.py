@@ -201,7 +201,9 @@ SYMBOLS = ["nb_abi_version", "nb_device_count", "nb_create", "nb_destroy", "nb_u
            "nb_set_neighbor_adapt", "nb_neighbor_adapt_stats", "nb_download_neighbor_radii", "nb_upload_neighbor_scheme",
            "nb_set_neighbor_levels", "nb_neighbor_level_stats", "nb_download_neighbor_levels", "nb_upload_neighbor_levels",
            "nb_set_hermite_order", "nb_hermite_order", "nb_download_snap", "nb_upload_derivs6",
-           "nb_set_block_steps6"]
+           "nb_set_block_steps6", "nb_set_start6", "nb_start6"]
+
+START6_ZERO, START6_CRACKLE = 0, 1      # nb_set_start6
 
 _lib = None
 
@@ -327,6 +329,9 @@ def load_library():
         L.nb_upload_derivs6.argtypes = [vp, vp, vp, vp, vp]
     if hasattr(L, "nb_set_block_steps6"):       # block steps on order-6 handles, likewise
         L.nb_set_block_steps6.argtypes = [vp, C.POINTER(nb_block_steps)]
+    if hasattr(L, "nb_set_start6"):             # the start mode of order-6 handles, likewise
+        L.nb_set_start6.argtypes = [vp, C.c_uint32]
+        L.nb_start6.argtypes = [vp, C.POINTER(C.c_uint32)]
     if hasattr(L, "nb_eqm_info"):           # the equal-mass kernels' report, also within 2.4 and detected by the symbol
         L.nb_eqm_info.argtypes = [vp, C.POINTER(C.c_int)]
     if hasattr(L, "nb_eqm_form"):           # which of the equal-mass forms, likewise
@@ -917,6 +922,25 @@ class Simulation:
         a, j, s, c = self._arr(accel, "accel"), self._arr(jerk, "jerk"), self._arr(snap, "snap"), self._arr(crackle, "crackle")
         self._check(self._L.nb_upload_derivs6(self._h, _ptr(a), _ptr(j), _ptr(s), _ptr(c)))
         return self
+
+    def set_start6(self, mode):
+        """nb_set_start6: how the engine makes the starts of an order-6 handle itself.  START6_ZERO (0): snap from the pass, crackle
+        0, block levels from (eta / 2)|a|/|j|; START6_CRACKLE (1): the crackle is the direct sum on (x, v, a, j) and dynamic block
+        levels come from the two-rule start.  A start or levels the engine made that no step has consumed are made again; uploaded
+        ones and a running state are kept."""
+        if not hasattr(self._L, "nb_set_start6"):
+            raise NBodyError(1, "set_start6(): the loaded library has no nb_set_start6")
+        self._check(self._L.nb_set_start6(self._h, int(mode)))
+        return self
+
+    @property
+    def start6(self):
+        """nb_start6: START6_ZERO or START6_CRACKLE."""
+        if not hasattr(self._L, "nb_start6"):
+            raise NBodyError(1, "start6: the loaded library has no nb_start6")
+        m = C.c_uint32()
+        self._check(self._L.nb_start6(self._h, C.byref(m)))
+        return int(m.value)
 
     # -- block individual time steps of a Hermite handle -----------------------
     def _need_block(self, what):

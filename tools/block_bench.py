@@ -11,7 +11,8 @@ every counterpart below then an order-6 handle too) on one GPU and prints ONE JS
                --outer-dt), |dE/E0| from nb_diagnostics, body_steps, block_steps and the level histogram; then shared-step Hermite at
                dt = 2^-k, k rising from --shared-from until its |dE/E0| is no worse (at most --shared-to: past that the run is recorded as
                not reached), with each run's wall time (--shared-to below --shared-from: no shared runs).  --eta sets the block steps' accuracy
-               parameter, --start-deeper K uploads the start rule's levels K deeper before the run.  --pair-half / --eps2 make the pairs hard (e.g. 0.001 and 1e-8: a period of ~0.1
+               parameter, --start-deeper K uploads the start rule's levels K deeper before the run, --start6 (order 6) switches the block handle
+               to set_start6(1): the exact crackle and the two-rule start levels; dE_first is |dE/E0| after the first outer step.  --pair-half / --eps2 make the pairs hard (e.g. 0.001 and 1e-8: a period of ~0.1
                time units at N = 16,384 instead of ~4.5), the case the step hierarchy is for
   (c) small    microseconds per block step with |A| = 64 at N = --full-n: frozen levels, 64 bodies at level 6 and the rest at level 0
                (64 block steps per outer step, 63 of them with |A| = 64) minus the same outer step with every body at level 0, over 63
@@ -104,9 +105,11 @@ def part_b(args, out):
         b, v = with_tight_pairs(n, half=args.pair_half)
         outer = int(round(1.0 / args.outer_dt))
         r = {"n": n, "pairs": int(0.01 * n) // 2, "precision": args.precision, "outer_dt": args.outer_dt, "eta": args.eta, "order": ORDER,
-             "start_deeper": args.start_deeper, "pair_half": args.pair_half, "eps2": args.eps2}
+             "start_deeper": args.start_deeper, "start6": int(args.start6), "pair_half": args.pair_half, "eps2": args.eps2}
         with hermite(n, args.precision, args.eps2) as sim:
             sim.init(b, v)
+            if args.start6:      # the engine's own start: exact crackle, two-rule levels
+                sim.set_start6(1)
             sim.set_params(args.outer_dt, 1.0)
             block_steps(sim, eta=args.eta, max_level=args.max_level)
             e0 = energy(sim)
@@ -115,8 +118,10 @@ def part_b(args, out):
                 lev0 = np.minimum(lev0 + args.start_deeper, args.max_level).astype(np.uint8)
                 sim.upload_levels(lev0)
             sim.block_stats(reset=True)
-            t = wall(sim, outer)
-            r["block"] = {"wall_s": t, "dE": abs((energy(sim) - e0) / e0), "stats": sim.block_stats(),
+            t = wall(sim, 1)
+            de_first = abs((energy(sim) - e0) / e0)
+            t += wall(sim, outer - 1)
+            r["block"] = {"wall_s": t, "dE_first": de_first, "dE": abs((energy(sim) - e0) / e0), "stats": sim.block_stats(),
                           "levels_start": np.bincount(lev0).tolist(), "levels_end": np.bincount(sim.read_levels()).tolist()}
         r["block"]["full_force_equivalents"] = r["block"]["stats"]["body_steps"] / n
         r["shared"] = []
@@ -176,6 +181,7 @@ def main():
     ap.add_argument("--order", type=int, default=4, choices=[4, 6], help="the Hermite order of every handle (6: set_hermite_order(6) + set_block_steps6)")
     ap.add_argument("--eta", type=float, default=0.02, help="(b): the accuracy parameter of the block steps")
     ap.add_argument("--start-deeper", type=int, default=0, help="(b): upload the start rule's levels this many levels deeper before the run")
+    ap.add_argument("--start6", action="store_true", help="(b): with --order 6, set_start6(1) on the block handle: exact crackle and two-rule start levels")
     ap.add_argument("--outer-dt", type=float, default=2.0 ** -4)
     ap.add_argument("--max-level", type=int, default=16)
     ap.add_argument("--shared-from", type=int, default=6)
@@ -186,6 +192,8 @@ def main():
     args = ap.parse_args()
     global ORDER
     ORDER = args.order
+    if args.start6 and ORDER != 6:
+        ap.error("--start6 needs --order 6")
     if capi.device_count() < 1:
         sys.exit("block_bench: no GPU")
     out = {"tool": "block_bench", "order": ORDER, "full": {}, "end2end": [], "small": {}}
