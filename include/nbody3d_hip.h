@@ -80,7 +80,9 @@ extern "C" {
                              2.4 (round 21) likewise within 2.4: nb_set_block_steps6.  Detected by the presence of the symbol
                                             nb_set_block_steps6
                              2.4 (round 22) likewise within 2.4: nb_set_start6, nb_start6, NB_START6_*.  Detected by the presence of the
-                                            symbol nb_set_start6 */
+                                            symbol nb_set_start6
+                             2.4 (round 23) likewise within 2.4: nb_set_pass_precision, nb_pass_precision, NB_PASS_*.  Detected by the presence
+                                            of the symbol nb_set_pass_precision */
 
 typedef struct nb_sim nb_sim; /* opaque */
 
@@ -501,7 +503,8 @@ int nb_upload_derivs(nb_sim *s, const void *accel, const void *jerk);
  *   - nb_force_pass still runs the full N x N pass into scratch.  nb_enable_timing / nb_step_times2 report one OUTER step per launch:
  *     force_ms is its whole span, integrate_ms = 0 (as on a fused handle).  nb_variant_name is unchanged.
  *   - binary32 handles store the state, a and j in binary32: below steps of about dt / 2^10 (Plummer units) a3 is rounding noise and
- *     the criterion degrades towards smaller steps -- safe, but slower.  Deep hierarchies belong on NB_F64 handles.
+ *     the criterion degrades towards smaller steps -- safe, but slower.  Deep hierarchies belong on NB_F64 handles (whose
+ *     pass may run in binary32 on double-single differences: nb_set_pass_precision below).
  *   - Leapfrog handles: all four calls return NB_ERR_STATE.  A NULL handle, a wrong struct_size, max_level > 30, min_level >
  *     max_level, eta <= 0 or NaN, unknown flag bits, an uploaded level outside [min_level, max_level]: NB_ERR_INVALID, with a message
  *     that names the function and the field. */
@@ -1322,6 +1325,42 @@ int nb_set_block_steps6(nb_sim *s, const nb_block_steps *cfg /* NULL: back to th
 #define NB_START6_CRACKLE 1u   /* c = the direct sum above; dynamic block levels from the two-rule start */
 int nb_set_start6(nb_sim *s, uint32_t mode);
 int nb_start6(nb_sim *s, uint32_t *mode);
+
+/* ---- the force+jerk pass of an NB_F64 Hermite handle in mixed precision: double-single differences (no reference analogue) ----
+ * nb_set_pass_precision(s, NB_PASS_MIXED) makes every force+jerk pass of an NB_F64 Hermite handle of order 4 run binary32 pair
+ * arithmetic on positions carried as a double-single pair of binary32 words (GRAPE-6, Sapporo, phi-GPU).  The STATE is unchanged:
+ * fp64 x, v, a, j, levels, every download and every checkpoint.  A handle that never calls the setter runs the native fp64 pass.
+ *   - Per body, from the fp64 row the pass reads
+ *         xh = (float)x      xl = (float)(x - (double)xh)      vf = (float)v      mf = (float)m
+ *   - Per pair, all in binary32, the two differences formed first and then added:
+ *         dr = (xh_j - xh_i) + (xl_j - xl_i)        dv = vf_j - vf_i
+ *     and from there the f32 handles' sequence: rho^2 = dr.dr + eps2, y = rsq(rho^2), s3 = (mf_j y) y^2, q = (dr.dv) y^2,
+ *     a_i += s3 dr, j_i += s3 (dv - 3 q dr) (one sum per component).  No self mask: for j = i the term is exactly 0.
+ *   - Sums: binary32 in two levels (at most 1,024 terms per register, then the j-chunk), then fp64 across the j-chunks in ascending
+ *     order, times G once, stored as double.  The j-chunks are a function of (n, the device's CU count), and of the active count for
+ *     the gathered pass of a block step: the summation order is fixed, two handles give the same bits.
+ *   - Accuracy.  dr is good to ~1e-7 OF ITSELF however close the pair is (binary32 positions at |x| ~ 1: 6e-8 / |dr|), so the
+ *     accelerations of a hard pair and the block-step criterion's differences of them are those of the fp64 pass to ~1e-6, and
+ *     dynamic levels follow the fp64 schedule.  It does NOT give fp64 derivatives: a and j carry binary32 pair-arithmetic and
+ *     summation error of about 1e-6 of the row's scale, velocities enter as binary32.  "Of the row's scale" matters for a body
+ *     whose sum is dominated by one partner: the other bodies' terms are added to a binary32 register that holds the partner's, and
+ *     those below half an ulp of it are lost -- pairs 2e-4 apart at N = 1,025 keep their mutual force to 1e-7 and their row to 1e-5,
+ *     but lose most of the external field on their members.  An energy audit to 1e-12 needs the native pass.
+ *   - With NB_PASS_MIXED every force+jerk pass the handle runs is the mixed one: the start, the shared step, the gathered pass of
+ *     nb_set_block_steps (dynamic and frozen) and nb_force_pass.  The queries (nb_field_eval, nb_list_force, nb_split_*, ...) are untouched.
+ *   - The mode takes effect from the next pass on.  The setter touches no state and marks nothing stale, neither the derivatives nor
+ *     the levels: the restore order nb_upload, nb_upload_derivs, nb_set_pass_precision, nb_set_block_steps, nb_upload_levels (the setter
+ *     anywhere in it) continues bit for bit.  It allocates three binary32 rows per body, released by NB_PASS_NATIVE and nb_destroy.
+ *   - nb_variant_name starts with "hermite4_f64mx_"; nb_shape_info reports the mixed pass's j-chunks.
+ *   - Errors: a NULL handle, a NULL out pointer and an unknown mode are NB_ERR_INVALID; a leapfrog handle, an NB_F32 handle, an
+ *     order-6 handle and a handle with the neighbour scheme on are NB_ERR_STATE.  On a mixed handle nb_set_hermite_order(6) and
+ *     nb_set_neighbor_scheme(non-NULL) are NB_ERR_STATE until the mode is NB_PASS_NATIVE again.
+ *   - Not built: mixed passes for order 6, for the neighbour scheme and for the queries; double-single sums or velocities;
+ *     nb_multi; anything on NB_F32 handles. */
+#define NB_PASS_NATIVE 0u   /* the handle's own precision (default) */
+#define NB_PASS_MIXED  1u   /* double-single differences, binary32 pair arithmetic, fp64 across chunks */
+int nb_set_pass_precision(nb_sim *s, uint32_t mode);
+int nb_pass_precision(nb_sim *s, uint32_t *mode);
 
 #if defined(__GNUC__)
 #pragma GCC visibility pop

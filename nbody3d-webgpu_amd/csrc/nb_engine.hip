@@ -647,6 +647,7 @@ struct hermite_order {
     const void *predict[2], *correct[2], *blk_predict[2], *blk_correct[2];
     void* nb_sim::*part;              // the partial sums the order's passes write (planes x chunks x n rows) ...
     uint32_t nb_sim::*chunks, nb_sim::*per;      // ... and the j-chunks of its full pass
+    bool mixed;                       // the [1] entries are binary32 kernels on an f64 handle's streams (nb_set_pass_precision): f32 shapes and partial rows
 };
 
 #define NB_BOTH(K) {(const void*)&nb::K<float>, (const void*)&nb::K<double>}
@@ -657,7 +658,7 @@ const hermite_order kOrder4 = {
     {(const void*)&nb::nb_blk_fj_pk<2>, (const void*)&nb::nb_blk_fj64<double>}, (const void*)&nb::nb_blk_fj_pk<1>,
     NB_BOTH(nb_hermite_predict), NB_BOTH(nb_hermite_correct), NB_BOTH(nb_blk_predict),
     {(const void*)&nb::nb_blk_correct<float, float>, (const void*)&nb::nb_blk_correct<double, double>},
-    &nb_sim::fj_part, &nb_sim::fj_chunks, &nb_sim::fj_per};
+    &nb_sim::fj_part, &nb_sim::fj_chunks, &nb_sim::fj_per, false};
 const hermite_order kOrder6 = {
     "hermite6_", 3, 3, 6, {nb::kH6Rows, nb::kH6Rows64}, {nb::kBlock * 4, nb::kH6Rows64},      // (the gathered kernels are NG = 2 and 1 whatever NB_H6_NG the full pass is built with)
     {(const void*)&nb::nb_h6_fjs_pk<nb::kH6NG>, (const void*)&nb::nb_h6_fjs64<double>},
@@ -665,25 +666,40 @@ const hermite_order kOrder6 = {
     {(const void*)&nb::nb_blk6_fjs_pk<2>, (const void*)&nb::nb_blk6_fjs64<double>}, (const void*)&nb::nb_blk6_fjs_pk<1>,
     NB_BOTH(nb_h6_predict), NB_BOTH(nb_h6_correct), NB_BOTH(nb_blk6_predict),
     {(const void*)&nb::nb_blk6_correct<float, float>, (const void*)&nb::nb_blk6_correct<double, double>},
-    &nb_sim::h6_part, &nb_sim::h6_chunks, &nb_sim::h6_per};
+    &nb_sim::h6_part, &nb_sim::h6_chunks, &nb_sim::h6_per, false};
 // The crackle pass of an order-6 start (nb_set_start6): a full pass only, in the order-6 pass's j-chunks and partial rows.
 const hermite_order kStart6 = {
     "hermite6_", 1, 4, 6, {nb::kH6CrkRows, nb::kH6Rows64}, {0, 0},
     {(const void*)&nb::nb_h6_crk_pk<nb::kH6CrkNG>, (const void*)&nb::nb_h6_crk64<double>},
     NB_BOTH(nb_h6_reduce1),
     {nullptr, nullptr}, nullptr, {nullptr, nullptr}, {nullptr, nullptr}, {nullptr, nullptr}, {nullptr, nullptr},
-    &nb_sim::h6_part, &nb_sim::h6_chunks, &nb_sim::h6_per};
+    &nb_sim::h6_part, &nb_sim::h6_chunks, &nb_sim::h6_per, false};
 #undef NB_BOTH
+// Order 4 on an f64 handle with nb_set_pass_precision(NB_PASS_MIXED) (kernels/mixed.hip.h): the pass reads the three binary32
+// streams (xh, xl, vf) the predictors write, in the f32 kernels' shapes, and leaves binary32 partial rows in fj_part; the reduce
+// and the correctors sum them in fp64 into the fp64 state.  f64 handles only: the [0] entries are never read.
+const hermite_order kMixed = {
+    "hermite4_", 2, 3, 4, {nb::kFjRows, nb::kFjRows}, {nb::kFjRows, nb::kFjRows},
+    {nullptr, (const void*)&nb::nb_mx_fj<nb::kFjNG>},
+    {nullptr, (const void*)&nb::nb_fj_reduce<float, double>},
+    {nullptr, (const void*)&nb::nb_mx_blk_fj<2>}, (const void*)&nb::nb_mx_blk_fj<1>,
+    {nullptr, (const void*)&nb::nb_mx_predict<>}, {nullptr, (const void*)&nb::nb_hermite_correct<double>},
+    {nullptr, (const void*)&nb::nb_mx_blk_predict<>}, {nullptr, (const void*)&nb::nb_blk_correct<float, double>},
+    &nb_sim::fj_part, &nb_sim::mx_chunks, &nb_sim::mx_per, true};
 
-const hermite_order& order_of(const nb_sim* s) { return s->h6 ? kOrder6 : kOrder4; }
+// The one place the pass precision is read for a step: the description everything below works from.
+const hermite_order& order_of(const nb_sim* s) { return s->mx ? kMixed : s->h6 ? kOrder6 : kOrder4; }
 
 // Sets the j-chunks of the order's full pass on the handle: chunk_shape with the pass's own rows per workgroup.
 void set_chunks(nb_sim* s, const hermite_order& o) { chunk_shape(s->n, o.rows[s->f64], s->n_cu, &(s->*o.chunks), &(s->*o.per)); }
 
-// The arrays of a handle in the order the kernels take them; an order reads its first `states` and `planes` of them.
+// The arrays of a handle in the order the kernels take them; an order reads its first `states`, `inputs` and `planes` of them.
+// in: what the predictor writes and the pass reads -- the predicted arrays, or a mixed handle's three streams; pred: what the pass's
+// reduce leaves for the corrector (a1, j1[, s1]).
 struct hermite_arrays {
-    void *state[6], *pred[3];
-    explicit hermite_arrays(nb_sim* s) : state{s->bodies[0], s->vel, s->acc, s->jerk, s->snap, s->crackle}, pred{s->hx, s->hv, s->ha} {}
+    void *state[6], *pred[3], *in[3];
+    explicit hermite_arrays(nb_sim* s) : state{s->bodies[0], s->vel, s->acc, s->jerk, s->snap, s->crackle}, pred{s->hx, s->hv, s->ha},
+        in{s->mx ? s->mx_in[0] : s->hx, s->mx ? s->mx_in[1] : s->hv, s->mx ? s->mx_in[2] : s->ha} {}
 };
 
 // The arguments of one launch, collected in the kernel's order: scalars one by one, the arrays of an order by their count.
@@ -724,13 +740,14 @@ void launch_pass(nb_sim* s, const hermite_order& o, void** in, void** out, uint3
     uint32_t n = s->n, irows = n;
     pass_shape sh = {o.rows[s->f64], s->*o.chunks, s->*o.per};
     const void* fn = o.pass[s->f64];
+    const bool wide = s->f64 && !o.mixed;      // fp64 kernels and partial rows (a mixed pass: the f32 kernels' arguments, shapes and rows)
     if (na) {
         irows = na;
-        sh = gathered_shape(n, na, o.gather_rows[s->f64], s->f64, s->*o.chunks, s->n_cu);
+        sh = gathered_shape(n, na, o.gather_rows[s->f64], wide, s->*o.chunks, s->n_cu);
         fn = sh.rows == o.gather_rows[s->f64] ? o.gather[s->f64] : o.gather_ng1;
     }
     pass_parts part = {sh.chunks, {}};
-    for (uint32_t p = 0; p < o.planes; ++p) part.plane[p] = (char*)(s->*o.part) + p * ((size_t)4 * s->esz * sh.chunks * irows);
+    for (uint32_t p = 0; p < o.planes; ++p) part.plane[p] = (char*)(s->*o.part) + p * ((size_t)4 * (wide ? 8 : 4) * sh.chunks * irows);
     double e2 = s->eps2, G = s->G;
     float e2f = (float)s->eps2;
     const void* zr = s->zero_row;
@@ -738,7 +755,7 @@ void launch_pass(nb_sim* s, const hermite_order& o, void** in, void** out, uint3
     a(in, o.inputs);
     if (na) a(&s->blk_act)(&na);
     a(part.plane, o.planes)(&n)(&sh.per);
-    if (s->f64) a(&e2); else a(&e2f)(&zr);
+    if (wide) a(&e2); else a(&e2f)(&zr);
     (void)hipLaunchKernel(fn, dim3(ceil_div(irows, sh.rows), sh.chunks), dim3(nb::kBlock), a.v, 0, s->stream);
     if (na) { *got = part; return; }
     kernel_args r;
@@ -747,6 +764,15 @@ void launch_pass(nb_sim* s, const hermite_order& o, void** in, void** out, uint3
 }
 
 int ensure_scheme(nb_sim* s, const char* who);
+
+// A mixed handle's three streams from the stored state (the start, nb_force_pass: a step's come from its predictor).
+void launch_split(nb_sim* s)
+{
+    uint32_t n = s->n;
+    kernel_args a;
+    a(&s->bodies[0])(&s->vel)(s->mx_in, 3)(&n);
+    (void)hipLaunchKernel((const void*)&nb::nb_mx_split<>, dim3(ceil_div(n, nb::kBlock)), dim3(nb::kBlock), a.v, 0, s->stream);
+}
 
 // Makes acc / jerk the derivatives of (bodies, vel) for the G in force (a no-op while they are current): the order-4 force+jerk
 // pass, on handles of either order.  With the neighbour scheme on they are the scheme's totals and come from its start.
@@ -758,7 +784,8 @@ int ensure_derivs(nb_sim* s, const char* who)
     if (s->derivs_ok && s->derivs_G == s->G) return NB_OK;
     s->snap_ok = false;      // an order-6 handle's snap and crackle belong to the (a, j) replaced here, whoever asked for them: its start runs again
     void *in[] = {s->bodies[0], s->vel}, *out[] = {s->acc, s->jerk};
-    launch_pass(s, kOrder4, in, out);
+    if (s->mx) { launch_split(s); launch_pass(s, kMixed, s->mx_in, out); }      // (a mixed handle is of order 4)
+    else launch_pass(s, kOrder4, in, out);
     NB_HIP(s, hipGetLastError());
     s->derivs_ok = true; s->derivs_any_G = false; s->derivs_G = s->G;
     return NB_OK;
@@ -792,7 +819,8 @@ void launch_oc(nb_sim* s, const hermite_order& o, bool correct)
     uint32_t n = s->n;
     double dt = s->dt;
     kernel_args a;
-    a(h.state, o.states)(h.pred, o.planes)(&n)(&dt);
+    if (correct) a(h.state, o.states)(h.pred, o.planes)(&n)(&dt);
+    else a(h.state, o.states)(h.in, o.inputs)(&n)(&dt);
     (void)hipLaunchKernel((correct ? o.correct : o.predict)[s->f64], dim3(ceil_div(n, nb::kBlock)), dim3(nb::kBlock), a.v, 0, s->stream);
 }
 
@@ -809,7 +837,7 @@ int hermite_step(nb_sim* s, uint32_t nsteps)
         if (rec) NB_HIP(s, hipEventRecord(ev.e[6], s->stream));
         launch_oc(s, o, false);
         if (rec) NB_HIP(s, hipEventRecord(ev.e[0], s->stream));
-        launch_pass(s, o, h.pred, h.pred);      // (a1, j1[, s1]) over the predicted state: the reduce runs after every read of it
+        launch_pass(s, o, h.in, h.pred);      // (a1, j1[, s1]) over the predicted state: the reduce runs after every read of it
         if (rec) NB_HIP(s, hipEventRecord(ev.e[1], s->stream));
         launch_oc(s, o, true);
         if (rec) { NB_HIP(s, hipEventRecord(ev.e[2], s->stream)); s->pending.push_back(ev); }
@@ -826,13 +854,19 @@ void h6_release(nb_sim* s)
     s->h6 = false; s->snap_ok = false; s->start_own = false; s->start6 = NB_START6_ZERO;
 }
 
+void mx_release(nb_sim* s)
+{
+    for (void*& p : s->mx_in) { if (p) (void)hipFree(p); p = nullptr; }
+    s->mx = false;
+}
+
 // what nb_variant_name and nb_shape_info report: the pass a step of the handle runs
 void hermite_names(nb_sim* s)
 {
     const hermite_order& o = order_of(s);
     const uint32_t c = s->*o.chunks, per = s->*o.per;
     s->jsplit = c; s->j_per_split = per;
-    s->variant = std::string(o.name) + (s->f64 ? "f64" : "f32pk") + "_c" + std::to_string(c) + "_j" + std::to_string(per);
+    s->variant = std::string(o.name) + (o.mixed ? "f64mx" : s->f64 ? "f64" : "f32pk") + "_c" + std::to_string(c) + "_j" + std::to_string(per);
 }
 
 // ---- block individual time steps (nb_set_block_steps, nb_set_block_steps6; kernels/block.hip.h, kernels/block6.hip.h) ----------
@@ -875,7 +909,7 @@ int block_step(nb_sim* s, uint32_t nsteps)
         void* sargs[] = {&s->blk_due, &s->blk_lev, &n, &s->blk_act, &s->blk_hdr, &s->blk_hdr_pub};
         (void)hipLaunchKernel((const void*)&nb::nb_blk_sched<nb::kBlkSched>, dim3(1), dim3(nb::kBlkSched), sargs, 0, s->stream);
         kernel_args p;
-        p(h.state, o.states)(&s->blk_due)(&s->blk_lev)(h.pred, o.planes)(&n)(&s->blk_hdr)(&Lk)(&tick);
+        p(h.state, o.states)(&s->blk_due)(&s->blk_lev)(h.in, o.inputs)(&n)(&s->blk_hdr)(&Lk)(&tick);
         (void)hipLaunchKernel(o.blk_predict[s->f64], dim3(ceil_div(n, nb::kBlock)), dim3(nb::kBlock), p.v, 0, s->stream);
     };
     bool ahead = false;      // the first schedule + predict of this outer step went out behind the previous one's last corrector
@@ -891,7 +925,7 @@ int block_step(nb_sim* s, uint32_t nsteps)
             if (na == 0 || na > n || t_next == 0 || t_next > end)
                 return fail(s, NB_ERR_HIP, "nb_step: block schedule out of range (active " + std::to_string(na) + ", tick " + std::to_string(t_next) + ")");
             pass_parts part;
-            launch_pass(s, o, h.pred, nullptr, na, &part);
+            launch_pass(s, o, h.in, nullptr, na, &part);
             kernel_args c;
             c(part.plane, o.planes)(&s->blk_act)(&na)(&part.chunks)(&G)(h.state, o.states)(&s->blk_due)(&s->blk_lev)(&s->blk_hdr)(&t_next)(&Lk)(&lmin)(&frozen)(&eta)(&dt);
             (void)hipLaunchKernel(o.blk_correct[s->f64], dim3(ceil_div(na, nb::kBlock)), dim3(nb::kBlock), c.v, 0, s->stream);
@@ -1354,7 +1388,8 @@ int nb_create(const nb_config* cfg_in, nb_sim** out)
         NB_HIPC(hipMalloc(&s->bodies[0], hrow * s->n));
         s->own_bodies = true;
         for (void** p : {&s->vel, &s->acc, &s->jerk, &s->hx, &s->hv}) NB_HIPC(hipMalloc(p, hrow * s->n));
-        NB_HIPC(hipMalloc(&s->fj_part, (size_t)2 * hrow * s->fj_chunks * s->n));
+        s->fj_part_bytes = (size_t)2 * hrow * s->fj_chunks * s->n;
+        NB_HIPC(hipMalloc(&s->fj_part, s->fj_part_bytes));
         NB_HIPC(hipMalloc(&s->zero_row, 64));
         NB_HIPC(hipMemsetAsync(s->zero_row, 0, 64, s->stream));
         s->diag_chunk = nb::kTile * std::min(16u, std::max(1u, s->n / 16384u));
@@ -1490,6 +1525,7 @@ void nb_destroy(nb_sim* s)
     if (s->blk_hdr_host) (void)hipHostFree(s->blk_hdr_host);
     ac_release(s);
     h6_release(s);
+    mx_release(s);
     if (s->diag) (void)hipFree(s->diag);
     for (auto* b : {&s->q_in[0], &s->q_in[1], &s->q_in[2], &s->q_in[3], &s->q_out[0], &s->q_out[1], &s->q_out[2], &s->q_out[3], &s->q_out[4], &s->q_out[5], &s->q_part, &s->q_off, &s->q_work, &s->q_inf, &s->q_seg, &s->q_segcnt, &s->knn_stat})
         if (b->p) (void)hipFree(b->p);
@@ -1744,6 +1780,7 @@ int nb_set_hermite_order(nb_sim* s, uint32_t order)
     if (!s->hermite) return fail(s, NB_ERR_STATE, "nb_set_hermite_order: needs a Hermite handle (nb_config.integrator = NB_INT_HERMITE4)");
     if (order == 6 && s->blk && !s->h6) return fail(s, NB_ERR_STATE, "nb_set_hermite_order: order = 6 while block steps are switched on (nb_set_block_steps): they exclude each other");
     if (order == 4 && s->blk && s->h6) return fail(s, NB_ERR_STATE, "nb_set_hermite_order: order = 4 while block steps of order 6 are switched on (nb_set_block_steps6): switch them off first");
+    if (order == 6 && s->mx) return fail(s, NB_ERR_STATE, "nb_set_hermite_order: order = 6 while the pass precision is NB_PASS_MIXED (nb_set_pass_precision): the mixed pass exists at order 4 only, set NB_PASS_NATIVE first");
     if (order == 6 && s->ac) return fail(s, NB_ERR_STATE, "nb_set_hermite_order: order = 6 while the neighbour scheme is switched on (nb_set_neighbor_scheme): they exclude each other");
     if ((order == 6) == s->h6) return NB_OK;
     NB_HIP(s, hipSetDevice(s->device));
@@ -1775,6 +1812,54 @@ int nb_hermite_order(nb_sim* s, uint32_t* order)
     if (!order) return fail(s, NB_ERR_INVALID, "nb_hermite_order: order is NULL");
     if (!s->hermite) return fail(s, NB_ERR_STATE, "nb_hermite_order: needs a Hermite handle (nb_config.integrator = NB_INT_HERMITE4)");
     *order = s->h6 ? 6u : 4u;
+    return NB_OK;
+}
+
+int nb_set_pass_precision(nb_sim* s, uint32_t mode)
+{
+    if (!s) return fail(nullptr, NB_ERR_INVALID, "nb_set_pass_precision: null handle");
+    if (mode != NB_PASS_NATIVE && mode != NB_PASS_MIXED) return fail(s, NB_ERR_INVALID, "nb_set_pass_precision: mode must be NB_PASS_NATIVE or NB_PASS_MIXED");
+    if (!s->hermite) return fail(s, NB_ERR_STATE, "nb_set_pass_precision: needs a Hermite handle (nb_config.integrator = NB_INT_HERMITE4)");
+    if (!s->f64) return fail(s, NB_ERR_STATE, "nb_set_pass_precision: precision NB_F32: the mixed pass keeps an fp64 state, it exists on NB_F64 handles only");
+    if (s->h6) return fail(s, NB_ERR_STATE, "nb_set_pass_precision: the handle's order is 6 (nb_set_hermite_order): the mixed pass exists at order 4 only");
+    if (s->ac) return fail(s, NB_ERR_STATE, "nb_set_pass_precision: the neighbour scheme is switched on (nb_set_neighbor_scheme): it has no mixed kernels");
+    if ((mode == NB_PASS_MIXED) == s->mx) return NB_OK;
+    NB_HIP(s, hipSetDevice(s->device));
+    NB_HIP(s, hipStreamSynchronize(s->stream));
+    // Neither direction touches the state, the derivatives or the levels: what they hold stays what it is, the next pass runs in the new mode.
+    if (mode == NB_PASS_NATIVE) {
+        mx_release(s);
+        hermite_names(s);
+        return NB_OK;
+    }
+    chunk_shape(s->n, kMixed.rows[1], s->n_cu, &s->mx_chunks, &s->mx_per);
+    hipError_t e = hipSuccess;
+    for (void*& p : s->mx_in)
+        if (e == hipSuccess) e = hipMalloc(&p, sizeof(float) * 4 * s->n);
+    // the partial rows were sized for the native pass (kFjRows64 rows per workgroup, 32-byte rows): the mixed shape has up to four
+    // times the chunks of 16-byte rows
+    const size_t need = (size_t)2 * 16 * s->mx_chunks * s->n;
+    if (e == hipSuccess && need > s->fj_part_bytes) {
+        void* grown = nullptr;
+        e = hipMalloc(&grown, need);
+        if (e == hipSuccess) { (void)hipFree(s->fj_part); s->fj_part = grown; s->fj_part_bytes = need; }
+    }
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        mx_release(s);
+        return fail(s, NB_ERR_HIP, std::string("nb_set_pass_precision: ") + hipGetErrorString(e));
+    }
+    s->mx = true;
+    hermite_names(s);
+    return NB_OK;
+}
+
+int nb_pass_precision(nb_sim* s, uint32_t* mode)
+{
+    if (!s) return fail(nullptr, NB_ERR_INVALID, "nb_pass_precision: null handle");
+    if (!mode) return fail(s, NB_ERR_INVALID, "nb_pass_precision: mode is NULL");
+    if (!s->hermite) return fail(s, NB_ERR_STATE, "nb_pass_precision: needs a Hermite handle (nb_config.integrator = NB_INT_HERMITE4)");
+    *mode = s->mx ? NB_PASS_MIXED : NB_PASS_NATIVE;
     return NB_OK;
 }
 
@@ -1950,6 +2035,7 @@ int nb_set_neighbor_scheme(nb_sim* s, const nb_neighbor_scheme* cfg)
         ac_release(s);
         return NB_OK;
     }
+    if (s->mx) return fail(s, NB_ERR_STATE, "nb_set_neighbor_scheme: the pass precision is NB_PASS_MIXED (nb_set_pass_precision): the neighbour scheme has no mixed kernels, set NB_PASS_NATIVE first");
     if (s->h6) return fail(s, NB_ERR_STATE, "nb_set_neighbor_scheme: the handle's order is 6 (nb_set_hermite_order): the neighbour scheme and the 6th-order scheme exclude each other");
     if (cfg->struct_size != sizeof(nb_neighbor_scheme)) return fail(s, NB_ERR_INVALID, "nb_set_neighbor_scheme: struct_size must be sizeof(nb_neighbor_scheme)");
     const uint32_t nsub = cfg->substeps ? cfg->substeps : 8u, cap = cfg->cap ? cfg->cap : 128u;
@@ -2444,8 +2530,9 @@ int nb_force_pass(nb_sim* s, uint32_t reps, double* avg_ms)
     if (int rc = ensure_eqm(s)) return rc;
     if (s->hermite && !s->params_set) return fail(s, NB_ERR_STATE, "nb_force_pass: nb_set_params has not been called (G)");
     if (s->h6) { if (int rc = ensure_start(s, "nb_force_pass")) return rc; }      // the pass streams the accelerations: they are made current, the state is untouched
+    if (s->hermite && s->mx) launch_split(s);      // a mixed handle's pass reads its three streams: made from the stored state, once
     auto once = [&]() -> int {
-        if (s->hermite) { hermite_arrays h(s); launch_pass(s, order_of(s), h.state, h.pred); return NB_OK; }      // the order's pass into the step's scratch: state and derivatives untouched
+        if (s->hermite) { hermite_arrays h(s); launch_pass(s, order_of(s), s->mx ? h.in : h.state, h.pred); return NB_OK; }      // the order's pass into the step's scratch: state and derivatives untouched
         if (s->sym_rank) return s->f64 ? nbi::sym_rank_phase_a_t<double>(s, nullptr, false) : nbi::sym_rank_phase_a_t<float>(s, nullptr, false);
         if (s->f64) launch_force<double>(s); else launch_force<float>(s);
         return NB_OK;

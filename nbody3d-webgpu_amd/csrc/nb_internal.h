@@ -182,6 +182,13 @@ struct nb_sim {
     uint32_t h6_chunks = 1, h6_per = 0;   // the force+jerk+snap pass's j-chunks and bodies per chunk
     bool snap_ok = false;          // snap / crackle belong to the current acc / jerk (which derivs_ok and derivs_G speak for); cleared by
                                    // ensure_derivs whenever it re-evaluates acc / jerk, set by the start and by nb_upload_derivs6
+    // nb_set_pass_precision(NB_PASS_MIXED) on an NB_F64 handle of order 4 (kernels/mixed.hip.h): every force+jerk pass reads the three
+    // binary32 streams below and writes binary32 partial rows into fj_part.  Allocated by the call, released by NB_PASS_NATIVE or
+    // nb_destroy.  Off: none of this is read.  The state, the derivatives and the levels are the handle's fp64 arrays either way.
+    bool mx = false;
+    void* mx_in[3] = {nullptr, nullptr, nullptr};   // (xh, mf), xl, vf: n float4 rows each, rewritten by every predictor / split
+    uint32_t mx_chunks = 1, mx_per = 0;   // the mixed pass's j-chunks (kFjRows i-bodies per workgroup) and bodies per chunk
+    size_t fj_part_bytes = 0;      // what fj_part holds (grown when the mixed shape needs more than the native one)
     uint32_t start6 = 0;           // nb_set_start6: NB_START6_ZERO | NB_START6_CRACKLE, what the engine's own starts (and start levels) are made by
     bool start_own = false;        // snap / crackle came from the engine's start and no step has consumed them (nb_set_start6 may drop them)
     // nb_set_block_steps: block individual time steps (kernels/block.hip.h).  Allocated when first switched on.

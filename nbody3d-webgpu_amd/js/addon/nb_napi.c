@@ -68,6 +68,8 @@ static int (*p_upload_derivs6)(nb_sim *, const void *, const void *, const void 
 static int (*p_set_block_steps6)(nb_sim *, const nb_block_steps *);     /* block steps on order-6 handles (round 21): optional */
 static int (*p_set_start6)(nb_sim *, uint32_t);                         /* the start mode of order-6 handles (round 22): optional */
 static int (*p_start6)(nb_sim *, uint32_t *);
+static int (*p_set_pass_precision)(nb_sim *, uint32_t);                 /* the mixed-precision pass of f64 Hermite handles (round 23): optional */
+static int (*p_pass_precision)(nb_sim *, uint32_t *);
 static int (*p_set_block_steps)(nb_sim *, const nb_block_steps *);      /* block time steps, also within ABI 2.4: optional symbols */
 static int (*p_block_stats)(nb_sim *, struct nb_block_stats *, int);
 static int (*p_download_levels)(nb_sim *, uint8_t *);
@@ -186,6 +188,8 @@ static napi_value js_load(napi_env env, napi_callback_info info)
         *(void **)(&p_set_block_steps6) = dlsym(h, "nb_set_block_steps6");
         *(void **)(&p_set_start6) = dlsym(h, "nb_set_start6");
         *(void **)(&p_start6) = dlsym(h, "nb_start6");
+        *(void **)(&p_set_pass_precision) = dlsym(h, "nb_set_pass_precision");
+        *(void **)(&p_pass_precision) = dlsym(h, "nb_pass_precision");
         *(void **)(&p_block_stats) = dlsym(h, "nb_block_stats");
         *(void **)(&p_download_levels) = dlsym(h, "nb_download_levels");
         *(void **)(&p_upload_levels) = dlsym(h, "nb_upload_levels");
@@ -1162,6 +1166,43 @@ static napi_value js_set_start6(napi_env env, napi_callback_info info)
     return undefined(env);
 }
 
+/* the single-device handle of a pass-precision call, or NULL with an exception pending */
+static handle_t *pass_handle(napi_env env, napi_value v, const void *sym, const char *where)
+{
+    handle_t *h = get_handle(env, v); if (!h) return NULL;
+    if (h->multi || !sym) { throw_msg(env, NB_ERR_STATE, "needs a single-device Hermite handle and a library with nb_set_pass_precision", where); return NULL; }
+    return h;
+}
+
+/* setPassPrecision(handle, mode): nb_set_pass_precision -- NB_PASS_NATIVE (0) or NB_PASS_MIXED (1). */
+static napi_value js_set_pass_precision(napi_env env, napi_callback_info info)
+{
+    size_t argc = 2; napi_value argv[2];
+    CHECK_NAPI(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    if (argc < 2) { napi_throw_type_error(env, NULL, "setPassPrecision(handle, mode)"); return NULL; }
+    handle_t *h = pass_handle(env, argv[0], (const void *)p_set_pass_precision, "nb_set_pass_precision"); if (!h) return NULL;
+    uint32_t mode = 0;
+    CHECK_NAPI(env, napi_get_value_uint32(env, argv[1], &mode));
+    int rc = p_set_pass_precision(h->sim, mode);
+    if (rc != NB_OK) return throw_nb(env, rc, h->sim, "nb_set_pass_precision");
+    return undefined(env);
+}
+
+/* passPrecision(handle) -> 0 or 1: nb_pass_precision. */
+static napi_value js_pass_precision(napi_env env, napi_callback_info info)
+{
+    size_t argc = 1; napi_value argv[1];
+    CHECK_NAPI(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    if (argc < 1) { napi_throw_type_error(env, NULL, "passPrecision(handle)"); return NULL; }
+    handle_t *h = pass_handle(env, argv[0], (const void *)p_pass_precision, "nb_pass_precision"); if (!h) return NULL;
+    uint32_t mode = 0;
+    int rc = p_pass_precision(h->sim, &mode);
+    if (rc != NB_OK) return throw_nb(env, rc, h->sim, "nb_pass_precision");
+    napi_value out;
+    CHECK_NAPI(env, napi_create_uint32(env, mode, &out));
+    return out;
+}
+
 /* start6(handle) -> 0 or 1: nb_start6. */
 static napi_value js_start6(napi_env env, napi_callback_info info)
 {
@@ -1589,7 +1630,7 @@ static napi_value init_module(napi_env env, napi_value exports)
         {"collectiveInfo", js_collective_info}, {"requestFrame", js_request_frame}, {"frame", js_frame}, {"planQuery", js_plan_query},
         {"fieldEval", js_field_eval}, {"downloadJerk", js_download_jerk}, {"uploadDerivs", js_upload_derivs},
         {"setHermiteOrder", js_set_hermite_order}, {"hermiteOrder", js_hermite_order}, {"downloadSnap", js_download_snap}, {"uploadDerivs6", js_upload_derivs6},
-        {"setStart6", js_set_start6}, {"start6", js_start6},
+        {"setStart6", js_set_start6}, {"start6", js_start6}, {"setPassPrecision", js_set_pass_precision}, {"passPrecision", js_pass_precision},
         {"setBlockSteps", js_set_block_steps}, {"setBlockSteps6", js_set_block_steps6}, {"blockStats", js_block_stats}, {"downloadLevels", js_download_levels},
         {"uploadLevels", js_upload_levels}, {"neighbors", js_neighbors}, {"neighborLists", js_neighbor_lists},
         {"knn", js_knn}, {"listForce", js_list_force}, {"splitForce", js_split_force}, {"splitLists", js_split_lists}, {"neighborSchemeFused", js_neighbor_scheme_fused},

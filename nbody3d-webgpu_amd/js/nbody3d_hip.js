@@ -241,6 +241,25 @@ class Simulation {
     return addon.start6(this._h);
   }
 
+  /** The precision of the force+jerk pass of an f64 'hermite4' simulation of order 4 (nb_set_pass_precision; no reference analogue):
+   *  'native' (0) -- the simulation's own; 'mixed' (1) -- binary32 pair arithmetic on double-single position differences, fp64 sums
+   *  across the j-chunks into the unchanged fp64 state.  Touches no state, derivatives or levels; holds from the next pass on. */
+  setPassPrecision(mode) {
+    if (typeof mode === 'string') {
+      if (mode !== 'native' && mode !== 'mixed') throw new RangeError(`setPassPrecision(): mode must be 'native', 'mixed', 0 or 1, not '${mode}'`);
+      mode = mode === 'mixed' ? 1 : 0;
+    }
+    this._need();
+    addon.setPassPrecision(this._h, mode >>> 0);
+    return this;
+  }
+
+  /** 'native' or 'mixed' (nb_pass_precision). */
+  passPrecision() {
+    this._need();
+    return addon.passPrecision(this._h) === 1 ? 'mixed' : 'native';
+  }
+
   /** Block individual time steps of a 'hermite4' simulation (nb_set_block_steps; no reference analogue): every body steps by
    *  dt / 2^level, minLevel <= level <= maxLevel, chosen from its own derivatives with the accuracy parameter eta; step() and
    *  simulate() still advance by whole dt.  {eta, maxLevel, minLevel, frozen}: missing eta / maxLevel take the library's defaults

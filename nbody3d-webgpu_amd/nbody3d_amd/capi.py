@@ -201,9 +201,11 @@ SYMBOLS = ["nb_abi_version", "nb_device_count", "nb_create", "nb_destroy", "nb_u
            "nb_set_neighbor_adapt", "nb_neighbor_adapt_stats", "nb_download_neighbor_radii", "nb_upload_neighbor_scheme",
            "nb_set_neighbor_levels", "nb_neighbor_level_stats", "nb_download_neighbor_levels", "nb_upload_neighbor_levels",
            "nb_set_hermite_order", "nb_hermite_order", "nb_download_snap", "nb_upload_derivs6",
-           "nb_set_block_steps6", "nb_set_start6", "nb_start6"]
+           "nb_set_block_steps6", "nb_set_start6", "nb_start6", "nb_set_pass_precision", "nb_pass_precision"]
 
 START6_ZERO, START6_CRACKLE = 0, 1      # nb_set_start6
+PASS_NATIVE, PASS_MIXED = 0, 1          # nb_set_pass_precision
+_PASS_MODES = {"native": PASS_NATIVE, "mixed": PASS_MIXED}
 
 _lib = None
 
@@ -332,6 +334,9 @@ def load_library():
     if hasattr(L, "nb_set_start6"):             # the start mode of order-6 handles, likewise
         L.nb_set_start6.argtypes = [vp, C.c_uint32]
         L.nb_start6.argtypes = [vp, C.POINTER(C.c_uint32)]
+    if hasattr(L, "nb_set_pass_precision"):     # the mixed-precision force+jerk pass of f64 Hermite handles, likewise
+        L.nb_set_pass_precision.argtypes = [vp, C.c_uint32]
+        L.nb_pass_precision.argtypes = [vp, C.POINTER(C.c_uint32)]
     if hasattr(L, "nb_eqm_info"):           # the equal-mass kernels' report, also within 2.4 and detected by the symbol
         L.nb_eqm_info.argtypes = [vp, C.POINTER(C.c_int)]
     if hasattr(L, "nb_eqm_form"):           # which of the equal-mass forms, likewise
@@ -941,6 +946,27 @@ class Simulation:
         m = C.c_uint32()
         self._check(self._L.nb_start6(self._h, C.byref(m)))
         return int(m.value)
+
+    def set_pass_precision(self, mode):
+        """nb_set_pass_precision: "native" (0), the handle's own precision, or "mixed" (1): every force+jerk pass of an f64 Hermite
+        handle of order 4 runs binary32 pair arithmetic on double-single position differences, with fp64 sums across the j-chunks
+        into the unchanged fp64 state.  Touches no state, derivatives or levels; takes effect from the next pass on."""
+        if isinstance(mode, str):
+            if mode not in _PASS_MODES:
+                raise ValueError("set_pass_precision(): mode must be 'native', 'mixed', 0 or 1, not %r" % (mode,))
+            mode = _PASS_MODES[mode]
+        if not hasattr(self._L, "nb_set_pass_precision"):
+            raise NBodyError(1, "set_pass_precision(): the loaded library has no nb_set_pass_precision")
+        self._check(self._L.nb_set_pass_precision(self._h, int(mode)))
+        return self
+
+    def pass_precision(self):
+        """nb_pass_precision: "native" or "mixed"."""
+        if not hasattr(self._L, "nb_pass_precision"):
+            raise NBodyError(1, "pass_precision(): the loaded library has no nb_pass_precision")
+        m = C.c_uint32()
+        self._check(self._L.nb_pass_precision(self._h, C.byref(m)))
+        return "mixed" if m.value == PASS_MIXED else "native"
 
     # -- block individual time steps of a Hermite handle -----------------------
     def _need_block(self, what):
