@@ -82,7 +82,9 @@ extern "C" {
                              2.4 (round 22) likewise within 2.4: nb_set_start6, nb_start6, NB_START6_*.  Detected by the presence of the
                                             symbol nb_set_start6
                              2.4 (round 23) likewise within 2.4: nb_set_pass_precision, nb_pass_precision, NB_PASS_*.  Detected by the presence
-                                            of the symbol nb_set_pass_precision */
+                                            of the symbol nb_set_pass_precision
+                             2.4 (round 24) likewise within 2.4: nb_set_pass_guard, nb_pass_guard.  Detected by the presence of the symbol
+                                            nb_set_pass_guard */
 
 typedef struct nb_sim nb_sim; /* opaque */
 
@@ -1355,12 +1357,52 @@ int nb_start6(nb_sim *s, uint32_t *mode);
  *   - Errors: a NULL handle, a NULL out pointer and an unknown mode are NB_ERR_INVALID; a leapfrog handle, an NB_F32 handle, an
  *     order-6 handle and a handle with the neighbour scheme on are NB_ERR_STATE.  On a mixed handle nb_set_hermite_order(6) and
  *     nb_set_neighbor_scheme(non-NULL) are NB_ERR_STATE until the mode is NB_PASS_NATIVE again.
- *   - Not built: mixed passes for order 6, for the neighbour scheme and for the queries; double-single sums or velocities;
+ *   - Not built: mixed passes for order 6, for the neighbour scheme and for the queries; double-single velocities (compensated
+ *     sums of the near terms: nb_set_pass_guard below);
  *     nb_multi; anything on NB_F32 handles. */
 #define NB_PASS_NATIVE 0u   /* the handle's own precision (default) */
 #define NB_PASS_MIXED  1u   /* double-single differences, binary32 pair arithmetic, fp64 across chunks */
 int nb_set_pass_precision(nb_sim *s, uint32_t mode);
 int nb_pass_precision(nb_sim *s, uint32_t *mode);
+
+/* ---- guarded sums of the mixed pass: the external field on hard pairs (no reference analogue) ----
+ * nb_set_pass_guard(s, r_near) gives the mixed pass of a handle whose pass precision is NB_PASS_MIXED a GUARD RADIUS: the terms of
+ * pairs closer than r_near leave the binary32 registers and are summed apart, compensated.  It is for the quantity that plain
+ * NB_PASS_MIXED loses (above): the field of the rest of the system on the members of a hard pair, and with it the acceleration and
+ * jerk of the pair's barycentre, where the partner's terms cancel.  r_near = 0 (the default) is plain NB_PASS_MIXED.
+ * With a guard, every force+jerk pass of the handle -- the start, the shared step, the gathered pass of nb_set_block_steps and
+ * nb_force_pass -- is defined as follows.
+ *   - The per-pair arithmetic is exactly NB_PASS_MIXED's, up to and including s3, dr and t = dv - 3 q dr.
+ *   - A pair is NEAR iff binary32 d2 < (float)(r_near * r_near): strict, and d2 is the value the pass has, rho^2 with eps2 in it.
+ *   - A FAR pair's terms go where they go without a guard: fma into the binary32 two-level sums.
+ *   - A NEAR pair's terms p = s3 * dr and p = s3 * t (rounded products) go into a second sum per component, kept as an unevaluated
+ *     binary32 pair (hi, lo) by branch-free TwoSum:
+ *         s = hi + p;  bb = s - hi;  e = (hi - (s - bb)) + (p - bb);  hi = s;  lo += e
+ *     in ascending j.  It is never flushed.
+ *   - Per j-chunk the partial row is ((double)far + (double)hi) + (double)lo, formed in the kernel's epilogue and stored as fp64
+ *     (the partial rows of a guarded handle are fp64 rows; the setter sizes them as nb_set_pass_precision does).
+ *   - Across chunks: fp64, ascending, times G once, as without a guard.
+ * Properties:
+ *   - A row's bits depend on the state and r_near only, not on which rows share its wave: where some lane of a wave has a near pair
+ *     every lane takes the slow sums, in which a lane without a near pair does exactly the fast path's fma, and a lane's near sum
+ *     takes p = 0 for far pairs -- TwoSum with 0 changes neither word.
+ *   - With r_near^2 <= eps2 no pair is near, and every array is plain NB_PASS_MIXED's bit for bit.
+ *   - The self pair is near when r_near^2 > eps2 and contributes exactly 0.
+ * Choosing r_near: everything outside r_near still enters binary32 registers, so r_near must cover the partners whose terms exceed the
+ * rest of the row by orders of magnitude, and no more: choose it so that a body has O(1) others inside it, for example a quarter of
+ * the mean interparticle distance.  When a third body enters the near set accuracy is kept, because the near sum is compensated;
+ * when hundreds do, the pass only gets slower.  What it does NOT give: fp64 derivatives.  Pair arithmetic stays binary32 (1e-7 of
+ * the pair's term), velocities enter as binary32, and the far sums keep their binary32 summation error relative to the FAR field.
+ *   - The setter is valid only while the handle's pass precision is NB_PASS_MIXED; otherwise NB_ERR_STATE, with a message that names
+ *     nb_set_pass_precision (a leapfrog handle, an NB_F32 handle, an order-6 handle, a native NB_F64 handle).  r_near negative, NaN
+ *     or infinite: NB_ERR_INVALID.  A NULL handle or out pointer: NB_ERR_INVALID.  The getter works on every Hermite handle and
+ *     returns 0 where the guard is off.  nb_set_pass_precision(NB_PASS_NATIVE) puts the guard back to 0.
+ *   - Like nb_set_pass_precision the setter touches no state and marks nothing stale, neither the derivatives nor the levels; it
+ *     holds from the next pass on and may stand anywhere in a restore after nb_set_pass_precision.
+ *   - nb_variant_name starts with "hermite4_f64mxg_" while a guard is set; the j-chunks are the mixed pass's.
+ *   - Not built: a guard for order 6, the neighbour scheme, the queries or NB_F32 handles; a per-body or adaptive radius. */
+int nb_set_pass_guard(nb_sim *s, double r_near);   /* 0 = off (default) */
+int nb_pass_guard(nb_sim *s, double *r_near);
 
 #if defined(__GNUC__)
 #pragma GCC visibility pop

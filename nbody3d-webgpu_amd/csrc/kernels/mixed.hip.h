@@ -93,11 +93,22 @@ __global__ __launch_bounds__(kBlock) void nb_mx_blk_predict(const double4* __res
 // tail, the stage-major issue over the chains, the two-level sums and the GATHER form (compact partial rows of the active list) are
 // that body's; the i-rows carry three more packed values per group (the lo words) and a pair three more packed additions per
 // component pair: 32 packed + 2 transcendental per two pairs = 144 issue cycles by DESIGN §4.1's accounting (nb_fj_pk: 120).
-template <int NG, bool GATHER>
+//   GUARD (nb_set_pass_guard, kernels/guard.hip.h): a pair with d2 < near2 is NEAR.  Per stage the compares' lane masks are ORed on
+// the scalar unit and one wave-uniform branch chooses between the sums above (no lane of the wave has a near pair among the stage's
+// rows) and the slow sums: the weight s3 goes by v_cndmask to exactly one of w_far and w_near, the far fma runs with w_far (a lane
+// without a near pair: exactly the fast path's fma), and the rounded products w_near * term enter an unevaluated binary32 pair
+// (hi, lo) per component by branch-free TwoSum (a far pair: p = 0, which changes neither word).  The 12 NG packed near words of a
+// lane live in LDS, [group][word][lane], touched on the slow path and in the epilogue only; they are never flushed.  The partial row is
+// ((double)far + (double)hi) + (double)lo, stored as fp64.  Without GUARD none of this is compiled.
+template <bool WIDE> struct mx_part { using type = float; };
+template <> struct mx_part<true> { using type = double; };
+
+template <int NG, bool GATHER, bool GUARD = false>
 __device__ __forceinline__ void fj_mx_body(const float4* __restrict__ xh, const float4* __restrict__ xl,
                                            const float4* __restrict__ vf, const uint32_t* __restrict__ act, uint32_t ni,
-                                           float4* __restrict__ pa, float4* __restrict__ pj, uint32_t n, uint32_t j_per_chunk,
-                                           float eps2, const float4* __restrict__ zero_row)
+                                           typename vec4<typename mx_part<GUARD>::type>::type* __restrict__ pa,
+                                           typename vec4<typename mx_part<GUARD>::type>::type* __restrict__ pj, uint32_t n,
+                                           uint32_t j_per_chunk, float eps2, const float4* __restrict__ zero_row, float near2 = 0.0f)
 {
     constexpr int TILE = kTile;
     constexpr int U = 8;                  // tile rows per unrolled chunk
@@ -105,6 +116,7 @@ __device__ __forceinline__ void fj_mx_body(const float4* __restrict__ xh, const 
     constexpr uint32_t ROWS = kBlock * 2 * NG;
     constexpr int NC = JB * NG;
     __shared__ float4 tile[2][3][TILE];   // [buffer][0 = (xh, mf), 1 = xl, 2 = vf][row]
+    __shared__ nb_f2 nearw[GUARD ? NG : 1][GUARD ? 12 : 1][GUARD ? kBlock : 1];      // GUARD: [group][2 * component + (0 = hi, 1 = lo)][lane]
     const int tid = threadIdx.x;
     const uint32_t i0 = blockIdx.x * ROWS;
     const uint32_t j0 = blockIdx.y * j_per_chunk;
@@ -127,6 +139,12 @@ __device__ __forceinline__ void fj_mx_body(const float4* __restrict__ xh, const 
     for (int g = 0; g < NG; ++g) {
         ax[g] = ay[g] = az[g] = jx[g] = jy[g] = jz[g] = zero;
         AX[g] = AY[g] = AZ[g] = JX[g] = JY[g] = JZ[g] = zero;
+    }
+    if constexpr (GUARD) {
+#pragma unroll
+        for (int g = 0; g < NG; ++g)
+#pragma unroll
+            for (int k = 0; k < 12; ++k) nearw[g][k][tid] = zero;         // a lane reads and writes its own words only: no barrier
     }
     const nb_f2 e2 = nb_f2{eps2, eps2};
     const nb_f2 m3 = nb_f2{-3.0f, -3.0f};
@@ -230,18 +248,63 @@ __device__ __forceinline__ void fj_mx_body(const float4* __restrict__ xh, const 
         for (int c = 0; c < NC; ++c) dv[c] = __builtin_elementwise_fma(rv[c], dy[c], dv[c]);
 #pragma unroll
         for (int c = 0; c < NC; ++c) dw[c] = __builtin_elementwise_fma(rv[c], dz[c], dw[c]);
+        auto fast = [&]() {
 #pragma unroll
-        for (int c = 0; c < NC; ++c) jx[c % NG] = __builtin_elementwise_fma(s[c], du[c], jx[c % NG]);
+            for (int c = 0; c < NC; ++c) jx[c % NG] = __builtin_elementwise_fma(s[c], du[c], jx[c % NG]);
 #pragma unroll
-        for (int c = 0; c < NC; ++c) jy[c % NG] = __builtin_elementwise_fma(s[c], dv[c], jy[c % NG]);
+            for (int c = 0; c < NC; ++c) jy[c % NG] = __builtin_elementwise_fma(s[c], dv[c], jy[c % NG]);
 #pragma unroll
-        for (int c = 0; c < NC; ++c) jz[c % NG] = __builtin_elementwise_fma(s[c], dw[c], jz[c % NG]);
+            for (int c = 0; c < NC; ++c) jz[c % NG] = __builtin_elementwise_fma(s[c], dw[c], jz[c % NG]);
 #pragma unroll
-        for (int c = 0; c < NC; ++c) ax[c % NG] = __builtin_elementwise_fma(s[c], dx[c], ax[c % NG]);
+            for (int c = 0; c < NC; ++c) ax[c % NG] = __builtin_elementwise_fma(s[c], dx[c], ax[c % NG]);
 #pragma unroll
-        for (int c = 0; c < NC; ++c) ay[c % NG] = __builtin_elementwise_fma(s[c], dy[c], ay[c % NG]);
+            for (int c = 0; c < NC; ++c) ay[c % NG] = __builtin_elementwise_fma(s[c], dy[c], ay[c % NG]);
 #pragma unroll
-        for (int c = 0; c < NC; ++c) az[c % NG] = __builtin_elementwise_fma(s[c], dz[c], az[c % NG]);
+            for (int c = 0; c < NC; ++c) az[c % NG] = __builtin_elementwise_fma(s[c], dz[c], az[c % NG]);
+        };
+        if constexpr (!GUARD) fast();
+        else {
+            bool nr[NC][2];
+            bool hit = false;
+#pragma unroll
+            for (int c = 0; c < NC; ++c) {
+                nr[c][0] = d2[c].x < near2; nr[c][1] = d2[c].y < near2;
+                hit |= nr[c][0] | nr[c][1];
+            }
+            if (__builtin_amdgcn_ballot_w64(hit) == 0) fast();      // wave-uniform: no lane has a near pair among these JB rows
+            else {
+                nb_f2 wn[NC], wf[NC];
+#pragma unroll
+                for (int c = 0; c < NC; ++c) {
+                    wn[c] = nb_f2{nr[c][0] ? s[c].x : 0.0f, nr[c][1] ? s[c].y : 0.0f};
+                    wf[c] = nb_f2{nr[c][0] ? 0.0f : s[c].x, nr[c][1] ? 0.0f : s[c].y};
+                }
+                // one component: the far fma, then the near TwoSum; c = u * NG + g: a row meets its pairs in ascending j
+                auto both = [&](const nb_f2 (&term)[NC], nb_f2 (&far)[NG], int k) {
+#pragma unroll
+                    for (int c = 0; c < NC; ++c) far[c % NG] = __builtin_elementwise_fma(wf[c], term[c], far[c % NG]);
+#pragma unroll
+                    for (int g = 0; g < NG; ++g) {
+                        nb_f2 hi = nearw[g][2 * k][tid], lo = nearw[g][2 * k + 1][tid];
+#pragma unroll
+                        for (int u = 0; u < JB; ++u) {
+                            const nb_f2 p = wn[u * NG + g] * term[u * NG + g];
+                            const nb_f2 sm = hi + p;
+                            const nb_f2 bb = sm - hi;
+                            const nb_f2 hs = sm - bb;
+                            const nb_f2 e0 = hi - hs;
+                            const nb_f2 e1 = p - bb;
+                            const nb_f2 e = e0 + e1;
+                            hi = sm;
+                            lo = lo + e;
+                        }
+                        nearw[g][2 * k][tid] = hi; nearw[g][2 * k + 1][tid] = lo;
+                    }
+                };
+                both(du, jx, 3); both(dv, jy, 4); both(dw, jz, 5);
+                both(dx, ax, 0); both(dy, ay, 1); both(dz, az, 2);
+            }
+        }
     };
     auto flush = [&]() {
 #pragma unroll
@@ -272,13 +335,32 @@ __device__ __forceinline__ void fj_mx_body(const float4* __restrict__ xh, const 
     }
     flush();
 
-    float4* oa = pa + (size_t)blockIdx.y * ni;
-    float4* oj = pj + (size_t)blockIdx.y * ni;
+    if constexpr (GUARD) {
+        double4* oa = pa + (size_t)blockIdx.y * ni;
+        double4* oj = pj + (size_t)blockIdx.y * ni;
 #pragma unroll
-    for (int g = 0; g < NG; ++g) {
-        const uint32_t il0 = i0 + (2 * g) * kBlock + tid, il1 = il0 + kBlock;
-        if (il0 < ni) { oa[il0] = float4{AX[g].x, AY[g].x, AZ[g].x, 0.0f}; oj[il0] = float4{JX[g].x, JY[g].x, JZ[g].x, 0.0f}; }
-        if (il1 < ni) { oa[il1] = float4{AX[g].y, AY[g].y, AZ[g].y, 0.0f}; oj[il1] = float4{JX[g].y, JY[g].y, JZ[g].y, 0.0f}; }
+        for (int g = 0; g < NG; ++g) {
+            const uint32_t il0 = i0 + (2 * g) * kBlock + tid, il1 = il0 + kBlock;
+            const nb_f2 far[6] = {AX[g], AY[g], AZ[g], JX[g], JY[g], JZ[g]};
+            double r0[6], r1[6];
+#pragma unroll
+            for (int k = 0; k < 6; ++k) {
+                const nb_f2 hi = nearw[g][2 * k][tid], lo = nearw[g][2 * k + 1][tid];
+                r0[k] = ((double)far[k].x + (double)hi.x) + (double)lo.x;
+                r1[k] = ((double)far[k].y + (double)hi.y) + (double)lo.y;
+            }
+            if (il0 < ni) { oa[il0] = double4{r0[0], r0[1], r0[2], 0.0}; oj[il0] = double4{r0[3], r0[4], r0[5], 0.0}; }
+            if (il1 < ni) { oa[il1] = double4{r1[0], r1[1], r1[2], 0.0}; oj[il1] = double4{r1[3], r1[4], r1[5], 0.0}; }
+        }
+    } else {
+        float4* oa = pa + (size_t)blockIdx.y * ni;
+        float4* oj = pj + (size_t)blockIdx.y * ni;
+#pragma unroll
+        for (int g = 0; g < NG; ++g) {
+            const uint32_t il0 = i0 + (2 * g) * kBlock + tid, il1 = il0 + kBlock;
+            if (il0 < ni) { oa[il0] = float4{AX[g].x, AY[g].x, AZ[g].x, 0.0f}; oj[il0] = float4{JX[g].x, JY[g].x, JZ[g].x, 0.0f}; }
+            if (il1 < ni) { oa[il1] = float4{AX[g].y, AY[g].y, AZ[g].y, 0.0f}; oj[il1] = float4{JX[g].y, JY[g].y, JZ[g].y, 0.0f}; }
+        }
     }
 }
 

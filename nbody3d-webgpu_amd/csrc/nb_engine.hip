@@ -648,6 +648,7 @@ struct hermite_order {
     void* nb_sim::*part;              // the partial sums the order's passes write (planes x chunks x n rows) ...
     uint32_t nb_sim::*chunks, nb_sim::*per;      // ... and the j-chunks of its full pass
     bool mixed;                       // the [1] entries are binary32 kernels on an f64 handle's streams (nb_set_pass_precision): f32 shapes and partial rows
+    bool guard = false;               // ... with guarded sums (nb_set_pass_guard): the pass takes near2 last and leaves fp64 partial rows
 };
 
 #define NB_BOTH(K) {(const void*)&nb::K<float>, (const void*)&nb::K<double>}
@@ -686,9 +687,19 @@ const hermite_order kMixed = {
     {nullptr, (const void*)&nb::nb_mx_predict<>}, {nullptr, (const void*)&nb::nb_hermite_correct<double>},
     {nullptr, (const void*)&nb::nb_mx_blk_predict<>}, {nullptr, (const void*)&nb::nb_blk_correct<float, double>},
     &nb_sim::fj_part, &nb_sim::mx_chunks, &nb_sim::mx_per, true};
+// ... and with a guard radius (nb_set_pass_guard, kernels/guard.hip.h): kMixed's streams, predictors, shapes and j-chunks; the passes
+// leave fp64 partial rows, which the native pass's reduce and block corrector sum.
+const hermite_order kGuard = {
+    "hermite4_", 2, 3, 4, {nb::kFjRows, nb::kFjRows}, {nb::kFjRows, nb::kFjRows},
+    {nullptr, (const void*)&nb::nb_mxg_fj<nb::kFjNG>},
+    {nullptr, (const void*)&nb::nb_fj_reduce<double, double>},
+    {nullptr, (const void*)&nb::nb_mxg_blk_fj<2>}, (const void*)&nb::nb_mxg_blk_fj<1>,
+    {nullptr, (const void*)&nb::nb_mx_predict<>}, {nullptr, (const void*)&nb::nb_hermite_correct<double>},
+    {nullptr, (const void*)&nb::nb_mx_blk_predict<>}, {nullptr, (const void*)&nb::nb_blk_correct<double, double>},
+    &nb_sim::fj_part, &nb_sim::mx_chunks, &nb_sim::mx_per, true, true};
 
-// The one place the pass precision is read for a step: the description everything below works from.
-const hermite_order& order_of(const nb_sim* s) { return s->mx ? kMixed : s->h6 ? kOrder6 : kOrder4; }
+// The one place the pass precision and the guard are read for a step: the description everything below works from.
+const hermite_order& order_of(const nb_sim* s) { return s->mx ? (s->mx_guard > 0.0 ? kGuard : kMixed) : s->h6 ? kOrder6 : kOrder4; }
 
 // Sets the j-chunks of the order's full pass on the handle: chunk_shape with the pass's own rows per workgroup.
 void set_chunks(nb_sim* s, const hermite_order& o) { chunk_shape(s->n, o.rows[s->f64], s->n_cu, &(s->*o.chunks), &(s->*o.per)); }
@@ -747,17 +758,27 @@ void launch_pass(nb_sim* s, const hermite_order& o, void** in, void** out, uint3
         fn = sh.rows == o.gather_rows[s->f64] ? o.gather[s->f64] : o.gather_ng1;
     }
     pass_parts part = {sh.chunks, {}};
-    for (uint32_t p = 0; p < o.planes; ++p) part.plane[p] = (char*)(s->*o.part) + p * ((size_t)4 * (wide ? 8 : 4) * sh.chunks * irows);
+    for (uint32_t p = 0; p < o.planes; ++p) part.plane[p] = (char*)(s->*o.part) + p * ((size_t)4 * (wide || o.guard ? 8 : 4) * sh.chunks * irows);
     double e2 = s->eps2, G = s->G;
-    float e2f = (float)s->eps2;
+    float e2f = (float)s->eps2, near2 = (float)(s->mx_guard * s->mx_guard);
     const void* zr = s->zero_row;
     kernel_args a;
     a(in, o.inputs);
     if (na) a(&s->blk_act)(&na);
     a(part.plane, o.planes)(&n)(&sh.per);
     if (wide) a(&e2); else a(&e2f)(&zr);
+    if (o.guard) a(&near2);
     (void)hipLaunchKernel(fn, dim3(ceil_div(irows, sh.rows), sh.chunks), dim3(nb::kBlock), a.v, 0, s->stream);
-    if (na) { *got = part; return; }
+    if (na) {
+        if (o.guard && part.chunks > nb::kGuardFoldFrom) {      // many fp64 chunk rows of few bodies: added here, in the corrector's order, into chunk row 0
+            kernel_args f;
+            f(part.plane, o.planes)(&na)(&part.chunks);
+            (void)hipLaunchKernel((const void*)&nb::nb_mxg_fold<>, dim3(na), dim3(nb::kBlock), f.v, 0, s->stream);
+            part.chunks = 1;
+        }
+        *got = part;
+        return;
+    }
     kernel_args r;
     r(part.plane, o.planes)(&n)(&part.chunks)(&G)(out, o.planes);
     (void)hipLaunchKernel(o.reduce[s->f64], dim3(ceil_div(n, nb::kBlock)), dim3(nb::kBlock), r.v, 0, s->stream);
@@ -784,7 +805,7 @@ int ensure_derivs(nb_sim* s, const char* who)
     if (s->derivs_ok && s->derivs_G == s->G) return NB_OK;
     s->snap_ok = false;      // an order-6 handle's snap and crackle belong to the (a, j) replaced here, whoever asked for them: its start runs again
     void *in[] = {s->bodies[0], s->vel}, *out[] = {s->acc, s->jerk};
-    if (s->mx) { launch_split(s); launch_pass(s, kMixed, s->mx_in, out); }      // (a mixed handle is of order 4)
+    if (s->mx) { launch_split(s); launch_pass(s, order_of(s), s->mx_in, out); }      // (a mixed handle is of order 4)
     else launch_pass(s, kOrder4, in, out);
     NB_HIP(s, hipGetLastError());
     s->derivs_ok = true; s->derivs_any_G = false; s->derivs_G = s->G;
@@ -857,7 +878,7 @@ void h6_release(nb_sim* s)
 void mx_release(nb_sim* s)
 {
     for (void*& p : s->mx_in) { if (p) (void)hipFree(p); p = nullptr; }
-    s->mx = false;
+    s->mx = false; s->mx_guard = 0.0;
 }
 
 // what nb_variant_name and nb_shape_info report: the pass a step of the handle runs
@@ -866,7 +887,7 @@ void hermite_names(nb_sim* s)
     const hermite_order& o = order_of(s);
     const uint32_t c = s->*o.chunks, per = s->*o.per;
     s->jsplit = c; s->j_per_split = per;
-    s->variant = std::string(o.name) + (o.mixed ? "f64mx" : s->f64 ? "f64" : "f32pk") + "_c" + std::to_string(c) + "_j" + std::to_string(per);
+    s->variant = std::string(o.name) + (o.guard ? "f64mxg" : o.mixed ? "f64mx" : s->f64 ? "f64" : "f32pk") + "_c" + std::to_string(c) + "_j" + std::to_string(per);
 }
 
 // ---- block individual time steps (nb_set_block_steps, nb_set_block_steps6; kernels/block.hip.h, kernels/block6.hip.h) ----------
@@ -1860,6 +1881,43 @@ int nb_pass_precision(nb_sim* s, uint32_t* mode)
     if (!mode) return fail(s, NB_ERR_INVALID, "nb_pass_precision: mode is NULL");
     if (!s->hermite) return fail(s, NB_ERR_STATE, "nb_pass_precision: needs a Hermite handle (nb_config.integrator = NB_INT_HERMITE4)");
     *mode = s->mx ? NB_PASS_MIXED : NB_PASS_NATIVE;
+    return NB_OK;
+}
+
+int nb_set_pass_guard(nb_sim* s, double r_near)
+{
+    if (!s) return fail(nullptr, NB_ERR_INVALID, "nb_set_pass_guard: null handle");
+    if (!(r_near >= 0.0) || std::isinf(r_near)) return fail(s, NB_ERR_INVALID, "nb_set_pass_guard: r_near must be finite and >= 0 (0 switches the guard off)");
+    if (!s->hermite) return fail(s, NB_ERR_STATE, "nb_set_pass_guard: needs a Hermite handle (nb_config.integrator = NB_INT_HERMITE4) whose pass precision is NB_PASS_MIXED (nb_set_pass_precision)");
+    if (!s->f64) return fail(s, NB_ERR_STATE, "nb_set_pass_guard: precision NB_F32: the guard belongs to the mixed pass of NB_F64 handles (nb_set_pass_precision)");
+    if (s->h6) return fail(s, NB_ERR_STATE, "nb_set_pass_guard: the handle's order is 6 (nb_set_hermite_order): the mixed pass (nb_set_pass_precision) and its guard exist at order 4 only");
+    if (!s->mx) return fail(s, NB_ERR_STATE, "nb_set_pass_guard: the pass precision is NB_PASS_NATIVE: set NB_PASS_MIXED first (nb_set_pass_precision)");
+    if ((r_near > 0.0) == (s->mx_guard > 0.0)) { s->mx_guard = r_near; return NB_OK; }      // another radius, or off and off: the kernels and the rows stay
+    NB_HIP(s, hipSetDevice(s->device));
+    NB_HIP(s, hipStreamSynchronize(s->stream));
+    // Neither direction touches the state, the derivatives or the levels.  The guarded passes leave fp64 partial rows in the mixed
+    // pass's j-chunks: twice the bytes.  (Grown once; a handle keeps the larger buffer.)
+    const size_t need = (size_t)2 * 32 * s->mx_chunks * s->n;
+    if (r_near > 0.0 && need > s->fj_part_bytes) {
+        void* grown = nullptr;
+        const hipError_t e = hipMalloc(&grown, need);
+        if (e != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(s, NB_ERR_HIP, std::string("nb_set_pass_guard: ") + hipGetErrorString(e));
+        }
+        (void)hipFree(s->fj_part); s->fj_part = grown; s->fj_part_bytes = need;
+    }
+    s->mx_guard = r_near;
+    hermite_names(s);
+    return NB_OK;
+}
+
+int nb_pass_guard(nb_sim* s, double* r_near)
+{
+    if (!s) return fail(nullptr, NB_ERR_INVALID, "nb_pass_guard: null handle");
+    if (!r_near) return fail(s, NB_ERR_INVALID, "nb_pass_guard: r_near is NULL");
+    if (!s->hermite) return fail(s, NB_ERR_STATE, "nb_pass_guard: needs a Hermite handle (nb_config.integrator = NB_INT_HERMITE4)");
+    *r_near = s->mx ? s->mx_guard : 0.0;
     return NB_OK;
 }
 

@@ -188,6 +188,7 @@ struct nb_sim {
     bool mx = false;
     void* mx_in[3] = {nullptr, nullptr, nullptr};   // (xh, mf), xl, vf: n float4 rows each, rewritten by every predictor / split
     uint32_t mx_chunks = 1, mx_per = 0;   // the mixed pass's j-chunks (kFjRows i-bodies per workgroup) and bodies per chunk
+    double mx_guard = 0.0;         // nb_set_pass_guard: r_near; > 0: the guarded kernels (kernels/guard.hip.h) and fp64 partial rows.  0 whenever !mx
     size_t fj_part_bytes = 0;      // what fj_part holds (grown when the mixed shape needs more than the native one)
     uint32_t start6 = 0;           // nb_set_start6: NB_START6_ZERO | NB_START6_CRACKLE, what the engine's own starts (and start levels) are made by
     bool start_own = false;        // snap / crackle came from the engine's start and no step has consumed them (nb_set_start6 may drop them)

@@ -70,6 +70,7 @@
 #include "kernels/split_lists.hip.h" // nb_spl_pk, nb_spl64, nb_spl_rows (nb_split_lists: the two sums and the neighbour rows from one pass)
 #include "kernels/block.hip.h"       // nb_blk_start, nb_blk_sched, nb_blk_predict, nb_blk_fj_pk, nb_blk_fj64, nb_blk_correct (nb_set_block_steps)
 #include "kernels/mixed.hip.h"       // nb_mx_split, nb_mx_predict, nb_mx_blk_predict, nb_mx_fj, nb_mx_blk_fj (nb_set_pass_precision: double-single force+jerk pass of f64 handles)
+#include "kernels/guard.hip.h"       // nb_mxg_fj, nb_mxg_blk_fj, nb_mxg_fold (nb_set_pass_guard: the mixed pass with guarded sums, fp64 partial rows)
 #include "kernels/ac_scheme.hip.h"   // nb_ac_sub32, nb_ac_sub64, nb_ac_predict0, nb_ac_regular, nb_ac_start (nb_set_neighbor_scheme: the Ahmad-Cohen neighbour scheme)
 #include "kernels/ac_levels.hip.h"   // nb_ac_lv_start, nb_ac_lv_begin, nb_ac_lv_sub32, nb_ac_lv_sub64 (nb_set_neighbor_levels: block individual irregular steps)
 #include "kernels/hermite6.hip.h"    // nb_h6_fjs_pk, nb_h6_fjs64, nb_h6_reduce, nb_h6_predict, nb_h6_correct (nb_set_hermite_order(6): force, jerk and snap); nb_h6_crk_pk, nb_h6_crk64, nb_h6_reduce1 (nb_set_start6: the crackle of a start)

@@ -70,6 +70,8 @@ static int (*p_set_start6)(nb_sim *, uint32_t);                         /* the s
 static int (*p_start6)(nb_sim *, uint32_t *);
 static int (*p_set_pass_precision)(nb_sim *, uint32_t);                 /* the mixed-precision pass of f64 Hermite handles (round 23): optional */
 static int (*p_pass_precision)(nb_sim *, uint32_t *);
+static int (*p_set_pass_guard)(nb_sim *, double);                       /* the guard radius of the mixed pass (round 24): optional */
+static int (*p_pass_guard)(nb_sim *, double *);
 static int (*p_set_block_steps)(nb_sim *, const nb_block_steps *);      /* block time steps, also within ABI 2.4: optional symbols */
 static int (*p_block_stats)(nb_sim *, struct nb_block_stats *, int);
 static int (*p_download_levels)(nb_sim *, uint8_t *);
@@ -190,6 +192,8 @@ static napi_value js_load(napi_env env, napi_callback_info info)
         *(void **)(&p_start6) = dlsym(h, "nb_start6");
         *(void **)(&p_set_pass_precision) = dlsym(h, "nb_set_pass_precision");
         *(void **)(&p_pass_precision) = dlsym(h, "nb_pass_precision");
+        *(void **)(&p_set_pass_guard) = dlsym(h, "nb_set_pass_guard");
+        *(void **)(&p_pass_guard) = dlsym(h, "nb_pass_guard");
         *(void **)(&p_block_stats) = dlsym(h, "nb_block_stats");
         *(void **)(&p_download_levels) = dlsym(h, "nb_download_levels");
         *(void **)(&p_upload_levels) = dlsym(h, "nb_upload_levels");
@@ -1203,6 +1207,35 @@ static napi_value js_pass_precision(napi_env env, napi_callback_info info)
     return out;
 }
 
+/* setPassGuard(handle, rNear): nb_set_pass_guard -- 0 switches the guard off. */
+static napi_value js_set_pass_guard(napi_env env, napi_callback_info info)
+{
+    size_t argc = 2; napi_value argv[2];
+    CHECK_NAPI(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    if (argc < 2) { napi_throw_type_error(env, NULL, "setPassGuard(handle, rNear)"); return NULL; }
+    handle_t *h = pass_handle(env, argv[0], (const void *)p_set_pass_guard, "nb_set_pass_guard"); if (!h) return NULL;
+    double r_near = 0.0;
+    CHECK_NAPI(env, napi_get_value_double(env, argv[1], &r_near));
+    int rc = p_set_pass_guard(h->sim, r_near);
+    if (rc != NB_OK) return throw_nb(env, rc, h->sim, "nb_set_pass_guard");
+    return undefined(env);
+}
+
+/* passGuard(handle) -> the guard radius (0: off): nb_pass_guard. */
+static napi_value js_pass_guard(napi_env env, napi_callback_info info)
+{
+    size_t argc = 1; napi_value argv[1];
+    CHECK_NAPI(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    if (argc < 1) { napi_throw_type_error(env, NULL, "passGuard(handle)"); return NULL; }
+    handle_t *h = pass_handle(env, argv[0], (const void *)p_pass_guard, "nb_pass_guard"); if (!h) return NULL;
+    double r_near = 0.0;
+    int rc = p_pass_guard(h->sim, &r_near);
+    if (rc != NB_OK) return throw_nb(env, rc, h->sim, "nb_pass_guard");
+    napi_value out;
+    CHECK_NAPI(env, napi_create_double(env, r_near, &out));
+    return out;
+}
+
 /* start6(handle) -> 0 or 1: nb_start6. */
 static napi_value js_start6(napi_env env, napi_callback_info info)
 {
@@ -1631,6 +1664,7 @@ static napi_value init_module(napi_env env, napi_value exports)
         {"fieldEval", js_field_eval}, {"downloadJerk", js_download_jerk}, {"uploadDerivs", js_upload_derivs},
         {"setHermiteOrder", js_set_hermite_order}, {"hermiteOrder", js_hermite_order}, {"downloadSnap", js_download_snap}, {"uploadDerivs6", js_upload_derivs6},
         {"setStart6", js_set_start6}, {"start6", js_start6}, {"setPassPrecision", js_set_pass_precision}, {"passPrecision", js_pass_precision},
+        {"setPassGuard", js_set_pass_guard}, {"passGuard", js_pass_guard},
         {"setBlockSteps", js_set_block_steps}, {"setBlockSteps6", js_set_block_steps6}, {"blockStats", js_block_stats}, {"downloadLevels", js_download_levels},
         {"uploadLevels", js_upload_levels}, {"neighbors", js_neighbors}, {"neighborLists", js_neighbor_lists},
         {"knn", js_knn}, {"listForce", js_list_force}, {"splitForce", js_split_force}, {"splitLists", js_split_lists}, {"neighborSchemeFused", js_neighbor_scheme_fused},

@@ -260,6 +260,22 @@ class Simulation {
     return addon.passPrecision(this._h) === 1 ? 'mixed' : 'native';
   }
 
+  /** The guard radius of the mixed pass (nb_set_pass_guard; no reference analogue; 0: off): the terms of pairs closer than rNear are
+   *  summed apart from the binary32 registers, compensated, so that a hard pair's members and its barycentre keep the field of the
+   *  rest of the system.  Valid while the pass precision is 'mixed'; touches no state, derivatives or levels. */
+  setPassGuard(rNear) {
+    if (typeof rNear !== 'number') throw new TypeError(`setPassGuard(): rNear must be a number, not ${typeof rNear}`);
+    this._need();
+    addon.setPassGuard(this._h, rNear);
+    return this;
+  }
+
+  /** The guard radius, 0 where the guard is off (nb_pass_guard). */
+  passGuard() {
+    this._need();
+    return addon.passGuard(this._h);
+  }
+
   /** Block individual time steps of a 'hermite4' simulation (nb_set_block_steps; no reference analogue): every body steps by
    *  dt / 2^level, minLevel <= level <= maxLevel, chosen from its own derivatives with the accuracy parameter eta; step() and
    *  simulate() still advance by whole dt.  {eta, maxLevel, minLevel, frozen}: missing eta / maxLevel take the library's defaults

@@ -201,7 +201,8 @@ SYMBOLS = ["nb_abi_version", "nb_device_count", "nb_create", "nb_destroy", "nb_u
            "nb_set_neighbor_adapt", "nb_neighbor_adapt_stats", "nb_download_neighbor_radii", "nb_upload_neighbor_scheme",
            "nb_set_neighbor_levels", "nb_neighbor_level_stats", "nb_download_neighbor_levels", "nb_upload_neighbor_levels",
            "nb_set_hermite_order", "nb_hermite_order", "nb_download_snap", "nb_upload_derivs6",
-           "nb_set_block_steps6", "nb_set_start6", "nb_start6", "nb_set_pass_precision", "nb_pass_precision"]
+           "nb_set_block_steps6", "nb_set_start6", "nb_start6", "nb_set_pass_precision", "nb_pass_precision",
+           "nb_set_pass_guard", "nb_pass_guard"]
 
 START6_ZERO, START6_CRACKLE = 0, 1      # nb_set_start6
 PASS_NATIVE, PASS_MIXED = 0, 1          # nb_set_pass_precision
@@ -337,6 +338,9 @@ def load_library():
     if hasattr(L, "nb_set_pass_precision"):     # the mixed-precision force+jerk pass of f64 Hermite handles, likewise
         L.nb_set_pass_precision.argtypes = [vp, C.c_uint32]
         L.nb_pass_precision.argtypes = [vp, C.POINTER(C.c_uint32)]
+    if hasattr(L, "nb_set_pass_guard"):         # the guard radius of the mixed pass, likewise
+        L.nb_set_pass_guard.argtypes = [vp, C.c_double]
+        L.nb_pass_guard.argtypes = [vp, C.POINTER(C.c_double)]
     if hasattr(L, "nb_eqm_info"):           # the equal-mass kernels' report, also within 2.4 and detected by the symbol
         L.nb_eqm_info.argtypes = [vp, C.POINTER(C.c_int)]
     if hasattr(L, "nb_eqm_form"):           # which of the equal-mass forms, likewise
@@ -967,6 +971,27 @@ class Simulation:
         m = C.c_uint32()
         self._check(self._L.nb_pass_precision(self._h, C.byref(m)))
         return "mixed" if m.value == PASS_MIXED else "native"
+
+    def set_pass_guard(self, r_near):
+        """nb_set_pass_guard: the guard radius of the mixed pass (0: off).  The terms of pairs closer than r_near are summed apart
+        from the binary32 registers, compensated (TwoSum), so that a hard pair's members -- and the pair's barycentre -- keep the
+        field of the rest of the system.  Valid while the pass precision is "mixed"; touches no state, derivatives or levels."""
+        try:
+            r_near = float(r_near)
+        except (TypeError, ValueError):
+            raise ValueError("set_pass_guard(): r_near must be a number, not %r" % (r_near,))
+        if not hasattr(self._L, "nb_set_pass_guard"):
+            raise NBodyError(1, "set_pass_guard(): the loaded library has no nb_set_pass_guard")
+        self._check(self._L.nb_set_pass_guard(self._h, r_near))
+        return self
+
+    def pass_guard(self):
+        """nb_pass_guard: the guard radius, 0.0 where the guard is off."""
+        if not hasattr(self._L, "nb_pass_guard"):
+            raise NBodyError(1, "pass_guard(): the loaded library has no nb_pass_guard")
+        r = C.c_double()
+        self._check(self._L.nb_pass_guard(self._h, C.byref(r)))
+        return float(r.value)
 
     # -- block individual time steps of a Hermite handle -----------------------
     def _need_block(self, what):
