@@ -84,7 +84,9 @@ extern "C" {
                              2.4 (round 23) likewise within 2.4: nb_set_pass_precision, nb_pass_precision, NB_PASS_*.  Detected by the presence
                                             of the symbol nb_set_pass_precision
                              2.4 (round 24) likewise within 2.4: nb_set_pass_guard, nb_pass_guard.  Detected by the presence of the symbol
-                                            nb_set_pass_guard */
+                                            nb_set_pass_guard
+                             2.4 (round 25) likewise within 2.4: nb_set_block_batch, nb_block_batch_stats, nb_block_batch,
+                                            NB_BLOCK_BATCH_SMALL_DEFAULT.  Detected by the presence of the symbol nb_set_block_batch */
 
 typedef struct nb_sim nb_sim; /* opaque */
 
@@ -501,7 +503,8 @@ int nb_upload_derivs(nb_sim *s, const void *accel, const void *jerk);
  *   - HOST SYNCHRONISATION (this first version's design).  nb_step on a block handle synchronises with the device ONCE PER BLOCK STEP:
  *     the host reads a small header (active count, next block time) from pinned memory and sizes the next launches by it; the
  *     clamp count and the finest level stay on the device until nb_block_stats asks.  Such a step cannot be captured into a
- *     caller's graph; ext_stream keeps working otherwise.
+ *     caller's graph; ext_stream keeps working otherwise.  nb_set_block_batch (below) lets block steps with a small active set run
+ *     from the device's own header, many of them per host wait.
  *   - nb_force_pass still runs the full N x N pass into scratch.  nb_enable_timing / nb_step_times2 report one OUTER step per launch:
  *     force_ms is its whole span, integrate_ms = 0 (as on a fused handle).  nb_variant_name is unchanged.
  *   - binary32 handles store the state, a and j in binary32: below steps of about dt / 2^10 (Plummer units) a3 is rounding noise and
@@ -537,6 +540,58 @@ int nb_block_stats(nb_sim *s, struct nb_block_stats *out, int reset);
  * (NB_ERR_STATE otherwise).  upload_levels is the last call of a checkpoint restore. */
 int nb_download_levels(nb_sim *s, uint8_t *levels /* n */);       /* blocks; initialises the levels first if they are not current */
 int nb_upload_levels(nb_sim *s, const uint8_t *levels /* n */);   /* after nb_upload (+ nb_upload_derivs): marks the levels current */
+
+/* ---- batched block steps (round 25): small block steps sized on the device, many per host wait ----------------------------------
+ * An opt-in mode of order-4 block-step handles with the native pass.  The scheme of an outer step is the one above (1-7); only who
+ * sizes the launches changes.  A SLOT is the launches of one block step with every grid fixed by (n, small_max, CU count): it
+ * schedules, predicts every body and reads the header on the device.
+ *   - 0 < |A| <= small_max and t_next != 2^L: the slot runs a SMALL step -- a force+jerk pass and a corrector shaped for a small set
+ *     (kernels/block_batch.hip.h); criterion, new levels and due are the block corrector's arithmetic.
+ *   - otherwise the slot PARKS: its schedule and prediction stand, every later slot of the batch is idle, and after its wait the
+ *     host runs that block step through the existing gathered path (a HOST step).  t_next == 2^L always parks: a batch never
+ *     crosses an outer step.
+ *   The host enqueues up to `depth` slots and waits ONCE per batch.  How many it enqueues is a function of what it has read so far
+ *   (one slot after nb_set_block_batch and after the levels went stale; then up to the next tick expected to park); no stored bit
+ *   and no nb_block_stats counter depends on it or on depth.
+ *   - With a fixed small_max, state, derivatives, levels and nb_block_stats do not depend on depth or on where batches end: nb_step(k)
+ *     equals k x nb_step(1), and a checkpoint (bodies, vel, accel, jerk, levels) restored by nb_upload, nb_upload_derivs,
+ *     nb_set_block_steps, nb_set_block_batch (same small_max, any depth), nb_upload_levels continues bit-identically.
+ *   - small_max = 0 is legal: no small steps, every block step is a host step, and every bit is that of a handle with the mode off.
+ *   - What a small step computes for a body depends on the predicted arrays and on n alone (its j-chunks are a function of n and
+ *     the CU count), not on |A|, on the body's place in the active list, on small_max or on depth.
+ *   - Which path a block step takes depends on small_max, and the two passes add in different orders: results for DIFFERENT small_max
+ *     agree to the pass's accuracy, not bit for bit.
+ *   - nb_block_stats keeps its meaning: block_steps and body_steps count small and host steps alike.  The header checks of nb_step
+ *     (NB_ERR_HIP with the numbers) apply at every wait.  nb_enable_timing, dt <= 0, stale levels, nb_download_levels /
+ *     nb_upload_levels, nb_force_pass and ext_stream are unchanged.
+ *   - nb_set_block_batch touches no state, no derivatives and no levels (none goes stale) and takes effect from the next nb_step.
+ *     NB_ERR_STATE (the message names the function and the reason): a leapfrog handle, a handle without nb_set_block_steps, an
+ *     order-6 handle, a handle with nb_set_pass_precision(NB_PASS_MIXED).  While the mode is on, nb_set_hermite_order(6) and
+ *     nb_set_pass_precision(NB_PASS_MIXED) return NB_ERR_STATE; nb_set_block_steps(NULL) switches the mode off too, a non-NULL
+ *     reconfiguration keeps it.  NB_ERR_INVALID (naming the field): a NULL handle, a wrong struct_size, depth > 1024, small_max >
+ *     1024 other than NB_BLOCK_BATCH_SMALL_DEFAULT, flags != 0. */
+#define NB_BLOCK_BATCH_SMALL_DEFAULT 0xffffffffu  /* small_max: the default (256); 0 itself means "no small steps" */
+typedef struct nb_block_batch {
+    uint32_t struct_size;  /* sizeof(nb_block_batch) */
+    uint32_t depth;        /* most block-step slots enqueued per host wait; 0 -> 32; at most 1,024 */
+    uint32_t small_max;    /* a block step with |A| <= small_max (and t_next != 2^L) runs as a small step; at most 1,024; 0: no small
+                              steps; NB_BLOCK_BATCH_SMALL_DEFAULT: 256 */
+    uint32_t flags;        /* must be 0 */
+} nb_block_batch;
+int nb_set_block_batch(nb_sim *s, const nb_block_batch *cfg /* NULL: off */);
+
+/* (a struct TAG without a typedef, as nb_block_stats) */
+struct nb_block_batch_stats {
+    uint32_t struct_size, enabled;
+    uint64_t host_waits;            /* hipStreamSynchronize calls of nb_step on this handle */
+    uint64_t slots;                 /* block-step slots enqueued */
+    uint64_t small_steps;           /* block steps done by a slot, no host in between */
+    uint64_t host_steps;            /* block steps sized by the host (the existing gathered path) */
+    uint64_t idle_slots;            /* slots that found nothing to do */
+};
+/* block_batch_stats: the counters since the last reset (set out->struct_size); reset != 0 zeroes them after the read.
+ * slots == small_steps + host_steps + idle_slots, host_steps <= host_waits <= slots. */
+int nb_block_batch_stats(nb_sim *s, struct nb_block_batch_stats *out, int reset);
 
 /* ---- viewer frame feed ------------------------------------------------
  * The reference's render pass reads bodyBuffer and velBuffer in place every frame

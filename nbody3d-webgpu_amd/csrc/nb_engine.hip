@@ -965,6 +965,116 @@ int block_step(nb_sim* s, uint32_t nsteps)
     return NB_OK;
 }
 
+// ---- nb_set_block_batch: block steps sized on the device, many per host wait (kernels/block_batch.hip.h) ----------
+// The j-chunks of the small pass: a function of n and the CU count alone (a row's bits must not depend on |A|, small_max or depth).
+// One chunk of whole tiles per CU: a wave's chain is a quarter of a chunk (64 rows of one tile up to 256 x CUs bodies), and the
+// corrector shares a slot's chunk rows among nb::kBbSumLanes lanes.
+void bb_shape(uint32_t n, int n_cu, uint32_t* chunks, uint32_t* per)
+{
+    const uint32_t tiles = ceil_div(n, (uint32_t)nb::kTile);
+    const uint32_t c = std::max(1u, std::min((uint32_t)n_cu, tiles));
+    *per = ceil_div(tiles, c) * nb::kTile;
+    *chunks = ceil_div(n, *per);
+}
+
+// How many slots the next batch has: a function of what the host has read so far.  Nothing read yet: one.  Otherwise up to the next
+// tick expected to park, that slot included: block times advance by the stride of the deepest level present, and ticks whose count
+// of trailing zeros reaches bb_park_ctz are expected to park (|A(t)| grows with ctz(t); 2^L always parks).
+uint32_t bb_plan_slots(const nb_sim* s)
+{
+    if (s->bb_fresh || s->bb_small_max == 0) return 1;
+    const uint32_t L = s->blk_L, fin = std::min(s->bb_finest, L);
+    const uint32_t z = std::max(std::min(s->bb_park_ctz, L), L - fin);
+    const uint64_t step = 1ull << z, stride = 1ull << (L - fin);
+    const uint64_t park = (s->bb_t / step + 1) * step;
+    const uint64_t count = (park - s->bb_t + stride - 1) / stride;
+    return (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(count, s->bb_depth));
+}
+
+// nb_step of an order-4 block-step handle with nb_set_block_batch on: block_step's outer step, with the slots of a batch enqueued
+// behind one another and ONE host wait per batch.  A slot that parked left its schedule and prediction: the host runs that block
+// step through the gathered path, as block_step does.
+int block_batch_step(nb_sim* s, uint32_t nsteps)
+{
+    const bool stale = s->levels != 2;
+    if (int rc = ensure_levels(s, "nb_step")) return rc;
+    if (stale) { s->bb_fresh = true; s->bb_t = 0; s->bb_park_ctz = s->blk_L; }
+    const hermite_order& o = order_of(s);
+    hermite_arrays h(s);
+    const uint32_t L = s->blk_L;
+    uint32_t n = s->n, lmin = s->blk_lmin, Lk = L, end = 1u << L, small_max = s->bb_small_max, chunks = s->bb_chunks, per = s->bb_per;
+    int frozen = s->blk_frozen ? 1 : 0;
+    double eta = s->blk_eta, dt = s->dt, G = s->G, tick = std::ldexp(s->dt, -(int)L), e2 = s->eps2;
+    float e2f = (float)s->eps2;
+    const void* zr = s->zero_row;
+    const size_t row = (size_t)4 * (s->f64 ? 8 : 4);
+    void* plane[2] = {s->bb_part, (char*)s->bb_part + row * chunks * nb::kBbMaxSmall};
+    const uint32_t gx_small = std::max(1u, ceil_div(small_max, s->f64 ? nb::kBbRows64 : nb::kBbRows));
+    auto enqueue_slot = [&](uint32_t first) {
+        void* sargs[] = {&s->blk_due, &s->blk_lev, &n, &s->blk_act, &s->blk_hdr, &s->blk_hdr_pub, &s->bb_words, &s->bb_pub, &first, &small_max, &end};
+        (void)hipLaunchKernel((const void*)&nb::nb_blkq_sched<nb::kBlkSched>, dim3(1), dim3(nb::kBlkSched), sargs, 0, s->stream);
+        kernel_args p;
+        p(h.state, o.states)(&s->blk_due)(&s->blk_lev)(h.in, o.inputs)(&n)(&s->blk_hdr)(&Lk)(&tick)(&s->bb_words);
+        (void)hipLaunchKernel(s->f64 ? (const void*)&nb::nb_blkq_predict<double> : (const void*)&nb::nb_blkq_predict<float>,
+                              dim3(ceil_div(n, nb::kBlock)), dim3(nb::kBlock), p.v, 0, s->stream);
+        if (small_max == 0) return;      // no small steps: every slot parks
+        kernel_args f;
+        f(h.in, o.inputs)(&s->blk_act)(&s->blk_hdr)(&s->bb_words)(&small_max)(plane, 2)(&n)(&per);
+        if (s->f64) f(&e2); else f(&e2f)(&zr);
+        (void)hipLaunchKernel(s->f64 ? (const void*)&nb::nb_blkq_fj64<double> : (const void*)&nb::nb_blkq_fj_pk<1>,
+                              dim3(gx_small, chunks), dim3(nb::kBlock), f.v, 0, s->stream);
+        kernel_args c;
+        c(plane, 2)(&s->blk_act)(&s->bb_words)(&small_max)(&chunks)(&G)(h.state, o.states)(&s->blk_due)(&s->blk_lev)(&s->blk_hdr)(&n)(&Lk)(&lmin)(&frozen)(&eta)(&dt);
+        (void)hipLaunchKernel(s->f64 ? (const void*)&nb::nb_blkq_correct<double, double> : (const void*)&nb::nb_blkq_correct<float, float>,
+                              dim3(ceil_div(small_max * nb::kBbSumLanes, nb::kBlock)), dim3(nb::kBlock), c.v, 0, s->stream);
+    };
+    for (uint32_t k = 0; k < nsteps; ++k) {
+        nb_events ev;
+        const bool rec = s->timing && get_events(s, &ev) == 0;
+        if (rec) NB_HIP(s, hipEventRecord(ev.e[0], s->stream));
+        for (;;) {
+            const uint32_t slots = bb_plan_slots(s);
+            for (uint32_t q = 0; q < slots; ++q) enqueue_slot(q == 0 ? 1u : 0u);
+            NB_HIP(s, hipGetLastError());
+            NB_HIP(s, hipStreamSynchronize(s->stream));      // the one host wait of a batch
+            ++s->bb_waits; s->bb_slots += slots;
+            const uint32_t na = s->blk_hdr_host[nb::kBlkCount], t_next = s->blk_hdr_host[nb::kBlkNext];
+            const uint32_t mode = s->bb_host[nb::kBbMode];
+            const uint32_t dsmall = s->bb_host[nb::kBbSmall] - s->bb_seen_small, dbody = s->bb_host[nb::kBbBody] - s->bb_seen_body;
+            s->bb_seen_small = s->bb_host[nb::kBbSmall]; s->bb_seen_body = s->bb_host[nb::kBbBody];
+            const bool parked = mode != nb::kBbModeSmall;
+            if (na == 0 || na > n || t_next == 0 || t_next > end || mode > nb::kBbModeParked || dsmall + (parked ? 1u : 0u) > slots ||
+                (uint64_t)dbody > (uint64_t)dsmall * small_max || (!parked && (na > small_max || t_next == end)))
+                return fail(s, NB_ERR_HIP, "nb_step: block schedule out of range (active " + std::to_string(na) + ", tick " + std::to_string(t_next) +
+                            ", batch of " + std::to_string(slots) + ": " + std::to_string(dsmall) + " small steps, mode " + std::to_string(mode) + ")");
+            s->bb_small += dsmall; s->blk_steps += dsmall; s->blk_body_steps += dbody;
+            s->bb_idle += slots - dsmall - (parked ? 1u : 0u);
+            // what the policy reads
+            s->bb_fresh = false;
+            s->bb_finest = s->bb_host[nb::kBbFinest];
+            s->bb_t = t_next == end ? 0u : t_next;
+            const uint32_t tz = (uint32_t)__builtin_ctz(t_next);
+            if (parked && t_next != end) s->bb_park_ctz = std::min(s->bb_park_ctz, tz);
+            else if (!parked && tz >= s->bb_park_ctz) s->bb_park_ctz = std::min(L, tz + 1);      // expected to park, and was small
+            if (!parked) continue;
+            pass_parts part;
+            uint32_t nah = na, tn = t_next;
+            launch_pass(s, o, h.in, nullptr, nah, &part);
+            kernel_args c;
+            c(part.plane, o.planes)(&s->blk_act)(&nah)(&part.chunks)(&G)(h.state, o.states)(&s->blk_due)(&s->blk_lev)(&s->blk_hdr)(&tn)(&Lk)(&lmin)(&frozen)(&eta)(&dt);
+            (void)hipLaunchKernel(o.blk_correct[s->f64], dim3(ceil_div(nah, nb::kBlock)), dim3(nb::kBlock), c.v, 0, s->stream);
+            ++s->bb_hoststeps; ++s->blk_steps; s->blk_body_steps += nah;
+            if (t_next == end) break;
+        }
+        if (rec) { NB_HIP(s, hipEventRecord(ev.e[1], s->stream)); ev.blk = true; s->pending.push_back(ev); }
+        NB_HIP(s, hipGetLastError());
+        ++s->blk_outer;
+        ++s->steps_done;
+        s->start_own = s->levels_own = false;
+    }
+    return NB_OK;
+}
+
 // ---- the Ahmad-Cohen neighbour scheme (nb_set_neighbor_scheme; kernels/ac_scheme.hip.h) ----------
 // One list build at the bodies: nb_split_force's four outputs into (ai, ji, ar, jr) and nb_neighbor_lists' rows and counts into
 // ac_list / ac_count, both through the engine's own entry points with device pointers, on the handle's stream -- or, where
@@ -1544,6 +1654,8 @@ void nb_destroy(nb_sim* s)
     if (s->sym_A) (void)hipFree(s->sym_A);
     for (void* p : {s->jerk, s->hx, s->hv, s->fj_part, (void*)s->blk_lev, (void*)s->blk_due, (void*)s->blk_act, (void*)s->blk_hdr}) if (p) (void)hipFree(p);
     if (s->blk_hdr_host) (void)hipHostFree(s->blk_hdr_host);
+    for (void* p : {(void*)s->bb_words, s->bb_part}) if (p) (void)hipFree(p);
+    if (s->bb_host) (void)hipHostFree(s->bb_host);
     ac_release(s);
     h6_release(s);
     mx_release(s);
@@ -1621,7 +1733,7 @@ int nb_step(nb_sim* s, uint32_t nsteps)
     if (!s->params_set) return fail(s, NB_ERR_STATE, "nb_step: nb_set_params has not been called");
     if (!(s->dt > 0.0)) return NB_OK;   // `if (dt > 0)` gate, nbody3d.js:474
     NB_HIP(s, hipSetDevice(s->device));
-    if (s->hermite) return s->ac ? ac_step(s, nsteps) : s->blk ? block_step(s, nsteps) : hermite_step(s, nsteps);
+    if (s->hermite) return s->ac ? ac_step(s, nsteps) : s->blk ? (s->bb ? block_batch_step(s, nsteps) : block_step(s, nsteps)) : hermite_step(s, nsteps);
     const bool exchange = s->xfn || s->rccl;
     ensure_pairs(s);      // the j-packed step's position copy, if something outside the step rewrote the positions or G
     if (gm_active(s) && !s->gm_ok) { if (int rc = finish_gather(s)) return rc; }
@@ -1799,6 +1911,7 @@ int nb_set_hermite_order(nb_sim* s, uint32_t order)
     if (!s) return fail(nullptr, NB_ERR_INVALID, "nb_set_hermite_order: null handle");
     if (order != 4 && order != 6) return fail(s, NB_ERR_INVALID, "nb_set_hermite_order: order must be 4 or 6");
     if (!s->hermite) return fail(s, NB_ERR_STATE, "nb_set_hermite_order: needs a Hermite handle (nb_config.integrator = NB_INT_HERMITE4)");
+    if (order == 6 && s->bb) return fail(s, NB_ERR_STATE, "nb_set_hermite_order: order = 6 while batched block steps are switched on (nb_set_block_batch): they exist at order 4 only, switch them off first");
     if (order == 6 && s->blk && !s->h6) return fail(s, NB_ERR_STATE, "nb_set_hermite_order: order = 6 while block steps are switched on (nb_set_block_steps): they exclude each other");
     if (order == 4 && s->blk && s->h6) return fail(s, NB_ERR_STATE, "nb_set_hermite_order: order = 4 while block steps of order 6 are switched on (nb_set_block_steps6): switch them off first");
     if (order == 6 && s->mx) return fail(s, NB_ERR_STATE, "nb_set_hermite_order: order = 6 while the pass precision is NB_PASS_MIXED (nb_set_pass_precision): the mixed pass exists at order 4 only, set NB_PASS_NATIVE first");
@@ -1844,6 +1957,7 @@ int nb_set_pass_precision(nb_sim* s, uint32_t mode)
     if (!s->f64) return fail(s, NB_ERR_STATE, "nb_set_pass_precision: precision NB_F32: the mixed pass keeps an fp64 state, it exists on NB_F64 handles only");
     if (s->h6) return fail(s, NB_ERR_STATE, "nb_set_pass_precision: the handle's order is 6 (nb_set_hermite_order): the mixed pass exists at order 4 only");
     if (s->ac) return fail(s, NB_ERR_STATE, "nb_set_pass_precision: the neighbour scheme is switched on (nb_set_neighbor_scheme): it has no mixed kernels");
+    if (mode == NB_PASS_MIXED && s->bb) return fail(s, NB_ERR_STATE, "nb_set_pass_precision: NB_PASS_MIXED while batched block steps are switched on (nb_set_block_batch): they run the native pass only, switch them off first");
     if ((mode == NB_PASS_MIXED) == s->mx) return NB_OK;
     NB_HIP(s, hipSetDevice(s->device));
     NB_HIP(s, hipStreamSynchronize(s->stream));
@@ -2013,7 +2127,7 @@ int nb_set_block_steps(nb_sim* s, const nb_block_steps* cfg)
 {
     if (!s) return fail(nullptr, NB_ERR_INVALID, "nb_set_block_steps: null handle");
     if (!s->hermite) return fail(s, NB_ERR_STATE, "nb_set_block_steps: needs a Hermite handle (nb_config.integrator = NB_INT_HERMITE4)");
-    if (!cfg) { s->blk = false; s->levels = 0; return NB_OK; }
+    if (!cfg) { s->blk = false; s->bb = false; s->levels = 0; return NB_OK; }      // (the batched mode belongs to the block steps: off with them)
     if (s->h6) return fail(s, NB_ERR_STATE, "nb_set_block_steps: the handle's order is 6 (nb_set_hermite_order): block steps and the 6th-order scheme exclude each other here, see nb_set_block_steps6");
     if (s->ac) return fail(s, NB_ERR_STATE, "nb_set_block_steps: the neighbour scheme is switched on (nb_set_neighbor_scheme): block steps and the neighbour scheme exclude each other");
     return blk_configure(s, cfg, "nb_set_block_steps");
@@ -2050,6 +2164,52 @@ int nb_block_stats(nb_sim* s, struct nb_block_stats* out, int reset)
         s->blk_outer = s->blk_steps = s->blk_body_steps = 0;
         NB_HIP(s, hipMemsetAsync(s->blk_hdr, 0, sizeof(uint32_t) * nb::kBlkWords, s->stream));
     }
+    return NB_OK;
+}
+
+int nb_set_block_batch(nb_sim* s, const nb_block_batch* cfg)
+{
+    if (!s) return fail(nullptr, NB_ERR_INVALID, "nb_set_block_batch: null handle");
+    if (!cfg) { s->bb = false; return NB_OK; }
+    if (cfg->struct_size != sizeof(nb_block_batch)) return fail(s, NB_ERR_INVALID, "nb_set_block_batch: struct_size must be sizeof(nb_block_batch)");
+    if (cfg->depth > 1024) return fail(s, NB_ERR_INVALID, "nb_set_block_batch: depth is at most 1024 (0: the default 32)");
+    if (cfg->small_max > nb::kBbMaxSmall && cfg->small_max != NB_BLOCK_BATCH_SMALL_DEFAULT)
+        return fail(s, NB_ERR_INVALID, "nb_set_block_batch: small_max is at most 1024 (NB_BLOCK_BATCH_SMALL_DEFAULT: the default 256)");
+    if (cfg->flags != 0) return fail(s, NB_ERR_INVALID, "nb_set_block_batch: flags must be 0");
+    if (!s->hermite) return fail(s, NB_ERR_STATE, "nb_set_block_batch: needs a Hermite handle (nb_config.integrator = NB_INT_HERMITE4) with block steps switched on (nb_set_block_steps)");
+    if (s->h6) return fail(s, NB_ERR_STATE, "nb_set_block_batch: the handle's order is 6 (nb_set_hermite_order): batched block steps exist at order 4 only");
+    if (!s->blk) return fail(s, NB_ERR_STATE, "nb_set_block_batch: block steps are not switched on (nb_set_block_steps)");
+    if (s->mx) return fail(s, NB_ERR_STATE, "nb_set_block_batch: the pass precision is NB_PASS_MIXED (nb_set_pass_precision): batched block steps run the native pass only");
+    NB_HIP(s, hipSetDevice(s->device));
+    NB_HIP(s, hipStreamSynchronize(s->stream));
+    bb_shape(s->n, s->n_cu, &s->bb_chunks, &s->bb_per);
+    if (!s->bb_words) {
+        NB_HIP(s, hipMalloc((void**)&s->bb_words, sizeof(uint32_t) * nb::kBbWords));
+        NB_HIP(s, hipMemset(s->bb_words, 0, sizeof(uint32_t) * nb::kBbWords));
+    }
+    if (!s->bb_host) {
+        NB_HIP(s, hipHostMalloc((void**)&s->bb_host, sizeof(uint32_t) * nb::kBbWords, hipHostMallocDefault));
+        std::memset(s->bb_host, 0, sizeof(uint32_t) * nb::kBbWords);
+    }
+    if (!s->bb_pub) NB_HIP(s, hipHostGetDevicePointer((void**)&s->bb_pub, s->bb_host, 0));
+    if (!s->bb_part) NB_HIP(s, hipMalloc(&s->bb_part, (size_t)2 * 4 * s->esz * s->bb_chunks * nb::kBbMaxSmall));
+    // Touches no state, no derivatives and no levels; the policy starts over (one slot).
+    s->bb = true;
+    s->bb_depth = cfg->depth ? cfg->depth : 32u;
+    s->bb_small_max = cfg->small_max == NB_BLOCK_BATCH_SMALL_DEFAULT ? 256u : cfg->small_max;
+    s->bb_fresh = true; s->bb_t = 0; s->bb_park_ctz = s->blk_L;
+    return NB_OK;
+}
+
+int nb_block_batch_stats(nb_sim* s, struct nb_block_batch_stats* out, int reset)
+{
+    if (!s) return fail(nullptr, NB_ERR_INVALID, "nb_block_batch_stats: null handle");
+    if (!out || out->struct_size != sizeof(struct nb_block_batch_stats)) return fail(s, NB_ERR_INVALID, "nb_block_batch_stats: set out->struct_size to sizeof(nb_block_batch_stats)");
+    std::memset(out, 0, sizeof(*out));
+    out->struct_size = sizeof(*out);
+    out->enabled = s->bb ? 1u : 0u;
+    out->host_waits = s->bb_waits; out->slots = s->bb_slots; out->small_steps = s->bb_small; out->host_steps = s->bb_hoststeps; out->idle_slots = s->bb_idle;
+    if (reset) s->bb_waits = s->bb_slots = s->bb_small = s->bb_hoststeps = s->bb_idle = 0;
     return NB_OK;
 }
 

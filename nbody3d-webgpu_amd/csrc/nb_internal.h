@@ -206,6 +206,20 @@ struct nb_sim {
                                      // 2: blk_lev / blk_due belong to the state, dt, G and the configuration
     bool levels_own = false;         // levels == 2 by the engine's own start rule, no block step since (nb_set_start6 may drop them)
     uint64_t blk_outer = 0, blk_steps = 0, blk_body_steps = 0;
+    // nb_set_block_batch: block steps sized on the device, many per host wait (kernels/block_batch.hip.h).  Allocated when first
+    // switched on, released by nb_destroy.  Off: none of this is read.
+    bool bb = false;
+    uint32_t bb_depth = 32, bb_small_max = 256;
+    uint32_t bb_chunks = 1, bb_per = 0;   // the small pass's j-chunks: a function of n and the CU count (bb_shape)
+    uint32_t* bb_words = nullptr;    // device: nb::kBbWords batch words
+    uint32_t* bb_host = nullptr;     // pinned host copy the step loop reads after its wait
+    uint32_t* bb_pub = nullptr;      // the device's address of bb_host
+    void* bb_part = nullptr;         // the small pass's partial rows: 2 planes x bb_chunks x nb::kBbMaxSmall rows
+    uint32_t bb_seen_small = 0, bb_seen_body = 0;      // the device's running counts as last read (differences per wait)
+    // the host's policy (how many slots the next batch has): a function of what was read so far
+    bool bb_fresh = true;            // nothing read since the mode was set or the levels went stale: one slot
+    uint32_t bb_t = 0, bb_finest = 0, bb_park_ctz = 0;      // the tick reached, the deepest level present, ticks with ctz >= bb_park_ctz are expected to park
+    uint64_t bb_waits = 0, bb_slots = 0, bb_small = 0, bb_hoststeps = 0, bb_idle = 0;
     // nb_set_neighbor_scheme: the Ahmad-Cohen neighbour scheme with two shared step levels (kernels/ac_scheme.hip.h).  Allocated
     // by the call, released by NULL or nb_destroy.  While it is on, acc / jerk hold the totals ai + ar0, ji + jr0.
     bool ac = false;

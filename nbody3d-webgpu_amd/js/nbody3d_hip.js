@@ -19,6 +19,7 @@
  *   readJerk()             (no reference analogue) the jerk of a {integrator: 'hermite4'} simulation
  *   setHermiteOrder(6 | 4), hermiteOrder(), readSnap(), uploadDerivs6(accel, jerk, snap, crackle)
  *                          (no reference analogue) the 6th-order scheme of a 'hermite4' simulation on force, jerk and snap
+ *   setBlockBatch() / blockBatchStats()
  *   setBlockSteps() / setBlockSteps6() / blockStats() / readLevels() / uploadLevels()
  *                          (no reference analogue) block individual time steps of a 'hermite4' simulation
  *   requestFrame()/frame() nbody3d.js:408-415,482-487 what the render pass reads each frame
@@ -300,6 +301,21 @@ class Simulation {
 
   /** {enabled, outerSteps, blockSteps, bodySteps, clamped, finestLevel} since the last reset (nb_block_stats). */
   blockStats(reset) { this._need(); return addon.blockStats(this._h, !!reset); }
+
+  /** Batched block steps (nb_set_block_batch; after setBlockSteps() on a 'hermite4' simulation of order 4 with the native pass):
+   *  block steps with at most smallMax active bodies (default 256; 0: none; at most 1024) run from the device's own header, up to
+   *  depth (default 32; at most 1024) of them per host wait.  No stored bit depends on depth.  setBlockBatch(null) switches the
+   *  mode off (so does setBlockSteps(null)); setBlockBatch() / setBlockBatch({}) take the defaults. */
+  setBlockBatch(options) {
+    this._need();
+    if (options === null) { addon.setBlockBatch(this._h, null); return this; }
+    const o = options || {};
+    addon.setBlockBatch(this._h, (o.depth || 0) >>> 0, (o.smallMax === undefined || o.smallMax === null) ? -1 : Number(o.smallMax));
+    return this;
+  }
+
+  /** {enabled, hostWaits, slots, smallSteps, hostSteps, idleSlots} since the last reset (nb_block_batch_stats). */
+  blockBatchStats(reset) { this._need(); return addon.blockBatchStats(this._h, !!reset); }
 
   /** The level of every body (Uint8Array of N; nb_download_levels), initialised first if not current. */
   readLevels() {

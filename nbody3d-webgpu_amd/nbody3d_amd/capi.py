@@ -133,6 +133,18 @@ class nb_block_steps(C.Structure):          # include/nbody3d_hip.h (block indiv
                 ("eta", C.c_double)]
 
 
+BLOCK_BATCH_SMALL_DEFAULT = 0xffffffff     # nb_block_batch.small_max: the default (256); 0 itself means "no small steps"
+
+
+class nb_block_batch(C.Structure):          # include/nbody3d_hip.h (block steps sized on the device, many per host wait)
+    _fields_ = [("struct_size", C.c_uint32), ("depth", C.c_uint32), ("small_max", C.c_uint32), ("flags", C.c_uint32)]
+
+
+class nb_block_batch_stats(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("enabled", C.c_uint32), ("host_waits", C.c_uint64), ("slots", C.c_uint64),
+                ("small_steps", C.c_uint64), ("host_steps", C.c_uint64), ("idle_slots", C.c_uint64)]
+
+
 class nb_block_stats(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("enabled", C.c_uint32), ("outer_steps", C.c_uint64), ("block_steps", C.c_uint64),
                 ("body_steps", C.c_uint64), ("clamped", C.c_uint64), ("finest_level", C.c_uint32), ("reserved", C.c_uint32)]
@@ -202,7 +214,7 @@ SYMBOLS = ["nb_abi_version", "nb_device_count", "nb_create", "nb_destroy", "nb_u
            "nb_set_neighbor_levels", "nb_neighbor_level_stats", "nb_download_neighbor_levels", "nb_upload_neighbor_levels",
            "nb_set_hermite_order", "nb_hermite_order", "nb_download_snap", "nb_upload_derivs6",
            "nb_set_block_steps6", "nb_set_start6", "nb_start6", "nb_set_pass_precision", "nb_pass_precision",
-           "nb_set_pass_guard", "nb_pass_guard"]
+           "nb_set_pass_guard", "nb_pass_guard", "nb_set_block_batch", "nb_block_batch_stats"]
 
 START6_ZERO, START6_CRACKLE = 0, 1      # nb_set_start6
 PASS_NATIVE, PASS_MIXED = 0, 1          # nb_set_pass_precision
@@ -320,6 +332,9 @@ def load_library():
         L.nb_neighbor_adapt_stats.argtypes = [vp, C.POINTER(nb_neighbor_adapt_stats), C.c_int]
         L.nb_download_neighbor_radii.argtypes = [vp, vp, vp]
         L.nb_upload_neighbor_scheme.argtypes = [vp, C.POINTER(nb_neighbor_checkpoint)]
+    if hasattr(L, "nb_set_block_batch"):        # batched block steps, likewise
+        L.nb_set_block_batch.argtypes = [vp, C.POINTER(nb_block_batch)]
+        L.nb_block_batch_stats.argtypes = [vp, C.POINTER(nb_block_batch_stats), C.c_int]
     if hasattr(L, "nb_set_neighbor_levels"):    # block individual irregular steps inside the scheme, also within 2.4
         L.nb_set_neighbor_levels.argtypes = [vp, C.POINTER(nb_neighbor_levels)]
         L.nb_neighbor_level_stats.argtypes = [vp, C.POINTER(nb_neighbor_level_stats), C.c_int]
@@ -1039,6 +1054,41 @@ class Simulation:
         st.struct_size = C.sizeof(nb_block_stats)
         self._check(self._L.nb_block_stats(self._h, C.byref(st), 1 if reset else 0))
         return {k: int(getattr(st, k)) for k in ("enabled", "outer_steps", "block_steps", "body_steps", "clamped", "finest_level")}
+
+    def set_block_batch(self, *args, **kw):
+        """set_block_batch(depth=None, small_max=None): nb_set_block_batch -- on an order-4 block-step handle with the native pass,
+        block steps with at most small_max active bodies (None: 256; 0: none; at most 1024) run from the device's own header, up
+        to depth (None: 32; at most 1024) of them per host wait.  No stored bit depends on depth.  Touches no state, derivatives
+        or levels.  set_block_batch(None) switches the mode off (so does set_block_steps(None))."""
+        if not hasattr(self._L, "nb_set_block_batch"):
+            raise NBodyError(1, "set_block_batch(): the loaded library has no nb_set_block_batch")
+        if args == (None,) and not kw:
+            self._check(self._L.nb_set_block_batch(self._h, None))
+            return self
+
+        def bind(depth=None, small_max=None):
+            return depth, small_max
+        depth, small_max = bind(*args, **kw)
+        if depth is not None and not 0 <= int(depth) <= 1024:
+            raise ValueError("depth must be in [0, 1024] (0 or None: 32)")
+        if small_max is not None and not 0 <= int(small_max) <= 1024:
+            raise ValueError("small_max must be in [0, 1024] (None: 256; 0: no small steps)")
+        cfg = nb_block_batch()
+        cfg.struct_size = C.sizeof(nb_block_batch)
+        cfg.depth = 0 if depth is None else int(depth)
+        cfg.small_max = BLOCK_BATCH_SMALL_DEFAULT if small_max is None else int(small_max)
+        cfg.flags = 0
+        self._check(self._L.nb_set_block_batch(self._h, C.byref(cfg)))
+        return self
+
+    def block_batch_stats(self, reset=False):
+        """nb_block_batch_stats: {enabled, host_waits, slots, small_steps, host_steps, idle_slots} since the last reset."""
+        if not hasattr(self._L, "nb_block_batch_stats"):
+            raise NBodyError(1, "block_batch_stats(): the loaded library has no nb_block_batch_stats")
+        st = nb_block_batch_stats()
+        st.struct_size = C.sizeof(nb_block_batch_stats)
+        self._check(self._L.nb_block_batch_stats(self._h, C.byref(st), 1 if reset else 0))
+        return {k: int(getattr(st, k)) for k in ("enabled", "host_waits", "slots", "small_steps", "host_steps", "idle_slots")}
 
     def read_levels(self):
         """nb_download_levels: the level of every body (uint8, shape (N,)); initialises them first if they are not current."""

@@ -16,9 +16,17 @@ every counterpart below then an order-6 handle too) on one GPU and prints ONE JS
                time units at N = 16,384 instead of ~4.5), the case the step hierarchy is for
   (c) small    microseconds per block step with |A| = 64 at N = --full-n: frozen levels, 64 bodies at level 6 and the rest at level 0
                (64 block steps per outer step, 63 of them with |A| = 64) minus the same outer step with every body at level 0, over 63
+  (i) idle     with --batch: what an idle slot costs.  N = --full-n, frozen, 64 bodies at level 6, 2,000 at level 5 (every even tick has
+               2,064 active bodies and parks) and the rest at level 0.  The first outer step after set_block_batch() enqueues one slot,
+               then a batch of min(depth, 63) slots whose first slot parks: with depth 32 that leaves 30 idle slots, with depth 3 one,
+               and every later batch is the same in both.  (first outer step at depth 32 - at depth 3) / 29, the arms in turns.
+
+--batch DEPTH,SMALL_MAX (order 4) switches set_block_batch(depth, small_max) on: (a) and (c) then run a handle with the mode on in
+turns with the one without, (b) runs with the mode on and records the five batch counters (run it without --batch for the other arm).
 
 Needs a GPU (no fallback)."""
 import argparse
+import contextlib
 import json
 import os
 import sys
@@ -43,6 +51,17 @@ def hermite(n, prec, eps2=None):
 
 def block_steps(sim, **kw):
     return sim.set_block_steps6(**kw) if ORDER == 6 else sim.set_block_steps(**kw)
+
+
+BATCH = None      # --batch: (depth, small_max)
+
+
+def batch_on(sim):
+    return sim.set_block_batch(depth=BATCH[0], small_max=BATCH[1])
+
+
+def spread(x):
+    return {"median": float(np.median(x)), "min": float(min(x)), "max": float(max(x)), "all": [float(y) for y in x]}
 
 
 def with_tight_pairs(n, seed=1, frac=0.01, half=0.02):
@@ -78,14 +97,21 @@ def part_a(args, out):
     n = args.full_n
     b, v = ic.plummer(n, seed=1)
     for prec in ("f32", "f64"):
-        with hermite(n, prec) as blk, hermite(n, prec) as plain:
-            for s in (blk, plain):
+        with contextlib.ExitStack() as stack:
+            blk, plain = stack.enter_context(hermite(n, prec)), stack.enter_context(hermite(n, prec))
+            bat = stack.enter_context(hermite(n, prec)) if BATCH else None      # the handle with the mode on
+            for s in (blk, plain) + ((bat,) if BATCH else ()):
                 s.init(b, v)
                 s.set_params(1e-3, 1.0)
             block_steps(blk, max_level=0, frozen=True)
+            if BATCH:
+                block_steps(bat, max_level=0, frozen=True)
+                batch_on(bat)
             est = plain.force_pass(2)
             reps = max(4, int(np.ceil(args.min_seconds * 1e3 / est)))
             got = {"force_pass_ms": [], "shared_step_ms": [], "block_step_ms": []}
+            if BATCH:
+                got["batch_block_step_ms"] = []
             for _ in range(args.rounds):
                 plain.force_pass(reps)
                 got["force_pass_ms"].append(plain.force_pass(reps))
@@ -93,10 +119,17 @@ def part_a(args, out):
                 got["shared_step_ms"].append(1e3 * wall(plain, reps) / reps)
                 wall(blk, reps)
                 got["block_step_ms"].append(1e3 * wall(blk, reps) / reps)
+                if BATCH:
+                    wall(bat, reps)
+                    got["batch_block_step_ms"].append(1e3 * wall(bat, reps) / reps)
             r = {k: {"median": float(np.median(x)), "best": min(x), "all": x} for k, x in got.items()}
             r["variant"] = plain.variant
             r["block_over_force_pass"] = r["block_step_ms"]["median"] / r["force_pass_ms"]["median"]
             r["block_over_shared_step"] = r["block_step_ms"]["median"] / r["shared_step_ms"]["median"]
+            if BATCH:
+                r["batch_over_block"] = r["batch_block_step_ms"]["median"] / r["block_step_ms"]["median"]
+                r["batch_over_block_rounds"] = [x / y for x, y in zip(got["batch_block_step_ms"], got["block_step_ms"])]
+                r["batch_stats"] = bat.block_batch_stats()
             out["full"]["%s_%d" % (prec, n)] = r
 
 
@@ -105,24 +138,31 @@ def part_b(args, out):
         b, v = with_tight_pairs(n, half=args.pair_half)
         outer = int(round(1.0 / args.outer_dt))
         r = {"n": n, "pairs": int(0.01 * n) // 2, "precision": args.precision, "outer_dt": args.outer_dt, "eta": args.eta, "order": ORDER,
-             "start_deeper": args.start_deeper, "start6": int(args.start6), "pair_half": args.pair_half, "eps2": args.eps2}
+             "start_deeper": args.start_deeper, "start6": int(args.start6), "pair_half": args.pair_half, "eps2": args.eps2,
+             "batch": list(BATCH) if BATCH else None}
         with hermite(n, args.precision, args.eps2) as sim:
             sim.init(b, v)
             if args.start6:      # the engine's own start: exact crackle, two-rule levels
                 sim.set_start6(1)
             sim.set_params(args.outer_dt, 1.0)
             block_steps(sim, eta=args.eta, max_level=args.max_level)
+            if BATCH:
+                batch_on(sim)
             e0 = energy(sim)
             lev0 = sim.read_levels()
             if args.start_deeper:      # the start rule's levels made deeper through nb_upload_levels: every body's first step shorter
                 lev0 = np.minimum(lev0 + args.start_deeper, args.max_level).astype(np.uint8)
                 sim.upload_levels(lev0)
             sim.block_stats(reset=True)
+            if BATCH:
+                sim.block_batch_stats(reset=True)
             t = wall(sim, 1)
             de_first = abs((energy(sim) - e0) / e0)
             t += wall(sim, outer - 1)
             r["block"] = {"wall_s": t, "dE_first": de_first, "dE": abs((energy(sim) - e0) / e0), "stats": sim.block_stats(),
                           "levels_start": np.bincount(lev0).tolist(), "levels_end": np.bincount(sim.read_levels()).tolist()}
+            if BATCH:
+                r["block"]["batch_stats"] = sim.block_batch_stats()
         r["block"]["full_force_equivalents"] = r["block"]["stats"]["body_steps"] / n
         r["shared"] = []
         for k in range(args.shared_from, args.shared_to + 1):
@@ -149,30 +189,88 @@ def part_c(args, out):
     b, v = ic.plummer(n, seed=1)
     lev = np.zeros(n, np.uint8)
     lev[np.random.default_rng(5).choice(n, k, replace=False)] = L
+    sets = (("all_level0", np.zeros(n, np.uint8)), ("64_at_level6", lev))
+    arms = ["off"] + (["on"] if BATCH else [])
     for prec in ("f32", "f64"):
-        t = {}
+        sims = {}
+        try:
+            for arm in arms:      # one handle per (arm, set of levels): the arms run in turns
+                for name, levels in sets:
+                    sim = sims[arm, name] = hermite(n, prec)
+                    sim.init(b, v)
+                    sim.set_params(1e-3, 1.0)
+                    block_steps(sim, max_level=L, frozen=True)
+                    if arm == "on":
+                        batch_on(sim)
+                    sim.upload_levels(levels)
+                    wall(sim, 4)
+                    sim.block_stats(reset=True)
+                    if arm == "on":
+                        sim.block_batch_stats(reset=True)
+            runs = {key: [] for key in sims}
+            for _ in range(args.rounds):
+                for arm in arms:
+                    for name, levels in sets:
+                        sim = sims[arm, name]
+                        sim.upload_levels(levels)      # the same state of the levels' clock before every timed run
+                        runs[arm, name].append(wall(sim, args.small_outer) / args.small_outer)
+            res = {}
+            for arm in arms:
+                t = {}
+                for name, _ in sets:
+                    st = sims[arm, name].block_stats(reset=True)
+                    t[name] = {"outer_step_us": 1e6 * float(np.median(runs[arm, name])), "outer_step_us_rounds": [1e6 * x for x in runs[arm, name]],
+                               "block_steps_per_outer": st["block_steps"] / st["outer_steps"], "body_steps_per_outer": st["body_steps"] / st["outer_steps"]}
+                    if arm == "on":
+                        t[name]["batch_stats"] = sims[arm, name].block_batch_stats()
+                per = [1e6 * (x - y) / (2 ** L - 1) for x, y in zip(runs[arm, "64_at_level6"], runs[arm, "all_level0"])]
+                t["us_per_small_block_step"] = (t["64_at_level6"]["outer_step_us"] - t["all_level0"]["outer_step_us"]) / (2 ** L - 1)
+                t["us_per_small_block_step_rounds"] = per
+                res[arm] = t
+            r = res["off"]
+            if BATCH:
+                r["batch"] = res["on"]
+                r["batch"]["config"] = list(BATCH)
+                r["batch_over_off"] = res["on"]["us_per_small_block_step"] / res["off"]["us_per_small_block_step"]
+                r["full_set_batch_over_off"] = res["on"]["all_level0"]["outer_step_us"] / res["off"]["all_level0"]["outer_step_us"]
+            out["small"]["%s_%d" % (prec, n)] = r
+        finally:
+            for sim in sims.values():
+                sim.close()
+
+
+def part_i(args, out):
+    n, L = args.full_n, 6
+    b, v = ic.plummer(n, seed=1)
+    pick = np.random.default_rng(5).choice(n, 2064, replace=False)
+    lev = np.zeros(n, np.uint8)
+    lev[pick[:64]] = L
+    lev[pick[64:]] = L - 1
+    for prec in ("f32", "f64"):
         with hermite(n, prec) as sim:
             sim.init(b, v)
             sim.set_params(1e-3, 1.0)
-            for name, levels in (("all_level0", np.zeros(n, np.uint8)), ("64_at_level6", lev)):
-                block_steps(sim, max_level=L, frozen=True)
-                sim.upload_levels(levels)
-                wall(sim, 4)
-                sim.block_stats(reset=True)
-                runs = []
-                for _ in range(args.rounds):
-                    sim.upload_levels(levels)      # the same state of the levels' clock before every timed run
-                    runs.append(wall(sim, args.small_outer) / args.small_outer)
-                st = sim.block_stats(reset=True)
-                t[name] = {"outer_step_us": 1e6 * float(np.median(runs)), "block_steps_per_outer": st["block_steps"] / st["outer_steps"],
-                           "body_steps_per_outer": st["body_steps"] / st["outer_steps"]}
-        t["us_per_small_block_step"] = (t["64_at_level6"]["outer_step_us"] - t["all_level0"]["outer_step_us"]) / (2 ** L - 1)
-        out["small"]["%s_%d" % (prec, n)] = t
+            block_steps(sim, max_level=L, frozen=True)
+            runs, idle = {3: [], 32: []}, {}
+            for r in range(args.rounds + 1):      # the first round warms up
+                for depth in (3, 32):
+                    sim.set_block_batch(depth=depth, small_max=BATCH[1])      # the policy starts over: one slot, then min(depth, 63)
+                    sim.upload_levels(lev)
+                    sim.block_batch_stats(reset=True)
+                    t = wall(sim, 1)
+                    idle[depth] = sim.block_batch_stats()
+                    if r:
+                        runs[depth].append(1e6 * t)
+            d = idle[32]["idle_slots"] - idle[3]["idle_slots"]
+            out["idle"]["%s_%d" % (prec, n)] = {"first_outer_step_us": {str(k): spread(x) for k, x in runs.items()}, "stats": {str(k): s for k, s in idle.items()},
+                                                "us_per_idle_slot": (float(np.median(runs[32])) - float(np.median(runs[3]))) / d if d else None,
+                                                "us_per_idle_slot_rounds": [(x - y) / d for x, y in zip(runs[32], runs[3])] if d else None}
 
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--only", choices=["a", "b", "c"], nargs="*", default=["a", "b", "c"])
+    ap.add_argument("--only", choices=["a", "b", "c", "i"], nargs="*", default=["a", "b", "c"])
+    ap.add_argument("--batch", default=None, metavar="DEPTH,SMALL_MAX", help="set_block_batch(depth, small_max) on the block handles (order 4)")
     ap.add_argument("--full-n", type=int, default=65536)
     ap.add_argument("--sizes", type=int, nargs="*", default=[16384, 65536])
     ap.add_argument("--precision", default="f32", choices=["f32", "f64"])
@@ -190,19 +288,27 @@ def main():
     ap.add_argument("--min-seconds", type=float, default=0.3)
     ap.add_argument("--rounds", type=int, default=3)
     args = ap.parse_args()
-    global ORDER
+    global ORDER, BATCH
     ORDER = args.order
+    if args.batch:
+        BATCH = tuple(int(x) for x in args.batch.split(","))
+        if len(BATCH) != 2 or ORDER != 4:
+            ap.error("--batch DEPTH,SMALL_MAX needs --order 4")
+    if "i" in args.only and not BATCH:
+        ap.error("--only i needs --batch")
     if args.start6 and ORDER != 6:
         ap.error("--start6 needs --order 6")
     if capi.device_count() < 1:
         sys.exit("block_bench: no GPU")
-    out = {"tool": "block_bench", "order": ORDER, "full": {}, "end2end": [], "small": {}}
+    out = {"tool": "block_bench", "order": ORDER, "batch": list(BATCH) if BATCH else None, "full": {}, "end2end": [], "small": {}, "idle": {}}
     if "a" in args.only:
         part_a(args, out)
     if "b" in args.only:
         part_b(args, out)
     if "c" in args.only:
         part_c(args, out)
+    if "i" in args.only:
+        part_i(args, out)
     print(json.dumps(out))
 
 
