@@ -86,7 +86,8 @@ extern "C" {
                              2.4 (round 24) likewise within 2.4: nb_set_pass_guard, nb_pass_guard.  Detected by the presence of the symbol
                                             nb_set_pass_guard
                              2.4 (round 25) likewise within 2.4: nb_set_block_batch, nb_block_batch_stats, nb_block_batch,
-                                            NB_BLOCK_BATCH_SMALL_DEFAULT.  Detected by the presence of the symbol nb_set_block_batch */
+                                            NB_BLOCK_BATCH_SMALL_DEFAULT.  Detected by the presence of the symbol nb_set_block_batch
+                             2.4 (round 26) likewise within 2.4: nb_set_block_batch6.  Detected by the presence of the symbol */
 
 typedef struct nb_sim nb_sim; /* opaque */
 
@@ -579,6 +580,29 @@ typedef struct nb_block_batch {
     uint32_t flags;        /* must be 0 */
 } nb_block_batch;
 int nb_set_block_batch(nb_sim *s, const nb_block_batch *cfg /* NULL: off */);
+
+/* nb_set_block_batch6 (round 26): the same mode on order-6 handles with nb_set_block_steps6 on -- NB_F64 handles with dynamic or
+ * frozen levels, NB_F32 handles with NB_BLOCK_FROZEN.  A separate entry point, as nb_set_block_steps6 is beside nb_set_block_steps:
+ * nb_set_block_batch(non-NULL) on an order-6 handle stays NB_ERR_STATE.  The struct, the defaults, the slot protocol, the host's
+ * policy and nb_block_batch_stats (enabled = 1 while either mode is on) are the ones above; inside a slot the scheme is
+ * nb_set_block_steps6's (steps 1-7): the order-6 predictor, a small force+jerk+snap pass (kernels/block_batch6.hip.h) and the order-6
+ * block corrector with its crackle and its a4 / a5 criterion.
+ *   - The contract above holds word for word: with a fixed small_max no stored bit and no nb_block_stats counter depends on depth
+ *     or on where batches end; nb_step(k) equals k x nb_step(1); two handles give the same bits; small_max = 0 is the mode off, bit
+ *     for bit; what a small step computes for a body depends on the predicted arrays and on n alone; results for different small_max
+ *     agree to the pass's accuracy, not bit for bit; t_next == 2^L always parks.
+ *   - Checkpoint: the seven arrays of nb_set_block_steps6 (bodies, vel, accel, jerk, snap, crackle, levels), restored by nb_upload,
+ *     nb_set_params, nb_set_hermite_order(6), nb_upload_derivs6, nb_set_block_steps6, nb_set_block_batch6 (same small_max, any
+ *     depth), nb_upload_levels: the restored handle continues bit for bit.
+ *   - The setter touches no state, no derived array and no levels, and restarts the policy at one slot.  nb_set_block_batch6(s, NULL),
+ *     nb_set_block_batch(s, NULL), nb_set_block_steps6(s, NULL) and nb_set_block_steps(s, NULL) switch the mode off; a non-NULL
+ *     nb_set_block_steps6 keeps it; nb_set_start6 keeps working; nb_set_hermite_order(4) and nb_set_neighbor_scheme(non-NULL) stay
+ *     NB_ERR_STATE, as on any handle with block steps of order 6.
+ *   - NB_ERR_STATE (the message names the function and the reason): a leapfrog handle, an order-4 handle (the message names
+ *     nb_set_hermite_order), an order-6 handle without nb_set_block_steps6.  NB_ERR_INVALID (naming nb_set_block_batch6 and the
+ *     field): a NULL handle, a wrong struct_size, depth > 1024, small_max > 1024 other than NB_BLOCK_BATCH_SMALL_DEFAULT, flags != 0.
+ *   - Not built: the mode on mixed or guarded handles, with the neighbour scheme or on nb_multi. */
+int nb_set_block_batch6(nb_sim *s, const nb_block_batch *cfg /* NULL: off */);
 
 /* (a struct TAG without a typedef, as nb_block_stats) */
 struct nb_block_batch_stats {
@@ -1350,7 +1374,8 @@ int nb_upload_derivs6(nb_sim *s, const void *accel, const void *jerk, const void
  *     nb_set_hermite_order; the argument checks are those of nb_set_block_steps, the message naming nb_set_block_steps6 and the field.
  *   - By default the start rule is order 4's and the first step runs with c = 0: on systems with hard pairs the first outer step
  *     makes most of a run's energy error (profiles/r21/block6.md).  nb_set_start6(s, NB_START6_CRACKLE) below is the start of its own.
- *   - Not built: the neighbour scheme on order-6 handles; block steps without the host wait per block step. */
+ *   - Block steps without the host wait per block step: nb_set_block_batch6 (beside nb_set_block_batch, above).
+ *   - Not built: the neighbour scheme on order-6 handles. */
 int nb_set_block_steps6(nb_sim *s, const nb_block_steps *cfg /* NULL: back to the shared order-6 step */);
 
 /* ---- the start of an order-6 handle: exact crackle, two-rule levels (no reference analogue) ----------------

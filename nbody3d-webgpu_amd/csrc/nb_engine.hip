@@ -649,6 +649,8 @@ struct hermite_order {
     uint32_t nb_sim::*chunks, nb_sim::*per;      // ... and the j-chunks of its full pass
     bool mixed;                       // the [1] entries are binary32 kernels on an f64 handle's streams (nb_set_pass_precision): f32 shapes and partial rows
     bool guard = false;               // ... with guarded sums (nb_set_pass_guard): the pass takes near2 last and leaves fp64 partial rows
+    // the kernels of a batched slot behind its scheduler (nb_set_block_batch, nb_set_block_batch6); null: the order has no batched mode
+    const void *bb_predict[2] = {nullptr, nullptr}, *bb_pass[2] = {nullptr, nullptr}, *bb_correct[2] = {nullptr, nullptr};
 };
 
 #define NB_BOTH(K) {(const void*)&nb::K<float>, (const void*)&nb::K<double>}
@@ -659,7 +661,9 @@ const hermite_order kOrder4 = {
     {(const void*)&nb::nb_blk_fj_pk<2>, (const void*)&nb::nb_blk_fj64<double>}, (const void*)&nb::nb_blk_fj_pk<1>,
     NB_BOTH(nb_hermite_predict), NB_BOTH(nb_hermite_correct), NB_BOTH(nb_blk_predict),
     {(const void*)&nb::nb_blk_correct<float, float>, (const void*)&nb::nb_blk_correct<double, double>},
-    &nb_sim::fj_part, &nb_sim::fj_chunks, &nb_sim::fj_per, false};
+    &nb_sim::fj_part, &nb_sim::fj_chunks, &nb_sim::fj_per, false, false,
+    NB_BOTH(nb_blkq_predict), {(const void*)&nb::nb_blkq_fj_pk<1>, (const void*)&nb::nb_blkq_fj64<double>},
+    {(const void*)&nb::nb_blkq_correct<float, float>, (const void*)&nb::nb_blkq_correct<double, double>}};
 const hermite_order kOrder6 = {
     "hermite6_", 3, 3, 6, {nb::kH6Rows, nb::kH6Rows64}, {nb::kBlock * 4, nb::kH6Rows64},      // (the gathered kernels are NG = 2 and 1 whatever NB_H6_NG the full pass is built with)
     {(const void*)&nb::nb_h6_fjs_pk<nb::kH6NG>, (const void*)&nb::nb_h6_fjs64<double>},
@@ -667,7 +671,9 @@ const hermite_order kOrder6 = {
     {(const void*)&nb::nb_blk6_fjs_pk<2>, (const void*)&nb::nb_blk6_fjs64<double>}, (const void*)&nb::nb_blk6_fjs_pk<1>,
     NB_BOTH(nb_h6_predict), NB_BOTH(nb_h6_correct), NB_BOTH(nb_blk6_predict),
     {(const void*)&nb::nb_blk6_correct<float, float>, (const void*)&nb::nb_blk6_correct<double, double>},
-    &nb_sim::h6_part, &nb_sim::h6_chunks, &nb_sim::h6_per, false};
+    &nb_sim::h6_part, &nb_sim::h6_chunks, &nb_sim::h6_per, false, false,
+    NB_BOTH(nb_blkq6_predict), {(const void*)&nb::nb_blkq6_fjs_pk<1>, (const void*)&nb::nb_blkq6_fjs64<double>},
+    {(const void*)&nb::nb_blkq6_correct<float, float>, (const void*)&nb::nb_blkq6_correct<double, double>}};
 // The crackle pass of an order-6 start (nb_set_start6): a full pass only, in the order-6 pass's j-chunks and partial rows.
 const hermite_order kStart6 = {
     "hermite6_", 1, 4, 6, {nb::kH6CrkRows, nb::kH6Rows64}, {0, 0},
@@ -965,7 +971,8 @@ int block_step(nb_sim* s, uint32_t nsteps)
     return NB_OK;
 }
 
-// ---- nb_set_block_batch: block steps sized on the device, many per host wait (kernels/block_batch.hip.h) ----------
+// ---- nb_set_block_batch, nb_set_block_batch6: block steps sized on the device, many per host wait (kernels/block_batch.hip.h,
+// kernels/block_batch6.hip.h) ----------
 // The j-chunks of the small pass: a function of n and the CU count alone (a row's bits must not depend on |A|, small_max or depth).
 // One chunk of whole tiles per CU: a wave's chain is a quarter of a chunk (64 rows of one tile up to 256 x CUs bodies), and the
 // corrector shares a slot's chunk rows among nb::kBbSumLanes lanes.
@@ -991,8 +998,8 @@ uint32_t bb_plan_slots(const nb_sim* s)
     return (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(count, s->bb_depth));
 }
 
-// nb_step of an order-4 block-step handle with nb_set_block_batch on: block_step's outer step, with the slots of a batch enqueued
-// behind one another and ONE host wait per batch.  A slot that parked left its schedule and prediction: the host runs that block
+// nb_step of a block-step handle of either order with nb_set_block_batch / nb_set_block_batch6 on: block_step's outer step, with
+// the slots of a batch enqueued behind one another and ONE host wait per batch; the slot's kernels and argument lists are the order's.  A slot that parked left its schedule and prediction: the host runs that block
 // step through the gathered path, as block_step does.
 int block_batch_step(nb_sim* s, uint32_t nsteps)
 {
@@ -1008,25 +1015,23 @@ int block_batch_step(nb_sim* s, uint32_t nsteps)
     float e2f = (float)s->eps2;
     const void* zr = s->zero_row;
     const size_t row = (size_t)4 * (s->f64 ? 8 : 4);
-    void* plane[2] = {s->bb_part, (char*)s->bb_part + row * chunks * nb::kBbMaxSmall};
+    void* plane[3] = {nullptr, nullptr, nullptr};
+    for (uint32_t p = 0; p < o.planes; ++p) plane[p] = (char*)s->bb_part + p * (row * chunks * nb::kBbMaxSmall);
     const uint32_t gx_small = std::max(1u, ceil_div(small_max, s->f64 ? nb::kBbRows64 : nb::kBbRows));
     auto enqueue_slot = [&](uint32_t first) {
         void* sargs[] = {&s->blk_due, &s->blk_lev, &n, &s->blk_act, &s->blk_hdr, &s->blk_hdr_pub, &s->bb_words, &s->bb_pub, &first, &small_max, &end};
         (void)hipLaunchKernel((const void*)&nb::nb_blkq_sched<nb::kBlkSched>, dim3(1), dim3(nb::kBlkSched), sargs, 0, s->stream);
         kernel_args p;
         p(h.state, o.states)(&s->blk_due)(&s->blk_lev)(h.in, o.inputs)(&n)(&s->blk_hdr)(&Lk)(&tick)(&s->bb_words);
-        (void)hipLaunchKernel(s->f64 ? (const void*)&nb::nb_blkq_predict<double> : (const void*)&nb::nb_blkq_predict<float>,
-                              dim3(ceil_div(n, nb::kBlock)), dim3(nb::kBlock), p.v, 0, s->stream);
+        (void)hipLaunchKernel(o.bb_predict[s->f64], dim3(ceil_div(n, nb::kBlock)), dim3(nb::kBlock), p.v, 0, s->stream);
         if (small_max == 0) return;      // no small steps: every slot parks
         kernel_args f;
-        f(h.in, o.inputs)(&s->blk_act)(&s->blk_hdr)(&s->bb_words)(&small_max)(plane, 2)(&n)(&per);
+        f(h.in, o.inputs)(&s->blk_act)(&s->blk_hdr)(&s->bb_words)(&small_max)(plane, o.planes)(&n)(&per);
         if (s->f64) f(&e2); else f(&e2f)(&zr);
-        (void)hipLaunchKernel(s->f64 ? (const void*)&nb::nb_blkq_fj64<double> : (const void*)&nb::nb_blkq_fj_pk<1>,
-                              dim3(gx_small, chunks), dim3(nb::kBlock), f.v, 0, s->stream);
+        (void)hipLaunchKernel(o.bb_pass[s->f64], dim3(gx_small, chunks), dim3(nb::kBlock), f.v, 0, s->stream);
         kernel_args c;
-        c(plane, 2)(&s->blk_act)(&s->bb_words)(&small_max)(&chunks)(&G)(h.state, o.states)(&s->blk_due)(&s->blk_lev)(&s->blk_hdr)(&n)(&Lk)(&lmin)(&frozen)(&eta)(&dt);
-        (void)hipLaunchKernel(s->f64 ? (const void*)&nb::nb_blkq_correct<double, double> : (const void*)&nb::nb_blkq_correct<float, float>,
-                              dim3(ceil_div(small_max * nb::kBbSumLanes, nb::kBlock)), dim3(nb::kBlock), c.v, 0, s->stream);
+        c(plane, o.planes)(&s->blk_act)(&s->bb_words)(&small_max)(&chunks)(&G)(h.state, o.states)(&s->blk_due)(&s->blk_lev)(&s->blk_hdr)(&n)(&Lk)(&lmin)(&frozen)(&eta)(&dt);
+        (void)hipLaunchKernel(o.bb_correct[s->f64], dim3(ceil_div(small_max * nb::kBbSumLanes, nb::kBlock)), dim3(nb::kBlock), c.v, 0, s->stream);
     };
     for (uint32_t k = 0; k < nsteps; ++k) {
         nb_events ev;
@@ -1911,7 +1916,7 @@ int nb_set_hermite_order(nb_sim* s, uint32_t order)
     if (!s) return fail(nullptr, NB_ERR_INVALID, "nb_set_hermite_order: null handle");
     if (order != 4 && order != 6) return fail(s, NB_ERR_INVALID, "nb_set_hermite_order: order must be 4 or 6");
     if (!s->hermite) return fail(s, NB_ERR_STATE, "nb_set_hermite_order: needs a Hermite handle (nb_config.integrator = NB_INT_HERMITE4)");
-    if (order == 6 && s->bb) return fail(s, NB_ERR_STATE, "nb_set_hermite_order: order = 6 while batched block steps are switched on (nb_set_block_batch): they exist at order 4 only, switch them off first");
+    if (order == 6 && s->bb && !s->h6) return fail(s, NB_ERR_STATE, "nb_set_hermite_order: order = 6 while batched block steps are switched on (nb_set_block_batch): they exist at order 4 only, switch them off first");
     if (order == 6 && s->blk && !s->h6) return fail(s, NB_ERR_STATE, "nb_set_hermite_order: order = 6 while block steps are switched on (nb_set_block_steps): they exclude each other");
     if (order == 4 && s->blk && s->h6) return fail(s, NB_ERR_STATE, "nb_set_hermite_order: order = 4 while block steps of order 6 are switched on (nb_set_block_steps6): switch them off first");
     if (order == 6 && s->mx) return fail(s, NB_ERR_STATE, "nb_set_hermite_order: order = 6 while the pass precision is NB_PASS_MIXED (nb_set_pass_precision): the mixed pass exists at order 4 only, set NB_PASS_NATIVE first");
@@ -2137,7 +2142,7 @@ int nb_set_block_steps6(nb_sim* s, const nb_block_steps* cfg)
 {
     if (!s) return fail(nullptr, NB_ERR_INVALID, "nb_set_block_steps6: null handle");
     if (!s->hermite) return fail(s, NB_ERR_STATE, "nb_set_block_steps6: needs a Hermite handle (nb_config.integrator = NB_INT_HERMITE4) of order 6 (nb_set_hermite_order)");
-    if (!cfg) { s->blk = false; s->levels = 0; return NB_OK; }
+    if (!cfg) { s->blk = false; s->bb = false; s->levels = 0; return NB_OK; }      // (the batched mode belongs to the block steps: off with them)
     if (!s->h6) return fail(s, NB_ERR_STATE, "nb_set_block_steps6: the handle's order is 4 (nb_set_hermite_order): see nb_set_block_steps");
     if (cfg->struct_size == sizeof(nb_block_steps) && !s->f64 && !(cfg->flags & NB_BLOCK_FROZEN))
         return fail(s, NB_ERR_STATE, "nb_set_block_steps6: precision NB_F32 without flags = NB_BLOCK_FROZEN: the criterion's a4 and a5 cannot be formed from binary32 derivatives (rounding noise); dynamic levels of order 6 need an NB_F64 handle");
@@ -2167,19 +2172,20 @@ int nb_block_stats(nb_sim* s, struct nb_block_stats* out, int reset)
     return NB_OK;
 }
 
-int nb_set_block_batch(nb_sim* s, const nb_block_batch* cfg)
+// The argument checks nb_set_block_batch and nb_set_block_batch6 share (who: the entry point's name).
+int bb_check(nb_sim* s, const nb_block_batch* cfg, const std::string& who)
 {
-    if (!s) return fail(nullptr, NB_ERR_INVALID, "nb_set_block_batch: null handle");
-    if (!cfg) { s->bb = false; return NB_OK; }
-    if (cfg->struct_size != sizeof(nb_block_batch)) return fail(s, NB_ERR_INVALID, "nb_set_block_batch: struct_size must be sizeof(nb_block_batch)");
-    if (cfg->depth > 1024) return fail(s, NB_ERR_INVALID, "nb_set_block_batch: depth is at most 1024 (0: the default 32)");
+    if (cfg->struct_size != sizeof(nb_block_batch)) return fail(s, NB_ERR_INVALID, who + ": struct_size must be sizeof(nb_block_batch)");
+    if (cfg->depth > 1024) return fail(s, NB_ERR_INVALID, who + ": depth is at most 1024 (0: the default 32)");
     if (cfg->small_max > nb::kBbMaxSmall && cfg->small_max != NB_BLOCK_BATCH_SMALL_DEFAULT)
-        return fail(s, NB_ERR_INVALID, "nb_set_block_batch: small_max is at most 1024 (NB_BLOCK_BATCH_SMALL_DEFAULT: the default 256)");
-    if (cfg->flags != 0) return fail(s, NB_ERR_INVALID, "nb_set_block_batch: flags must be 0");
-    if (!s->hermite) return fail(s, NB_ERR_STATE, "nb_set_block_batch: needs a Hermite handle (nb_config.integrator = NB_INT_HERMITE4) with block steps switched on (nb_set_block_steps)");
-    if (s->h6) return fail(s, NB_ERR_STATE, "nb_set_block_batch: the handle's order is 6 (nb_set_hermite_order): batched block steps exist at order 4 only");
-    if (!s->blk) return fail(s, NB_ERR_STATE, "nb_set_block_batch: block steps are not switched on (nb_set_block_steps)");
-    if (s->mx) return fail(s, NB_ERR_STATE, "nb_set_block_batch: the pass precision is NB_PASS_MIXED (nb_set_pass_precision): batched block steps run the native pass only");
+        return fail(s, NB_ERR_INVALID, who + ": small_max is at most 1024 (NB_BLOCK_BATCH_SMALL_DEFAULT: the default 256)");
+    if (cfg->flags != 0) return fail(s, NB_ERR_INVALID, who + ": flags must be 0");
+    return NB_OK;
+}
+
+// ... and what they do behind their state checks: the mode on, for the order the handle has.
+int bb_configure(nb_sim* s, const nb_block_batch* cfg)
+{
     NB_HIP(s, hipSetDevice(s->device));
     NB_HIP(s, hipStreamSynchronize(s->stream));
     bb_shape(s->n, s->n_cu, &s->bb_chunks, &s->bb_per);
@@ -2192,13 +2198,41 @@ int nb_set_block_batch(nb_sim* s, const nb_block_batch* cfg)
         std::memset(s->bb_host, 0, sizeof(uint32_t) * nb::kBbWords);
     }
     if (!s->bb_pub) NB_HIP(s, hipHostGetDevicePointer((void**)&s->bb_pub, s->bb_host, 0));
-    if (!s->bb_part) NB_HIP(s, hipMalloc(&s->bb_part, (size_t)2 * 4 * s->esz * s->bb_chunks * nb::kBbMaxSmall));
+    const uint32_t planes = order_of(s).planes;
+    if (s->bb_part && s->bb_planes != planes) { NB_HIP(s, hipFree(s->bb_part)); s->bb_part = nullptr; }      // the order changed since
+    if (!s->bb_part) {
+        NB_HIP(s, hipMalloc(&s->bb_part, (size_t)planes * 4 * s->esz * s->bb_chunks * nb::kBbMaxSmall));
+        s->bb_planes = planes;
+    }
     // Touches no state, no derivatives and no levels; the policy starts over (one slot).
     s->bb = true;
     s->bb_depth = cfg->depth ? cfg->depth : 32u;
     s->bb_small_max = cfg->small_max == NB_BLOCK_BATCH_SMALL_DEFAULT ? 256u : cfg->small_max;
     s->bb_fresh = true; s->bb_t = 0; s->bb_park_ctz = s->blk_L;
     return NB_OK;
+}
+
+int nb_set_block_batch(nb_sim* s, const nb_block_batch* cfg)
+{
+    if (!s) return fail(nullptr, NB_ERR_INVALID, "nb_set_block_batch: null handle");
+    if (!cfg) { s->bb = false; return NB_OK; }
+    if (int rc = bb_check(s, cfg, "nb_set_block_batch")) return rc;
+    if (!s->hermite) return fail(s, NB_ERR_STATE, "nb_set_block_batch: needs a Hermite handle (nb_config.integrator = NB_INT_HERMITE4) with block steps switched on (nb_set_block_steps)");
+    if (s->h6) return fail(s, NB_ERR_STATE, "nb_set_block_batch: the handle's order is 6 (nb_set_hermite_order): batched block steps exist at order 4 only");
+    if (!s->blk) return fail(s, NB_ERR_STATE, "nb_set_block_batch: block steps are not switched on (nb_set_block_steps)");
+    if (s->mx) return fail(s, NB_ERR_STATE, "nb_set_block_batch: the pass precision is NB_PASS_MIXED (nb_set_pass_precision): batched block steps run the native pass only");
+    return bb_configure(s, cfg);
+}
+
+int nb_set_block_batch6(nb_sim* s, const nb_block_batch* cfg)
+{
+    if (!s) return fail(nullptr, NB_ERR_INVALID, "nb_set_block_batch6: null handle");
+    if (!cfg) { s->bb = false; return NB_OK; }
+    if (int rc = bb_check(s, cfg, "nb_set_block_batch6")) return rc;
+    if (!s->hermite) return fail(s, NB_ERR_STATE, "nb_set_block_batch6: needs a Hermite handle (nb_config.integrator = NB_INT_HERMITE4) of order 6 (nb_set_hermite_order) with block steps switched on (nb_set_block_steps6)");
+    if (!s->h6) return fail(s, NB_ERR_STATE, "nb_set_block_batch6: the handle's order is 4 (nb_set_hermite_order): see nb_set_block_batch");
+    if (!s->blk) return fail(s, NB_ERR_STATE, "nb_set_block_batch6: block steps are not switched on (nb_set_block_steps6)");
+    return bb_configure(s, cfg);
 }
 
 int nb_block_batch_stats(nb_sim* s, struct nb_block_batch_stats* out, int reset)

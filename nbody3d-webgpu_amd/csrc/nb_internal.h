@@ -206,15 +206,16 @@ struct nb_sim {
                                      // 2: blk_lev / blk_due belong to the state, dt, G and the configuration
     bool levels_own = false;         // levels == 2 by the engine's own start rule, no block step since (nb_set_start6 may drop them)
     uint64_t blk_outer = 0, blk_steps = 0, blk_body_steps = 0;
-    // nb_set_block_batch: block steps sized on the device, many per host wait (kernels/block_batch.hip.h).  Allocated when first
-    // switched on, released by nb_destroy.  Off: none of this is read.
+    // nb_set_block_batch / nb_set_block_batch6: block steps sized on the device, many per host wait (kernels/block_batch.hip.h,
+    // kernels/block_batch6.hip.h).  Allocated when first switched on, released by nb_destroy.  Off: none of this is read.
     bool bb = false;
     uint32_t bb_depth = 32, bb_small_max = 256;
     uint32_t bb_chunks = 1, bb_per = 0;   // the small pass's j-chunks: a function of n and the CU count (bb_shape)
     uint32_t* bb_words = nullptr;    // device: nb::kBbWords batch words
     uint32_t* bb_host = nullptr;     // pinned host copy the step loop reads after its wait
     uint32_t* bb_pub = nullptr;      // the device's address of bb_host
-    void* bb_part = nullptr;         // the small pass's partial rows: 2 planes x bb_chunks x nb::kBbMaxSmall rows
+    void* bb_part = nullptr;         // the small pass's partial rows: bb_planes planes x bb_chunks x nb::kBbMaxSmall rows
+    uint32_t bb_planes = 0;          // the planes bb_part holds (2 | 3: the order it was last switched on for)
     uint32_t bb_seen_small = 0, bb_seen_body = 0;      // the device's running counts as last read (differences per wait)
     // the host's policy (how many slots the next batch has): a function of what was read so far
     bool bb_fresh = true;            // nothing read since the mode was set or the levels went stale: one slot

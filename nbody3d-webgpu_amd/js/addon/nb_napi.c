@@ -76,6 +76,7 @@ static int (*p_set_block_steps)(nb_sim *, const nb_block_steps *);      /* block
 static int (*p_block_stats)(nb_sim *, struct nb_block_stats *, int);
 static int (*p_set_block_batch)(nb_sim *, const nb_block_batch *);      /* batched block steps (round 25): optional */
 static int (*p_block_batch_stats)(nb_sim *, struct nb_block_batch_stats *, int);
+static int (*p_set_block_batch6)(nb_sim *, const nb_block_batch *);     /* ... on order-6 handles (round 26): optional */
 static int (*p_download_levels)(nb_sim *, uint8_t *);
 static int (*p_upload_levels)(nb_sim *, const uint8_t *);
 static int (*p_neighbors)(nb_sim *, const nb_neighbor_request *);       /* neighbour queries, also within ABI 2.4: optional symbols */
@@ -199,6 +200,7 @@ static napi_value js_load(napi_env env, napi_callback_info info)
         *(void **)(&p_block_stats) = dlsym(h, "nb_block_stats");
         *(void **)(&p_set_block_batch) = dlsym(h, "nb_set_block_batch");
         *(void **)(&p_block_batch_stats) = dlsym(h, "nb_block_batch_stats");
+        *(void **)(&p_set_block_batch6) = dlsym(h, "nb_set_block_batch6");
         *(void **)(&p_download_levels) = dlsym(h, "nb_download_levels");
         *(void **)(&p_upload_levels) = dlsym(h, "nb_upload_levels");
         *(void **)(&p_neighbors) = dlsym(h, "nb_neighbors");
@@ -1358,18 +1360,19 @@ static napi_value js_block_stats(napi_env env, napi_callback_info info)
     return o;
 }
 
-/* setBlockBatch(handle, null) | setBlockBatch(handle, depth, smallMax): nb_set_block_batch (depth 0: the default; smallMax < 0: the default) */
-static napi_value js_set_block_batch(napi_env env, napi_callback_info info)
+/* setBlockBatch(handle, null) | setBlockBatch(handle, depth, smallMax): nb_set_block_batch (depth 0: the default; smallMax < 0: the
+ * default); setBlockBatch6 likewise through nb_set_block_batch6 */
+static napi_value set_block_batch_by(napi_env env, napi_callback_info info, int (*fn)(nb_sim *, const nb_block_batch *), const char *sym)
 {
     size_t argc = 3; napi_value argv[3];
     CHECK_NAPI(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
-    if (argc < 2) { napi_throw_type_error(env, NULL, "setBlockBatch(handle, null | depth, smallMax)"); return NULL; }
-    handle_t *h = block_handle(env, argv[0], *(void **)&p_set_block_batch, "nb_set_block_batch"); if (!h) return NULL;
+    if (argc < 2) { napi_throw_type_error(env, NULL, "setBlockBatch[6](handle, null | depth, smallMax)"); return NULL; }
+    handle_t *h = block_handle(env, argv[0], *(void **)&fn, sym); if (!h) return NULL;
     napi_valuetype t; napi_typeof(env, argv[1], &t);
     int rc;
-    if (t == napi_null || t == napi_undefined) rc = p_set_block_batch(h->sim, NULL);
+    if (t == napi_null || t == napi_undefined) rc = fn(h->sim, NULL);
     else {
-        if (argc < 3) { napi_throw_type_error(env, NULL, "setBlockBatch(handle, depth, smallMax)"); return NULL; }
+        if (argc < 3) { napi_throw_type_error(env, NULL, "setBlockBatch[6](handle, depth, smallMax)"); return NULL; }
         nb_block_batch cfg;
         memset(&cfg, 0, sizeof cfg);
         cfg.struct_size = sizeof cfg;
@@ -1377,11 +1380,13 @@ static napi_value js_set_block_batch(napi_env env, napi_callback_info info)
         CHECK_NAPI(env, napi_get_value_uint32(env, argv[1], &u)); cfg.depth = u;
         CHECK_NAPI(env, napi_get_value_double(env, argv[2], &sm));
         cfg.small_max = sm < 0.0 ? NB_BLOCK_BATCH_SMALL_DEFAULT : sm > 4294967294.0 ? 0xfffffffeu : (uint32_t)sm;
-        rc = p_set_block_batch(h->sim, &cfg);
+        rc = fn(h->sim, &cfg);
     }
-    if (rc != NB_OK) return throw_nb(env, rc, h->sim, "nb_set_block_batch");
+    if (rc != NB_OK) return throw_nb(env, rc, h->sim, sym);
     return undefined(env);
 }
+static napi_value js_set_block_batch(napi_env env, napi_callback_info info) { return set_block_batch_by(env, info, p_set_block_batch, "nb_set_block_batch"); }
+static napi_value js_set_block_batch6(napi_env env, napi_callback_info info) { return set_block_batch_by(env, info, p_set_block_batch6, "nb_set_block_batch6"); }
 
 /* blockBatchStats(handle, reset) -> {enabled, hostWaits, slots, smallSteps, hostSteps, idleSlots} (counts as doubles) */
 static napi_value js_block_batch_stats(napi_env env, napi_callback_info info)
@@ -1719,7 +1724,7 @@ static napi_value init_module(napi_env env, napi_value exports)
         {"setHermiteOrder", js_set_hermite_order}, {"hermiteOrder", js_hermite_order}, {"downloadSnap", js_download_snap}, {"uploadDerivs6", js_upload_derivs6},
         {"setStart6", js_set_start6}, {"start6", js_start6}, {"setPassPrecision", js_set_pass_precision}, {"passPrecision", js_pass_precision},
         {"setPassGuard", js_set_pass_guard}, {"passGuard", js_pass_guard},
-        {"setBlockSteps", js_set_block_steps}, {"setBlockSteps6", js_set_block_steps6}, {"blockStats", js_block_stats}, {"setBlockBatch", js_set_block_batch}, {"blockBatchStats", js_block_batch_stats}, {"downloadLevels", js_download_levels},
+        {"setBlockSteps", js_set_block_steps}, {"setBlockSteps6", js_set_block_steps6}, {"blockStats", js_block_stats}, {"setBlockBatch", js_set_block_batch}, {"setBlockBatch6", js_set_block_batch6}, {"blockBatchStats", js_block_batch_stats}, {"downloadLevels", js_download_levels},
         {"uploadLevels", js_upload_levels}, {"neighbors", js_neighbors}, {"neighborLists", js_neighbor_lists},
         {"knn", js_knn}, {"listForce", js_list_force}, {"splitForce", js_split_force}, {"splitLists", js_split_lists}, {"neighborSchemeFused", js_neighbor_scheme_fused},
         {"setNeighborScheme", js_set_neighbor_scheme}, {"neighborSchemeStats", js_neighbor_scheme_stats},

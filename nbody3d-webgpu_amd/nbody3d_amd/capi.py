@@ -214,7 +214,7 @@ SYMBOLS = ["nb_abi_version", "nb_device_count", "nb_create", "nb_destroy", "nb_u
            "nb_set_neighbor_levels", "nb_neighbor_level_stats", "nb_download_neighbor_levels", "nb_upload_neighbor_levels",
            "nb_set_hermite_order", "nb_hermite_order", "nb_download_snap", "nb_upload_derivs6",
            "nb_set_block_steps6", "nb_set_start6", "nb_start6", "nb_set_pass_precision", "nb_pass_precision",
-           "nb_set_pass_guard", "nb_pass_guard", "nb_set_block_batch", "nb_block_batch_stats"]
+           "nb_set_pass_guard", "nb_pass_guard", "nb_set_block_batch", "nb_block_batch_stats", "nb_set_block_batch6"]
 
 START6_ZERO, START6_CRACKLE = 0, 1      # nb_set_start6
 PASS_NATIVE, PASS_MIXED = 0, 1          # nb_set_pass_precision
@@ -335,6 +335,8 @@ def load_library():
     if hasattr(L, "nb_set_block_batch"):        # batched block steps, likewise
         L.nb_set_block_batch.argtypes = [vp, C.POINTER(nb_block_batch)]
         L.nb_block_batch_stats.argtypes = [vp, C.POINTER(nb_block_batch_stats), C.c_int]
+    if hasattr(L, "nb_set_block_batch6"):       # ... on order-6 handles, likewise
+        L.nb_set_block_batch6.argtypes = [vp, C.POINTER(nb_block_batch)]
     if hasattr(L, "nb_set_neighbor_levels"):    # block individual irregular steps inside the scheme, also within 2.4
         L.nb_set_neighbor_levels.argtypes = [vp, C.POINTER(nb_neighbor_levels)]
         L.nb_neighbor_level_stats.argtypes = [vp, C.POINTER(nb_neighbor_level_stats), C.c_int]
@@ -1060,10 +1062,21 @@ class Simulation:
         block steps with at most small_max active bodies (None: 256; 0: none; at most 1024) run from the device's own header, up
         to depth (None: 32; at most 1024) of them per host wait.  No stored bit depends on depth.  Touches no state, derivatives
         or levels.  set_block_batch(None) switches the mode off (so does set_block_steps(None))."""
-        if not hasattr(self._L, "nb_set_block_batch"):
-            raise NBodyError(1, "set_block_batch(): the loaded library has no nb_set_block_batch")
+        return self._set_block_batch("nb_set_block_batch", args, kw)
+
+    def set_block_batch6(self, *args, **kw):
+        """set_block_batch6(depth=None, small_max=None): nb_set_block_batch6 -- set_block_batch()'s mode on an order-6 handle with
+        set_block_steps6() on (f64: dynamic or frozen levels; f32: frozen levels).  The same arguments, defaults and refusals;
+        block_batch_stats() serves both.  set_block_batch6(None) switches the mode off (so do set_block_batch(None),
+        set_block_steps6(None) and set_block_steps(None))."""
+        return self._set_block_batch("nb_set_block_batch6", args, kw)
+
+    def _set_block_batch(self, symbol, args, kw):
+        who = symbol[3:]
+        if not hasattr(self._L, symbol):
+            raise NBodyError(1, "%s(): the loaded library has no %s" % (who, symbol))
         if args == (None,) and not kw:
-            self._check(self._L.nb_set_block_batch(self._h, None))
+            self._check(getattr(self._L, symbol)(self._h, None))
             return self
 
         def bind(depth=None, small_max=None):
@@ -1078,7 +1091,7 @@ class Simulation:
         cfg.depth = 0 if depth is None else int(depth)
         cfg.small_max = BLOCK_BATCH_SMALL_DEFAULT if small_max is None else int(small_max)
         cfg.flags = 0
-        self._check(self._L.nb_set_block_batch(self._h, C.byref(cfg)))
+        self._check(getattr(self._L, symbol)(self._h, C.byref(cfg)))
         return self
 
     def block_batch_stats(self, reset=False):

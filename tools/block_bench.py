@@ -21,7 +21,7 @@ every counterpart below then an order-6 handle too) on one GPU and prints ONE JS
                then a batch of min(depth, 63) slots whose first slot parks: with depth 32 that leaves 30 idle slots, with depth 3 one,
                and every later batch is the same in both.  (first outer step at depth 32 - at depth 3) / 29, the arms in turns.
 
---batch DEPTH,SMALL_MAX (order 4) switches set_block_batch(depth, small_max) on: (a) and (c) then run a handle with the mode on in
+--batch DEPTH,SMALL_MAX switches set_block_batch(depth, small_max) on (with --order 6: set_block_batch6): (a) and (c) then run a handle with the mode on in
 turns with the one without, (b) runs with the mode on and records the five batch counters (run it without --batch for the other arm).
 
 Needs a GPU (no fallback)."""
@@ -56,8 +56,9 @@ def block_steps(sim, **kw):
 BATCH = None      # --batch: (depth, small_max)
 
 
-def batch_on(sim):
-    return sim.set_block_batch(depth=BATCH[0], small_max=BATCH[1])
+def batch_on(sim, depth=None):
+    setter = sim.set_block_batch6 if ORDER == 6 else sim.set_block_batch
+    return setter(depth=BATCH[0] if depth is None else depth, small_max=BATCH[1])
 
 
 def spread(x):
@@ -254,7 +255,7 @@ def part_i(args, out):
             runs, idle = {3: [], 32: []}, {}
             for r in range(args.rounds + 1):      # the first round warms up
                 for depth in (3, 32):
-                    sim.set_block_batch(depth=depth, small_max=BATCH[1])      # the policy starts over: one slot, then min(depth, 63)
+                    batch_on(sim, depth)      # the policy starts over: one slot, then min(depth, 63)
                     sim.upload_levels(lev)
                     sim.block_batch_stats(reset=True)
                     t = wall(sim, 1)
@@ -270,7 +271,7 @@ def part_i(args, out):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--only", choices=["a", "b", "c", "i"], nargs="*", default=["a", "b", "c"])
-    ap.add_argument("--batch", default=None, metavar="DEPTH,SMALL_MAX", help="set_block_batch(depth, small_max) on the block handles (order 4)")
+    ap.add_argument("--batch", default=None, metavar="DEPTH,SMALL_MAX", help="set_block_batch(depth, small_max) on the block handles (with --order 6: set_block_batch6)")
     ap.add_argument("--full-n", type=int, default=65536)
     ap.add_argument("--sizes", type=int, nargs="*", default=[16384, 65536])
     ap.add_argument("--precision", default="f32", choices=["f32", "f64"])
@@ -292,8 +293,8 @@ def main():
     ORDER = args.order
     if args.batch:
         BATCH = tuple(int(x) for x in args.batch.split(","))
-        if len(BATCH) != 2 or ORDER != 4:
-            ap.error("--batch DEPTH,SMALL_MAX needs --order 4")
+        if len(BATCH) != 2:
+            ap.error("--batch takes DEPTH,SMALL_MAX")
     if "i" in args.only and not BATCH:
         ap.error("--only i needs --batch")
     if args.start6 and ORDER != 6:
