@@ -87,7 +87,8 @@ extern "C" {
                                             nb_set_pass_guard
                              2.4 (round 25) likewise within 2.4: nb_set_block_batch, nb_block_batch_stats, nb_block_batch,
                                             NB_BLOCK_BATCH_SMALL_DEFAULT.  Detected by the presence of the symbol nb_set_block_batch
-                             2.4 (round 26) likewise within 2.4: nb_set_block_batch6.  Detected by the presence of the symbol */
+                             2.4 (round 26) likewise within 2.4: nb_set_block_batch6.  Detected by the presence of the symbol
+                             2.4 (round 27) likewise within 2.4: nb_set_block_batch_mixed.  Detected by the presence of the symbol */
 
 typedef struct nb_sim nb_sim; /* opaque */
 
@@ -567,10 +568,10 @@ int nb_upload_levels(nb_sim *s, const uint8_t *levels /* n */);   /* after nb_up
  *     nb_upload_levels, nb_force_pass and ext_stream are unchanged.
  *   - nb_set_block_batch touches no state, no derivatives and no levels (none goes stale) and takes effect from the next nb_step.
  *     NB_ERR_STATE (the message names the function and the reason): a leapfrog handle, a handle without nb_set_block_steps, an
- *     order-6 handle, a handle with nb_set_pass_precision(NB_PASS_MIXED).  While the mode is on, nb_set_hermite_order(6) and
- *     nb_set_pass_precision(NB_PASS_MIXED) return NB_ERR_STATE; nb_set_block_steps(NULL) switches the mode off too, a non-NULL
- *     reconfiguration keeps it.  NB_ERR_INVALID (naming the field): a NULL handle, a wrong struct_size, depth > 1024, small_max >
- *     1024 other than NB_BLOCK_BATCH_SMALL_DEFAULT, flags != 0. */
+ *     order-6 handle, a handle with nb_set_pass_precision(NB_PASS_MIXED) (its mode: nb_set_block_batch_mixed below).  While the
+ *     mode is on, nb_set_hermite_order(6) and nb_set_pass_precision(NB_PASS_MIXED) return NB_ERR_STATE; nb_set_block_steps(NULL)
+ *     switches the mode off too, a non-NULL reconfiguration keeps it.  NB_ERR_INVALID (naming the field): a NULL handle, a wrong
+ *     struct_size, depth > 1024, small_max > 1024 other than NB_BLOCK_BATCH_SMALL_DEFAULT, flags != 0. */
 #define NB_BLOCK_BATCH_SMALL_DEFAULT 0xffffffffu  /* small_max: the default (256); 0 itself means "no small steps" */
 typedef struct nb_block_batch {
     uint32_t struct_size;  /* sizeof(nb_block_batch) */
@@ -601,8 +602,39 @@ int nb_set_block_batch(nb_sim *s, const nb_block_batch *cfg /* NULL: off */);
  *   - NB_ERR_STATE (the message names the function and the reason): a leapfrog handle, an order-4 handle (the message names
  *     nb_set_hermite_order), an order-6 handle without nb_set_block_steps6.  NB_ERR_INVALID (naming nb_set_block_batch6 and the
  *     field): a NULL handle, a wrong struct_size, depth > 1024, small_max > 1024 other than NB_BLOCK_BATCH_SMALL_DEFAULT, flags != 0.
- *   - Not built: the mode on mixed or guarded handles, with the neighbour scheme or on nb_multi. */
+ *   - Not built: the mode on guarded handles (mixed handles: nb_set_block_batch_mixed below), with the neighbour scheme or on
+ *     nb_multi. */
 int nb_set_block_batch6(nb_sim *s, const nb_block_batch *cfg /* NULL: off */);
+
+/* nb_set_block_batch_mixed (round 27): the same mode on mixed-precision handles -- an NB_F64 Hermite handle of order 4 with
+ * nb_set_block_steps on (dynamic or frozen levels), nb_set_pass_precision(NB_PASS_MIXED) and guard radius 0.  A separate entry
+ * point, as nb_set_block_batch6 is: nb_set_block_batch(non-NULL) on a mixed handle stays NB_ERR_STATE.  The struct, the defaults,
+ * the slot protocol, the scheduler, the host's policy, the header checks at every wait and nb_block_batch_stats (enabled = 1 while
+ * any of the three modes is on) are the ones above; inside a slot the predictor writes the mixed pass's three binary32 streams
+ * (xh, mf), xl, vf, a small pass runs the mixed pass's pair arithmetic on them (dr = (xh_j - xh_i) + (xl_j - xl_i), dv = vf_j - vf_i,
+ * nothing re-associated; kernels/block_batch_mixed.hip.h) and leaves binary32 chunk rows, and the corrector adds them in fp64 across
+ * the chunks into the fp64 state.  A parked slot's host step is the mixed handle's gathered pass and block corrector.
+ *   - The contract above holds word for word: with a fixed small_max no stored bit and no nb_block_stats counter depends on depth
+ *     or on where batches end; nb_step(k) equals k x nb_step(1); two handles give the same bits; read-only calls between steps
+ *     change nothing; small_max = 0 is a mixed handle with the mode off, bit for bit; t_next == 2^L always parks.
+ *   - What a small step computes for a body depends on the three predicted streams and on n alone (its j-chunks are a function of n
+ *     and the CU count), not on |A|, on the body's place in the active list, on small_max or on depth.  Results for DIFFERENT
+ *     small_max agree to the pass's accuracy only.
+ *   - Checkpoint: the five arrays bodies, vel, accel, jerk and levels, all fp64.  A handle restored by nb_upload, nb_upload_derivs,
+ *     nb_set_pass_precision(NB_PASS_MIXED) (anywhere before the batch setter), nb_set_block_steps, nb_set_block_batch_mixed (same
+ *     small_max, any depth), nb_upload_levels continues bit for bit.
+ *   - nb_force_pass, nb_enable_timing, dt <= 0, stale levels, nb_download_levels / nb_upload_levels and ext_stream are unchanged.
+ *   - The setter touches no state, no derivative and no level, and restarts the policy at one slot.  nb_set_block_batch_mixed(s, NULL),
+ *     nb_set_block_batch(s, NULL), nb_set_block_batch6(s, NULL) and nb_set_block_steps(s, NULL) switch the mode off; a non-NULL
+ *     nb_set_block_steps keeps it.  While the mode is on, nb_set_pass_precision with a mode that would change the precision,
+ *     nb_set_pass_guard(r > 0), nb_set_hermite_order(6) and nb_set_neighbor_scheme(non-NULL) are NB_ERR_STATE; calls that change
+ *     nothing (NB_PASS_MIXED again, nb_set_pass_guard(0)) stay NB_OK.
+ *   - NB_ERR_STATE (the message names the function and the setter to call): a leapfrog handle, an NB_F32 handle, an order-6 handle,
+ *     a handle without nb_set_block_steps, a native-precision handle (nb_set_pass_precision, or nb_set_block_batch), a handle with
+ *     nb_set_pass_guard > 0.  NB_ERR_INVALID (naming nb_set_block_batch_mixed and the field): a NULL handle, a wrong struct_size,
+ *     depth > 1024, small_max > 1024 other than NB_BLOCK_BATCH_SMALL_DEFAULT, flags != 0.
+ *   - Not built: the mode on guarded handles, at order 6 with a mixed pass, with the neighbour scheme or on nb_multi. */
+int nb_set_block_batch_mixed(nb_sim *s, const nb_block_batch *cfg /* NULL: off */);
 
 /* (a struct TAG without a typedef, as nb_block_stats) */
 struct nb_block_batch_stats {

@@ -649,7 +649,8 @@ struct hermite_order {
     uint32_t nb_sim::*chunks, nb_sim::*per;      // ... and the j-chunks of its full pass
     bool mixed;                       // the [1] entries are binary32 kernels on an f64 handle's streams (nb_set_pass_precision): f32 shapes and partial rows
     bool guard = false;               // ... with guarded sums (nb_set_pass_guard): the pass takes near2 last and leaves fp64 partial rows
-    // the kernels of a batched slot behind its scheduler (nb_set_block_batch, nb_set_block_batch6); null: the order has no batched mode
+    // the kernels of a batched slot behind its scheduler (nb_set_block_batch, nb_set_block_batch6, nb_set_block_batch_mixed); null: the
+    // order has no batched mode
     const void *bb_predict[2] = {nullptr, nullptr}, *bb_pass[2] = {nullptr, nullptr}, *bb_correct[2] = {nullptr, nullptr};
 };
 
@@ -692,9 +693,11 @@ const hermite_order kMixed = {
     {nullptr, (const void*)&nb::nb_mx_blk_fj<2>}, (const void*)&nb::nb_mx_blk_fj<1>,
     {nullptr, (const void*)&nb::nb_mx_predict<>}, {nullptr, (const void*)&nb::nb_hermite_correct<double>},
     {nullptr, (const void*)&nb::nb_mx_blk_predict<>}, {nullptr, (const void*)&nb::nb_blk_correct<float, double>},
-    &nb_sim::fj_part, &nb_sim::mx_chunks, &nb_sim::mx_per, true};
+    &nb_sim::fj_part, &nb_sim::mx_chunks, &nb_sim::mx_per, true, false,
+    {nullptr, (const void*)&nb::nb_blkqm_predict<>}, {nullptr, (const void*)&nb::nb_blkqm_fj<1>},
+    {nullptr, (const void*)&nb::nb_blkq_correct<float, double>}};
 // ... and with a guard radius (nb_set_pass_guard, kernels/guard.hip.h): kMixed's streams, predictors, shapes and j-chunks; the passes
-// leave fp64 partial rows, which the native pass's reduce and block corrector sum.
+// leave fp64 partial rows, which the native pass's reduce and block corrector sum.  No batched mode.
 const hermite_order kGuard = {
     "hermite4_", 2, 3, 4, {nb::kFjRows, nb::kFjRows}, {nb::kFjRows, nb::kFjRows},
     {nullptr, (const void*)&nb::nb_mxg_fj<nb::kFjNG>},
@@ -971,8 +974,8 @@ int block_step(nb_sim* s, uint32_t nsteps)
     return NB_OK;
 }
 
-// ---- nb_set_block_batch, nb_set_block_batch6: block steps sized on the device, many per host wait (kernels/block_batch.hip.h,
-// kernels/block_batch6.hip.h) ----------
+// ---- nb_set_block_batch, nb_set_block_batch6, nb_set_block_batch_mixed: block steps sized on the device, many per host wait
+// (kernels/block_batch.hip.h, kernels/block_batch6.hip.h, kernels/block_batch_mixed.hip.h) ----------
 // The j-chunks of the small pass: a function of n and the CU count alone (a row's bits must not depend on |A|, small_max or depth).
 // One chunk of whole tiles per CU: a wave's chain is a quarter of a chunk (64 rows of one tile up to 256 x CUs bodies), and the
 // corrector shares a slot's chunk rows among nb::kBbSumLanes lanes.
@@ -998,7 +1001,7 @@ uint32_t bb_plan_slots(const nb_sim* s)
     return (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(count, s->bb_depth));
 }
 
-// nb_step of a block-step handle of either order with nb_set_block_batch / nb_set_block_batch6 on: block_step's outer step, with
+// nb_step of a block-step handle of either order with nb_set_block_batch / nb_set_block_batch6 / nb_set_block_batch_mixed on: block_step's outer step, with
 // the slots of a batch enqueued behind one another and ONE host wait per batch; the slot's kernels and argument lists are the order's.  A slot that parked left its schedule and prediction: the host runs that block
 // step through the gathered path, as block_step does.
 int block_batch_step(nb_sim* s, uint32_t nsteps)
@@ -1014,10 +1017,11 @@ int block_batch_step(nb_sim* s, uint32_t nsteps)
     double eta = s->blk_eta, dt = s->dt, G = s->G, tick = std::ldexp(s->dt, -(int)L), e2 = s->eps2;
     float e2f = (float)s->eps2;
     const void* zr = s->zero_row;
-    const size_t row = (size_t)4 * (s->f64 ? 8 : 4);
+    const bool wide = s->f64 && !o.mixed;      // fp64 kernels and rows, as in launch_pass (a mixed slot: the f32 pass's shape and arguments)
+    const size_t row = (size_t)4 * (s->f64 ? 8 : 4);      // the stride of a plane: bb_configure's (a mixed plane's 16-byte rows fill half of it)
     void* plane[3] = {nullptr, nullptr, nullptr};
     for (uint32_t p = 0; p < o.planes; ++p) plane[p] = (char*)s->bb_part + p * (row * chunks * nb::kBbMaxSmall);
-    const uint32_t gx_small = std::max(1u, ceil_div(small_max, s->f64 ? nb::kBbRows64 : nb::kBbRows));
+    const uint32_t gx_small = std::max(1u, ceil_div(small_max, wide ? nb::kBbRows64 : nb::kBbRows));
     auto enqueue_slot = [&](uint32_t first) {
         void* sargs[] = {&s->blk_due, &s->blk_lev, &n, &s->blk_act, &s->blk_hdr, &s->blk_hdr_pub, &s->bb_words, &s->bb_pub, &first, &small_max, &end};
         (void)hipLaunchKernel((const void*)&nb::nb_blkq_sched<nb::kBlkSched>, dim3(1), dim3(nb::kBlkSched), sargs, 0, s->stream);
@@ -1027,7 +1031,7 @@ int block_batch_step(nb_sim* s, uint32_t nsteps)
         if (small_max == 0) return;      // no small steps: every slot parks
         kernel_args f;
         f(h.in, o.inputs)(&s->blk_act)(&s->blk_hdr)(&s->bb_words)(&small_max)(plane, o.planes)(&n)(&per);
-        if (s->f64) f(&e2); else f(&e2f)(&zr);
+        if (wide) f(&e2); else f(&e2f)(&zr);
         (void)hipLaunchKernel(o.bb_pass[s->f64], dim3(gx_small, chunks), dim3(nb::kBlock), f.v, 0, s->stream);
         kernel_args c;
         c(plane, o.planes)(&s->blk_act)(&s->bb_words)(&small_max)(&chunks)(&G)(h.state, o.states)(&s->blk_due)(&s->blk_lev)(&s->blk_hdr)(&n)(&Lk)(&lmin)(&frozen)(&eta)(&dt);
@@ -1962,7 +1966,8 @@ int nb_set_pass_precision(nb_sim* s, uint32_t mode)
     if (!s->f64) return fail(s, NB_ERR_STATE, "nb_set_pass_precision: precision NB_F32: the mixed pass keeps an fp64 state, it exists on NB_F64 handles only");
     if (s->h6) return fail(s, NB_ERR_STATE, "nb_set_pass_precision: the handle's order is 6 (nb_set_hermite_order): the mixed pass exists at order 4 only");
     if (s->ac) return fail(s, NB_ERR_STATE, "nb_set_pass_precision: the neighbour scheme is switched on (nb_set_neighbor_scheme): it has no mixed kernels");
-    if (mode == NB_PASS_MIXED && s->bb) return fail(s, NB_ERR_STATE, "nb_set_pass_precision: NB_PASS_MIXED while batched block steps are switched on (nb_set_block_batch): they run the native pass only, switch them off first");
+    if (mode == NB_PASS_MIXED && s->bb && !s->mx) return fail(s, NB_ERR_STATE, "nb_set_pass_precision: NB_PASS_MIXED while batched block steps are switched on (nb_set_block_batch): they run the native pass only, switch them off first");
+    if (mode == NB_PASS_NATIVE && s->bb && s->mx) return fail(s, NB_ERR_STATE, "nb_set_pass_precision: NB_PASS_NATIVE while the batched block steps of a mixed handle are switched on (nb_set_block_batch_mixed): they run the mixed pass only, switch them off first");
     if ((mode == NB_PASS_MIXED) == s->mx) return NB_OK;
     NB_HIP(s, hipSetDevice(s->device));
     NB_HIP(s, hipStreamSynchronize(s->stream));
@@ -2011,6 +2016,7 @@ int nb_set_pass_guard(nb_sim* s, double r_near)
     if (!s->f64) return fail(s, NB_ERR_STATE, "nb_set_pass_guard: precision NB_F32: the guard belongs to the mixed pass of NB_F64 handles (nb_set_pass_precision)");
     if (s->h6) return fail(s, NB_ERR_STATE, "nb_set_pass_guard: the handle's order is 6 (nb_set_hermite_order): the mixed pass (nb_set_pass_precision) and its guard exist at order 4 only");
     if (!s->mx) return fail(s, NB_ERR_STATE, "nb_set_pass_guard: the pass precision is NB_PASS_NATIVE: set NB_PASS_MIXED first (nb_set_pass_precision)");
+    if (r_near > 0.0 && s->bb) return fail(s, NB_ERR_STATE, "nb_set_pass_guard: r_near > 0 while batched block steps are switched on (nb_set_block_batch_mixed): they have no guarded pass, switch them off first");
     if ((r_near > 0.0) == (s->mx_guard > 0.0)) { s->mx_guard = r_near; return NB_OK; }      // another radius, or off and off: the kernels and the rows stay
     NB_HIP(s, hipSetDevice(s->device));
     NB_HIP(s, hipStreamSynchronize(s->stream));
@@ -2172,7 +2178,7 @@ int nb_block_stats(nb_sim* s, struct nb_block_stats* out, int reset)
     return NB_OK;
 }
 
-// The argument checks nb_set_block_batch and nb_set_block_batch6 share (who: the entry point's name).
+// The argument checks nb_set_block_batch, nb_set_block_batch6 and nb_set_block_batch_mixed share (who: the entry point's name).
 int bb_check(nb_sim* s, const nb_block_batch* cfg, const std::string& who)
 {
     if (cfg->struct_size != sizeof(nb_block_batch)) return fail(s, NB_ERR_INVALID, who + ": struct_size must be sizeof(nb_block_batch)");
@@ -2232,6 +2238,20 @@ int nb_set_block_batch6(nb_sim* s, const nb_block_batch* cfg)
     if (!s->hermite) return fail(s, NB_ERR_STATE, "nb_set_block_batch6: needs a Hermite handle (nb_config.integrator = NB_INT_HERMITE4) of order 6 (nb_set_hermite_order) with block steps switched on (nb_set_block_steps6)");
     if (!s->h6) return fail(s, NB_ERR_STATE, "nb_set_block_batch6: the handle's order is 4 (nb_set_hermite_order): see nb_set_block_batch");
     if (!s->blk) return fail(s, NB_ERR_STATE, "nb_set_block_batch6: block steps are not switched on (nb_set_block_steps6)");
+    return bb_configure(s, cfg);
+}
+
+int nb_set_block_batch_mixed(nb_sim* s, const nb_block_batch* cfg)
+{
+    if (!s) return fail(nullptr, NB_ERR_INVALID, "nb_set_block_batch_mixed: null handle");
+    if (!cfg) { s->bb = false; return NB_OK; }
+    if (int rc = bb_check(s, cfg, "nb_set_block_batch_mixed")) return rc;
+    if (!s->hermite) return fail(s, NB_ERR_STATE, "nb_set_block_batch_mixed: needs a Hermite handle (nb_config.integrator = NB_INT_HERMITE4) with block steps switched on (nb_set_block_steps)");
+    if (!s->f64) return fail(s, NB_ERR_STATE, "nb_set_block_batch_mixed: precision NB_F32: the mixed pass (nb_set_pass_precision) exists on NB_F64 handles only, see nb_set_block_batch");
+    if (s->h6) return fail(s, NB_ERR_STATE, "nb_set_block_batch_mixed: the handle's order is 6 (nb_set_hermite_order): the mixed pass exists at order 4 only, see nb_set_block_batch6");
+    if (!s->blk) return fail(s, NB_ERR_STATE, "nb_set_block_batch_mixed: block steps are not switched on (nb_set_block_steps)");
+    if (!s->mx) return fail(s, NB_ERR_STATE, "nb_set_block_batch_mixed: the pass precision is NB_PASS_NATIVE: set NB_PASS_MIXED first (nb_set_pass_precision), or see nb_set_block_batch");
+    if (s->mx_guard > 0.0) return fail(s, NB_ERR_STATE, "nb_set_block_batch_mixed: a guard radius is set (nb_set_pass_guard): batched block steps have no guarded pass, call nb_set_pass_guard(0) first");
     return bb_configure(s, cfg);
 }
 

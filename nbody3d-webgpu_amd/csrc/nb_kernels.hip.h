@@ -77,3 +77,4 @@
 #include "kernels/hermite6.hip.h"    // nb_h6_fjs_pk, nb_h6_fjs64, nb_h6_reduce, nb_h6_predict, nb_h6_correct (nb_set_hermite_order(6): force, jerk and snap); nb_h6_crk_pk, nb_h6_crk64, nb_h6_reduce1 (nb_set_start6: the crackle of a start)
 #include "kernels/block6.hip.h"      // nb_blk6_start, nb_blk6_predict, nb_blk6_fjs_pk, nb_blk6_fjs64, nb_blk6_correct (nb_set_block_steps6: block steps on order-6 handles)
 #include "kernels/block_batch6.hip.h" // nb_blkq6_predict, nb_blkq6_fjs_pk, nb_blkq6_fjs64, nb_blkq6_correct (nb_set_block_batch6: block steps sized on the device, order-6 handles)
+#include "kernels/block_batch_mixed.hip.h" // nb_blkqm_predict, nb_blkqm_fj (nb_set_block_batch_mixed: block steps sized on the device, mixed-precision handles)

@@ -77,6 +77,7 @@ static int (*p_block_stats)(nb_sim *, struct nb_block_stats *, int);
 static int (*p_set_block_batch)(nb_sim *, const nb_block_batch *);      /* batched block steps (round 25): optional */
 static int (*p_block_batch_stats)(nb_sim *, struct nb_block_batch_stats *, int);
 static int (*p_set_block_batch6)(nb_sim *, const nb_block_batch *);     /* ... on order-6 handles (round 26): optional */
+static int (*p_set_block_batch_mixed)(nb_sim *, const nb_block_batch *);     /* ... on mixed-precision handles (round 27): optional */
 static int (*p_download_levels)(nb_sim *, uint8_t *);
 static int (*p_upload_levels)(nb_sim *, const uint8_t *);
 static int (*p_neighbors)(nb_sim *, const nb_neighbor_request *);       /* neighbour queries, also within ABI 2.4: optional symbols */
@@ -201,6 +202,7 @@ static napi_value js_load(napi_env env, napi_callback_info info)
         *(void **)(&p_set_block_batch) = dlsym(h, "nb_set_block_batch");
         *(void **)(&p_block_batch_stats) = dlsym(h, "nb_block_batch_stats");
         *(void **)(&p_set_block_batch6) = dlsym(h, "nb_set_block_batch6");
+        *(void **)(&p_set_block_batch_mixed) = dlsym(h, "nb_set_block_batch_mixed");
         *(void **)(&p_download_levels) = dlsym(h, "nb_download_levels");
         *(void **)(&p_upload_levels) = dlsym(h, "nb_upload_levels");
         *(void **)(&p_neighbors) = dlsym(h, "nb_neighbors");
@@ -1361,7 +1363,7 @@ static napi_value js_block_stats(napi_env env, napi_callback_info info)
 }
 
 /* setBlockBatch(handle, null) | setBlockBatch(handle, depth, smallMax): nb_set_block_batch (depth 0: the default; smallMax < 0: the
- * default); setBlockBatch6 likewise through nb_set_block_batch6 */
+ * default); setBlockBatch6 and setBlockBatchMixed likewise through nb_set_block_batch6 and nb_set_block_batch_mixed */
 static napi_value set_block_batch_by(napi_env env, napi_callback_info info, int (*fn)(nb_sim *, const nb_block_batch *), const char *sym)
 {
     size_t argc = 3; napi_value argv[3];
@@ -1387,6 +1389,7 @@ static napi_value set_block_batch_by(napi_env env, napi_callback_info info, int 
 }
 static napi_value js_set_block_batch(napi_env env, napi_callback_info info) { return set_block_batch_by(env, info, p_set_block_batch, "nb_set_block_batch"); }
 static napi_value js_set_block_batch6(napi_env env, napi_callback_info info) { return set_block_batch_by(env, info, p_set_block_batch6, "nb_set_block_batch6"); }
+static napi_value js_set_block_batch_mixed(napi_env env, napi_callback_info info) { return set_block_batch_by(env, info, p_set_block_batch_mixed, "nb_set_block_batch_mixed"); }
 
 /* blockBatchStats(handle, reset) -> {enabled, hostWaits, slots, smallSteps, hostSteps, idleSlots} (counts as doubles) */
 static napi_value js_block_batch_stats(napi_env env, napi_callback_info info)
@@ -1724,7 +1727,7 @@ static napi_value init_module(napi_env env, napi_value exports)
         {"setHermiteOrder", js_set_hermite_order}, {"hermiteOrder", js_hermite_order}, {"downloadSnap", js_download_snap}, {"uploadDerivs6", js_upload_derivs6},
         {"setStart6", js_set_start6}, {"start6", js_start6}, {"setPassPrecision", js_set_pass_precision}, {"passPrecision", js_pass_precision},
         {"setPassGuard", js_set_pass_guard}, {"passGuard", js_pass_guard},
-        {"setBlockSteps", js_set_block_steps}, {"setBlockSteps6", js_set_block_steps6}, {"blockStats", js_block_stats}, {"setBlockBatch", js_set_block_batch}, {"setBlockBatch6", js_set_block_batch6}, {"blockBatchStats", js_block_batch_stats}, {"downloadLevels", js_download_levels},
+        {"setBlockSteps", js_set_block_steps}, {"setBlockSteps6", js_set_block_steps6}, {"blockStats", js_block_stats}, {"setBlockBatch", js_set_block_batch}, {"setBlockBatch6", js_set_block_batch6}, {"setBlockBatchMixed", js_set_block_batch_mixed}, {"blockBatchStats", js_block_batch_stats}, {"downloadLevels", js_download_levels},
         {"uploadLevels", js_upload_levels}, {"neighbors", js_neighbors}, {"neighborLists", js_neighbor_lists},
         {"knn", js_knn}, {"listForce", js_list_force}, {"splitForce", js_split_force}, {"splitLists", js_split_lists}, {"neighborSchemeFused", js_neighbor_scheme_fused},
         {"setNeighborScheme", js_set_neighbor_scheme}, {"neighborSchemeStats", js_neighbor_scheme_stats},

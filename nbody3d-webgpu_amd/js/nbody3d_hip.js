@@ -19,7 +19,7 @@
  *   readJerk()             (no reference analogue) the jerk of a {integrator: 'hermite4'} simulation
  *   setHermiteOrder(6 | 4), hermiteOrder(), readSnap(), uploadDerivs6(accel, jerk, snap, crackle)
  *                          (no reference analogue) the 6th-order scheme of a 'hermite4' simulation on force, jerk and snap
- *   setBlockBatch() / setBlockBatch6() / blockBatchStats()
+ *   setBlockBatch() / setBlockBatch6() / setBlockBatchMixed() / blockBatchStats()
  *   setBlockSteps() / setBlockSteps6() / blockStats() / readLevels() / uploadLevels()
  *                          (no reference analogue) block individual time steps of a 'hermite4' simulation
  *   requestFrame()/frame() nbody3d.js:408-415,482-487 what the render pass reads each frame
@@ -322,6 +322,18 @@ class Simulation {
     if (options === null) { addon.setBlockBatch6(this._h, null); return this; }
     const o = options || {};
     addon.setBlockBatch6(this._h, (o.depth || 0) >>> 0, (o.smallMax === undefined || o.smallMax === null) ? -1 : Number(o.smallMax));
+    return this;
+  }
+
+  /** setBlockBatch()'s mode on an f64 simulation of order 4 with setBlockSteps() on, setPassPrecision('mixed') and no guard
+   *  (nb_set_block_batch_mixed): the small steps run the double-single pass.  The same options, defaults and refusals;
+   *  blockBatchStats() serves all three.  setBlockBatchMixed(null) switches the mode off (so do setBlockBatch(null),
+   *  setBlockBatch6(null) and setBlockSteps(null)). */
+  setBlockBatchMixed(options) {
+    this._need();
+    if (options === null) { addon.setBlockBatchMixed(this._h, null); return this; }
+    const o = options || {};
+    addon.setBlockBatchMixed(this._h, (o.depth || 0) >>> 0, (o.smallMax === undefined || o.smallMax === null) ? -1 : Number(o.smallMax));
     return this;
   }
 

@@ -214,7 +214,8 @@ SYMBOLS = ["nb_abi_version", "nb_device_count", "nb_create", "nb_destroy", "nb_u
            "nb_set_neighbor_levels", "nb_neighbor_level_stats", "nb_download_neighbor_levels", "nb_upload_neighbor_levels",
            "nb_set_hermite_order", "nb_hermite_order", "nb_download_snap", "nb_upload_derivs6",
            "nb_set_block_steps6", "nb_set_start6", "nb_start6", "nb_set_pass_precision", "nb_pass_precision",
-           "nb_set_pass_guard", "nb_pass_guard", "nb_set_block_batch", "nb_block_batch_stats", "nb_set_block_batch6"]
+           "nb_set_pass_guard", "nb_pass_guard", "nb_set_block_batch", "nb_block_batch_stats", "nb_set_block_batch6",
+           "nb_set_block_batch_mixed"]
 
 START6_ZERO, START6_CRACKLE = 0, 1      # nb_set_start6
 PASS_NATIVE, PASS_MIXED = 0, 1          # nb_set_pass_precision
@@ -337,6 +338,8 @@ def load_library():
         L.nb_block_batch_stats.argtypes = [vp, C.POINTER(nb_block_batch_stats), C.c_int]
     if hasattr(L, "nb_set_block_batch6"):       # ... on order-6 handles, likewise
         L.nb_set_block_batch6.argtypes = [vp, C.POINTER(nb_block_batch)]
+    if hasattr(L, "nb_set_block_batch_mixed"):  # ... on mixed-precision handles, likewise
+        L.nb_set_block_batch_mixed.argtypes = [vp, C.POINTER(nb_block_batch)]
     if hasattr(L, "nb_set_neighbor_levels"):    # block individual irregular steps inside the scheme, also within 2.4
         L.nb_set_neighbor_levels.argtypes = [vp, C.POINTER(nb_neighbor_levels)]
         L.nb_neighbor_level_stats.argtypes = [vp, C.POINTER(nb_neighbor_level_stats), C.c_int]
@@ -1070,6 +1073,13 @@ class Simulation:
         block_batch_stats() serves both.  set_block_batch6(None) switches the mode off (so do set_block_batch(None),
         set_block_steps6(None) and set_block_steps(None))."""
         return self._set_block_batch("nb_set_block_batch6", args, kw)
+
+    def set_block_batch_mixed(self, *args, **kw):
+        """set_block_batch_mixed(depth=None, small_max=None): nb_set_block_batch_mixed -- set_block_batch()'s mode on an f64 order-4
+        handle with set_block_steps() on, set_pass_precision("mixed") and no guard: the small steps run the double-single pass.
+        The same arguments, defaults and refusals; block_batch_stats() serves all three.  set_block_batch_mixed(None) switches
+        the mode off (so do set_block_batch(None), set_block_batch6(None) and set_block_steps(None))."""
+        return self._set_block_batch("nb_set_block_batch_mixed", args, kw)
 
     def _set_block_batch(self, symbol, args, kw):
         who = symbol[3:]

@@ -24,6 +24,10 @@ every counterpart below then an order-6 handle too) on one GPU and prints ONE JS
 --batch DEPTH,SMALL_MAX switches set_block_batch(depth, small_max) on (with --order 6: set_block_batch6): (a) and (c) then run a handle with the mode on in
 turns with the one without, (b) runs with the mode on and records the five batch counters (run it without --batch for the other arm).
 
+--pass-precision mixed (order 4, f64 only: (a), (c) and (i) run their f64 case alone, (b) needs --precision f64) calls
+set_pass_precision("mixed") on every handle with block steps -- the plain Hermite handles of (a) and the shared runs of (b) stay
+native -- and --batch then goes through set_block_batch_mixed.
+
 Needs a GPU (no fallback)."""
 import argparse
 import contextlib
@@ -49,7 +53,16 @@ def hermite(n, prec, eps2=None):
     return sim
 
 
+MIXED = False      # --pass-precision mixed: the block handles (f64 only) run the double-single pass
+
+
+def precisions():
+    return ("f64",) if MIXED else ("f32", "f64")
+
+
 def block_steps(sim, **kw):
+    if MIXED:
+        sim.set_pass_precision("mixed")
     return sim.set_block_steps6(**kw) if ORDER == 6 else sim.set_block_steps(**kw)
 
 
@@ -57,7 +70,7 @@ BATCH = None      # --batch: (depth, small_max)
 
 
 def batch_on(sim, depth=None):
-    setter = sim.set_block_batch6 if ORDER == 6 else sim.set_block_batch
+    setter = sim.set_block_batch6 if ORDER == 6 else sim.set_block_batch_mixed if MIXED else sim.set_block_batch
     return setter(depth=BATCH[0] if depth is None else depth, small_max=BATCH[1])
 
 
@@ -97,7 +110,7 @@ def energy(sim):
 def part_a(args, out):
     n = args.full_n
     b, v = ic.plummer(n, seed=1)
-    for prec in ("f32", "f64"):
+    for prec in precisions():
         with contextlib.ExitStack() as stack:
             blk, plain = stack.enter_context(hermite(n, prec)), stack.enter_context(hermite(n, prec))
             bat = stack.enter_context(hermite(n, prec)) if BATCH else None      # the handle with the mode on
@@ -140,7 +153,7 @@ def part_b(args, out):
         outer = int(round(1.0 / args.outer_dt))
         r = {"n": n, "pairs": int(0.01 * n) // 2, "precision": args.precision, "outer_dt": args.outer_dt, "eta": args.eta, "order": ORDER,
              "start_deeper": args.start_deeper, "start6": int(args.start6), "pair_half": args.pair_half, "eps2": args.eps2,
-             "batch": list(BATCH) if BATCH else None}
+             "batch": list(BATCH) if BATCH else None, "pass_precision": "mixed" if MIXED else "native"}
         with hermite(n, args.precision, args.eps2) as sim:
             sim.init(b, v)
             if args.start6:      # the engine's own start: exact crackle, two-rule levels
@@ -192,7 +205,7 @@ def part_c(args, out):
     lev[np.random.default_rng(5).choice(n, k, replace=False)] = L
     sets = (("all_level0", np.zeros(n, np.uint8)), ("64_at_level6", lev))
     arms = ["off"] + (["on"] if BATCH else [])
-    for prec in ("f32", "f64"):
+    for prec in precisions():
         sims = {}
         try:
             for arm in arms:      # one handle per (arm, set of levels): the arms run in turns
@@ -247,7 +260,7 @@ def part_i(args, out):
     lev = np.zeros(n, np.uint8)
     lev[pick[:64]] = L
     lev[pick[64:]] = L - 1
-    for prec in ("f32", "f64"):
+    for prec in precisions():
         with hermite(n, prec) as sim:
             sim.init(b, v)
             sim.set_params(1e-3, 1.0)
@@ -272,6 +285,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--only", choices=["a", "b", "c", "i"], nargs="*", default=["a", "b", "c"])
     ap.add_argument("--batch", default=None, metavar="DEPTH,SMALL_MAX", help="set_block_batch(depth, small_max) on the block handles (with --order 6: set_block_batch6)")
+    ap.add_argument("--pass-precision", default="native", choices=["native", "mixed"], help="mixed: set_pass_precision('mixed') on the block handles (f64 only); --batch then uses set_block_batch_mixed")
     ap.add_argument("--full-n", type=int, default=65536)
     ap.add_argument("--sizes", type=int, nargs="*", default=[16384, 65536])
     ap.add_argument("--precision", default="f32", choices=["f32", "f64"])
@@ -289,8 +303,13 @@ def main():
     ap.add_argument("--min-seconds", type=float, default=0.3)
     ap.add_argument("--rounds", type=int, default=3)
     args = ap.parse_args()
-    global ORDER, BATCH
+    global ORDER, BATCH, MIXED
     ORDER = args.order
+    MIXED = args.pass_precision == "mixed"
+    if MIXED and ORDER != 4:
+        ap.error("--pass-precision mixed needs --order 4")
+    if MIXED and "b" in args.only and args.precision != "f64":
+        ap.error("--pass-precision mixed with (b) needs --precision f64")
     if args.batch:
         BATCH = tuple(int(x) for x in args.batch.split(","))
         if len(BATCH) != 2:
@@ -301,7 +320,7 @@ def main():
         ap.error("--start6 needs --order 6")
     if capi.device_count() < 1:
         sys.exit("block_bench: no GPU")
-    out = {"tool": "block_bench", "order": ORDER, "batch": list(BATCH) if BATCH else None, "full": {}, "end2end": [], "small": {}, "idle": {}}
+    out = {"tool": "block_bench", "order": ORDER, "batch": list(BATCH) if BATCH else None, "pass_precision": args.pass_precision, "full": {}, "end2end": [], "small": {}, "idle": {}}
     if "a" in args.only:
         part_a(args, out)
     if "b" in args.only:
