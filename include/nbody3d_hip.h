@@ -88,7 +88,10 @@ extern "C" {
                              2.4 (round 25) likewise within 2.4: nb_set_block_batch, nb_block_batch_stats, nb_block_batch,
                                             NB_BLOCK_BATCH_SMALL_DEFAULT.  Detected by the presence of the symbol nb_set_block_batch
                              2.4 (round 26) likewise within 2.4: nb_set_block_batch6.  Detected by the presence of the symbol
-                             2.4 (round 27) likewise within 2.4: nb_set_block_batch_mixed.  Detected by the presence of the symbol */
+                             2.4 (round 27) likewise within 2.4: nb_set_block_batch_mixed.  Detected by the presence of the symbol
+                             2.4 (round 28) likewise within 2.4: nb_set_encounter_watch, nb_encounter_stats, nb_download_encounters,
+                                            nb_upload_encounters, nb_reset_encounters, nb_encounter_watch, NB_ENC_STOP.  Detected by
+                                            the presence of the symbol nb_set_encounter_watch */
 
 typedef struct nb_sim nb_sim; /* opaque */
 
@@ -648,6 +651,70 @@ struct nb_block_batch_stats {
 /* block_batch_stats: the counters since the last reset (set out->struct_size); reset != 0 zeroes them after the read.
  * slots == small_steps + host_steps + idle_slots, host_steps <= host_waits <= slots. */
 int nb_block_batch_stats(nb_sim *s, struct nb_block_batch_stats *out, int reset);
+
+/* nb_set_encounter_watch (round 28): the closest approach every watched body sees INSIDE block steps.  Between nb_step calls every
+ * body stands at a multiple of dt; a hard pair runs through hundreds of orbits inside one outer step, and nb_neighbors at the boundary
+ * sees whatever phase it happens to be in.  The gathered pass of a block step already forms rho^2 = |dr|^2 + eps2 for every (active
+ * body, body) pair at the active body's own time: with the watch on it keeps the smallest one below the body's threshold, as the
+ * force libraries of the GRAPE family return the nearest neighbour with the force.  The primitive under collision and merger
+ * detection, close-encounter stopping conditions and the search for pairs to regularise.
+ *   - Opt-in, on a Hermite handle of order 4 with nb_set_block_steps on (dynamic or frozen levels), the native pass, NB_F32 or
+ *     NB_F64, no batched mode.  No stored bit of the state, the derivatives or the levels and no nb_block_stats counter depends on
+ *     the watch: the pass's sums are the same instructions on the same values.
+ *   - Body i has a watch radius h_i >= 0: `radius` for all bodies, or radii[i] (n elements of the handle's precision, host memory,
+ *     copied by the call); 0: the body is not watched.  The threshold is w_i = h_i^2 + eps2, evaluated in fp64 and rounded once to
+ *     the handle's precision.
+ *   - When: at every gathered pass of a block step, for every active body i with h_i > 0 -- the full-set step that ends an outer
+ *     step included; the start's pass and read-only calls (nb_force_pass, the queries) not.
+ *   - Candidates: bodies j != i BY INDEX, j < n, whose rho^2_ij is strictly below w_i; rho^2_ij is the value the pass holds (the same
+ *     fma order on the same predicted rows).  A distinct body at the same position is a candidate with rho^2 = eps2.  The pass's
+ *     answer for i is the candidate of smallest rho^2, equal rho^2 to the smallest index (nb_neighbors' rule).
+ *   - The record of a body lives until reset: rho2 (the smallest answer so far, the handle's precision; +inf at the start), partner
+ *     (uint32; 0xffffffff at the start), time (double, +inf at the start: the number of outer steps the handle had run when that
+ *     outer step began + t_next / 2^max_level; exact, independent of dt), count (uint32: own steps that had an answer).  A new answer
+ *     replaces (rho2, partner, time) only when strictly smaller -- the earliest time wins a tie --, every step with an answer
+ *     increments count.  Only the active body records: a pair is seen from both sides, at each member's own steps.
+ *   - Nothing depends on timing: floating-point values are compared, never added; the atomics are integer counts and an integer
+ *     minimum for the statistics.
+ *   - NB_ENC_STOP: nb_step(k) returns NB_OK after the first outer step at whose end hits (below) is non-zero since the last reset,
+ *     with stopped = 1 and steps_left = the outer steps not run.  One extra host wait per outer step, with the flag only.
+ *   - nb_upload keeps the configuration and the counters and clears the records.  nb_set_encounter_watch(non-NULL) while the watch
+ *     is on replaces radii and flags and keeps records and counters; switched on from off, both start over.
+ *     nb_set_encounter_watch(s, NULL) and nb_set_block_steps(s, NULL) switch it off.  While it is on, nb_set_block_batch,
+ *     nb_set_block_batch6, nb_set_block_batch_mixed (non-NULL), nb_set_pass_precision(NB_PASS_MIXED), nb_set_hermite_order(6) and
+ *     nb_set_neighbor_scheme(non-NULL) are NB_ERR_STATE.
+ *   - Checkpoint: the four record arrays beside the state's (nb_download_encounters / nb_upload_encounters, the last calls of a
+ *     restore, behind nb_set_encounter_watch).  The times count the handle's own outer steps.
+ *   - Errors.  NB_ERR_INVALID: a NULL handle, unknown flag bits, a radius or radii element negative, NaN or infinite, a NULL out
+ *     pointer, a NULL array or a partner that is neither another body's index nor 0xffffffff in nb_upload_encounters.  NB_ERR_STATE
+ *     (the message names the function and the reason): a leapfrog handle, block steps off, an order-6 handle, a mixed or guarded
+ *     pass, a batched mode on, the neighbour scheme on; the four other calls on a handle without the watch.
+ *   - Not built: the watch in batched slots, in the mixed and guarded passes, at order 6, with the neighbour scheme, on nb_multi; a
+ *     criterion on r_i + r_j. */
+enum { NB_ENC_STOP = 1u };      /* nb_encounter_watch.flags: nb_step returns after the first outer step that had a hit */
+typedef struct nb_encounter_watch {
+    double radius;          /* h for every body (radii == NULL) */
+    const void *radii;      /* n elements of the handle's precision, host memory; NULL: radius */
+    uint32_t flags;         /* NB_ENC_* */
+} nb_encounter_watch;
+int nb_set_encounter_watch(nb_sim *s, const nb_encounter_watch *cfg /* NULL: off */);
+
+/* (a struct TAG without a typedef, as nb_block_stats) */
+struct nb_encounter_stats {
+    uint64_t passes;        /* gathered passes that ran with the watch on */
+    uint64_t hits;          /* body steps that had an answer */
+    double first_time;      /* the earliest block time with an answer, as the records' time; +inf: none */
+    uint32_t stopped;       /* the last nb_step returned early (NB_ENC_STOP) ... */
+    uint32_t steps_left;    /* ... with this many of its outer steps not run */
+};
+/* encounter_stats: the counters since the last reset; reset != 0 zeroes passes, hits and first_time after the read (the records stay). */
+int nb_encounter_stats(nb_sim *s, struct nb_encounter_stats *out, int reset /* counters only */);
+/* download_encounters / upload_encounters: the records, n elements each -- rho2 in the handle's precision.  Download: each pointer
+ * may be NULL; changes nothing.  Upload: all four are required. */
+int nb_download_encounters(nb_sim *s, void *rho2, uint32_t *partner, double *time, uint32_t *count);
+int nb_upload_encounters(nb_sim *s, const void *rho2, const uint32_t *partner, const double *time, const uint32_t *count);
+/* reset_encounters: the records to their start values, the counters and stopped / steps_left to 0. */
+int nb_reset_encounters(nb_sim *s);
 
 /* ---- viewer frame feed ------------------------------------------------
  * The reference's render pass reads bodyBuffer and velBuffer in place every frame

@@ -38,29 +38,46 @@ constexpr uint32_t kFjFlush = 4;                    // tiles between two flushes
 //   The body is shared with nb_blk_fj_pk (kernels/block.hip.h): with GATHER the ni i-rows are act[0 .. ni) and the partial rows are
 // compact (row k of chunk c belongs to act[k]); without it ni == n and row k is body k.  Everything between the prologue's loads
 // and the epilogue's stores is the same code.
-template <int NG, bool GATHER>
+//   WATCH (nb_set_encounter_watch, kernels/encounter.hip.h; with GATHER only): wth[i] is body i's threshold w_i.  Per stage the
+// compares rho^2 < w_i of its chains are ORed on the scalar unit and ONE wave-uniform branch skips the slow path, which tests the
+// index (own row, rows past the chunk) and keeps the lane's smallest (rho^2, j), equal rho^2 to the smaller j.  The best pair, the
+// own indices live in LDS beside the tiles (touched on the slow path only: nb_blk_fj_pk<2> stands at 228 VGPRs) and leave in the
+// .w lanes of the two partial rows.  The sums are the same instructions on the same values: no bit of them moves.  Without WATCH
+// none of this is compiled.
+template <int NG, bool GATHER, bool WATCH = false>
 __device__ __forceinline__ void fj_pk_body(const float4* __restrict__ pos, const float4* __restrict__ vel,
                                            const uint32_t* __restrict__ act, uint32_t ni, float4* __restrict__ pa,
                                            float4* __restrict__ pj, uint32_t n, uint32_t j_per_chunk, float eps2,
-                                           const float4* __restrict__ zero_row)
+                                           const float4* __restrict__ zero_row, const float* __restrict__ wth = nullptr)
 {
+    static_assert(GATHER || !WATCH, "the watch exists on the gathered pass only");
     constexpr int TILE = kTile;
     constexpr int U = 8;                  // tile rows per unrolled chunk
     constexpr int JB = 4 / NG;            // j-bodies per stage: JB * NG = 4 independent chains
     constexpr uint32_t ROWS = kBlock * 2 * NG;
     constexpr int NC = JB * NG;
     __shared__ float4 tile[2][2][TILE];   // [buffer][0 = positions, 1 = velocities][row]
+    __shared__ nb_f2 enc_r[WATCH ? NG : 1][WATCH ? kBlock : 1];      // WATCH: the lane's smallest rho^2 so far, per packed half
+    __shared__ uint2 enc_j[WATCH ? NG : 1][WATCH ? kBlock : 1];      // ... its index (0xffffffff: none)
+    __shared__ uint2 enc_o[WATCH ? NG : 1][WATCH ? kBlock : 1];      // ... and the lane's own bodies
     const int tid = threadIdx.x;
     const uint32_t i0 = blockIdx.x * ROWS;
     const uint32_t j0 = blockIdx.y * j_per_chunk;
     const uint32_t j1 = j0 + j_per_chunk < n ? j0 + j_per_chunk : n;
 
     nb_f2 xi[NG], yi[NG], zi[NG], ui[NG], vi[NG], wi[NG];
+    nb_f2 wq[WATCH ? NG : 1];             // WATCH: the thresholds of the lane's bodies
 #pragma unroll
     for (int g = 0; g < NG; ++g) {
         const uint32_t il0 = i0 + (2 * g) * kBlock + tid, il1 = il0 + kBlock;
         uint32_t c0 = il0 < ni ? il0 : ni - 1, c1 = il1 < ni ? il1 : ni - 1;        // clamped, branch-free (never stored)
         if constexpr (GATHER) { c0 = act[c0]; c1 = act[c1]; }
+        if constexpr (WATCH) {            // a clamped lane watches nothing (rho^2 < 0 never holds); a lane reads and writes its own words only: no barrier
+            wq[g] = nb_f2{il0 < ni ? wth[c0] : 0.0f, il1 < ni ? wth[c1] : 0.0f};
+            enc_r[g][tid] = nb_f2{__builtin_inff(), __builtin_inff()};
+            enc_j[g][tid] = uint2{0xffffffffu, 0xffffffffu};
+            enc_o[g][tid] = uint2{c0, c1};
+        }
         const float4 b0 = ld4(pos + c0), b1 = ld4(pos + c1), v0 = ld4(vel + c0), v1 = ld4(vel + c1);
         xi[g] = nb_f2{b0.x, b1.x}; yi[g] = nb_f2{b0.y, b1.y}; zi[g] = nb_f2{b0.z, b1.z};
         ui[g] = nb_f2{v0.x, v1.x}; vi[g] = nb_f2{v0.y, v1.y}; wi[g] = nb_f2{v0.z, v1.z};
@@ -103,7 +120,8 @@ __device__ __forceinline__ void fj_pk_body(const float4* __restrict__ pos, const
     };
 
     // one stage: JB tile rows (positions p, velocities q) against the lane's NG packed groups, stage-major over the NC chains
-    auto math = [&](const float4* p, const float4* q) {
+    // (jrow: the body index of row p[0], read by the watch only)
+    auto math = [&](const float4* p, const float4* q, uint32_t jrow) {
         nb_f2 bx[JB], by[JB], bz[JB], bu[JB], bv[JB], bw[JB];
         float bm[JB];
 #pragma unroll
@@ -125,6 +143,36 @@ __device__ __forceinline__ void fj_pk_body(const float4* __restrict__ pos, const
         for (int c = 0; c < NC; ++c) d2[c] = __builtin_elementwise_fma(dy[c], dy[c], d2[c]);
 #pragma unroll
         for (int c = 0; c < NC; ++c) d2[c] = __builtin_elementwise_fma(dz[c], dz[c], d2[c]);
+        if constexpr (WATCH) {
+            bool lt[NC][2];
+            bool hit = false;
+#pragma unroll
+            for (int c = 0; c < NC; ++c) {
+                lt[c][0] = d2[c].x < wq[c % NG].x; lt[c][1] = d2[c].y < wq[c % NG].y;
+                hit |= lt[c][0] | lt[c][1];
+            }
+            if (__builtin_amdgcn_ballot_w64(hit) != 0) {      // wave-uniform: some lane has a pair below its threshold among these JB rows
+#pragma unroll
+                for (int g = 0; g < NG; ++g) {
+                    nb_f2 br = enc_r[g][tid];
+                    uint2 bj = enc_j[g][tid];
+                    const uint2 own = enc_o[g][tid];
+#pragma unroll
+                    for (int u = 0; u < JB; ++u) {             // c = u * NG + g: a row meets its pairs in ascending j
+                        const uint32_t j = jrow + (uint32_t)u;
+                        const nb_f2 r = d2[u * NG + g];
+                        const bool in = j < j1;                // a row past the chunk is padding (zero_row sits at the origin)
+                        // (bitwise, then selects: no branch per lane inside the slow path)
+                        const bool t0 = lt[u * NG + g][0] & in & (j != own.x) & ((r.x < br.x) | ((r.x == br.x) & (j < bj.x)));
+                        const bool t1 = lt[u * NG + g][1] & in & (j != own.y) & ((r.y < br.y) | ((r.y == br.y) & (j < bj.y)));
+                        br.x = t0 ? r.x : br.x; bj.x = t0 ? j : bj.x;
+                        br.y = t1 ? r.y : br.y; bj.y = t1 ? j : bj.y;
+                    }
+                    enc_r[g][tid] = br;
+                    enc_j[g][tid] = bj;
+                }
+            }
+        }
 #pragma unroll
         for (int c = 0; c < NC; ++c) y[c] = nb_f2{nb_rsq(d2[c].x), nb_rsq(d2[c].y)};
         // the velocity differences and dr.dv need nothing of the reciprocal roots: they fill the slots behind them
@@ -189,7 +237,8 @@ __device__ __forceinline__ void fj_pk_body(const float4* __restrict__ pos, const
         const int chunks = (cnt + U - 1) / U;             // rows past the range are staged zero-mass bodies
         for (int ch = 0; ch < chunks; ++ch) {
 #pragma unroll 2
-            for (int uu = 0; uu < U / JB; ++uu) math(&tile[cur][0][ch * U + uu * JB], &tile[cur][1][ch * U + uu * JB]);
+            for (int uu = 0; uu < U / JB; ++uu)
+                math(&tile[cur][0][ch * U + uu * JB], &tile[cur][1][ch * U + uu * JB], j0 + t * TILE + (uint32_t)(ch * U + uu * JB));
         }
         if ((t & (kFjFlush - 1)) == kFjFlush - 1) flush();
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -202,8 +251,14 @@ __device__ __forceinline__ void fj_pk_body(const float4* __restrict__ pos, const
 #pragma unroll
     for (int g = 0; g < NG; ++g) {
         const uint32_t il0 = i0 + (2 * g) * kBlock + tid, il1 = il0 + kBlock;
-        if (il0 < ni) { oa[il0] = float4{AX[g].x, AY[g].x, AZ[g].x, 0.0f}; oj[il0] = float4{JX[g].x, JY[g].x, JZ[g].x, 0.0f}; }
-        if (il1 < ni) { oa[il1] = float4{AX[g].y, AY[g].y, AZ[g].y, 0.0f}; oj[il1] = float4{JX[g].y, JY[g].y, JZ[g].y, 0.0f}; }
+        float r0 = 0.0f, r1 = 0.0f, k0 = 0.0f, k1 = 0.0f;      // WATCH: the chunk's answer, rho^2 and the index bit-cast
+        if constexpr (WATCH) {
+            const nb_f2 br = enc_r[g][tid];
+            const uint2 bj = enc_j[g][tid];
+            r0 = br.x; r1 = br.y; k0 = __uint_as_float(bj.x); k1 = __uint_as_float(bj.y);
+        }
+        if (il0 < ni) { oa[il0] = float4{AX[g].x, AY[g].x, AZ[g].x, r0}; oj[il0] = float4{JX[g].x, JY[g].x, JZ[g].x, k0}; }
+        if (il1 < ni) { oa[il1] = float4{AX[g].y, AY[g].y, AZ[g].y, r1}; oj[il1] = float4{JX[g].y, JY[g].y, JZ[g].y, k1}; }
     }
 }
 
@@ -218,13 +273,16 @@ void nb_fj_pk(const float4* __restrict__ pos, const float4* __restrict__ vel, fl
 
 // fp64 handles (T = double).  One body per lane, the two j-tiles staged through registers; v_rsq_f64 seed + one correction as in
 // nb_field64 (y0 (1 + e/2), e = 1 - rho^2 y0^2: relative error ~ 3 e^2 / 8 < 1e-16); every difference, product and sum is fp64.
-// fj64_body<T, GATHER>: shared with nb_blk_fj64, as fj_pk_body above.
-template <typename T, bool GATHER>
+// fj64_body<T, GATHER>: shared with nb_blk_fj64, as fj_pk_body above.  WATCH: as there, one compare per pair, the lane masks tested
+// on the scalar unit; the lane's best pair stays in registers and leaves in the .w lanes (the index as an exact double).  The loop
+// ends at the chunk's last row: a zero row of the tile is never met.
+template <typename T, bool GATHER, bool WATCH = false>
 __device__ __forceinline__ void fj64_body(const typename vec4<T>::type* __restrict__ pos,
                                           const typename vec4<T>::type* __restrict__ vel, const uint32_t* __restrict__ act,
                                           uint32_t ni, double4* __restrict__ pa, double4* __restrict__ pj, uint32_t n,
-                                          uint32_t j_per_chunk, double eps2)
+                                          uint32_t j_per_chunk, double eps2, const T* __restrict__ wth = nullptr)
 {
+    static_assert(GATHER || !WATCH, "the watch exists on the gathered pass only");
     __shared__ double4 tp[kTile];
     __shared__ double4 tv[kTile];
     const int tid = threadIdx.x;
@@ -238,6 +296,9 @@ __device__ __forceinline__ void fj64_body(const typename vec4<T>::type* __restri
     const double xi = (double)bi.x, yi = (double)bi.y, zi = (double)bi.z;
     const double ui = (double)wi.x, vi = (double)wi.y, wz = (double)wi.z;
     double ax = 0.0, ay = 0.0, az = 0.0, jx = 0.0, jy = 0.0, jz = 0.0;
+    double wq = 0.0, br = __builtin_inf();      // WATCH: the lane's threshold (a clamped lane watches nothing), its smallest rho^2 so far ...
+    uint32_t bj = 0xffffffffu;                  // ... and that pair's index (0xffffffff: none)
+    if constexpr (WATCH) wq = il < ni ? (double)wth[ic] : 0.0;
     for (uint32_t jt = j0; jt < j1; jt += kTile) {
         const uint32_t j = jt + tid;
         __syncthreads();                                          // the previous tile has been read
@@ -260,6 +321,13 @@ __device__ __forceinline__ void fj64_body(const typename vec4<T>::type* __restri
             const double dx = b.x - xi, dy = b.y - yi, dz = b.z - zi;
             const double du = c.x - ui, dv = c.y - vi, dw = c.z - wz;
             const double r2 = nb_fma(dz, dz, nb_fma(dy, dy, nb_fma(dx, dx, eps2)));
+            if constexpr (WATCH) {
+                const bool lt = r2 < wq;
+                if (__builtin_amdgcn_ballot_w64(lt) != 0) {      // wave-uniform: some lane has this row below its threshold
+                    const uint32_t jb = jt + (uint32_t)jj;
+                    if (lt && jb != ic && (r2 < br || (r2 == br && jb < bj))) { br = r2; bj = jb; }
+                }
+            }
             const double y0 = __builtin_amdgcn_rsq(r2);
             const double e = nb_fma(-(r2 * y0), y0, 1.0);
             const double y = nb_fma(0.5 * y0, e, y0);
@@ -272,8 +340,8 @@ __device__ __forceinline__ void fj64_body(const typename vec4<T>::type* __restri
         }
     }
     if (il < ni) {
-        pa[(size_t)blockIdx.y * ni + il] = double4{ax, ay, az, 0.0};
-        pj[(size_t)blockIdx.y * ni + il] = double4{jx, jy, jz, 0.0};
+        pa[(size_t)blockIdx.y * ni + il] = double4{ax, ay, az, WATCH ? br : 0.0};
+        pj[(size_t)blockIdx.y * ni + il] = double4{jx, jy, jz, WATCH ? (double)bj : 0.0};
     }
 }
 

@@ -652,6 +652,10 @@ struct hermite_order {
     // the kernels of a batched slot behind its scheduler (nb_set_block_batch, nb_set_block_batch6, nb_set_block_batch_mixed); null: the
     // order has no batched mode
     const void *bb_predict[2] = {nullptr, nullptr}, *bb_pass[2] = {nullptr, nullptr}, *bb_correct[2] = {nullptr, nullptr};
+    // the encounter watch (nb_set_encounter_watch): the gathered pass takes the thresholds last and leaves its answers in the .w lanes;
+    // enc_fold reads them behind it
+    bool watch = false;
+    const void* enc_fold[2] = {nullptr, nullptr};
 };
 
 #define NB_BOTH(K) {(const void*)&nb::K<float>, (const void*)&nb::K<double>}
@@ -665,6 +669,18 @@ const hermite_order kOrder4 = {
     &nb_sim::fj_part, &nb_sim::fj_chunks, &nb_sim::fj_per, false, false,
     NB_BOTH(nb_blkq_predict), {(const void*)&nb::nb_blkq_fj_pk<1>, (const void*)&nb::nb_blkq_fj64<double>},
     {(const void*)&nb::nb_blkq_correct<float, float>, (const void*)&nb::nb_blkq_correct<double, double>}};
+// Order 4 with the encounter watch on (kernels/encounter.hip.h): kOrder4's kernels, shapes, j-chunks and partial rows; the gathered
+// kernels are the same bodies with the watch compiled in.  No batched mode.
+const hermite_order kWatch = {
+    "hermite4_", 2, 2, 4, {nb::kFjRows, nb::kFjRows64}, {nb::kFjRows, nb::kFjRows64},
+    {(const void*)&nb::nb_fj_pk<nb::kFjNG>, (const void*)&nb::nb_fj64<double>},
+    {(const void*)&nb::nb_fj_reduce<float, float>, (const void*)&nb::nb_fj_reduce<double, double>},
+    {(const void*)&nb::nb_enc_fj_pk<2>, (const void*)&nb::nb_enc_fj64<double>}, (const void*)&nb::nb_enc_fj_pk<1>,
+    NB_BOTH(nb_hermite_predict), NB_BOTH(nb_hermite_correct), NB_BOTH(nb_blk_predict),
+    {(const void*)&nb::nb_blk_correct<float, float>, (const void*)&nb::nb_blk_correct<double, double>},
+    &nb_sim::fj_part, &nb_sim::fj_chunks, &nb_sim::fj_per, false, false,
+    {nullptr, nullptr}, {nullptr, nullptr}, {nullptr, nullptr}, true,
+    {(const void*)&nb::nb_enc_fold<float, float>, (const void*)&nb::nb_enc_fold<double, double>}};
 const hermite_order kOrder6 = {
     "hermite6_", 3, 3, 6, {nb::kH6Rows, nb::kH6Rows64}, {nb::kBlock * 4, nb::kH6Rows64},      // (the gathered kernels are NG = 2 and 1 whatever NB_H6_NG the full pass is built with)
     {(const void*)&nb::nb_h6_fjs_pk<nb::kH6NG>, (const void*)&nb::nb_h6_fjs64<double>},
@@ -708,7 +724,8 @@ const hermite_order kGuard = {
     &nb_sim::fj_part, &nb_sim::mx_chunks, &nb_sim::mx_per, true, true};
 
 // The one place the pass precision and the guard are read for a step: the description everything below works from.
-const hermite_order& order_of(const nb_sim* s) { return s->mx ? (s->mx_guard > 0.0 ? kGuard : kMixed) : s->h6 ? kOrder6 : kOrder4; }
+// (the encounter watch is on only on native order-4 handles with block steps: its setter and the other setters see to it)
+const hermite_order& order_of(const nb_sim* s) { return s->mx ? (s->mx_guard > 0.0 ? kGuard : kMixed) : s->h6 ? kOrder6 : s->enc && s->blk ? kWatch : kOrder4; }
 
 // Sets the j-chunks of the order's full pass on the handle: chunk_shape with the pass's own rows per workgroup.
 void set_chunks(nb_sim* s, const hermite_order& o) { chunk_shape(s->n, o.rows[s->f64], s->n_cu, &(s->*o.chunks), &(s->*o.per)); }
@@ -777,6 +794,7 @@ void launch_pass(nb_sim* s, const hermite_order& o, void** in, void** out, uint3
     a(part.plane, o.planes)(&n)(&sh.per);
     if (wide) a(&e2); else a(&e2f)(&zr);
     if (o.guard) a(&near2);
+    if (o.watch && na) a(&s->enc_w);
     (void)hipLaunchKernel(fn, dim3(ceil_div(irows, sh.rows), sh.chunks), dim3(nb::kBlock), a.v, 0, s->stream);
     if (na) {
         if (o.guard && part.chunks > nb::kGuardFoldFrom) {      // many fp64 chunk rows of few bodies: added here, in the corrector's order, into chunk row 0
@@ -928,6 +946,7 @@ int ensure_levels(nb_sim* s, const char* who)
 // pass over the active bodies, reduce + correct + new levels.
 int block_step(nb_sim* s, uint32_t nsteps)
 {
+    s->enc_stopped = 0; s->enc_steps_left = 0;
     if (int rc = ensure_levels(s, "nb_step")) return rc;
     const hermite_order& o = order_of(s);
     hermite_arrays h(s);
@@ -956,6 +975,15 @@ int block_step(nb_sim* s, uint32_t nsteps)
                 return fail(s, NB_ERR_HIP, "nb_step: block schedule out of range (active " + std::to_string(na) + ", tick " + std::to_string(t_next) + ")");
             pass_parts part;
             launch_pass(s, o, h.in, nullptr, na, &part);
+            if (o.watch) {      // the answers in the .w lanes of the partial rows, into the records of the active bodies (exact: t_next <= 2^L <= 2^30)
+                double t = (double)s->steps_done + std::ldexp((double)t_next, -(int)L);
+                kernel_args f;
+                uint32_t lpr = 1;      // lanes that share a row's chunks: the next power of two, at most a wave, while the rows alone do not fill 256 workgroups
+                while (lpr < part.chunks && lpr < 64 && (uint64_t)na * lpr * 2 <= 65536) lpr *= 2;
+                f(part.plane, o.planes)(&s->blk_act)(&na)(&part.chunks)(&lpr)(&s->enc_rho2)(&s->enc_partner)(&s->enc_time)(&s->enc_count)(&s->enc_words)(&s->enc_pub)(&t);
+                (void)hipLaunchKernel(o.enc_fold[s->f64], dim3(ceil_div(na, nb::kBlock / lpr)), dim3(nb::kBlock), f.v, 0, s->stream);
+                ++s->enc_passes;
+            }
             kernel_args c;
             c(part.plane, o.planes)(&s->blk_act)(&na)(&part.chunks)(&G)(h.state, o.states)(&s->blk_due)(&s->blk_lev)(&s->blk_hdr)(&t_next)(&Lk)(&lmin)(&frozen)(&eta)(&dt);
             (void)hipLaunchKernel(o.blk_correct[s->f64], dim3(ceil_div(na, nb::kBlock)), dim3(nb::kBlock), c.v, 0, s->stream);
@@ -965,11 +993,17 @@ int block_step(nb_sim* s, uint32_t nsteps)
             NB_HIP(s, hipGetLastError());
         }
         if (rec) { NB_HIP(s, hipEventRecord(ev.e[1], s->stream)); ev.blk = true; s->pending.push_back(ev); }
-        if (k + 1 < nsteps && !s->timing) { schedule_and_predict(); ahead = true; }      // (timed steps launch it inside their own span)
+        bool stop = false;
+        if (o.watch && (s->enc_flags & NB_ENC_STOP)) {      // the one extra host wait per outer step: hits as the last fold published them
+            NB_HIP(s, hipStreamSynchronize(s->stream));
+            stop = *(volatile unsigned long long*)s->enc_host != 0;
+        }
+        if (k + 1 < nsteps && !s->timing && !stop) { schedule_and_predict(); ahead = true; }      // (timed steps launch it inside their own span)
         NB_HIP(s, hipGetLastError());
         ++s->blk_outer;
         ++s->steps_done;
         s->start_own = s->levels_own = false;      // consumed: state and levels are running ones (nb_set_start6 leaves them alone)
+        if (stop) { s->enc_stopped = 1; s->enc_steps_left = nsteps - (k + 1); return NB_OK; }
     }
     return NB_OK;
 }
@@ -1665,6 +1699,8 @@ void nb_destroy(nb_sim* s)
     if (s->blk_hdr_host) (void)hipHostFree(s->blk_hdr_host);
     for (void* p : {(void*)s->bb_words, s->bb_part}) if (p) (void)hipFree(p);
     if (s->bb_host) (void)hipHostFree(s->bb_host);
+    for (void* p : {s->enc_w, s->enc_rho2, (void*)s->enc_partner, (void*)s->enc_time, (void*)s->enc_count, (void*)s->enc_words}) if (p) (void)hipFree(p);
+    if (s->enc_host) (void)hipHostFree(s->enc_host);
     ac_release(s);
     h6_release(s);
     mx_release(s);
@@ -1677,6 +1713,8 @@ void nb_destroy(nb_sim* s)
 }
 
 const char* nb_last_error(nb_sim* s) { return s ? s->err.c_str() : g_create_error.c_str(); }
+
+static int enc_clear_records(nb_sim* s);
 
 int nb_upload(nb_sim* s, const void* bodies, const void* vel, const void* accel)
 {
@@ -1695,6 +1733,7 @@ int nb_upload(nb_sim* s, const void* bodies, const void* vel, const void* accel)
         s->derivs_ok = false;
         s->ac_ok = false;
         s->levels = 0;
+        if (s->enc) return enc_clear_records(s);      // the watch's records belonged to the state replaced here; its configuration and counters stay
         return NB_OK;
     }
     if (accel) NB_HIP(s, hipMemcpy(s->acc, (const char*)accel + row * s->sb, row * s->sc, hipMemcpyHostToDevice));
@@ -1920,6 +1959,7 @@ int nb_set_hermite_order(nb_sim* s, uint32_t order)
     if (!s) return fail(nullptr, NB_ERR_INVALID, "nb_set_hermite_order: null handle");
     if (order != 4 && order != 6) return fail(s, NB_ERR_INVALID, "nb_set_hermite_order: order must be 4 or 6");
     if (!s->hermite) return fail(s, NB_ERR_STATE, "nb_set_hermite_order: needs a Hermite handle (nb_config.integrator = NB_INT_HERMITE4)");
+    if (order == 6 && s->enc) return fail(s, NB_ERR_STATE, "nb_set_hermite_order: order = 6 while the encounter watch is switched on (nb_set_encounter_watch): it exists at order 4 only, switch it off first");
     if (order == 6 && s->bb && !s->h6) return fail(s, NB_ERR_STATE, "nb_set_hermite_order: order = 6 while batched block steps are switched on (nb_set_block_batch): they exist at order 4 only, switch them off first");
     if (order == 6 && s->blk && !s->h6) return fail(s, NB_ERR_STATE, "nb_set_hermite_order: order = 6 while block steps are switched on (nb_set_block_steps): they exclude each other");
     if (order == 4 && s->blk && s->h6) return fail(s, NB_ERR_STATE, "nb_set_hermite_order: order = 4 while block steps of order 6 are switched on (nb_set_block_steps6): switch them off first");
@@ -1968,6 +2008,7 @@ int nb_set_pass_precision(nb_sim* s, uint32_t mode)
     if (s->ac) return fail(s, NB_ERR_STATE, "nb_set_pass_precision: the neighbour scheme is switched on (nb_set_neighbor_scheme): it has no mixed kernels");
     if (mode == NB_PASS_MIXED && s->bb && !s->mx) return fail(s, NB_ERR_STATE, "nb_set_pass_precision: NB_PASS_MIXED while batched block steps are switched on (nb_set_block_batch): they run the native pass only, switch them off first");
     if (mode == NB_PASS_NATIVE && s->bb && s->mx) return fail(s, NB_ERR_STATE, "nb_set_pass_precision: NB_PASS_NATIVE while the batched block steps of a mixed handle are switched on (nb_set_block_batch_mixed): they run the mixed pass only, switch them off first");
+    if (mode == NB_PASS_MIXED && s->enc) return fail(s, NB_ERR_STATE, "nb_set_pass_precision: NB_PASS_MIXED while the encounter watch is switched on (nb_set_encounter_watch): it runs in the native pass only, switch it off first");
     if ((mode == NB_PASS_MIXED) == s->mx) return NB_OK;
     NB_HIP(s, hipSetDevice(s->device));
     NB_HIP(s, hipStreamSynchronize(s->stream));
@@ -2138,7 +2179,7 @@ int nb_set_block_steps(nb_sim* s, const nb_block_steps* cfg)
 {
     if (!s) return fail(nullptr, NB_ERR_INVALID, "nb_set_block_steps: null handle");
     if (!s->hermite) return fail(s, NB_ERR_STATE, "nb_set_block_steps: needs a Hermite handle (nb_config.integrator = NB_INT_HERMITE4)");
-    if (!cfg) { s->blk = false; s->bb = false; s->levels = 0; return NB_OK; }      // (the batched mode belongs to the block steps: off with them)
+    if (!cfg) { s->blk = false; s->bb = false; s->enc = false; s->levels = 0; return NB_OK; }      // (the batched mode and the encounter watch belong to the block steps: off with them)
     if (s->h6) return fail(s, NB_ERR_STATE, "nb_set_block_steps: the handle's order is 6 (nb_set_hermite_order): block steps and the 6th-order scheme exclude each other here, see nb_set_block_steps6");
     if (s->ac) return fail(s, NB_ERR_STATE, "nb_set_block_steps: the neighbour scheme is switched on (nb_set_neighbor_scheme): block steps and the neighbour scheme exclude each other");
     return blk_configure(s, cfg, "nb_set_block_steps");
@@ -2223,6 +2264,7 @@ int nb_set_block_batch(nb_sim* s, const nb_block_batch* cfg)
     if (!s) return fail(nullptr, NB_ERR_INVALID, "nb_set_block_batch: null handle");
     if (!cfg) { s->bb = false; return NB_OK; }
     if (int rc = bb_check(s, cfg, "nb_set_block_batch")) return rc;
+    if (s->enc) return fail(s, NB_ERR_STATE, "nb_set_block_batch: the encounter watch is switched on (nb_set_encounter_watch): it runs on the base path of block steps only, switch it off first");
     if (!s->hermite) return fail(s, NB_ERR_STATE, "nb_set_block_batch: needs a Hermite handle (nb_config.integrator = NB_INT_HERMITE4) with block steps switched on (nb_set_block_steps)");
     if (s->h6) return fail(s, NB_ERR_STATE, "nb_set_block_batch: the handle's order is 6 (nb_set_hermite_order): batched block steps exist at order 4 only");
     if (!s->blk) return fail(s, NB_ERR_STATE, "nb_set_block_batch: block steps are not switched on (nb_set_block_steps)");
@@ -2235,6 +2277,7 @@ int nb_set_block_batch6(nb_sim* s, const nb_block_batch* cfg)
     if (!s) return fail(nullptr, NB_ERR_INVALID, "nb_set_block_batch6: null handle");
     if (!cfg) { s->bb = false; return NB_OK; }
     if (int rc = bb_check(s, cfg, "nb_set_block_batch6")) return rc;
+    if (s->enc) return fail(s, NB_ERR_STATE, "nb_set_block_batch6: the encounter watch is switched on (nb_set_encounter_watch): it runs on the base path of block steps only, switch it off first");
     if (!s->hermite) return fail(s, NB_ERR_STATE, "nb_set_block_batch6: needs a Hermite handle (nb_config.integrator = NB_INT_HERMITE4) of order 6 (nb_set_hermite_order) with block steps switched on (nb_set_block_steps6)");
     if (!s->h6) return fail(s, NB_ERR_STATE, "nb_set_block_batch6: the handle's order is 4 (nb_set_hermite_order): see nb_set_block_batch");
     if (!s->blk) return fail(s, NB_ERR_STATE, "nb_set_block_batch6: block steps are not switched on (nb_set_block_steps6)");
@@ -2246,6 +2289,7 @@ int nb_set_block_batch_mixed(nb_sim* s, const nb_block_batch* cfg)
     if (!s) return fail(nullptr, NB_ERR_INVALID, "nb_set_block_batch_mixed: null handle");
     if (!cfg) { s->bb = false; return NB_OK; }
     if (int rc = bb_check(s, cfg, "nb_set_block_batch_mixed")) return rc;
+    if (s->enc) return fail(s, NB_ERR_STATE, "nb_set_block_batch_mixed: the encounter watch is switched on (nb_set_encounter_watch): it runs on the base path of block steps only, switch it off first");
     if (!s->hermite) return fail(s, NB_ERR_STATE, "nb_set_block_batch_mixed: needs a Hermite handle (nb_config.integrator = NB_INT_HERMITE4) with block steps switched on (nb_set_block_steps)");
     if (!s->f64) return fail(s, NB_ERR_STATE, "nb_set_block_batch_mixed: precision NB_F32: the mixed pass (nb_set_pass_precision) exists on NB_F64 handles only, see nb_set_block_batch");
     if (s->h6) return fail(s, NB_ERR_STATE, "nb_set_block_batch_mixed: the handle's order is 6 (nb_set_hermite_order): the mixed pass exists at order 4 only, see nb_set_block_batch6");
@@ -2296,6 +2340,145 @@ int nb_upload_levels(nb_sim* s, const uint8_t* levels)
     NB_HIP(s, hipMemcpy(s->blk_lev, levels, s->n, hipMemcpyHostToDevice));
     s->levels = 1;      // the start kernel keeps these levels and starts the clock (due_i = s_i)
     return NB_OK;
+}
+
+// ---- nb_set_encounter_watch: closest approaches seen inside block steps (kernels/encounter.hip.h) ----------
+static int enc_clear_counters(nb_sim* s)
+{
+    const double inf = HUGE_VAL;
+    unsigned long long w[nb::kEncWords] = {};
+    std::memcpy(&w[nb::kEncFirst], &inf, sizeof inf);
+    NB_HIP(s, hipStreamSynchronize(s->stream));
+    NB_HIP(s, hipMemcpy(s->enc_words, w, sizeof w, hipMemcpyHostToDevice));
+    *s->enc_host = 0;
+    s->enc_passes = 0;
+    return NB_OK;
+}
+
+static int enc_clear_records(nb_sim* s)
+{
+    NB_HIP(s, hipStreamSynchronize(s->stream));
+    std::vector<double> t(s->n, HUGE_VAL);
+    NB_HIP(s, hipMemcpy(s->enc_time, t.data(), sizeof(double) * s->n, hipMemcpyHostToDevice));
+    if (s->f64) NB_HIP(s, hipMemcpy(s->enc_rho2, t.data(), sizeof(double) * s->n, hipMemcpyHostToDevice));
+    else {
+        std::vector<float> r(s->n, HUGE_VALF);
+        NB_HIP(s, hipMemcpy(s->enc_rho2, r.data(), sizeof(float) * s->n, hipMemcpyHostToDevice));
+    }
+    NB_HIP(s, hipMemset(s->enc_partner, 0xff, sizeof(uint32_t) * s->n));
+    NB_HIP(s, hipMemset(s->enc_count, 0, sizeof(uint32_t) * s->n));
+    NB_HIP(s, hipDeviceSynchronize());
+    return NB_OK;
+}
+
+// the state checks the watch's calls other than the setter share
+static int enc_on(nb_sim* s, const char* who)
+{
+    if (!s->hermite) return fail(s, NB_ERR_STATE, std::string(who) + ": needs a Hermite handle (nb_config.integrator = NB_INT_HERMITE4) with the encounter watch switched on (nb_set_encounter_watch)");
+    if (!s->enc) return fail(s, NB_ERR_STATE, std::string(who) + ": the encounter watch is not switched on (nb_set_encounter_watch)");
+    NB_HIP(s, hipSetDevice(s->device));
+    return NB_OK;
+}
+
+int nb_set_encounter_watch(nb_sim* s, const nb_encounter_watch* cfg)
+{
+    if (!s) return fail(nullptr, NB_ERR_INVALID, "nb_set_encounter_watch: null handle");
+    if (!cfg) { s->enc = false; return NB_OK; }
+    if (cfg->flags & ~(uint32_t)NB_ENC_STOP) return fail(s, NB_ERR_INVALID, "nb_set_encounter_watch: unknown flags");
+    if (!(cfg->radius >= 0.0) || std::isinf(cfg->radius)) return fail(s, NB_ERR_INVALID, "nb_set_encounter_watch: radius must be finite and >= 0");
+    if (!s->hermite) return fail(s, NB_ERR_STATE, "nb_set_encounter_watch: needs a Hermite handle (nb_config.integrator = NB_INT_HERMITE4) with block steps switched on (nb_set_block_steps)");
+    if (cfg->radii) {
+        for (uint32_t i = 0; i < s->n; ++i) {
+            const double h = s->f64 ? ((const double*)cfg->radii)[i] : (double)((const float*)cfg->radii)[i];
+            if (!(h >= 0.0) || std::isinf(h)) return fail(s, NB_ERR_INVALID, "nb_set_encounter_watch: radii[" + std::to_string(i) + "] must be finite and >= 0");
+        }
+    }
+    if (s->h6) return fail(s, NB_ERR_STATE, "nb_set_encounter_watch: the handle's order is 6 (nb_set_hermite_order): the watch exists at order 4 only");
+    if (s->ac) return fail(s, NB_ERR_STATE, "nb_set_encounter_watch: the neighbour scheme is switched on (nb_set_neighbor_scheme): the watch runs in the gathered pass of block steps only");
+    if (!s->blk) return fail(s, NB_ERR_STATE, "nb_set_encounter_watch: block steps are not switched on (nb_set_block_steps)");
+    if (s->mx) return fail(s, NB_ERR_STATE, "nb_set_encounter_watch: the pass precision is NB_PASS_MIXED (nb_set_pass_precision, nb_set_pass_guard): the watch runs in the native pass only, set NB_PASS_NATIVE first");
+    if (s->bb) return fail(s, NB_ERR_STATE, "nb_set_encounter_watch: batched block steps are switched on (nb_set_block_batch): the watch runs on the base path of block steps only, switch them off first");
+    NB_HIP(s, hipSetDevice(s->device));
+    NB_HIP(s, hipStreamSynchronize(s->stream));
+    if (!s->enc_w) NB_HIP(s, hipMalloc(&s->enc_w, s->esz * s->n));
+    if (!s->enc_rho2) NB_HIP(s, hipMalloc(&s->enc_rho2, s->esz * s->n));
+    if (!s->enc_partner) NB_HIP(s, hipMalloc((void**)&s->enc_partner, sizeof(uint32_t) * s->n));
+    if (!s->enc_time) NB_HIP(s, hipMalloc((void**)&s->enc_time, sizeof(double) * s->n));
+    if (!s->enc_count) NB_HIP(s, hipMalloc((void**)&s->enc_count, sizeof(uint32_t) * s->n));
+    if (!s->enc_words) NB_HIP(s, hipMalloc((void**)&s->enc_words, sizeof(unsigned long long) * nb::kEncWords));
+    if (!s->enc_host) NB_HIP(s, hipHostMalloc((void**)&s->enc_host, sizeof(unsigned long long), hipHostMallocDefault));
+    if (!s->enc_pub) NB_HIP(s, hipHostGetDevicePointer((void**)&s->enc_pub, s->enc_host, 0));
+    // w_i = h_i^2 + eps2 in fp64, rounded once to the handle's precision; h_i = 0: 0, below every rho^2
+    auto w_of = [&](double h) { return h > 0.0 ? h * h + s->eps2 : 0.0; };
+    if (s->f64) {
+        std::vector<double> w(s->n);
+        for (uint32_t i = 0; i < s->n; ++i) w[i] = w_of(cfg->radii ? ((const double*)cfg->radii)[i] : cfg->radius);
+        NB_HIP(s, hipMemcpy(s->enc_w, w.data(), sizeof(double) * s->n, hipMemcpyHostToDevice));
+    } else {
+        std::vector<float> w(s->n);
+        for (uint32_t i = 0; i < s->n; ++i) w[i] = (float)w_of(cfg->radii ? (double)((const float*)cfg->radii)[i] : cfg->radius);
+        NB_HIP(s, hipMemcpy(s->enc_w, w.data(), sizeof(float) * s->n, hipMemcpyHostToDevice));
+    }
+    if (!s->enc) {      // switched on: the records and the counters start over (a call while it is on keeps them)
+        if (int rc = enc_clear_records(s)) return rc;
+        if (int rc = enc_clear_counters(s)) return rc;
+        s->enc_stopped = s->enc_steps_left = 0;
+    }
+    s->enc = true;
+    s->enc_flags = cfg->flags;
+    return NB_OK;
+}
+
+int nb_encounter_stats(nb_sim* s, struct nb_encounter_stats* out, int reset)
+{
+    if (!s) return fail(nullptr, NB_ERR_INVALID, "nb_encounter_stats: null handle");
+    if (!out) return fail(s, NB_ERR_INVALID, "nb_encounter_stats: out is NULL");
+    if (int rc = enc_on(s, "nb_encounter_stats")) return rc;
+    unsigned long long w[nb::kEncWords];
+    NB_HIP(s, hipStreamSynchronize(s->stream));
+    NB_HIP(s, hipMemcpy(w, s->enc_words, sizeof w, hipMemcpyDeviceToHost));
+    out->passes = s->enc_passes; out->hits = w[nb::kEncHits];
+    std::memcpy(&out->first_time, &w[nb::kEncFirst], sizeof(double));
+    out->stopped = s->enc_stopped; out->steps_left = s->enc_steps_left;
+    if (reset) return enc_clear_counters(s);
+    return NB_OK;
+}
+
+int nb_download_encounters(nb_sim* s, void* rho2, uint32_t* partner, double* time, uint32_t* count)
+{
+    if (!s) return fail(nullptr, NB_ERR_INVALID, "nb_download_encounters: null handle");
+    if (int rc = enc_on(s, "nb_download_encounters")) return rc;
+    NB_HIP(s, hipStreamSynchronize(s->stream));
+    if (rho2) NB_HIP(s, hipMemcpy(rho2, s->enc_rho2, s->esz * s->n, hipMemcpyDeviceToHost));
+    if (partner) NB_HIP(s, hipMemcpy(partner, s->enc_partner, sizeof(uint32_t) * s->n, hipMemcpyDeviceToHost));
+    if (time) NB_HIP(s, hipMemcpy(time, s->enc_time, sizeof(double) * s->n, hipMemcpyDeviceToHost));
+    if (count) NB_HIP(s, hipMemcpy(count, s->enc_count, sizeof(uint32_t) * s->n, hipMemcpyDeviceToHost));
+    return NB_OK;
+}
+
+int nb_upload_encounters(nb_sim* s, const void* rho2, const uint32_t* partner, const double* time, const uint32_t* count)
+{
+    if (!s) return fail(nullptr, NB_ERR_INVALID, "nb_upload_encounters: null handle");
+    if (!rho2 || !partner || !time || !count) return fail(s, NB_ERR_INVALID, "nb_upload_encounters: rho2, partner, time and count are required");
+    if (int rc = enc_on(s, "nb_upload_encounters")) return rc;
+    for (uint32_t i = 0; i < s->n; ++i)
+        if (partner[i] != nb::kEncNone && (partner[i] >= s->n || partner[i] == i))
+            return fail(s, NB_ERR_INVALID, "nb_upload_encounters: partner[" + std::to_string(i) + "] must be another body's index or 0xffffffff");
+    NB_HIP(s, hipStreamSynchronize(s->stream));
+    NB_HIP(s, hipMemcpy(s->enc_rho2, rho2, s->esz * s->n, hipMemcpyHostToDevice));
+    NB_HIP(s, hipMemcpy(s->enc_partner, partner, sizeof(uint32_t) * s->n, hipMemcpyHostToDevice));
+    NB_HIP(s, hipMemcpy(s->enc_time, time, sizeof(double) * s->n, hipMemcpyHostToDevice));
+    NB_HIP(s, hipMemcpy(s->enc_count, count, sizeof(uint32_t) * s->n, hipMemcpyHostToDevice));
+    return NB_OK;
+}
+
+int nb_reset_encounters(nb_sim* s)
+{
+    if (!s) return fail(nullptr, NB_ERR_INVALID, "nb_reset_encounters: null handle");
+    if (int rc = enc_on(s, "nb_reset_encounters")) return rc;
+    if (int rc = enc_clear_records(s)) return rc;
+    s->enc_stopped = s->enc_steps_left = 0;
+    return enc_clear_counters(s);
 }
 
 int nb_set_neighbor_scheme(nb_sim* s, const nb_neighbor_scheme* cfg)

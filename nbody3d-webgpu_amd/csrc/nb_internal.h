@@ -221,6 +221,20 @@ struct nb_sim {
     bool bb_fresh = true;            // nothing read since the mode was set or the levels went stale: one slot
     uint32_t bb_t = 0, bb_finest = 0, bb_park_ctz = 0;      // the tick reached, the deepest level present, ticks with ctz >= bb_park_ctz are expected to park
     uint64_t bb_waits = 0, bb_slots = 0, bb_small = 0, bb_hoststeps = 0, bb_idle = 0;
+    // nb_set_encounter_watch: closest approaches seen inside block steps (kernels/encounter.hip.h).  Allocated when first switched on,
+    // released by nb_destroy.  Off: none of this is read.
+    bool enc = false;
+    uint32_t enc_flags = 0;          // NB_ENC_*
+    void* enc_w = nullptr;           // device: n thresholds w_i = h_i^2 + eps2 of the handle's precision (0: not watched)
+    void* enc_rho2 = nullptr;        // device: the records, n each -- rho2 (the handle's precision) ...
+    uint32_t* enc_partner = nullptr; // ... partner ...
+    double* enc_time = nullptr;      // ... time ...
+    uint32_t* enc_count = nullptr;   // ... count
+    unsigned long long* enc_words = nullptr;   // device: nb::kEncWords words (hits, the bits of first_time, the fold's ticket)
+    unsigned long long* enc_host = nullptr;    // pinned host word: hits as nb_enc_fold last published them
+    unsigned long long* enc_pub = nullptr;     // the device's address of enc_host
+    uint64_t enc_passes = 0;         // gathered passes that ran with the watch on
+    uint32_t enc_stopped = 0, enc_steps_left = 0;      // of the last nb_step (NB_ENC_STOP)
     // nb_set_neighbor_scheme: the Ahmad-Cohen neighbour scheme with two shared step levels (kernels/ac_scheme.hip.h).  Allocated
     // by the call, released by NULL or nb_destroy.  While it is on, acc / jerk hold the totals ai + ar0, ji + jr0.
     bool ac = false;

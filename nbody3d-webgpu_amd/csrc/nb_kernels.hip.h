@@ -78,3 +78,4 @@
 #include "kernels/block6.hip.h"      // nb_blk6_start, nb_blk6_predict, nb_blk6_fjs_pk, nb_blk6_fjs64, nb_blk6_correct (nb_set_block_steps6: block steps on order-6 handles)
 #include "kernels/block_batch6.hip.h" // nb_blkq6_predict, nb_blkq6_fjs_pk, nb_blkq6_fjs64, nb_blkq6_correct (nb_set_block_batch6: block steps sized on the device, order-6 handles)
 #include "kernels/block_batch_mixed.hip.h" // nb_blkqm_predict, nb_blkqm_fj (nb_set_block_batch_mixed: block steps sized on the device, mixed-precision handles)
+#include "kernels/encounter.hip.h"   // nb_enc_fj_pk, nb_enc_fj64, nb_enc_fold (nb_set_encounter_watch: closest approaches seen inside block steps)

@@ -78,6 +78,11 @@ static int (*p_set_block_batch)(nb_sim *, const nb_block_batch *);      /* batch
 static int (*p_block_batch_stats)(nb_sim *, struct nb_block_batch_stats *, int);
 static int (*p_set_block_batch6)(nb_sim *, const nb_block_batch *);     /* ... on order-6 handles (round 26): optional */
 static int (*p_set_block_batch_mixed)(nb_sim *, const nb_block_batch *);     /* ... on mixed-precision handles (round 27): optional */
+static int (*p_set_encounter_watch)(nb_sim *, const nb_encounter_watch *);     /* the encounter watch of block steps (round 28): optional */
+static int (*p_encounter_stats)(nb_sim *, struct nb_encounter_stats *, int);
+static int (*p_download_encounters)(nb_sim *, void *, uint32_t *, double *, uint32_t *);
+static int (*p_upload_encounters)(nb_sim *, const void *, const uint32_t *, const double *, const uint32_t *);
+static int (*p_reset_encounters)(nb_sim *);
 static int (*p_download_levels)(nb_sim *, uint8_t *);
 static int (*p_upload_levels)(nb_sim *, const uint8_t *);
 static int (*p_neighbors)(nb_sim *, const nb_neighbor_request *);       /* neighbour queries, also within ABI 2.4: optional symbols */
@@ -203,6 +208,11 @@ static napi_value js_load(napi_env env, napi_callback_info info)
         *(void **)(&p_block_batch_stats) = dlsym(h, "nb_block_batch_stats");
         *(void **)(&p_set_block_batch6) = dlsym(h, "nb_set_block_batch6");
         *(void **)(&p_set_block_batch_mixed) = dlsym(h, "nb_set_block_batch_mixed");
+        *(void **)(&p_set_encounter_watch) = dlsym(h, "nb_set_encounter_watch");
+        *(void **)(&p_encounter_stats) = dlsym(h, "nb_encounter_stats");
+        *(void **)(&p_download_encounters) = dlsym(h, "nb_download_encounters");
+        *(void **)(&p_upload_encounters) = dlsym(h, "nb_upload_encounters");
+        *(void **)(&p_reset_encounters) = dlsym(h, "nb_reset_encounters");
         *(void **)(&p_download_levels) = dlsym(h, "nb_download_levels");
         *(void **)(&p_upload_levels) = dlsym(h, "nb_upload_levels");
         *(void **)(&p_neighbors) = dlsym(h, "nb_neighbors");
@@ -1509,6 +1519,90 @@ static napi_value js_set_neighbor_scheme(napi_env env, napi_callback_info info)
     return undefined(env);
 }
 
+/* setEncounterWatch(handle, null) | setEncounterWatch(handle, radius, radii | null, stop): nb_set_encounter_watch; radii: n elements of
+ * the handle's precision, copied by the call */
+static napi_value js_set_encounter_watch(napi_env env, napi_callback_info info)
+{
+    size_t argc = 4; napi_value argv[4];
+    CHECK_NAPI(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    if (argc < 2) { napi_throw_type_error(env, NULL, "setEncounterWatch(handle, null | radius, radii, stop)"); return NULL; }
+    handle_t *h = block_handle(env, argv[0], *(void **)&p_set_encounter_watch, "nb_set_encounter_watch"); if (!h) return NULL;
+    napi_valuetype t; napi_typeof(env, argv[1], &t);
+    int rc;
+    if (argc < 4 && (t == napi_null || t == napi_undefined)) rc = p_set_encounter_watch(h->sim, NULL);
+    else {
+        if (argc < 4) { napi_throw_type_error(env, NULL, "setEncounterWatch(handle, radius, radii, stop)"); return NULL; }
+        nb_encounter_watch cfg;
+        memset(&cfg, 0, sizeof cfg);
+        void *radii = NULL; bool stop = false;
+        CHECK_NAPI(env, napi_get_value_double(env, argv[1], &cfg.radius));
+        if (!get_typed(env, argv[2], h->f64 ? napi_float64_array : napi_float32_array, h->n, 1, &radii, "radii must be null or a typed array of n elements of the simulation's precision")) return NULL;
+        cfg.radii = radii;
+        napi_get_value_bool(env, argv[3], &stop);
+        cfg.flags = stop ? NB_ENC_STOP : 0u;
+        rc = p_set_encounter_watch(h->sim, &cfg);
+    }
+    if (rc != NB_OK) return throw_nb(env, rc, h->sim, "nb_set_encounter_watch");
+    return undefined(env);
+}
+
+/* encounterStats(handle, reset) -> {passes, hits, firstTime, stopped, stepsLeft} (counts as doubles) */
+static napi_value js_encounter_stats(napi_env env, napi_callback_info info)
+{
+    size_t argc = 2; napi_value argv[2];
+    CHECK_NAPI(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    if (argc < 1) { napi_throw_type_error(env, NULL, "encounterStats(handle, reset)"); return NULL; }
+    handle_t *h = block_handle(env, argv[0], *(void **)&p_encounter_stats, "nb_encounter_stats"); if (!h) return NULL;
+    bool reset = false;
+    if (argc > 1) napi_get_value_bool(env, argv[1], &reset);
+    struct nb_encounter_stats st;
+    memset(&st, 0, sizeof st);
+    int rc = p_encounter_stats(h->sim, &st, reset ? 1 : 0);
+    if (rc != NB_OK) return throw_nb(env, rc, h->sim, "nb_encounter_stats");
+    napi_value o, v;
+    CHECK_NAPI(env, napi_create_object(env, &o));
+    napi_create_double(env, (double)st.passes, &v); napi_set_named_property(env, o, "passes", v);
+    napi_create_double(env, (double)st.hits, &v); napi_set_named_property(env, o, "hits", v);
+    napi_create_double(env, st.first_time, &v); napi_set_named_property(env, o, "firstTime", v);
+    napi_get_boolean(env, st.stopped != 0, &v); napi_set_named_property(env, o, "stopped", v);
+    napi_create_uint32(env, st.steps_left, &v); napi_set_named_property(env, o, "stepsLeft", v);
+    return o;
+}
+
+/* downloadEncounters(handle, rho2Out, partnerOut, timeOut, countOut) / uploadEncounters(handle, rho2, partner, time, count): the
+ * records, n elements each -- rho2 of the handle's precision, partner and count Uint32Array, time Float64Array */
+static napi_value encounters_by(napi_env env, napi_callback_info info, int upload)
+{
+    size_t argc = 5; napi_value argv[5];
+    CHECK_NAPI(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    if (argc < 5) { napi_throw_type_error(env, NULL, "downloadEncounters | uploadEncounters(handle, rho2, partner, time, count)"); return NULL; }
+    const char *sym = upload ? "nb_upload_encounters" : "nb_download_encounters";
+    handle_t *h = block_handle(env, argv[0], upload ? *(void **)&p_upload_encounters : *(void **)&p_download_encounters, sym); if (!h) return NULL;
+    void *rho2, *partner, *time, *count;
+    if (!get_typed(env, argv[1], h->f64 ? napi_float64_array : napi_float32_array, h->n, 0, &rho2, "rho2 must be a typed array of n elements of the simulation's precision")) return NULL;
+    if (!get_typed(env, argv[2], napi_uint32_array, h->n, 0, &partner, "partner must be a Uint32Array of n elements")) return NULL;
+    if (!get_typed(env, argv[3], napi_float64_array, h->n, 0, &time, "time must be a Float64Array of n elements")) return NULL;
+    if (!get_typed(env, argv[4], napi_uint32_array, h->n, 0, &count, "count must be a Uint32Array of n elements")) return NULL;
+    int rc = upload ? p_upload_encounters(h->sim, rho2, (const uint32_t *)partner, (const double *)time, (const uint32_t *)count)
+                    : p_download_encounters(h->sim, rho2, (uint32_t *)partner, (double *)time, (uint32_t *)count);
+    if (rc != NB_OK) return throw_nb(env, rc, h->sim, sym);
+    return undefined(env);
+}
+static napi_value js_download_encounters(napi_env env, napi_callback_info info) { return encounters_by(env, info, 0); }
+static napi_value js_upload_encounters(napi_env env, napi_callback_info info) { return encounters_by(env, info, 1); }
+
+/* resetEncounters(handle): nb_reset_encounters */
+static napi_value js_reset_encounters(napi_env env, napi_callback_info info)
+{
+    size_t argc = 1; napi_value argv[1];
+    CHECK_NAPI(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    if (argc < 1) { napi_throw_type_error(env, NULL, "resetEncounters(handle)"); return NULL; }
+    handle_t *h = block_handle(env, argv[0], *(void **)&p_reset_encounters, "nb_reset_encounters"); if (!h) return NULL;
+    int rc = p_reset_encounters(h->sim);
+    if (rc != NB_OK) return throw_nb(env, rc, h->sim, "nb_reset_encounters");
+    return undefined(env);
+}
+
 /* neighborSchemeStats(handle, reset) -> {enabled, regularSteps, substeps, entries, builds, maxCount, overflowed} (counts as doubles) */
 static napi_value js_neighbor_scheme_stats(napi_env env, napi_callback_info info)
 {
@@ -1728,6 +1822,8 @@ static napi_value init_module(napi_env env, napi_value exports)
         {"setStart6", js_set_start6}, {"start6", js_start6}, {"setPassPrecision", js_set_pass_precision}, {"passPrecision", js_pass_precision},
         {"setPassGuard", js_set_pass_guard}, {"passGuard", js_pass_guard},
         {"setBlockSteps", js_set_block_steps}, {"setBlockSteps6", js_set_block_steps6}, {"blockStats", js_block_stats}, {"setBlockBatch", js_set_block_batch}, {"setBlockBatch6", js_set_block_batch6}, {"setBlockBatchMixed", js_set_block_batch_mixed}, {"blockBatchStats", js_block_batch_stats}, {"downloadLevels", js_download_levels},
+        {"setEncounterWatch", js_set_encounter_watch}, {"encounterStats", js_encounter_stats}, {"downloadEncounters", js_download_encounters},
+        {"uploadEncounters", js_upload_encounters}, {"resetEncounters", js_reset_encounters},
         {"uploadLevels", js_upload_levels}, {"neighbors", js_neighbors}, {"neighborLists", js_neighbor_lists},
         {"knn", js_knn}, {"listForce", js_list_force}, {"splitForce", js_split_force}, {"splitLists", js_split_lists}, {"neighborSchemeFused", js_neighbor_scheme_fused},
         {"setNeighborScheme", js_set_neighbor_scheme}, {"neighborSchemeStats", js_neighbor_scheme_stats},

@@ -21,6 +21,7 @@
  *                          (no reference analogue) the 6th-order scheme of a 'hermite4' simulation on force, jerk and snap
  *   setBlockBatch() / setBlockBatch6() / setBlockBatchMixed() / blockBatchStats()
  *   setBlockSteps() / setBlockSteps6() / blockStats() / readLevels() / uploadLevels()
+ *   setEncounterWatch() / encounterStats() / downloadEncounters() / uploadEncounters() / resetEncounters()
  *                          (no reference analogue) block individual time steps of a 'hermite4' simulation
  *   requestFrame()/frame() nbody3d.js:408-415,482-487 what the render pass reads each frame
  *                          (bodies + speed), delivered asynchronously to a host-side viewer
@@ -339,6 +340,53 @@ class Simulation {
 
   /** {enabled, hostWaits, slots, smallSteps, hostSteps, idleSlots} since the last reset (nb_block_batch_stats). */
   blockBatchStats(reset) { this._need(); return addon.blockBatchStats(this._h, !!reset); }
+
+  /** The encounter watch (nb_set_encounter_watch; after setBlockSteps() on a 'hermite4' simulation of order 4 with the native pass,
+   *  no batched mode): every body with a watch radius > 0 -- {radius} for all or {radii} one per body (copied; 0: not watched) --
+   *  records the closest body it meets below that radius at its OWN block steps: downloadEncounters().  {stop: true} makes step()
+   *  return after the first outer step that had a hit (encounterStats().stopped, .stepsLeft).  Changes no bit of the state.
+   *  setEncounterWatch(null) switches the watch off (so does setBlockSteps(null)). */
+  setEncounterWatch(options) {
+    this._need();
+    if (options === null || options === undefined) { addon.setEncounterWatch(this._h, null); return this; }
+    const T = this.ArrayType, r = options.radii, one = options.radius;
+    if ((one === undefined || one === null) === (r === undefined || r === null)) throw new TypeError('setEncounterWatch(): give exactly one of radius and radii');
+    const radii = r === null || r === undefined ? null : (r instanceof T ? r : T.from(r));
+    if (radii && radii.length !== this.nBodies) throw new RangeError('radii: expected ' + this.nBodies + ' elements, got ' + radii.length);
+    if (!radii && !(+one >= 0 && Number.isFinite(+one))) throw new RangeError('setEncounterWatch(): radius must be finite and >= 0');
+    addon.setEncounterWatch(this._h, radii ? 0 : +one, radii, !!options.stop);
+    return this;
+  }
+
+  /** {passes, hits, firstTime, stopped, stepsLeft} (nb_encounter_stats); reset zeroes the counters, not the records. */
+  encounterStats(reset) { this._need(); return addon.encounterStats(this._h, !!reset); }
+
+  /** The records (nb_download_encounters): {rho2 (the simulation's precision; Infinity: none), partner (Uint32Array; 0xffffffff:
+   *  none), time (Float64Array, in outer steps), count (Uint32Array)}, N elements each. */
+  downloadEncounters() {
+    this._need();
+    const n = this.nBodies;
+    const out = { rho2: new this.ArrayType(n), partner: new Uint32Array(n), time: new Float64Array(n), count: new Uint32Array(n) };
+    addon.downloadEncounters(this._h, out.rho2, out.partner, out.time, out.count);
+    return out;
+  }
+
+  /** The records of a checkpoint back (nb_upload_encounters; what downloadEncounters() gave), behind setEncounterWatch(). */
+  uploadEncounters(rec) {
+    this._need();
+    const T = this.ArrayType, n = this.nBodies;
+    const as = (a, A, name) => {
+      const t = a instanceof A ? a : A.from(a);
+      if (t.length !== n) throw new RangeError(name + ': expected ' + n + ' elements, got ' + t.length);
+      return t;
+    };
+    addon.uploadEncounters(this._h, as(rec.rho2, T, 'rho2'), as(rec.partner, Uint32Array, 'partner'), as(rec.time, Float64Array, 'time'),
+      as(rec.count, Uint32Array, 'count'));
+    return this;
+  }
+
+  /** The records to their start values and the counters to 0 (nb_reset_encounters). */
+  resetEncounters() { this._need(); addon.resetEncounters(this._h); return this; }
 
   /** The level of every body (Uint8Array of N; nb_download_levels), initialised first if not current. */
   readLevels() {

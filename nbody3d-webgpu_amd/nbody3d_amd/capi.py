@@ -140,6 +140,19 @@ class nb_block_batch(C.Structure):          # include/nbody3d_hip.h (block steps
     _fields_ = [("struct_size", C.c_uint32), ("depth", C.c_uint32), ("small_max", C.c_uint32), ("flags", C.c_uint32)]
 
 
+NB_ENC_STOP = 1                             # nb_encounter_watch.flags
+ENC_NONE = 0xffffffff                       # the partner of a body without a record
+
+
+class nb_encounter_watch(C.Structure):      # include/nbody3d_hip.h (closest approaches seen inside block steps)
+    _fields_ = [("radius", C.c_double), ("radii", C.c_void_p), ("flags", C.c_uint32)]
+
+
+class nb_encounter_stats(C.Structure):
+    _fields_ = [("passes", C.c_uint64), ("hits", C.c_uint64), ("first_time", C.c_double), ("stopped", C.c_uint32),
+                ("steps_left", C.c_uint32)]
+
+
 class nb_block_batch_stats(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("enabled", C.c_uint32), ("host_waits", C.c_uint64), ("slots", C.c_uint64),
                 ("small_steps", C.c_uint64), ("host_steps", C.c_uint64), ("idle_slots", C.c_uint64)]
@@ -215,7 +228,8 @@ SYMBOLS = ["nb_abi_version", "nb_device_count", "nb_create", "nb_destroy", "nb_u
            "nb_set_hermite_order", "nb_hermite_order", "nb_download_snap", "nb_upload_derivs6",
            "nb_set_block_steps6", "nb_set_start6", "nb_start6", "nb_set_pass_precision", "nb_pass_precision",
            "nb_set_pass_guard", "nb_pass_guard", "nb_set_block_batch", "nb_block_batch_stats", "nb_set_block_batch6",
-           "nb_set_block_batch_mixed"]
+           "nb_set_block_batch_mixed",
+           "nb_set_encounter_watch", "nb_encounter_stats", "nb_download_encounters", "nb_upload_encounters", "nb_reset_encounters"]
 
 START6_ZERO, START6_CRACKLE = 0, 1      # nb_set_start6
 PASS_NATIVE, PASS_MIXED = 0, 1          # nb_set_pass_precision
@@ -340,6 +354,12 @@ def load_library():
         L.nb_set_block_batch6.argtypes = [vp, C.POINTER(nb_block_batch)]
     if hasattr(L, "nb_set_block_batch_mixed"):  # ... on mixed-precision handles, likewise
         L.nb_set_block_batch_mixed.argtypes = [vp, C.POINTER(nb_block_batch)]
+    if hasattr(L, "nb_set_encounter_watch"):    # the encounter watch of block steps, likewise
+        L.nb_set_encounter_watch.argtypes = [vp, C.POINTER(nb_encounter_watch)]
+        L.nb_encounter_stats.argtypes = [vp, C.POINTER(nb_encounter_stats), C.c_int]
+        L.nb_download_encounters.argtypes = [vp, vp, vp, vp, vp]
+        L.nb_upload_encounters.argtypes = [vp, vp, vp, vp, vp]
+        L.nb_reset_encounters.argtypes = [vp]
     if hasattr(L, "nb_set_neighbor_levels"):    # block individual irregular steps inside the scheme, also within 2.4
         L.nb_set_neighbor_levels.argtypes = [vp, C.POINTER(nb_neighbor_levels)]
         L.nb_neighbor_level_stats.argtypes = [vp, C.POINTER(nb_neighbor_level_stats), C.c_int]
@@ -1112,6 +1132,81 @@ class Simulation:
         st.struct_size = C.sizeof(nb_block_batch_stats)
         self._check(self._L.nb_block_batch_stats(self._h, C.byref(st), 1 if reset else 0))
         return {k: int(getattr(st, k)) for k in ("enabled", "host_waits", "slots", "small_steps", "host_steps", "idle_slots")}
+
+    # -- the encounter watch of a block-step handle -----------------------------
+    def _need_watch(self, what):
+        if not hasattr(self._L, "nb_set_encounter_watch"):
+            raise NBodyError(1, "%s: the loaded library has no nb_set_encounter_watch" % what)
+
+    def set_encounter_watch(self, *args, **kw):
+        """set_encounter_watch(radius=None, radii=None, stop=False): nb_set_encounter_watch -- on an order-4 block-step handle with
+        the native pass, every body with a watch radius > 0 (``radius`` for all, or ``radii`` of shape (N,); 0: not watched)
+        records the closest body it meets below that radius at its OWN block steps: download_encounters().  stop=True makes
+        step() return after the first outer step that had a hit (encounter_stats()["stopped"], ["steps_left"]).  Changes no bit of
+        the state.  set_encounter_watch(None) switches the watch off (so does set_block_steps(None))."""
+        self._need_watch("set_encounter_watch()")
+        if args == (None,) and not kw:
+            self._check(self._L.nb_set_encounter_watch(self._h, None))
+            return self
+
+        def bind(radius=None, radii=None, stop=False):
+            return radius, radii, stop
+        radius, radii, stop = bind(*args, **kw)
+        if (radius is None) == (radii is None):
+            raise ValueError("set_encounter_watch(): give exactly one of radius and radii")
+        cfg = nb_encounter_watch()
+        cfg.flags = NB_ENC_STOP if stop else 0
+        keep = None
+        if radii is None:
+            try:
+                radius = float(radius)
+            except (TypeError, ValueError):
+                raise ValueError("set_encounter_watch(): radius must be a number, not %r" % (radius,))
+            if not (radius >= 0.0) or radius == float("inf"):
+                raise ValueError("set_encounter_watch(): radius must be finite and >= 0")
+            cfg.radius = radius
+        else:
+            keep = np.ascontiguousarray(radii, dtype=self.dtype)
+            if keep.shape != (self.n,):
+                raise ValueError("radii must have shape (%d,)" % self.n)
+            if not (np.isfinite(keep).all() and (keep >= 0).all()):
+                raise ValueError("set_encounter_watch(): radii must be finite and >= 0")
+            cfg.radii = _ptr(keep)
+        self._check(self._L.nb_set_encounter_watch(self._h, C.byref(cfg)))
+        return self
+
+    def encounter_stats(self, reset=False):
+        """nb_encounter_stats: {passes, hits, first_time, stopped, steps_left}; reset=True zeroes the counters (not the records)."""
+        self._need_watch("encounter_stats()")
+        st = nb_encounter_stats()
+        self._check(self._L.nb_encounter_stats(self._h, C.byref(st), 1 if reset else 0))
+        return {"passes": int(st.passes), "hits": int(st.hits), "first_time": float(st.first_time), "stopped": int(st.stopped),
+                "steps_left": int(st.steps_left)}
+
+    def download_encounters(self):
+        """nb_download_encounters: {rho2 (the handle's dtype; +inf: none), partner (uint32; ENC_NONE: none), time (float64),
+        count (uint32)}, each of shape (N,)."""
+        self._need_watch("download_encounters()")
+        out = {"rho2": np.zeros(self.n, self.dtype), "partner": np.zeros(self.n, np.uint32), "time": np.zeros(self.n, np.float64),
+               "count": np.zeros(self.n, np.uint32)}
+        self._check(self._L.nb_download_encounters(self._h, _ptr(out["rho2"]), _ptr(out["partner"]), _ptr(out["time"]), _ptr(out["count"])))
+        return out
+
+    def upload_encounters(self, rho2, partner, time, count):
+        """nb_upload_encounters: the records of a checkpoint (what download_encounters() gave), behind set_encounter_watch()."""
+        self._need_watch("upload_encounters()")
+        arrs = [np.ascontiguousarray(a, dtype=t) for a, t in ((rho2, self.dtype), (partner, np.uint32), (time, np.float64), (count, np.uint32))]
+        for a, name in zip(arrs, ("rho2", "partner", "time", "count")):
+            if a.shape != (self.n,):
+                raise ValueError("%s must have shape (%d,)" % (name, self.n))
+        self._check(self._L.nb_upload_encounters(self._h, *[_ptr(a) for a in arrs]))
+        return self
+
+    def reset_encounters(self):
+        """nb_reset_encounters: the records to their start values and the counters to 0."""
+        self._need_watch("reset_encounters()")
+        self._check(self._L.nb_reset_encounters(self._h))
+        return self
 
     def read_levels(self):
         """nb_download_levels: the level of every body (uint8, shape (N,)); initialises them first if they are not current."""

@@ -28,6 +28,11 @@ turns with the one without, (b) runs with the mode on and records the five batch
 set_pass_precision("mixed") on every handle with block steps -- the plain Hermite handles of (a) and the shared runs of (b) stay
 native -- and --batch then goes through set_block_batch_mixed.
 
+--watch RADIUS (order 4, native pass, not with --batch) switches set_encounter_watch(radius=RADIUS) on: (a) and (c) run a handle with
+the watch on in turns with the one without (the keys --batch names batch_* are then watch_*; watch_stats holds the counters and
+the hits per body and pass), (b) runs with the watch on and records the counters, how many bodies carry a record against the pair
+members, and the distribution of the recorded rho2 - eps2 of the pair members (run it without --watch for the other arm).
+
 Needs a GPU (no fallback)."""
 import argparse
 import contextlib
@@ -69,7 +74,25 @@ def block_steps(sim, **kw):
 BATCH = None      # --batch: (depth, small_max)
 
 
-def batch_on(sim, depth=None):
+WATCH = None      # --watch: the radius
+
+
+def second_arm():
+    """The name of the second arm of (a) and (c), or None."""
+    return "batch" if BATCH else "watch" if WATCH is not None else None
+
+
+def watch_stats(sim):
+    st = sim.encounter_stats()
+    rec = sim.download_encounters()
+    st["bodies_with_record"] = int((rec["partner"] != capi.ENC_NONE).sum())
+    st["hits_per_body_and_pass"] = float(st["hits"]) / max(1, st["passes"]) / sim.n      # (a hit is a body step with at least one candidate)
+    return st
+
+
+def second_arm_on(sim, depth=None):
+    if WATCH is not None:
+        return sim.set_encounter_watch(radius=WATCH)
     setter = sim.set_block_batch6 if ORDER == 6 else sim.set_block_batch_mixed if MIXED else sim.set_block_batch
     return setter(depth=BATCH[0] if depth is None else depth, small_max=BATCH[1])
 
@@ -113,19 +136,19 @@ def part_a(args, out):
     for prec in precisions():
         with contextlib.ExitStack() as stack:
             blk, plain = stack.enter_context(hermite(n, prec)), stack.enter_context(hermite(n, prec))
-            bat = stack.enter_context(hermite(n, prec)) if BATCH else None      # the handle with the mode on
-            for s in (blk, plain) + ((bat,) if BATCH else ()):
+            bat = stack.enter_context(hermite(n, prec)) if second_arm() else None      # the handle of the second arm: the batched mode or the watch on
+            for s in (blk, plain) + ((bat,) if second_arm() else ()):
                 s.init(b, v)
                 s.set_params(1e-3, 1.0)
             block_steps(blk, max_level=0, frozen=True)
-            if BATCH:
+            if second_arm():
                 block_steps(bat, max_level=0, frozen=True)
-                batch_on(bat)
+                second_arm_on(bat)
             est = plain.force_pass(2)
             reps = max(4, int(np.ceil(args.min_seconds * 1e3 / est)))
             got = {"force_pass_ms": [], "shared_step_ms": [], "block_step_ms": []}
-            if BATCH:
-                got["batch_block_step_ms"] = []
+            if second_arm():
+                got[second_arm() + "_block_step_ms"] = []
             for _ in range(args.rounds):
                 plain.force_pass(reps)
                 got["force_pass_ms"].append(plain.force_pass(reps))
@@ -133,17 +156,17 @@ def part_a(args, out):
                 got["shared_step_ms"].append(1e3 * wall(plain, reps) / reps)
                 wall(blk, reps)
                 got["block_step_ms"].append(1e3 * wall(blk, reps) / reps)
-                if BATCH:
+                if second_arm():
                     wall(bat, reps)
-                    got["batch_block_step_ms"].append(1e3 * wall(bat, reps) / reps)
+                    got[second_arm() + "_block_step_ms"].append(1e3 * wall(bat, reps) / reps)
             r = {k: {"median": float(np.median(x)), "best": min(x), "all": x} for k, x in got.items()}
             r["variant"] = plain.variant
             r["block_over_force_pass"] = r["block_step_ms"]["median"] / r["force_pass_ms"]["median"]
             r["block_over_shared_step"] = r["block_step_ms"]["median"] / r["shared_step_ms"]["median"]
-            if BATCH:
-                r["batch_over_block"] = r["batch_block_step_ms"]["median"] / r["block_step_ms"]["median"]
-                r["batch_over_block_rounds"] = [x / y for x, y in zip(got["batch_block_step_ms"], got["block_step_ms"])]
-                r["batch_stats"] = bat.block_batch_stats()
+            if second_arm():
+                r[second_arm() + "_over_block"] = r[second_arm() + "_block_step_ms"]["median"] / r["block_step_ms"]["median"]
+                r[second_arm() + "_over_block_rounds"] = [x / y for x, y in zip(got[second_arm() + "_block_step_ms"], got["block_step_ms"])]
+                r[second_arm() + "_stats"] = bat.block_batch_stats() if BATCH else watch_stats(bat)
             out["full"]["%s_%d" % (prec, n)] = r
 
 
@@ -153,15 +176,15 @@ def part_b(args, out):
         outer = int(round(1.0 / args.outer_dt))
         r = {"n": n, "pairs": int(0.01 * n) // 2, "precision": args.precision, "outer_dt": args.outer_dt, "eta": args.eta, "order": ORDER,
              "start_deeper": args.start_deeper, "start6": int(args.start6), "pair_half": args.pair_half, "eps2": args.eps2,
-             "batch": list(BATCH) if BATCH else None, "pass_precision": "mixed" if MIXED else "native"}
+             "batch": list(BATCH) if BATCH else None, "watch": WATCH, "pass_precision": "mixed" if MIXED else "native"}
         with hermite(n, args.precision, args.eps2) as sim:
             sim.init(b, v)
             if args.start6:      # the engine's own start: exact crackle, two-rule levels
                 sim.set_start6(1)
             sim.set_params(args.outer_dt, 1.0)
             block_steps(sim, eta=args.eta, max_level=args.max_level)
-            if BATCH:
-                batch_on(sim)
+            if second_arm():
+                second_arm_on(sim)
             e0 = energy(sim)
             lev0 = sim.read_levels()
             if args.start_deeper:      # the start rule's levels made deeper through nb_upload_levels: every body's first step shorter
@@ -177,6 +200,13 @@ def part_b(args, out):
                           "levels_start": np.bincount(lev0).tolist(), "levels_end": np.bincount(sim.read_levels()).tolist()}
             if BATCH:
                 r["block"]["batch_stats"] = sim.block_batch_stats()
+            if WATCH is not None:      # who carries a record, and the pair members' closest approaches (the pairs are bodies 0 .. 2 pairs - 1)
+                rec, members = sim.download_encounters(), 2 * r["pairs"]
+                have = rec["partner"] != capi.ENC_NONE
+                peri = np.sqrt(np.maximum(rec["rho2"][:members][have[:members]].astype(np.float64) - (1e-4 if args.eps2 is None else args.eps2), 0.0))
+                r["block"]["watch_stats"] = dict(watch_stats(sim), pair_members=members, pair_members_with_record=int(have[:members].sum()),
+                                                 partner_is_the_mate=int((rec["partner"][:members][have[:members]] == (np.arange(members) ^ 1)[have[:members]]).sum()),
+                                                 pericentre_quantiles=dict(zip(("min", "p10", "p50", "p90", "max"), np.quantile(peri, [0, 0.1, 0.5, 0.9, 1]).tolist())) if len(peri) else None)
         r["block"]["full_force_equivalents"] = r["block"]["stats"]["body_steps"] / n
         r["shared"] = []
         for k in range(args.shared_from, args.shared_to + 1):
@@ -204,7 +234,8 @@ def part_c(args, out):
     lev = np.zeros(n, np.uint8)
     lev[np.random.default_rng(5).choice(n, k, replace=False)] = L
     sets = (("all_level0", np.zeros(n, np.uint8)), ("64_at_level6", lev))
-    arms = ["off"] + (["on"] if BATCH else [])
+    second = second_arm()
+    arms = ["off"] + (["on"] if second else [])
     for prec in precisions():
         sims = {}
         try:
@@ -215,11 +246,11 @@ def part_c(args, out):
                     sim.set_params(1e-3, 1.0)
                     block_steps(sim, max_level=L, frozen=True)
                     if arm == "on":
-                        batch_on(sim)
+                        second_arm_on(sim)
                     sim.upload_levels(levels)
                     wall(sim, 4)
                     sim.block_stats(reset=True)
-                    if arm == "on":
+                    if arm == "on" and BATCH:
                         sim.block_batch_stats(reset=True)
             runs = {key: [] for key in sims}
             for _ in range(args.rounds):
@@ -236,17 +267,17 @@ def part_c(args, out):
                     t[name] = {"outer_step_us": 1e6 * float(np.median(runs[arm, name])), "outer_step_us_rounds": [1e6 * x for x in runs[arm, name]],
                                "block_steps_per_outer": st["block_steps"] / st["outer_steps"], "body_steps_per_outer": st["body_steps"] / st["outer_steps"]}
                     if arm == "on":
-                        t[name]["batch_stats"] = sims[arm, name].block_batch_stats()
+                        t[name][second + "_stats"] = sims[arm, name].block_batch_stats() if BATCH else watch_stats(sims[arm, name])
                 per = [1e6 * (x - y) / (2 ** L - 1) for x, y in zip(runs[arm, "64_at_level6"], runs[arm, "all_level0"])]
                 t["us_per_small_block_step"] = (t["64_at_level6"]["outer_step_us"] - t["all_level0"]["outer_step_us"]) / (2 ** L - 1)
                 t["us_per_small_block_step_rounds"] = per
                 res[arm] = t
             r = res["off"]
-            if BATCH:
-                r["batch"] = res["on"]
-                r["batch"]["config"] = list(BATCH)
-                r["batch_over_off"] = res["on"]["us_per_small_block_step"] / res["off"]["us_per_small_block_step"]
-                r["full_set_batch_over_off"] = res["on"]["all_level0"]["outer_step_us"] / res["off"]["all_level0"]["outer_step_us"]
+            if second:
+                r[second] = res["on"]
+                r[second]["config"] = list(BATCH) if BATCH else WATCH
+                r[second + "_over_off"] = res["on"]["us_per_small_block_step"] / res["off"]["us_per_small_block_step"]
+                r["full_set_" + second + "_over_off"] = res["on"]["all_level0"]["outer_step_us"] / res["off"]["all_level0"]["outer_step_us"]
             out["small"]["%s_%d" % (prec, n)] = r
         finally:
             for sim in sims.values():
@@ -268,7 +299,7 @@ def part_i(args, out):
             runs, idle = {3: [], 32: []}, {}
             for r in range(args.rounds + 1):      # the first round warms up
                 for depth in (3, 32):
-                    batch_on(sim, depth)      # the policy starts over: one slot, then min(depth, 63)
+                    second_arm_on(sim, depth)      # the policy starts over: one slot, then min(depth, 63)
                     sim.upload_levels(lev)
                     sim.block_batch_stats(reset=True)
                     t = wall(sim, 1)
@@ -285,6 +316,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--only", choices=["a", "b", "c", "i"], nargs="*", default=["a", "b", "c"])
     ap.add_argument("--batch", default=None, metavar="DEPTH,SMALL_MAX", help="set_block_batch(depth, small_max) on the block handles (with --order 6: set_block_batch6)")
+    ap.add_argument("--watch", type=float, default=None, metavar="RADIUS", help="set_encounter_watch(radius=RADIUS) on the block handles (order 4, native pass, not with --batch)")
     ap.add_argument("--pass-precision", default="native", choices=["native", "mixed"], help="mixed: set_pass_precision('mixed') on the block handles (f64 only); --batch then uses set_block_batch_mixed")
     ap.add_argument("--full-n", type=int, default=65536)
     ap.add_argument("--sizes", type=int, nargs="*", default=[16384, 65536])
@@ -303,7 +335,10 @@ def main():
     ap.add_argument("--min-seconds", type=float, default=0.3)
     ap.add_argument("--rounds", type=int, default=3)
     args = ap.parse_args()
-    global ORDER, BATCH, MIXED
+    global ORDER, BATCH, MIXED, WATCH
+    WATCH = args.watch
+    if WATCH is not None and (args.batch or args.order != 4 or args.pass_precision != "native" or not WATCH >= 0):
+        ap.error("--watch takes a radius >= 0 and needs --order 4, the native pass and no --batch")
     ORDER = args.order
     MIXED = args.pass_precision == "mixed"
     if MIXED and ORDER != 4:
@@ -320,7 +355,7 @@ def main():
         ap.error("--start6 needs --order 6")
     if capi.device_count() < 1:
         sys.exit("block_bench: no GPU")
-    out = {"tool": "block_bench", "order": ORDER, "batch": list(BATCH) if BATCH else None, "pass_precision": args.pass_precision, "full": {}, "end2end": [], "small": {}, "idle": {}}
+    out = {"tool": "block_bench", "order": ORDER, "batch": list(BATCH) if BATCH else None, "watch": args.watch, "pass_precision": args.pass_precision, "full": {}, "end2end": [], "small": {}, "idle": {}}
     if "a" in args.only:
         part_a(args, out)
     if "b" in args.only:
