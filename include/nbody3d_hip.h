@@ -91,7 +91,8 @@ extern "C" {
                              2.4 (round 27) likewise within 2.4: nb_set_block_batch_mixed.  Detected by the presence of the symbol
                              2.4 (round 28) likewise within 2.4: nb_set_encounter_watch, nb_encounter_stats, nb_download_encounters,
                                             nb_upload_encounters, nb_reset_encounters, nb_encounter_watch, NB_ENC_STOP.  Detected by
-                                            the presence of the symbol nb_set_encounter_watch */
+                                            the presence of the symbol nb_set_encounter_watch
+                             2.4 (round 29) likewise within 2.4: nb_set_block_batch_watch.  Detected by the presence of the symbol */
 
 typedef struct nb_sim nb_sim; /* opaque */
 
@@ -636,8 +637,49 @@ int nb_set_block_batch6(nb_sim *s, const nb_block_batch *cfg /* NULL: off */);
  *     a handle without nb_set_block_steps, a native-precision handle (nb_set_pass_precision, or nb_set_block_batch), a handle with
  *     nb_set_pass_guard > 0.  NB_ERR_INVALID (naming nb_set_block_batch_mixed and the field): a NULL handle, a wrong struct_size,
  *     depth > 1024, small_max > 1024 other than NB_BLOCK_BATCH_SMALL_DEFAULT, flags != 0.
- *   - Not built: the mode on guarded handles, at order 6 with a mixed pass, with the neighbour scheme or on nb_multi. */
+ *   - Not built: the mode on guarded handles, at order 6 with a mixed pass, with the neighbour scheme or on nb_multi; the encounter
+ *     watch in mixed and order-6 slots (native order-4 slots: nb_set_block_batch_watch below). */
 int nb_set_block_batch_mixed(nb_sim *s, const nb_block_batch *cfg /* NULL: off */);
+
+/* nb_set_block_batch_watch (round 29): nb_set_block_batch's mode on a handle with the encounter watch on (nb_set_encounter_watch,
+ * below) -- a Hermite handle of order 4, NB_F32 or NB_F64, with nb_set_block_steps on (dynamic or frozen levels), the native pass,
+ * the watch on and no other batched mode on.  Order of the setters: nb_set_block_steps, nb_set_encounter_watch,
+ * nb_set_block_batch_watch.  A separate entry point, as nb_set_block_batch6 and nb_set_block_batch_mixed are: with the watch on,
+ * nb_set_block_batch, nb_set_block_batch6 and nb_set_block_batch_mixed (non-NULL) stay NB_ERR_STATE, and with one of those modes on
+ * nb_set_encounter_watch stays NB_ERR_STATE.  The struct, the defaults, the limits, the slot protocol, the scheduler, the predictor,
+ * the host's policy, the header checks at every wait and nb_block_batch_stats (enabled = 1) are nb_set_block_batch's.  Inside a slot
+ * the small pass keeps, beside its sums, the slot's closest candidate of each j-chunk, and the small corrector folds the chunks'
+ * answers into the body's record before it corrects (kernels/encounter_batch.hip.h): no launch is added to a slot.  A parked slot's
+ * host step is the watched handle's gathered pass, fold and block corrector.
+ *   - State, derivatives and levels carry nb_set_block_batch's contract word for word: with a fixed small_max nothing depends on
+ *     depth or on where batches end; nb_step(k) equals k x nb_step(1); two handles give the same bits; small_max = 0 is the mode
+ *     off, bit for bit; t_next == 2^L always parks.
+ *   - No stored bit of the state, the derivatives or the levels and no nb_block_stats or nb_block_batch_stats counter depends on the
+ *     watch: a handle with nb_set_block_batch (same depth and small_max) and no watch holds the same bits after the same steps.
+ *   - The records follow nb_set_encounter_watch's rules unchanged (candidates, the smallest rho^2 and the smallest index on a tie,
+ *     strictly smaller replaces, count per own step with an answer, time = outer steps run + t_next / 2^max_level, rho^2 the value
+ *     the pass that ran the step holds) and carry the state's contract: with a fixed small_max no record and no counter (passes,
+ *     hits, first_time) depends on depth or on where batches end; with small_max = 0 they are those of the watch without the mode,
+ *     bit for bit.  What a small step records for a body depends on the predicted arrays, the body's threshold and n alone, not on
+ *     |A|, on the body's place in the list or on depth.  passes counts small and host steps alike: it equals
+ *     nb_block_stats.block_steps over the same interval.
+ *   - NB_ENC_STOP keeps its meaning: one extra host wait per outer step, after the outer step's last (host) block step, whose fold
+ *     publishes the running hits, those of the small slots included.
+ *   - nb_set_block_batch_watch(s, NULL), nb_set_block_batch(s, NULL), nb_set_block_batch6(s, NULL), nb_set_block_batch_mixed(s, NULL)
+ *     and nb_set_block_steps(s, NULL) switch the mode off; the watch stays on with the first four.  nb_set_encounter_watch(s, NULL)
+ *     switches the watch off and the mode with it.  nb_set_encounter_watch(non-NULL) while this mode is on replaces radii and flags
+ *     and keeps records and counters; nb_set_block_batch_watch(non-NULL) while it is on sets depth and small_max anew.  A non-NULL
+ *     nb_set_block_steps keeps both.  nb_set_hermite_order(6), nb_set_pass_precision(NB_PASS_MIXED),
+ *     nb_set_neighbor_scheme(non-NULL) and the three other batch setters (non-NULL) stay NB_ERR_STATE, as on any watched handle.
+ *   - Checkpoint: the state's five arrays and the four record arrays.  A handle restored by nb_upload, nb_upload_derivs,
+ *     nb_set_block_steps, nb_set_encounter_watch, nb_set_block_batch_watch (same small_max, any depth), nb_upload_levels,
+ *     nb_upload_encounters continues bit for bit, records included.
+ *   - NB_ERR_STATE (the message names nb_set_block_batch_watch and the setter to call): a leapfrog handle, an order-6 handle, a
+ *     handle without nb_set_block_steps, a mixed or guarded pass, the watch off (nb_set_encounter_watch; nb_set_block_batch for the
+ *     mode without a watch), another batched mode on.  NB_ERR_INVALID (naming the field): a NULL handle, a wrong struct_size,
+ *     depth > 1024, small_max > 1024 other than NB_BLOCK_BATCH_SMALL_DEFAULT, flags != 0.
+ *   - Not built: the watch in mixed, guarded and order-6 slots, with the neighbour scheme, on nb_multi. */
+int nb_set_block_batch_watch(nb_sim *s, const nb_block_batch *cfg /* NULL: off */);
 
 /* (a struct TAG without a typedef, as nb_block_stats) */
 struct nb_block_batch_stats {
@@ -659,7 +701,7 @@ int nb_block_batch_stats(nb_sim *s, struct nb_block_batch_stats *out, int reset)
  * force libraries of the GRAPE family return the nearest neighbour with the force.  The primitive under collision and merger
  * detection, close-encounter stopping conditions and the search for pairs to regularise.
  *   - Opt-in, on a Hermite handle of order 4 with nb_set_block_steps on (dynamic or frozen levels), the native pass, NB_F32 or
- *     NB_F64, no batched mode.  No stored bit of the state, the derivatives or the levels and no nb_block_stats counter depends on
+ *     NB_F64, no batched mode (the watch inside batched slots: nb_set_block_batch_watch above, called with the watch on).  No stored bit of the state, the derivatives or the levels and no nb_block_stats counter depends on
  *     the watch: the pass's sums are the same instructions on the same values.
  *   - Body i has a watch radius h_i >= 0: `radius` for all bodies, or radii[i] (n elements of the handle's precision, host memory,
  *     copied by the call); 0: the body is not watched.  The threshold is w_i = h_i^2 + eps2, evaluated in fp64 and rounded once to
@@ -680,7 +722,7 @@ int nb_block_batch_stats(nb_sim *s, struct nb_block_batch_stats *out, int reset)
  *     with stopped = 1 and steps_left = the outer steps not run.  One extra host wait per outer step, with the flag only.
  *   - nb_upload keeps the configuration and the counters and clears the records.  nb_set_encounter_watch(non-NULL) while the watch
  *     is on replaces radii and flags and keeps records and counters; switched on from off, both start over.
- *     nb_set_encounter_watch(s, NULL) and nb_set_block_steps(s, NULL) switch it off.  While it is on, nb_set_block_batch,
+ *     nb_set_encounter_watch(s, NULL) and nb_set_block_steps(s, NULL) switch it off (and nb_set_block_batch_watch's mode with it).  While it is on, nb_set_block_batch,
  *     nb_set_block_batch6, nb_set_block_batch_mixed (non-NULL), nb_set_pass_precision(NB_PASS_MIXED), nb_set_hermite_order(6) and
  *     nb_set_neighbor_scheme(non-NULL) are NB_ERR_STATE.
  *   - Checkpoint: the four record arrays beside the state's (nb_download_encounters / nb_upload_encounters, the last calls of a
@@ -689,8 +731,8 @@ int nb_block_batch_stats(nb_sim *s, struct nb_block_batch_stats *out, int reset)
  *     pointer, a NULL array or a partner that is neither another body's index nor 0xffffffff in nb_upload_encounters.  NB_ERR_STATE
  *     (the message names the function and the reason): a leapfrog handle, block steps off, an order-6 handle, a mixed or guarded
  *     pass, a batched mode on, the neighbour scheme on; the four other calls on a handle without the watch.
- *   - Not built: the watch in batched slots, in the mixed and guarded passes, at order 6, with the neighbour scheme, on nb_multi; a
- *     criterion on r_i + r_j. */
+ *   - Not built: the watch in the mixed and guarded passes and their batched slots, at order 6, with the neighbour scheme, on
+ *     nb_multi; a criterion on r_i + r_j. */
 enum { NB_ENC_STOP = 1u };      /* nb_encounter_watch.flags: nb_step returns after the first outer step that had a hit */
 typedef struct nb_encounter_watch {
     double radius;          /* h for every body (radii == NULL) */

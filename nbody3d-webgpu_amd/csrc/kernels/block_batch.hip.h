@@ -161,18 +161,27 @@ __global__ __launch_bounds__(kBlock) void nb_blkq_predict(const typename vec4<T>
 // quarter of the chunk.  The four waves' binary32 sums meet in LDS and are added in wave order; one compact partial row per
 // (j-chunk, list slot) at pa[c * small_max + k].  Lanes past |A| clamp and store nothing; a workgroup whose first slot is past |A|
 // leaves after the header loads.
-template <int NG>
-__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(2, 2)))
-void nb_blkq_fj_pk(const float4* __restrict__ pos, const float4* __restrict__ vel, const uint32_t* __restrict__ act,
-                   const uint32_t* __restrict__ hdr, const uint32_t* __restrict__ bb, uint32_t small_max, float4* __restrict__ pa,
-                   float4* __restrict__ pj, uint32_t n, uint32_t j_per_chunk, float eps2, const float4* __restrict__ zero_row)
+//   The body is shared with nb_encq_fj_pk (kernels/encounter_batch.hip.h).  WATCH (nb_set_block_batch_watch): wth[i] is body i's
+// threshold w_i, as in fj_pk_body.  Per stage the eight compares rho^2 < w of its chains are ORed on the scalar unit and ONE
+// wave-uniform branch skips the slow path, which tests the index (the own row, rows past the chunk) and keeps the lane's smallest
+// (rho^2, j) per packed half in registers.  The four waves hold the same slots and sweep different quarters of each tile: their
+// four bests meet in LDS beside red and are merged under the total order (rho^2, index), and the slot's answer for the chunk leaves
+// in the .w lanes of the two rows (rho^2; the index bit-cast, 0xffffffff: none).  The sums are the same instructions on the same
+// values; without WATCH none of this is compiled.
+template <bool WATCH>
+__device__ __forceinline__ void blkq_fj_pk_body(const float4* __restrict__ pos, const float4* __restrict__ vel,
+                                                const uint32_t* __restrict__ act, const uint32_t* __restrict__ hdr,
+                                                const uint32_t* __restrict__ bb, uint32_t small_max, float4* __restrict__ pa,
+                                                float4* __restrict__ pj, uint32_t n, uint32_t j_per_chunk, float eps2,
+                                                const float4* __restrict__ zero_row, const float* __restrict__ wth = nullptr)
 {
-    static_assert(NG == 1, "one packed pair per lane");
     constexpr int TILE = kTile;
     constexpr int U = 8;                  // tile rows per unrolled chunk
     constexpr int JB = 4;                 // j-bodies per stage: four independent chains
     __shared__ float4 tile[2][2][TILE];   // [buffer][0 = positions, 1 = velocities][row]
     __shared__ float red[4][6][kBbRows];  // [wave][ax ay az jx jy jz][slot]
+    __shared__ float enc_r[WATCH ? 4 : 1][WATCH ? kBbRows : 1];         // WATCH: [wave][slot] the wave's smallest rho^2 ...
+    __shared__ uint32_t enc_j[WATCH ? 4 : 1][WATCH ? kBbRows : 1];      // ... and its index (0xffffffff: none)
     const uint32_t i0 = blockIdx.x * kBbRows;
     if (bb[kBbMode] != kBbModeSmall) return;
     const uint32_t ni = hdr[kBlkCount];
@@ -182,11 +191,17 @@ void nb_blkq_fj_pk(const float4* __restrict__ pos, const float4* __restrict__ ve
     const uint32_t j1 = j0 + j_per_chunk < n ? j0 + j_per_chunk : n;
 
     nb_f2 xi, yi, zi, ui, vi, wi;
+    nb_f2 wq = nb_f2{0, 0}, br = nb_f2{__builtin_inff(), __builtin_inff()};      // WATCH: the thresholds of the lane's bodies, the smallest rho^2 so far ...
+    uint32_t bj0 = 0xffffffffu, bj1 = 0xffffffffu, own0 = 0, own1 = 0;           // ... its index per half, and the lane's own bodies
     {
         const uint32_t il0 = i0 + lane, il1 = il0 + 64;
         uint32_t c0 = il0 < ni ? il0 : ni - 1, c1 = il1 < ni ? il1 : ni - 1;        // clamped, branch-free (never stored)
         c0 = act[c0]; c1 = act[c1];
         c0 = c0 < n ? c0 : n - 1; c1 = c1 < n ? c1 : n - 1;
+        if constexpr (WATCH) {            // a clamped lane watches nothing (rho^2 < 0 never holds)
+            wq = nb_f2{il0 < ni ? wth[c0] : 0.0f, il1 < ni ? wth[c1] : 0.0f};
+            own0 = c0; own1 = c1;
+        }
         const float4 b0 = ld4(pos + c0), b1 = ld4(pos + c1), v0 = ld4(vel + c0), v1 = ld4(vel + c1);
         xi = nb_f2{b0.x, b1.x}; yi = nb_f2{b0.y, b1.y}; zi = nb_f2{b0.z, b1.z};
         ui = nb_f2{v0.x, v1.x}; vi = nb_f2{v0.y, v1.y}; wi = nb_f2{v0.z, v1.z};
@@ -224,8 +239,8 @@ void nb_blkq_fj_pk(const float4* __restrict__ pos, const float4* __restrict__ ve
     };
 
     // one stage: JB tile rows (positions p, velocities q) against the lane's packed pair, stage-major over the JB chains
-    // (fj_pk_body::math with NG = 1)
-    auto math = [&](const float4* p, const float4* q) {
+    // (fj_pk_body::math with NG = 1; jrow: the body index of row p[0], read by the watch only)
+    auto math = [&](const float4* p, const float4* q, uint32_t jrow) {
         nb_f2 bx[JB], by[JB], bz[JB], bu[JB], bv[JB], bw[JB];
         float bm[JB];
 #pragma unroll
@@ -247,6 +262,28 @@ void nb_blkq_fj_pk(const float4* __restrict__ pos, const float4* __restrict__ ve
         for (int c = 0; c < JB; ++c) d2[c] = __builtin_elementwise_fma(dy[c], dy[c], d2[c]);
 #pragma unroll
         for (int c = 0; c < JB; ++c) d2[c] = __builtin_elementwise_fma(dz[c], dz[c], d2[c]);
+        if constexpr (WATCH) {
+            bool lt[JB][2];
+            bool hit = false;
+#pragma unroll
+            for (int c = 0; c < JB; ++c) {
+                lt[c][0] = d2[c].x < wq.x; lt[c][1] = d2[c].y < wq.y;
+                hit |= lt[c][0] | lt[c][1];
+            }
+            if (__builtin_amdgcn_ballot_w64(hit) != 0) {      // wave-uniform: some lane has a pair below its threshold among these JB rows
+#pragma unroll
+                for (int u = 0; u < JB; ++u) {                // a slot meets the rows of its quarter in ascending j
+                    const uint32_t j = jrow + (uint32_t)u;
+                    const nb_f2 r = d2[u];
+                    const bool in = j < j1;                   // a row past the chunk is padding (zero_row sits at the origin)
+                    // (bitwise, then selects: no branch per lane inside the slow path)
+                    const bool t0 = lt[u][0] & in & (j != own0) & ((r.x < br.x) | ((r.x == br.x) & (j < bj0)));
+                    const bool t1 = lt[u][1] & in & (j != own1) & ((r.y < br.y) | ((r.y == br.y) & (j < bj1)));
+                    br.x = t0 ? r.x : br.x; bj0 = t0 ? j : bj0;
+                    br.y = t1 ? r.y : br.y; bj1 = t1 ? j : bj1;
+                }
+            }
+        }
 #pragma unroll
         for (int c = 0; c < JB; ++c) y[c] = nb_f2{nb_rsq(d2[c].x), nb_rsq(d2[c].y)};
 #pragma unroll
@@ -307,8 +344,8 @@ void nb_blkq_fj_pk(const float4* __restrict__ pos, const float4* __restrict__ ve
         const int cntu = (cnt + U - 1) / U * U;           // rows past the range are staged zero-mass bodies
         const int lo = 64 * wave, hi = lo + 64 < cntu ? lo + 64 : cntu;      // the wave's quarter of the tile
         for (int r = lo; r < hi; r += U) {
-            math(&tile[cur][0][r], &tile[cur][1][r]);
-            math(&tile[cur][0][r + JB], &tile[cur][1][r + JB]);
+            math(&tile[cur][0][r], &tile[cur][1][r], j0 + t * TILE + (uint32_t)r);
+            math(&tile[cur][0][r + JB], &tile[cur][1][r + JB], j0 + t * TILE + (uint32_t)(r + JB));
         }
         if ((t & 15u) == 15u) flush();                    // 1,024 terms per chain, as nb_fj_pk
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -322,29 +359,60 @@ void nb_blkq_fj_pk(const float4* __restrict__ pos, const float4* __restrict__ ve
     red[wave][3][lane] = JX.x; red[wave][3][lane + 64] = JX.y;
     red[wave][4][lane] = JY.x; red[wave][4][lane + 64] = JY.y;
     red[wave][5][lane] = JZ.x; red[wave][5][lane + 64] = JZ.y;
+    if constexpr (WATCH) {
+        enc_r[wave][lane] = br.x; enc_r[wave][lane + 64] = br.y;
+        enc_j[wave][lane] = bj0; enc_j[wave][lane + 64] = bj1;
+    }
     __syncthreads();
     const uint32_t k = i0 + (uint32_t)tid;
     if (tid < (int)kBbRows && k < ni) {
         float r[6];
 #pragma unroll
         for (int c = 0; c < 6; ++c) r[c] = ((red[0][c][tid] + red[1][c][tid]) + red[2][c][tid]) + red[3][c][tid];
-        pa[(size_t)blockIdx.y * small_max + k] = float4{r[0], r[1], r[2], 0.0f};
-        pj[(size_t)blockIdx.y * small_max + k] = float4{r[3], r[4], r[5], 0.0f};
+        float er = 0.0f, ej = 0.0f;       // WATCH: the chunk's answer, rho^2 and the index bit-cast
+        if constexpr (WATCH) {            // the four quarters' bests under the total order (rho^2, index)
+            float mr = enc_r[0][tid];
+            uint32_t mj = enc_j[0][tid];
+#pragma unroll
+            for (int w = 1; w < 4; ++w) {
+                const float wr = enc_r[w][tid];
+                const uint32_t wj = enc_j[w][tid];
+                const bool t = (wj != 0xffffffffu) & ((wr < mr) | ((wr == mr) & (wj < mj)));
+                mr = t ? wr : mr; mj = t ? wj : mj;
+            }
+            er = mr; ej = __uint_as_float(mj);
+        }
+        pa[(size_t)blockIdx.y * small_max + k] = float4{r[0], r[1], r[2], er};
+        pj[(size_t)blockIdx.y * small_max + k] = float4{r[3], r[4], r[5], ej};
     }
+}
+
+template <int NG>
+__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(2, 2)))
+void nb_blkq_fj_pk(const float4* __restrict__ pos, const float4* __restrict__ vel, const uint32_t* __restrict__ act,
+                   const uint32_t* __restrict__ hdr, const uint32_t* __restrict__ bb, uint32_t small_max, float4* __restrict__ pa,
+                   float4* __restrict__ pj, uint32_t n, uint32_t j_per_chunk, float eps2, const float4* __restrict__ zero_row)
+{
+    static_assert(NG == 1, "one packed pair per lane");
+    blkq_fj_pk_body<false>(pos, vel, act, hdr, bb, small_max, pa, pj, n, j_per_chunk, eps2, zero_row);
 }
 
 // f64: the same shape on fj64_body's arithmetic (v_rsq_f64 seed + one correction, everything in fp64).  Grid (ceil(small_max / 64),
 // j-chunks); the four waves hold the same 64 list slots, one body per lane, wave w sweeps rows [64 w, 64 w + 64) of each tile.
-template <typename T>
-__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(2, 2)))
-void nb_blkq_fj64(const typename vec4<T>::type* __restrict__ pos, const typename vec4<T>::type* __restrict__ vel,
-                  const uint32_t* __restrict__ act, const uint32_t* __restrict__ hdr, const uint32_t* __restrict__ bb,
-                  uint32_t small_max, double4* __restrict__ pa, double4* __restrict__ pj, uint32_t n, uint32_t j_per_chunk,
-                  double eps2)
+// WATCH: as blkq_fj_pk_body, one compare per pair and the lane masks tested on the scalar unit; the four waves' bests meet in LDS
+// and the index leaves as an exact double.  The loop ends at the chunk's last row: a zero row of the tile is never met.
+template <typename T, bool WATCH>
+__device__ __forceinline__ void blkq_fj64_body(const typename vec4<T>::type* __restrict__ pos,
+                                               const typename vec4<T>::type* __restrict__ vel, const uint32_t* __restrict__ act,
+                                               const uint32_t* __restrict__ hdr, const uint32_t* __restrict__ bb,
+                                               uint32_t small_max, double4* __restrict__ pa, double4* __restrict__ pj, uint32_t n,
+                                               uint32_t j_per_chunk, double eps2, const T* __restrict__ wth = nullptr)
 {
     __shared__ double4 tp[kTile];
     __shared__ double4 tv[kTile];
     __shared__ double red[4][6][kBbRows64];
+    __shared__ double enc_r[WATCH ? 4 : 1][WATCH ? kBbRows64 : 1];        // WATCH: [wave][slot] the wave's smallest rho^2 ...
+    __shared__ uint32_t enc_j[WATCH ? 4 : 1][WATCH ? kBbRows64 : 1];      // ... and its index (0xffffffff: none)
     const uint32_t i0 = blockIdx.x * kBbRows64;
     if (bb[kBbMode] != kBbModeSmall) return;
     const uint32_t ni = hdr[kBlkCount];
@@ -361,6 +429,9 @@ void nb_blkq_fj64(const typename vec4<T>::type* __restrict__ pos, const typename
     const double xi = (double)bi.x, yi = (double)bi.y, zi = (double)bi.z;
     const double ui = (double)wi.x, vi = (double)wi.y, wz = (double)wi.z;
     double ax = 0.0, ay = 0.0, az = 0.0, jx = 0.0, jy = 0.0, jz = 0.0;
+    double wq = 0.0, br = __builtin_inf();      // WATCH: the lane's threshold (a clamped lane watches nothing), its smallest rho^2 so far ...
+    uint32_t bj = 0xffffffffu;                  // ... and that pair's index (0xffffffff: none)
+    if constexpr (WATCH) wq = il < ni ? (double)wth[ic] : 0.0;
     for (uint32_t jt = j0; jt < j1; jt += kTile) {
         const uint32_t j = jt + tid;
         __syncthreads();                                          // the previous tile has been read
@@ -377,35 +448,88 @@ void nb_blkq_fj64(const typename vec4<T>::type* __restrict__ pos, const typename
         const uint32_t left = j1 - jt;
         const int cnt = left < (uint32_t)kTile ? (int)left : kTile;
         const int lo = 64 * wave, hi = lo + 64 < cnt ? lo + 64 : cnt;      // the wave's quarter of the tile
+        if constexpr (WATCH) {
+            // the loop below, statement for statement, with the watch behind rho^2 -- two rows per trip and an odd last row, written
+            // out: the wave-wide test keeps the compiler from unrolling a loop of unknown length with a remainder, as it does below
+            auto row = [&](int jj) {
+                const double4 b = tp[jj];
+                const double4 c = tv[jj];
+                const double dx = b.x - xi, dy = b.y - yi, dz = b.z - zi;
+                const double du = c.x - ui, dv = c.y - vi, dw = c.z - wz;
+                const double r2 = nb_fma(dz, dz, nb_fma(dy, dy, nb_fma(dx, dx, eps2)));
+                const bool lt = r2 < wq;
+                if (__builtin_amdgcn_ballot_w64(lt) != 0) {      // wave-uniform: some lane has this row below its threshold
+                    const uint32_t jb = jt + (uint32_t)jj;
+                    if (lt && jb != ic && (r2 < br || (r2 == br && jb < bj))) { br = r2; bj = jb; }
+                }
+                const double y0 = __builtin_amdgcn_rsq(r2);
+                const double e = nb_fma(-(r2 * y0), y0, 1.0);
+                const double y = nb_fma(0.5 * y0, e, y0);
+                const double y2 = y * y;
+                const double s3 = (b.w * y) * y2;
+                const double q3 = -3.0 * (nb_fma(dz, dw, nb_fma(dy, dv, dx * du)) * y2);
+                const double tx = nb_fma(q3, dx, du), ty = nb_fma(q3, dy, dv), tz = nb_fma(q3, dz, dw);
+                jx = nb_fma(s3, tx, jx); jy = nb_fma(s3, ty, jy); jz = nb_fma(s3, tz, jz);
+                ax = nb_fma(s3, dx, ax); ay = nb_fma(s3, dy, ay); az = nb_fma(s3, dz, az);
+            };
+            int jj = lo;
+            for (; jj + 2 <= hi; jj += 2) { row(jj); row(jj + 1); }
+            if (jj < hi) row(jj);
+        } else {
 #pragma unroll 2
-        for (int jj = lo; jj < hi; ++jj) {
-            const double4 b = tp[jj];
-            const double4 c = tv[jj];
-            const double dx = b.x - xi, dy = b.y - yi, dz = b.z - zi;
-            const double du = c.x - ui, dv = c.y - vi, dw = c.z - wz;
-            const double r2 = nb_fma(dz, dz, nb_fma(dy, dy, nb_fma(dx, dx, eps2)));
-            const double y0 = __builtin_amdgcn_rsq(r2);
-            const double e = nb_fma(-(r2 * y0), y0, 1.0);
-            const double y = nb_fma(0.5 * y0, e, y0);
-            const double y2 = y * y;
-            const double s3 = (b.w * y) * y2;
-            const double q3 = -3.0 * (nb_fma(dz, dw, nb_fma(dy, dv, dx * du)) * y2);
-            const double tx = nb_fma(q3, dx, du), ty = nb_fma(q3, dy, dv), tz = nb_fma(q3, dz, dw);
-            jx = nb_fma(s3, tx, jx); jy = nb_fma(s3, ty, jy); jz = nb_fma(s3, tz, jz);
-            ax = nb_fma(s3, dx, ax); ay = nb_fma(s3, dy, ay); az = nb_fma(s3, dz, az);
+            for (int jj = lo; jj < hi; ++jj) {
+                const double4 b = tp[jj];
+                const double4 c = tv[jj];
+                const double dx = b.x - xi, dy = b.y - yi, dz = b.z - zi;
+                const double du = c.x - ui, dv = c.y - vi, dw = c.z - wz;
+                const double r2 = nb_fma(dz, dz, nb_fma(dy, dy, nb_fma(dx, dx, eps2)));
+                const double y0 = __builtin_amdgcn_rsq(r2);
+                const double e = nb_fma(-(r2 * y0), y0, 1.0);
+                const double y = nb_fma(0.5 * y0, e, y0);
+                const double y2 = y * y;
+                const double s3 = (b.w * y) * y2;
+                const double q3 = -3.0 * (nb_fma(dz, dw, nb_fma(dy, dv, dx * du)) * y2);
+                const double tx = nb_fma(q3, dx, du), ty = nb_fma(q3, dy, dv), tz = nb_fma(q3, dz, dw);
+                jx = nb_fma(s3, tx, jx); jy = nb_fma(s3, ty, jy); jz = nb_fma(s3, tz, jz);
+                ax = nb_fma(s3, dx, ax); ay = nb_fma(s3, dy, ay); az = nb_fma(s3, dz, az);
+            }
         }
     }
     red[wave][0][lane] = ax; red[wave][1][lane] = ay; red[wave][2][lane] = az;
     red[wave][3][lane] = jx; red[wave][4][lane] = jy; red[wave][5][lane] = jz;
+    if constexpr (WATCH) { enc_r[wave][lane] = br; enc_j[wave][lane] = bj; }
     __syncthreads();
     const uint32_t k = i0 + (uint32_t)tid;
     if (tid < (int)kBbRows64 && k < ni) {
         double r[6];
 #pragma unroll
         for (int c = 0; c < 6; ++c) r[c] = ((red[0][c][tid] + red[1][c][tid]) + red[2][c][tid]) + red[3][c][tid];
-        pa[(size_t)blockIdx.y * small_max + k] = double4{r[0], r[1], r[2], 0.0};
-        pj[(size_t)blockIdx.y * small_max + k] = double4{r[3], r[4], r[5], 0.0};
+        double er = 0.0, ej = 0.0;        // WATCH: the chunk's answer, rho^2 and the index as an exact double
+        if constexpr (WATCH) {            // the four quarters' bests under the total order (rho^2, index)
+            double mr = enc_r[0][tid];
+            uint32_t mj = enc_j[0][tid];
+#pragma unroll
+            for (int w = 1; w < 4; ++w) {
+                const double wr = enc_r[w][tid];
+                const uint32_t wj = enc_j[w][tid];
+                const bool t = (wj != 0xffffffffu) & ((wr < mr) | ((wr == mr) & (wj < mj)));
+                mr = t ? wr : mr; mj = t ? wj : mj;
+            }
+            er = mr; ej = (double)mj;
+        }
+        pa[(size_t)blockIdx.y * small_max + k] = double4{r[0], r[1], r[2], er};
+        pj[(size_t)blockIdx.y * small_max + k] = double4{r[3], r[4], r[5], ej};
     }
+}
+
+template <typename T>
+__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(2, 2)))
+void nb_blkq_fj64(const typename vec4<T>::type* __restrict__ pos, const typename vec4<T>::type* __restrict__ vel,
+                  const uint32_t* __restrict__ act, const uint32_t* __restrict__ hdr, const uint32_t* __restrict__ bb,
+                  uint32_t small_max, double4* __restrict__ pa, double4* __restrict__ pj, uint32_t n, uint32_t j_per_chunk,
+                  double eps2)
+{
+    blkq_fj64_body<T, false>(pos, vel, act, hdr, bb, small_max, pa, pj, n, j_per_chunk, eps2);
 }
 
 // nb_blk_correct with |A| and t_next from the device header and the small pass's rows (chunk c, slot k at pa[c * small_max + k]).
@@ -413,16 +537,26 @@ void nb_blkq_fj64(const typename vec4<T>::type* __restrict__ pos, const typename
 // order in fp64, and the lanes' sums are added in lane order -- an order fixed by the chunk count, i.e. by n and the CU count.
 // Everything behind the sums (times G, corrector, criterion, new level, due) is nb_blk_correct's, statement for statement, on
 // the slot's first lane.  Grid ceil(small_max kBbSumLanes / kBlock).
-template <typename TP, typename T>
-__global__ __launch_bounds__(kBlock) void nb_blkq_correct(const typename vec4<TP>::type* __restrict__ pa,
-                                                         const typename vec4<TP>::type* __restrict__ pj,
-                                                         const uint32_t* __restrict__ act, const uint32_t* __restrict__ bb,
-                                                         uint32_t small_max, uint32_t chunks, double G,
-                                                         typename vec4<T>::type* __restrict__ x, typename vec4<T>::type* __restrict__ v,
-                                                         typename vec4<T>::type* __restrict__ a, typename vec4<T>::type* __restrict__ j,
-                                                         uint32_t* __restrict__ due, uint8_t* __restrict__ lev,
-                                                         uint32_t* __restrict__ hdr, uint32_t n, uint32_t L, uint32_t lmin,
-                                                         int frozen, double eta, double dt)
+//   The body is shared with nb_encq_correct (kernels/encounter_batch.hip.h).  WATCH: nb_enc_fold's work inside this launch.  Each
+// lane keeps the minimum over its chunks' .w pairs under the rule of the pass (smaller rho^2, equal rho^2 to the smaller index: a
+// total order, so the minimum is the one a single ascending chain finds), the lanes' minima meet by shuffles before any lane
+// leaves, and the slot's first lane updates the record of its body: count, and (rho2, partner, time) when strictly smaller.  The
+// block time is formed here, exactly: t = tbase + t_next 2^-L, tbase the outer steps run when this outer step began.  A wave's hits
+// are counted by ballot and added once per wave that has any: an integer add and an integer minimum (the bits of t, read first),
+// no floating-point atomics, no workgroup barrier (lanes leave early above).  Without WATCH none of this is compiled.
+template <typename TP, typename T, bool WATCH>
+__device__ __forceinline__ void blkq_correct_body(const typename vec4<TP>::type* __restrict__ pa,
+                                                  const typename vec4<TP>::type* __restrict__ pj,
+                                                  const uint32_t* __restrict__ act, const uint32_t* __restrict__ bb,
+                                                  uint32_t small_max, uint32_t chunks, double G,
+                                                  typename vec4<T>::type* __restrict__ x, typename vec4<T>::type* __restrict__ v,
+                                                  typename vec4<T>::type* __restrict__ a, typename vec4<T>::type* __restrict__ j,
+                                                  uint32_t* __restrict__ due, uint8_t* __restrict__ lev,
+                                                  uint32_t* __restrict__ hdr, uint32_t n, uint32_t L, uint32_t lmin,
+                                                  int frozen, double eta, double dt, T* __restrict__ rho2 = nullptr,
+                                                  uint32_t* __restrict__ partner = nullptr, double* __restrict__ time = nullptr,
+                                                  uint32_t* __restrict__ count = nullptr,
+                                                  unsigned long long* __restrict__ words = nullptr, double tbase = 0.0)
 {
     using V4 = typename vec4<T>::type;
     if (bb[kBbMode] != kBbModeSmall) return;
@@ -435,12 +569,19 @@ __global__ __launch_bounds__(kBlock) void nb_blkq_correct(const typename vec4<TP
     double px = 0.0, py = 0.0, pz = 0.0, qx = 0.0, qy = 0.0, qz = 0.0;
     const uint32_t w = (chunks + kBbSumLanes - 1) / kBbSumLanes;
     const uint32_t c0 = q * w < chunks ? q * w : chunks, c1 = c0 + w < chunks ? c0 + w : chunks;
+    TP er = (TP)__builtin_inf();          // WATCH: the smallest (rho^2, index) of the lane's chunks
+    uint32_t ej = kEncNone;
 #pragma unroll 8
     for (uint32_t c = c0; c < c1; ++c) {
         const auto pa_ = ld4(pa + (size_t)c * small_max + k);
         const auto pj_ = ld4(pj + (size_t)c * small_max + k);
         px += (double)pa_.x; py += (double)pa_.y; pz += (double)pa_.z;
         qx += (double)pj_.x; qy += (double)pj_.y; qz += (double)pj_.z;
+        if constexpr (WATCH) {
+            const TP r = pa_.w;
+            const uint32_t jb = enc_index(pj_.w);
+            if (jb != kEncNone && (r < er || (r == er && jb < ej))) { er = r; ej = jb; }
+        }
     }
     const int first = (int)((threadIdx.x & 63u) - q);         // the slot's first lane in the wave
     double sx = __shfl(px, first), sy = __shfl(py, first), sz = __shfl(pz, first);
@@ -449,6 +590,26 @@ __global__ __launch_bounds__(kBlock) void nb_blkq_correct(const typename vec4<TP
     for (int o = 1; o < (int)kBbSumLanes; ++o) {
         sx += __shfl(px, first + o); sy += __shfl(py, first + o); sz += __shfl(pz, first + o);
         tx += __shfl(qx, first + o); ty += __shfl(qy, first + o); tz += __shfl(qz, first + o);
+    }
+    if constexpr (WATCH) {
+#pragma unroll
+        for (int o = (int)kBbSumLanes >> 1; o > 0; o >>= 1) {      // (a slot's lanes are kBbSumLanes aligned lanes of one wave, all here)
+            const TP r = __shfl_xor(er, o);
+            const uint32_t jb = (uint32_t)__shfl_xor((int)ej, o);
+            if (jb != kEncNone && (r < er || (r == er && jb < ej))) { er = r; ej = jb; }
+        }
+        const bool hit = q == 0 && ej != kEncNone;
+        const unsigned long long hits = __ballot(hit);             // over the lanes still here
+        if (hit) {
+            const double t = tbase + __builtin_ldexp((double)t_next, -(int)L);      // exact: t_next <= 2^L <= 2^30
+            count[il] += 1u;                                       // a body is in the list once: its record has one writer
+            if ((T)er < rho2[il]) { rho2[il] = (T)er; partner[il] = ej; time[il] = t; }
+            if ((threadIdx.x & 63u) == (uint32_t)__ffsll(hits) - 1u) {      // once per wave that has any
+                atomicAdd(words + kEncHits, (unsigned long long)__popcll(hits));
+                const unsigned long long tb = (unsigned long long)__double_as_longlong(t);
+                if (tb < __hip_atomic_load(words + kEncFirst, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMin(words + kEncFirst, tb);
+            }
+        }
     }
     if (q != 0) return;
     const V4 A1 = V4{(T)(G * sx), (T)(G * sy), (T)(G * sz), (T)0};
@@ -485,6 +646,20 @@ __global__ __launch_bounds__(kBlock) void nb_blkq_correct(const typename vec4<TP
         if (ln > l) atomicMax(hdr + kBlkFinest, ln);
     }
     due[il] = (t_next == (1u << L) ? 0u : t_next) + (1u << (L - ln));
+}
+
+template <typename TP, typename T>
+__global__ __launch_bounds__(kBlock) void nb_blkq_correct(const typename vec4<TP>::type* __restrict__ pa,
+                                                         const typename vec4<TP>::type* __restrict__ pj,
+                                                         const uint32_t* __restrict__ act, const uint32_t* __restrict__ bb,
+                                                         uint32_t small_max, uint32_t chunks, double G,
+                                                         typename vec4<T>::type* __restrict__ x, typename vec4<T>::type* __restrict__ v,
+                                                         typename vec4<T>::type* __restrict__ a, typename vec4<T>::type* __restrict__ j,
+                                                         uint32_t* __restrict__ due, uint8_t* __restrict__ lev,
+                                                         uint32_t* __restrict__ hdr, uint32_t n, uint32_t L, uint32_t lmin,
+                                                         int frozen, double eta, double dt)
+{
+    blkq_correct_body<TP, T, false>(pa, pj, act, bb, small_max, chunks, G, x, v, a, j, due, lev, hdr, n, L, lmin, frozen, eta, dt);
 }
 
 }  // namespace nb

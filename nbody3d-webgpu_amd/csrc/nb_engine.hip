@@ -670,7 +670,9 @@ const hermite_order kOrder4 = {
     NB_BOTH(nb_blkq_predict), {(const void*)&nb::nb_blkq_fj_pk<1>, (const void*)&nb::nb_blkq_fj64<double>},
     {(const void*)&nb::nb_blkq_correct<float, float>, (const void*)&nb::nb_blkq_correct<double, double>}};
 // Order 4 with the encounter watch on (kernels/encounter.hip.h): kOrder4's kernels, shapes, j-chunks and partial rows; the gathered
-// kernels are the same bodies with the watch compiled in.  No batched mode.
+// kernels are the same bodies with the watch compiled in.  Its batched mode (nb_set_block_batch_watch, kernels/encounter_batch.hip.h):
+// kOrder4's slot with the watch compiled into the small pass (the thresholds last) and into the small corrector (the records, the
+// words and the outer-step base last).
 const hermite_order kWatch = {
     "hermite4_", 2, 2, 4, {nb::kFjRows, nb::kFjRows64}, {nb::kFjRows, nb::kFjRows64},
     {(const void*)&nb::nb_fj_pk<nb::kFjNG>, (const void*)&nb::nb_fj64<double>},
@@ -679,7 +681,8 @@ const hermite_order kWatch = {
     NB_BOTH(nb_hermite_predict), NB_BOTH(nb_hermite_correct), NB_BOTH(nb_blk_predict),
     {(const void*)&nb::nb_blk_correct<float, float>, (const void*)&nb::nb_blk_correct<double, double>},
     &nb_sim::fj_part, &nb_sim::fj_chunks, &nb_sim::fj_per, false, false,
-    {nullptr, nullptr}, {nullptr, nullptr}, {nullptr, nullptr}, true,
+    NB_BOTH(nb_blkq_predict), {(const void*)&nb::nb_encq_fj_pk<1>, (const void*)&nb::nb_encq_fj64<double>},
+    {(const void*)&nb::nb_encq_correct<float, float>, (const void*)&nb::nb_encq_correct<double, double>}, true,
     {(const void*)&nb::nb_enc_fold<float, float>, (const void*)&nb::nb_enc_fold<double, double>}};
 const hermite_order kOrder6 = {
     "hermite6_", 3, 3, 6, {nb::kH6Rows, nb::kH6Rows64}, {nb::kBlock * 4, nb::kH6Rows64},      // (the gathered kernels are NG = 2 and 1 whatever NB_H6_NG the full pass is built with)
@@ -741,7 +744,7 @@ struct hermite_arrays {
 
 // The arguments of one launch, collected in the kernel's order: scalars one by one, the arrays of an order by their count.
 struct kernel_args {
-    void* v[24];
+    void* v[32];
     uint32_t k = 0;
     kernel_args& operator()(void* p) { v[k++] = p; return *this; }
     kernel_args& operator()(void** arr, uint32_t count) { for (uint32_t i = 0; i < count; ++i) v[k++] = &arr[i]; return *this; }
@@ -941,6 +944,20 @@ int ensure_levels(nb_sim* s, const char* who)
     return NB_OK;
 }
 
+// The fold behind a gathered pass of a watched handle (block_step, and the host steps of block_batch_step): the answers in the .w
+// lanes of the partial rows, into the records of the active bodies, at the block time t_next of the running outer step (exact:
+// t_next <= 2^L <= 2^30).
+void launch_enc_fold(nb_sim* s, const hermite_order& o, pass_parts& part, uint32_t na, uint32_t t_next)
+{
+    double t = (double)s->steps_done + std::ldexp((double)t_next, -(int)s->blk_L);
+    kernel_args f;
+    uint32_t lpr = 1;      // lanes that share a row's chunks: the next power of two, at most a wave, while the rows alone do not fill 256 workgroups
+    while (lpr < part.chunks && lpr < 64 && (uint64_t)na * lpr * 2 <= 65536) lpr *= 2;
+    f(part.plane, o.planes)(&s->blk_act)(&na)(&part.chunks)(&lpr)(&s->enc_rho2)(&s->enc_partner)(&s->enc_time)(&s->enc_count)(&s->enc_words)(&s->enc_pub)(&t);
+    (void)hipLaunchKernel(o.enc_fold[s->f64], dim3(ceil_div(na, nb::kBlock / lpr)), dim3(nb::kBlock), f.v, 0, s->stream);
+    ++s->enc_passes;
+}
+
 // nb_step of a block-step handle of either order: nsteps outer steps of dt.  Per block step: schedule and predict-all (launched
 // right behind the previous corrector), ONE host wait for the header (the active count sizes the next launch), the order's gathered
 // pass over the active bodies, reduce + correct + new levels.
@@ -975,15 +992,7 @@ int block_step(nb_sim* s, uint32_t nsteps)
                 return fail(s, NB_ERR_HIP, "nb_step: block schedule out of range (active " + std::to_string(na) + ", tick " + std::to_string(t_next) + ")");
             pass_parts part;
             launch_pass(s, o, h.in, nullptr, na, &part);
-            if (o.watch) {      // the answers in the .w lanes of the partial rows, into the records of the active bodies (exact: t_next <= 2^L <= 2^30)
-                double t = (double)s->steps_done + std::ldexp((double)t_next, -(int)L);
-                kernel_args f;
-                uint32_t lpr = 1;      // lanes that share a row's chunks: the next power of two, at most a wave, while the rows alone do not fill 256 workgroups
-                while (lpr < part.chunks && lpr < 64 && (uint64_t)na * lpr * 2 <= 65536) lpr *= 2;
-                f(part.plane, o.planes)(&s->blk_act)(&na)(&part.chunks)(&lpr)(&s->enc_rho2)(&s->enc_partner)(&s->enc_time)(&s->enc_count)(&s->enc_words)(&s->enc_pub)(&t);
-                (void)hipLaunchKernel(o.enc_fold[s->f64], dim3(ceil_div(na, nb::kBlock / lpr)), dim3(nb::kBlock), f.v, 0, s->stream);
-                ++s->enc_passes;
-            }
+            if (o.watch) launch_enc_fold(s, o, part, na, t_next);
             kernel_args c;
             c(part.plane, o.planes)(&s->blk_act)(&na)(&part.chunks)(&G)(h.state, o.states)(&s->blk_due)(&s->blk_lev)(&s->blk_hdr)(&t_next)(&Lk)(&lmin)(&frozen)(&eta)(&dt);
             (void)hipLaunchKernel(o.blk_correct[s->f64], dim3(ceil_div(na, nb::kBlock)), dim3(nb::kBlock), c.v, 0, s->stream);
@@ -1040,6 +1049,7 @@ uint32_t bb_plan_slots(const nb_sim* s)
 // step through the gathered path, as block_step does.
 int block_batch_step(nb_sim* s, uint32_t nsteps)
 {
+    s->enc_stopped = 0; s->enc_steps_left = 0;
     const bool stale = s->levels != 2;
     if (int rc = ensure_levels(s, "nb_step")) return rc;
     if (stale) { s->bb_fresh = true; s->bb_t = 0; s->bb_park_ctz = s->blk_L; }
@@ -1056,6 +1066,7 @@ int block_batch_step(nb_sim* s, uint32_t nsteps)
     void* plane[3] = {nullptr, nullptr, nullptr};
     for (uint32_t p = 0; p < o.planes; ++p) plane[p] = (char*)s->bb_part + p * (row * chunks * nb::kBbMaxSmall);
     const uint32_t gx_small = std::max(1u, ceil_div(small_max, wide ? nb::kBbRows64 : nb::kBbRows));
+    double tbase = 0.0;      // o.watch: the outer steps run when the running outer step began (the small corrector forms its block time from it)
     auto enqueue_slot = [&](uint32_t first) {
         void* sargs[] = {&s->blk_due, &s->blk_lev, &n, &s->blk_act, &s->blk_hdr, &s->blk_hdr_pub, &s->bb_words, &s->bb_pub, &first, &small_max, &end};
         (void)hipLaunchKernel((const void*)&nb::nb_blkq_sched<nb::kBlkSched>, dim3(1), dim3(nb::kBlkSched), sargs, 0, s->stream);
@@ -1066,15 +1077,18 @@ int block_batch_step(nb_sim* s, uint32_t nsteps)
         kernel_args f;
         f(h.in, o.inputs)(&s->blk_act)(&s->blk_hdr)(&s->bb_words)(&small_max)(plane, o.planes)(&n)(&per);
         if (wide) f(&e2); else f(&e2f)(&zr);
+        if (o.watch) f(&s->enc_w);
         (void)hipLaunchKernel(o.bb_pass[s->f64], dim3(gx_small, chunks), dim3(nb::kBlock), f.v, 0, s->stream);
         kernel_args c;
         c(plane, o.planes)(&s->blk_act)(&s->bb_words)(&small_max)(&chunks)(&G)(h.state, o.states)(&s->blk_due)(&s->blk_lev)(&s->blk_hdr)(&n)(&Lk)(&lmin)(&frozen)(&eta)(&dt);
+        if (o.watch) c(&s->enc_rho2)(&s->enc_partner)(&s->enc_time)(&s->enc_count)(&s->enc_words)(&tbase);
         (void)hipLaunchKernel(o.bb_correct[s->f64], dim3(ceil_div(small_max * nb::kBbSumLanes, nb::kBlock)), dim3(nb::kBlock), c.v, 0, s->stream);
     };
     for (uint32_t k = 0; k < nsteps; ++k) {
         nb_events ev;
         const bool rec = s->timing && get_events(s, &ev) == 0;
         if (rec) NB_HIP(s, hipEventRecord(ev.e[0], s->stream));
+        tbase = (double)s->steps_done;
         for (;;) {
             const uint32_t slots = bb_plan_slots(s);
             for (uint32_t q = 0; q < slots; ++q) enqueue_slot(q == 0 ? 1u : 0u);
@@ -1091,6 +1105,7 @@ int block_batch_step(nb_sim* s, uint32_t nsteps)
                 return fail(s, NB_ERR_HIP, "nb_step: block schedule out of range (active " + std::to_string(na) + ", tick " + std::to_string(t_next) +
                             ", batch of " + std::to_string(slots) + ": " + std::to_string(dsmall) + " small steps, mode " + std::to_string(mode) + ")");
             s->bb_small += dsmall; s->blk_steps += dsmall; s->blk_body_steps += dbody;
+            if (o.watch) s->enc_passes += dsmall;      // (a small step's fold is in its corrector)
             s->bb_idle += slots - dsmall - (parked ? 1u : 0u);
             // what the policy reads
             s->bb_fresh = false;
@@ -1103,6 +1118,7 @@ int block_batch_step(nb_sim* s, uint32_t nsteps)
             pass_parts part;
             uint32_t nah = na, tn = t_next;
             launch_pass(s, o, h.in, nullptr, nah, &part);
+            if (o.watch) launch_enc_fold(s, o, part, nah, tn);
             kernel_args c;
             c(part.plane, o.planes)(&s->blk_act)(&nah)(&part.chunks)(&G)(h.state, o.states)(&s->blk_due)(&s->blk_lev)(&s->blk_hdr)(&tn)(&Lk)(&lmin)(&frozen)(&eta)(&dt);
             (void)hipLaunchKernel(o.blk_correct[s->f64], dim3(ceil_div(nah, nb::kBlock)), dim3(nb::kBlock), c.v, 0, s->stream);
@@ -1110,10 +1126,16 @@ int block_batch_step(nb_sim* s, uint32_t nsteps)
             if (t_next == end) break;
         }
         if (rec) { NB_HIP(s, hipEventRecord(ev.e[1], s->stream)); ev.blk = true; s->pending.push_back(ev); }
+        bool stop = false;
+        if (o.watch && (s->enc_flags & NB_ENC_STOP)) {      // the one extra host wait per outer step, as in block_step: the last (host) step's fold published the running hits, those of the small slots included
+            NB_HIP(s, hipStreamSynchronize(s->stream));
+            stop = *(volatile unsigned long long*)s->enc_host != 0;
+        }
         NB_HIP(s, hipGetLastError());
         ++s->blk_outer;
         ++s->steps_done;
         s->start_own = s->levels_own = false;
+        if (stop) { s->enc_stopped = 1; s->enc_steps_left = nsteps - (k + 1); return NB_OK; }
     }
     return NB_OK;
 }
@@ -2299,6 +2321,22 @@ int nb_set_block_batch_mixed(nb_sim* s, const nb_block_batch* cfg)
     return bb_configure(s, cfg);
 }
 
+// nb_set_block_batch's mode on a handle with the encounter watch on (the other three setters refuse such a handle): the slot's pass
+// and corrector are kWatch's.
+int nb_set_block_batch_watch(nb_sim* s, const nb_block_batch* cfg)
+{
+    if (!s) return fail(nullptr, NB_ERR_INVALID, "nb_set_block_batch_watch: null handle");
+    if (!cfg) { s->bb = false; return NB_OK; }
+    if (int rc = bb_check(s, cfg, "nb_set_block_batch_watch")) return rc;
+    if (!s->hermite) return fail(s, NB_ERR_STATE, "nb_set_block_batch_watch: needs a Hermite handle (nb_config.integrator = NB_INT_HERMITE4) with block steps (nb_set_block_steps) and the encounter watch (nb_set_encounter_watch) switched on");
+    if (s->h6) return fail(s, NB_ERR_STATE, "nb_set_block_batch_watch: the handle's order is 6 (nb_set_hermite_order): the encounter watch exists at order 4 only, see nb_set_block_batch6");
+    if (!s->blk) return fail(s, NB_ERR_STATE, "nb_set_block_batch_watch: block steps are not switched on (nb_set_block_steps)");
+    if (s->mx) return fail(s, NB_ERR_STATE, "nb_set_block_batch_watch: the pass precision is NB_PASS_MIXED (nb_set_pass_precision, nb_set_pass_guard): the encounter watch runs in the native pass only, set NB_PASS_NATIVE first or see nb_set_block_batch_mixed");
+    if (s->bb && !s->enc) return fail(s, NB_ERR_STATE, "nb_set_block_batch_watch: another batched mode is switched on (nb_set_block_batch): switch it off first (nb_set_block_batch(s, NULL)), then nb_set_encounter_watch, then this call");
+    if (!s->enc) return fail(s, NB_ERR_STATE, "nb_set_block_batch_watch: the encounter watch is not switched on: call nb_set_encounter_watch first, or nb_set_block_batch for the mode without a watch");
+    return bb_configure(s, cfg);      // (while this mode is on: depth and small_max anew, as the other setters)
+}
+
 int nb_block_batch_stats(nb_sim* s, struct nb_block_batch_stats* out, int reset)
 {
     if (!s) return fail(nullptr, NB_ERR_INVALID, "nb_block_batch_stats: null handle");
@@ -2383,7 +2421,7 @@ static int enc_on(nb_sim* s, const char* who)
 int nb_set_encounter_watch(nb_sim* s, const nb_encounter_watch* cfg)
 {
     if (!s) return fail(nullptr, NB_ERR_INVALID, "nb_set_encounter_watch: null handle");
-    if (!cfg) { s->enc = false; return NB_OK; }
+    if (!cfg) { if (s->enc) s->bb = false; s->enc = false; return NB_OK; }      // (its batched mode, nb_set_block_batch_watch, goes with it)
     if (cfg->flags & ~(uint32_t)NB_ENC_STOP) return fail(s, NB_ERR_INVALID, "nb_set_encounter_watch: unknown flags");
     if (!(cfg->radius >= 0.0) || std::isinf(cfg->radius)) return fail(s, NB_ERR_INVALID, "nb_set_encounter_watch: radius must be finite and >= 0");
     if (!s->hermite) return fail(s, NB_ERR_STATE, "nb_set_encounter_watch: needs a Hermite handle (nb_config.integrator = NB_INT_HERMITE4) with block steps switched on (nb_set_block_steps)");
@@ -2397,7 +2435,8 @@ int nb_set_encounter_watch(nb_sim* s, const nb_encounter_watch* cfg)
     if (s->ac) return fail(s, NB_ERR_STATE, "nb_set_encounter_watch: the neighbour scheme is switched on (nb_set_neighbor_scheme): the watch runs in the gathered pass of block steps only");
     if (!s->blk) return fail(s, NB_ERR_STATE, "nb_set_encounter_watch: block steps are not switched on (nb_set_block_steps)");
     if (s->mx) return fail(s, NB_ERR_STATE, "nb_set_encounter_watch: the pass precision is NB_PASS_MIXED (nb_set_pass_precision, nb_set_pass_guard): the watch runs in the native pass only, set NB_PASS_NATIVE first");
-    if (s->bb) return fail(s, NB_ERR_STATE, "nb_set_encounter_watch: batched block steps are switched on (nb_set_block_batch): the watch runs on the base path of block steps only, switch them off first");
+    // (batched and watched: nb_set_block_batch_watch's mode, the one batched mode the watch has; the call re-configures radii and flags)
+    if (s->bb && !s->enc) return fail(s, NB_ERR_STATE, "nb_set_encounter_watch: batched block steps are switched on (nb_set_block_batch): the watch runs on the base path of block steps only, switch them off first");
     NB_HIP(s, hipSetDevice(s->device));
     NB_HIP(s, hipStreamSynchronize(s->stream));
     if (!s->enc_w) NB_HIP(s, hipMalloc(&s->enc_w, s->esz * s->n));

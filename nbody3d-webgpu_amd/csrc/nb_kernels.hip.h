@@ -69,6 +69,7 @@
 #include "kernels/split_force.hip.h" // nb_split_pk, nb_split64, nb_split_reduce (nb_split_force: regular and irregular force+jerk in one pass)
 #include "kernels/split_lists.hip.h" // nb_spl_pk, nb_spl64, nb_spl_rows (nb_split_lists: the two sums and the neighbour rows from one pass)
 #include "kernels/block.hip.h"       // nb_blk_start, nb_blk_sched, nb_blk_predict, nb_blk_fj_pk, nb_blk_fj64, nb_blk_correct (nb_set_block_steps)
+#include "kernels/encounter.hip.h"   // nb_enc_fj_pk, nb_enc_fj64, nb_enc_fold (nb_set_encounter_watch: closest approaches seen inside block steps)
 #include "kernels/block_batch.hip.h" // nb_blkq_sched, nb_blkq_predict, nb_blkq_fj_pk, nb_blkq_fj64, nb_blkq_correct (nb_set_block_batch: block steps sized on the device)
 #include "kernels/mixed.hip.h"       // nb_mx_split, nb_mx_predict, nb_mx_blk_predict, nb_mx_fj, nb_mx_blk_fj (nb_set_pass_precision: double-single force+jerk pass of f64 handles)
 #include "kernels/guard.hip.h"       // nb_mxg_fj, nb_mxg_blk_fj, nb_mxg_fold (nb_set_pass_guard: the mixed pass with guarded sums, fp64 partial rows)
@@ -78,4 +79,4 @@
 #include "kernels/block6.hip.h"      // nb_blk6_start, nb_blk6_predict, nb_blk6_fjs_pk, nb_blk6_fjs64, nb_blk6_correct (nb_set_block_steps6: block steps on order-6 handles)
 #include "kernels/block_batch6.hip.h" // nb_blkq6_predict, nb_blkq6_fjs_pk, nb_blkq6_fjs64, nb_blkq6_correct (nb_set_block_batch6: block steps sized on the device, order-6 handles)
 #include "kernels/block_batch_mixed.hip.h" // nb_blkqm_predict, nb_blkqm_fj (nb_set_block_batch_mixed: block steps sized on the device, mixed-precision handles)
-#include "kernels/encounter.hip.h"   // nb_enc_fj_pk, nb_enc_fj64, nb_enc_fold (nb_set_encounter_watch: closest approaches seen inside block steps)
+#include "kernels/encounter_batch.hip.h" // nb_encq_fj_pk, nb_encq_fj64, nb_encq_correct (nb_set_block_batch_watch: the encounter watch inside batched slots)

@@ -78,6 +78,7 @@ static int (*p_set_block_batch)(nb_sim *, const nb_block_batch *);      /* batch
 static int (*p_block_batch_stats)(nb_sim *, struct nb_block_batch_stats *, int);
 static int (*p_set_block_batch6)(nb_sim *, const nb_block_batch *);     /* ... on order-6 handles (round 26): optional */
 static int (*p_set_block_batch_mixed)(nb_sim *, const nb_block_batch *);     /* ... on mixed-precision handles (round 27): optional */
+static int (*p_set_block_batch_watch)(nb_sim *, const nb_block_batch *);     /* ... on watched handles (round 29): optional */
 static int (*p_set_encounter_watch)(nb_sim *, const nb_encounter_watch *);     /* the encounter watch of block steps (round 28): optional */
 static int (*p_encounter_stats)(nb_sim *, struct nb_encounter_stats *, int);
 static int (*p_download_encounters)(nb_sim *, void *, uint32_t *, double *, uint32_t *);
@@ -208,6 +209,7 @@ static napi_value js_load(napi_env env, napi_callback_info info)
         *(void **)(&p_block_batch_stats) = dlsym(h, "nb_block_batch_stats");
         *(void **)(&p_set_block_batch6) = dlsym(h, "nb_set_block_batch6");
         *(void **)(&p_set_block_batch_mixed) = dlsym(h, "nb_set_block_batch_mixed");
+        *(void **)(&p_set_block_batch_watch) = dlsym(h, "nb_set_block_batch_watch");
         *(void **)(&p_set_encounter_watch) = dlsym(h, "nb_set_encounter_watch");
         *(void **)(&p_encounter_stats) = dlsym(h, "nb_encounter_stats");
         *(void **)(&p_download_encounters) = dlsym(h, "nb_download_encounters");
@@ -1373,7 +1375,8 @@ static napi_value js_block_stats(napi_env env, napi_callback_info info)
 }
 
 /* setBlockBatch(handle, null) | setBlockBatch(handle, depth, smallMax): nb_set_block_batch (depth 0: the default; smallMax < 0: the
- * default); setBlockBatch6 and setBlockBatchMixed likewise through nb_set_block_batch6 and nb_set_block_batch_mixed */
+ * default); setBlockBatch6, setBlockBatchMixed and setBlockBatchWatch likewise through nb_set_block_batch6, nb_set_block_batch_mixed
+ * and nb_set_block_batch_watch */
 static napi_value set_block_batch_by(napi_env env, napi_callback_info info, int (*fn)(nb_sim *, const nb_block_batch *), const char *sym)
 {
     size_t argc = 3; napi_value argv[3];
@@ -1400,6 +1403,7 @@ static napi_value set_block_batch_by(napi_env env, napi_callback_info info, int 
 static napi_value js_set_block_batch(napi_env env, napi_callback_info info) { return set_block_batch_by(env, info, p_set_block_batch, "nb_set_block_batch"); }
 static napi_value js_set_block_batch6(napi_env env, napi_callback_info info) { return set_block_batch_by(env, info, p_set_block_batch6, "nb_set_block_batch6"); }
 static napi_value js_set_block_batch_mixed(napi_env env, napi_callback_info info) { return set_block_batch_by(env, info, p_set_block_batch_mixed, "nb_set_block_batch_mixed"); }
+static napi_value js_set_block_batch_watch(napi_env env, napi_callback_info info) { return set_block_batch_by(env, info, p_set_block_batch_watch, "nb_set_block_batch_watch"); }
 
 /* blockBatchStats(handle, reset) -> {enabled, hostWaits, slots, smallSteps, hostSteps, idleSlots} (counts as doubles) */
 static napi_value js_block_batch_stats(napi_env env, napi_callback_info info)
@@ -1821,7 +1825,7 @@ static napi_value init_module(napi_env env, napi_value exports)
         {"setHermiteOrder", js_set_hermite_order}, {"hermiteOrder", js_hermite_order}, {"downloadSnap", js_download_snap}, {"uploadDerivs6", js_upload_derivs6},
         {"setStart6", js_set_start6}, {"start6", js_start6}, {"setPassPrecision", js_set_pass_precision}, {"passPrecision", js_pass_precision},
         {"setPassGuard", js_set_pass_guard}, {"passGuard", js_pass_guard},
-        {"setBlockSteps", js_set_block_steps}, {"setBlockSteps6", js_set_block_steps6}, {"blockStats", js_block_stats}, {"setBlockBatch", js_set_block_batch}, {"setBlockBatch6", js_set_block_batch6}, {"setBlockBatchMixed", js_set_block_batch_mixed}, {"blockBatchStats", js_block_batch_stats}, {"downloadLevels", js_download_levels},
+        {"setBlockSteps", js_set_block_steps}, {"setBlockSteps6", js_set_block_steps6}, {"blockStats", js_block_stats}, {"setBlockBatch", js_set_block_batch}, {"setBlockBatch6", js_set_block_batch6}, {"setBlockBatchMixed", js_set_block_batch_mixed}, {"setBlockBatchWatch", js_set_block_batch_watch}, {"blockBatchStats", js_block_batch_stats}, {"downloadLevels", js_download_levels},
         {"setEncounterWatch", js_set_encounter_watch}, {"encounterStats", js_encounter_stats}, {"downloadEncounters", js_download_encounters},
         {"uploadEncounters", js_upload_encounters}, {"resetEncounters", js_reset_encounters},
         {"uploadLevels", js_upload_levels}, {"neighbors", js_neighbors}, {"neighborLists", js_neighbor_lists},

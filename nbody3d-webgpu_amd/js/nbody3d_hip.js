@@ -19,7 +19,7 @@
  *   readJerk()             (no reference analogue) the jerk of a {integrator: 'hermite4'} simulation
  *   setHermiteOrder(6 | 4), hermiteOrder(), readSnap(), uploadDerivs6(accel, jerk, snap, crackle)
  *                          (no reference analogue) the 6th-order scheme of a 'hermite4' simulation on force, jerk and snap
- *   setBlockBatch() / setBlockBatch6() / setBlockBatchMixed() / blockBatchStats()
+ *   setBlockBatch() / setBlockBatch6() / setBlockBatchMixed() / setBlockBatchWatch() / blockBatchStats()
  *   setBlockSteps() / setBlockSteps6() / blockStats() / readLevels() / uploadLevels()
  *   setEncounterWatch() / encounterStats() / downloadEncounters() / uploadEncounters() / resetEncounters()
  *                          (no reference analogue) block individual time steps of a 'hermite4' simulation
@@ -335,6 +335,18 @@ class Simulation {
     if (options === null) { addon.setBlockBatchMixed(this._h, null); return this; }
     const o = options || {};
     addon.setBlockBatchMixed(this._h, (o.depth || 0) >>> 0, (o.smallMax === undefined || o.smallMax === null) ? -1 : Number(o.smallMax));
+    return this;
+  }
+
+  /** setBlockBatch()'s mode on a simulation with the encounter watch on (nb_set_block_batch_watch; call setBlockSteps(),
+   *  setEncounterWatch(), then this): the small steps watch too, and the records depend on depth as little as the state does.
+   *  The same options, defaults and refusals; blockBatchStats() serves all four.  setBlockBatchWatch(null) switches the mode off
+   *  and keeps the watch; setEncounterWatch(null) switches off both. */
+  setBlockBatchWatch(options) {
+    this._need();
+    if (options === null) { addon.setBlockBatchWatch(this._h, null); return this; }
+    const o = options || {};
+    addon.setBlockBatchWatch(this._h, (o.depth || 0) >>> 0, (o.smallMax === undefined || o.smallMax === null) ? -1 : Number(o.smallMax));
     return this;
   }
 

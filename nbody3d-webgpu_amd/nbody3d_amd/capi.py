@@ -229,7 +229,8 @@ SYMBOLS = ["nb_abi_version", "nb_device_count", "nb_create", "nb_destroy", "nb_u
            "nb_set_block_steps6", "nb_set_start6", "nb_start6", "nb_set_pass_precision", "nb_pass_precision",
            "nb_set_pass_guard", "nb_pass_guard", "nb_set_block_batch", "nb_block_batch_stats", "nb_set_block_batch6",
            "nb_set_block_batch_mixed",
-           "nb_set_encounter_watch", "nb_encounter_stats", "nb_download_encounters", "nb_upload_encounters", "nb_reset_encounters"]
+           "nb_set_encounter_watch", "nb_encounter_stats", "nb_download_encounters", "nb_upload_encounters", "nb_reset_encounters",
+           "nb_set_block_batch_watch"]
 
 START6_ZERO, START6_CRACKLE = 0, 1      # nb_set_start6
 PASS_NATIVE, PASS_MIXED = 0, 1          # nb_set_pass_precision
@@ -360,6 +361,8 @@ def load_library():
         L.nb_download_encounters.argtypes = [vp, vp, vp, vp, vp]
         L.nb_upload_encounters.argtypes = [vp, vp, vp, vp, vp]
         L.nb_reset_encounters.argtypes = [vp]
+    if hasattr(L, "nb_set_block_batch_watch"):  # batched block steps on a watched handle, likewise
+        L.nb_set_block_batch_watch.argtypes = [vp, C.POINTER(nb_block_batch)]
     if hasattr(L, "nb_set_neighbor_levels"):    # block individual irregular steps inside the scheme, also within 2.4
         L.nb_set_neighbor_levels.argtypes = [vp, C.POINTER(nb_neighbor_levels)]
         L.nb_neighbor_level_stats.argtypes = [vp, C.POINTER(nb_neighbor_level_stats), C.c_int]
@@ -1100,6 +1103,14 @@ class Simulation:
         The same arguments, defaults and refusals; block_batch_stats() serves all three.  set_block_batch_mixed(None) switches
         the mode off (so do set_block_batch(None), set_block_batch6(None) and set_block_steps(None))."""
         return self._set_block_batch("nb_set_block_batch_mixed", args, kw)
+
+    def set_block_batch_watch(self, *args, **kw):
+        """set_block_batch_watch(depth=None, small_max=None): nb_set_block_batch_watch -- set_block_batch()'s mode on a handle with
+        the encounter watch on (order 4, the native pass; call set_block_steps(), set_encounter_watch(), then this): the small
+        steps watch too, and the records and counters depend on depth as little as the state does.  The same arguments, defaults
+        and refusals; block_batch_stats() serves all four.  set_block_batch_watch(None) switches the mode off and keeps the watch
+        (so do the three other batch setters with None); set_encounter_watch(None) switches off both."""
+        return self._set_block_batch("nb_set_block_batch_watch", args, kw)
 
     def _set_block_batch(self, symbol, args, kw):
         who = symbol[3:]

@@ -28,10 +28,12 @@ turns with the one without, (b) runs with the mode on and records the five batch
 set_pass_precision("mixed") on every handle with block steps -- the plain Hermite handles of (a) and the shared runs of (b) stay
 native -- and --batch then goes through set_block_batch_mixed.
 
---watch RADIUS (order 4, native pass, not with --batch) switches set_encounter_watch(radius=RADIUS) on: (a) and (c) run a handle with
+--watch RADIUS (order 4, native pass) switches set_encounter_watch(radius=RADIUS) on: (a) and (c) run a handle with
 the watch on in turns with the one without (the keys --batch names batch_* are then watch_*; watch_stats holds the counters and
 the hits per body and pass), (b) runs with the watch on and records the counters, how many bodies carry a record against the pair
 members, and the distribution of the recorded rho2 - eps2 of the pair members (run it without --watch for the other arm).
+--watch R --batch D,S together switch the watch on and then set_block_batch_watch(depth, small_max): the second arm is the watched
+batched mode, the keys are --batch's batch_*, and watch_stats is recorded beside them.
 
 Needs a GPU (no fallback)."""
 import argparse
@@ -92,8 +94,10 @@ def watch_stats(sim):
 
 def second_arm_on(sim, depth=None):
     if WATCH is not None:
-        return sim.set_encounter_watch(radius=WATCH)
-    setter = sim.set_block_batch6 if ORDER == 6 else sim.set_block_batch_mixed if MIXED else sim.set_block_batch
+        sim.set_encounter_watch(radius=WATCH)
+        if not BATCH:
+            return sim
+    setter = sim.set_block_batch_watch if WATCH is not None else sim.set_block_batch6 if ORDER == 6 else sim.set_block_batch_mixed if MIXED else sim.set_block_batch
     return setter(depth=BATCH[0] if depth is None else depth, small_max=BATCH[1])
 
 
@@ -167,6 +171,8 @@ def part_a(args, out):
                 r[second_arm() + "_over_block"] = r[second_arm() + "_block_step_ms"]["median"] / r["block_step_ms"]["median"]
                 r[second_arm() + "_over_block_rounds"] = [x / y for x, y in zip(got[second_arm() + "_block_step_ms"], got["block_step_ms"])]
                 r[second_arm() + "_stats"] = bat.block_batch_stats() if BATCH else watch_stats(bat)
+                if BATCH and WATCH is not None:
+                    r["watch_stats"] = watch_stats(bat)
             out["full"]["%s_%d" % (prec, n)] = r
 
 
@@ -268,6 +274,8 @@ def part_c(args, out):
                                "block_steps_per_outer": st["block_steps"] / st["outer_steps"], "body_steps_per_outer": st["body_steps"] / st["outer_steps"]}
                     if arm == "on":
                         t[name][second + "_stats"] = sims[arm, name].block_batch_stats() if BATCH else watch_stats(sims[arm, name])
+                        if BATCH and WATCH is not None:
+                            t[name]["watch_stats"] = watch_stats(sims[arm, name])
                 per = [1e6 * (x - y) / (2 ** L - 1) for x, y in zip(runs[arm, "64_at_level6"], runs[arm, "all_level0"])]
                 t["us_per_small_block_step"] = (t["64_at_level6"]["outer_step_us"] - t["all_level0"]["outer_step_us"]) / (2 ** L - 1)
                 t["us_per_small_block_step_rounds"] = per
@@ -316,7 +324,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--only", choices=["a", "b", "c", "i"], nargs="*", default=["a", "b", "c"])
     ap.add_argument("--batch", default=None, metavar="DEPTH,SMALL_MAX", help="set_block_batch(depth, small_max) on the block handles (with --order 6: set_block_batch6)")
-    ap.add_argument("--watch", type=float, default=None, metavar="RADIUS", help="set_encounter_watch(radius=RADIUS) on the block handles (order 4, native pass, not with --batch)")
+    ap.add_argument("--watch", type=float, default=None, metavar="RADIUS", help="set_encounter_watch(radius=RADIUS) on the block handles (order 4, native pass); with --batch: set_block_batch_watch")
     ap.add_argument("--pass-precision", default="native", choices=["native", "mixed"], help="mixed: set_pass_precision('mixed') on the block handles (f64 only); --batch then uses set_block_batch_mixed")
     ap.add_argument("--full-n", type=int, default=65536)
     ap.add_argument("--sizes", type=int, nargs="*", default=[16384, 65536])
@@ -337,8 +345,8 @@ def main():
     args = ap.parse_args()
     global ORDER, BATCH, MIXED, WATCH
     WATCH = args.watch
-    if WATCH is not None and (args.batch or args.order != 4 or args.pass_precision != "native" or not WATCH >= 0):
-        ap.error("--watch takes a radius >= 0 and needs --order 4, the native pass and no --batch")
+    if WATCH is not None and (args.order != 4 or args.pass_precision != "native" or not WATCH >= 0):
+        ap.error("--watch takes a radius >= 0 and needs --order 4 and the native pass")
     ORDER = args.order
     MIXED = args.pass_precision == "mixed"
     if MIXED and ORDER != 4:
